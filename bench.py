@@ -18,6 +18,8 @@ collective other than that gather).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 ...             # the driver's form: used as is
     python bench.py --gpus 2 --dry-run-cpu   # plumbing check without a GPU: gloo, 2 ranks, stub kernels (value is null)
+    python bench.py --dump-outputs DIR       # + the last timed step's token ids / counts / scores as DIR/*.npy: the inputs
+                                             #   are seeded, so two builds can be compared output for output
 
 Prints ONE JSON line on rank 0 (contract in the task statement): `value` comes from the wall time of EXACTLY K steps
 bracketed by barrier + synchronize (max over ranks).  Extra fields:
@@ -225,7 +227,12 @@ def parse_args():
                          "collectives; the real workload and the whole multi-rank flow, NOT a measurement")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="no GPU: gloo backend and a stub step; exercises launch, sharding, gather and timing plumbing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (token ids, token counts, scores "
+                         "of every utterance) as DIR/<name>.npy, float32 / float64, to compare two builds output for output")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus is None:
         a.gpus = 8 if a.config == "cfg3" else 1
     defaults = {"cfg1": (200, 10, 1, 498), "cfg2": (300, 10, 32, 1000), "cfg3": (300, 10, 32, 1000),
@@ -235,6 +242,30 @@ def parse_args():
     a.batch = defaults[2] if a.batch is None else a.batch
     a.frames = defaults[3] if a.frames is None else a.frames
     return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out):
+    """--dump-outputs: one step's (tokens [N, L], n_tokens [N], score [N]) as out_dir/{tokens,n_tokens,scores,rows}.npy.
+    Token ids and counts are written as float32 (exact below 2^24), scores as float64.  A caller reads the ids
+    tokens[i, :n_tokens[i]]; the rest of each row is written as -1, since a decoder may leave it unwritten.  Above
+    DUMP_LIMIT_BYTES a fixed, seeded sample of the utterances is written; rows.npy holds the indices of the rows written."""
+    tokens, n, score = (t.detach().cpu().numpy() for t in out[:3])
+    n = n.astype(np.int64)
+    tokens = np.where(np.arange(tokens.shape[1])[None, :] < n[:, None], tokens, -1).astype(np.float32)
+    rows = np.arange(tokens.shape[0])
+    row_bytes = tokens.shape[1] * 4 + 4 + 8 + 8
+    keep = DUMP_LIMIT_BYTES // row_bytes
+    if len(rows) > keep:
+        rows = np.sort(np.random.default_rng(0).choice(len(rows), size=keep, replace=False))
+    arrays = {"tokens": tokens[rows], "n_tokens": n[rows].astype(np.float32), "scores": score[rows].astype(np.float64),
+              "rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": sorted(arrays), "rows": int(len(rows)), "of_rows": int(tokens.shape[0])}
 
 
 def free_port():
@@ -909,6 +940,8 @@ def main():
         elapsed = float(t.item())
     # the gathered batch really holds every rank's utterances
     assert out[0].shape[0] == w.expect_rows(), (out[0].shape, w.expect_rows())
+    # copied to the host now: the legs below run more steps, which may reuse the buffers of `out`
+    dumped = dump_outputs(args.dump_outputs, out) if (args.dump_outputs and rank == 0) else None
     ms_per_step = elapsed / args.steps * 1e3
     audio_s_per_step = getattr(w, "audio_s_global", None) or world * w.audio_s
     value = audio_s_per_step / (elapsed / args.steps)
@@ -1038,7 +1071,7 @@ def main():
             "median_ms_per_step": None if median_ms is None else round(median_ms, 3),
             "value_from_median": None if median_ms is None else round(audio_s_per_step / (median_ms * 1e-3), 1),
             "timed_region_s": round(elapsed, 3), "n_ranks_seen": n_ranks_seen, "backend": backend if world > 1 else None,
-            "roofline": roofline, "cpu_baseline": cpu,
+            "roofline": roofline, "cpu_baseline": cpu, "dumped_outputs": dumped,
         }
         print(json.dumps(line), flush=True)
     if world > 1:

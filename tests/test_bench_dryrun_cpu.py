@@ -31,6 +31,30 @@ def test_under_the_drivers_launcher():
     assert line["n_ranks_seen"] == 2 and line["scaling"] == "weak"
 
 
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's gathered (tokens, n_tokens, scores) as float32 / float64 .npy files, the
+    same for two runs with the same arguments; --steps sets the timed steps and the line carries ms_per_step."""
+    import numpy as np
+    dumps = []
+    for k in ("a", "b"):
+        d = str(tmp_path / k)
+        line = _run([sys.executable, "bench.py", "--gpus", "2", "--dry-run-cpu", "--steps", "4", "--warmup", "1",
+                     "--dump-outputs", d])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        assert line["dumped_outputs"]["rows"] == line["dumped_outputs"]["of_rows"] == 64
+        dumps.append({n: np.load(os.path.join(d, n + ".npy")) for n in ("tokens", "n_tokens", "scores", "rows")})
+    a, b = dumps
+    assert a["tokens"].dtype == np.float32 and a["n_tokens"].dtype == np.float32 and a["scores"].dtype == np.float64
+    assert a["tokens"].shape[0] == a["n_tokens"].shape[0] == a["scores"].shape[0] == 64
+    assert np.array_equal(a["rows"], np.arange(64))
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, "bench.py", "--dry-run-cpu", "--steps", "0"], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_every_profiled_kernel_has_an_accounting_class():
     """bench.class_of maps every ppasr kernel name of the committed rocprofv3 traces (profiles/r03c_*_kernel_trace_bench.txt,
     names possibly truncated by the summary) to an accounting class, and the classes that carry the step's matrix work

@@ -49,10 +49,10 @@ np.savez(sys.argv[1], **out)
 """ % ROOT
 
 
-def test_block_lists_compute_what_the_padded_grid_computes():
+def test_block_lists_compute_what_the_padded_grid_computes(tmp_path):
     outs = []
     for flag in ("1", "0"):
-        path = f"/tmp/_blocktab_{flag}.npz"
+        path = str(tmp_path / f"blocktab_{flag}.npz")
         subprocess.check_call([sys.executable, "-c", CODE, path], env=dict(os.environ, PPASR_BLOCK_TABLE=flag), cwd=ROOT)
         outs.append(np.load(path))
     assert sorted(outs[0].files) == sorted(outs[1].files) and len(outs[0].files) == 6
