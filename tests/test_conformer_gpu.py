@@ -1,8 +1,8 @@
 """GPU parity: HIP Conformer path (through the C-ABI) vs the CPU oracle, stage by stage.
 
-Tolerance: BASELINE.json north_star asks <= 1e-3 relative on encoder logits; every
-intermediate is checked to the same bound (measured errors are ~1e-5), relative to the
-tensor's max magnitude.  Greedy token ids must match the oracle exactly on frames whose
+Tolerance: the fp32 error budget of tests/numerics.py (F32_BUDGET, set from the measured
+error of the fp32 routes against a float64 oracle) on encoder logits; every intermediate
+is checked to the same bound, relative to the tensor's max magnitude.  Greedy token ids must match the oracle exactly on frames whose
 oracle top-1 margin exceeds the measured logit error (all frames, in practice).
 """
 import numpy as np
@@ -12,10 +12,11 @@ import torch
 from oracle.conformer_oracle import ConformerOracle
 from oracle.ctc_decoders_oracle import greedy_tokens
 from ppasr_amd.utils.synth import conformer_state_dict, synth_features
+from numerics import F32_BUDGET
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-3
+TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
 
 
 def _rel(a, b):
@@ -126,7 +127,7 @@ def test_fused_attention_route_equals_two_kernel_route(B, T, lens):
     f, s = fused.cpu().numpy(), split.cpu().numpy()
     scale = np.abs(ref).max()
     assert np.abs(f - s).max() / scale < 1e-5
-    assert np.abs(f - ref).max() / scale < 1e-3
+    assert np.abs(f - ref).max() / scale < TOL
 
 
 @pytest.mark.parametrize("B,T,lens,k", [(3, 331, [331, 250, 90], 15), (2, 523, [523, 300], 31), (1, 67, [67], 7)])
@@ -143,7 +144,7 @@ def test_non_streaming_model_non_causal_conv(B, T, lens, k):
     torch.cuda.synchronize()
     oracle = ConformerOracle(sd, num_blocks=L, cnn_module_kernel=k, causal=False)
     ref_probs, ref_logits = oracle.get_encoder_out(x, lens, return_logits=True)
-    assert np.abs(logits.cpu().numpy() - ref_logits.numpy()).max() / np.abs(ref_logits.numpy()).max() < 1e-3
+    assert np.abs(logits.cpu().numpy() - ref_logits.numpy()).max() / np.abs(ref_logits.numpy()).max() < TOL
     # and it differs from the causal module on the same weights (the test would be vacuous otherwise)
     causal_logits = ConformerOracle(sd, num_blocks=L, cnn_module_kernel=k, causal=True).get_encoder_out(
         x, lens, return_logits=True)[1]

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 import torch
+from numerics import F32_BUDGET, F32_BUDGET_DS2
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "family_oracle_golden.npz")
@@ -44,12 +45,12 @@ def test_squeezeformer_and_efficient_conformer_match_fixtures():
     for mode in (-1, 0):
         m.set_ffn_split(mode)
         _, lg = m.get_encoder_out(c["sq_x"], c["sq_lens"], return_logits=True)
-        assert _rel(lg.cpu().numpy(), g["sq_logits"]) < 1e-3, mode
+        assert _rel(lg.cpu().numpy(), g["sq_logits"]) < F32_BUDGET, mode
     m = EfficientConformerModel(80, 53, streaming=True, encoder_conf=c["eff_conf"], state_dict=c["eff_sd"], device="cuda:0")
     for mode in (-1, 0):
         m.set_ffn_split(mode)
         _, lg = m.get_encoder_out(c["eff_x"], c["eff_lens"], return_logits=True)
-        assert _rel(lg.cpu().numpy(), g["eff_logits"]) < 1e-3, mode
+        assert _rel(lg.cpu().numpy(), g["eff_logits"]) < F32_BUDGET, mode
 
 
 @pytest.mark.gpu
@@ -61,8 +62,8 @@ def test_deepspeech2_matches_fixtures(key, streaming):
                          state_dict=c[key + "_sd"], device="cuda:0")
     probs, lens, h, _ = m.get_encoder_out_chunk(c[key + "_x"], c[key + "_lens"])
     assert lens.cpu().tolist() == g[key + "_lens"].tolist()
-    assert _rel(probs.cpu().numpy(), g[key + "_probs"]) < 1e-3
-    assert _rel(h.cpu().numpy(), g[key + "_h"]) < 1e-3
+    assert _rel(probs.cpu().numpy(), g[key + "_probs"]) < F32_BUDGET_DS2
+    assert _rel(h.cpu().numpy(), g[key + "_h"]) < F32_BUDGET_DS2
 
 
 @pytest.mark.gpu

@@ -9,9 +9,10 @@ import torch
 from oracle.ctc_decoders_oracle import greedy_tokens
 from ppasr_amd.utils.synth import (conformer_state_dict, efficient_conformer_state_dict, squeezeformer_state_dict,
                                    synth_features)
+from numerics import F32_BUDGET
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-3
+TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
 
 
 def _rel(a, b):

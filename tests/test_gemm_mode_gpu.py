@@ -1,10 +1,11 @@
 """GPU: the opt-in fp16 x3 arithmetic of the feed-forward GEMMs (ppasr_set_gemm_mode, csrc/h3.h) against the torch-CPU
 oracle and against the default fp32-MFMA mode.  Every operand is split into two fp16 pieces (22 significant bits), the
 products of pieces are exact in fp32 and accumulate in fp32, so the mode is held to the SAME bar as the fp32 kernels:
-logits within 1e-3 of the oracle (measured: the fp32 kernels' own 1e-6 class), greedy ids identical."""
+logits within 1e-3 of the oracle, the fp32 route within the fp32 budget of tests/numerics.py (measured: the fp32 kernels' own 1e-6 class), greedy ids identical."""
 import numpy as np
 import pytest
 import torch
+from numerics import F32_BUDGET
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +44,7 @@ def test_f16x3_mode_against_the_oracle_and_the_fp32_mode(B, T, lens):
     _, lo = orc.get_encoder_out(torch.as_tensor(x), torch.as_tensor(la), return_logits=True)
     lo = lo.numpy()
     e32, eh = _rel(l32, lo), _rel(lh, lo)
-    assert e32 < 1e-3 and eh < 1e-3, (e32, eh)
+    assert e32 < F32_BUDGET and eh < 1e-3, (e32, eh)
     assert eh < 2e-5, eh  # (measured 1e-6 .. 3e-6: the same class as the fp32 kernels)
     assert np.array_equal(lh.argmax(-1), l32.argmax(-1))
     # back to the default: bit-identical to the first pass

@@ -1,7 +1,7 @@
 """GPU: the general Conformer layer route (csrc/capi_generic.hip) on seeded random combinations of the ConformerEncoder
 constructor arguments (conformer/encoder.py:38-48), ragged / degenerate batches and chunked streaming, against
 oracle/conformer_oracle.py -- whose option branches are pinned to the reference's own source on the opt_* / act_* cases of
-tests/golden/ref_small.npz (tests/test_ref_pin_cpu.py).  Tolerance as everywhere: 1e-3 of the tensor's largest magnitude
+tests/golden/ref_small.npz (tests/test_ref_pin_cpu.py).  Tolerance as everywhere: the fp32 budget (tests/numerics.py) of the tensor's largest magnitude
 (north_star); measured values are printed."""
 import numpy as np
 import pytest
@@ -9,9 +9,10 @@ import torch
 
 from oracle.conformer_oracle import ConformerOracle
 from ppasr_amd.utils.synth import conformer_state_dict, synth_features
+from numerics import F32_BUDGET
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-3
+TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
 # (hardshrink is left to its fixture, tests/test_ref_pin_gpu.py[act_hardshrink]: a DISCONTINUOUS activation -- x -> 0 below
 #  |x| = 0.5 -- turns a 1e-7 difference in a pre-activation next to the threshold into a 0.5 step, so two correct fp32
 #  implementations agree only as far as no value happens to sit there; seen here: 8e-3 on one draw)

@@ -2,12 +2,12 @@
 (tests/golden/ref_small.npz / ref_full.npz; tests/golden/make_ref_goldens.py runs /root/reference/ppasr/model_utils
 unmodified on oracle/paddle_shim).  No oracle is involved at run time.
 
-Tolerances (BASELINE.json north_star): encoder logits / probabilities within 1e-3 relative to the tensor's largest
-magnitude; greedy ids bit-exact (frames whose reference top-2 logit margin is below 1e-3 are near-ties of the fp32
+Tolerances: encoder logits / probabilities within the fp32 error budget of tests/numerics.py (F32_BUDGET; the
+recurrences F32_BUDGET_DS2) relative to the tensor's largest magnitude; greedy ids bit-exact (frames whose reference top-2 logit margin is below 1e-3 are near-ties of the fp32
 reference itself and are compared through the margin instead).
 
 The batched tests run twice: in the default arithmetic and with the opt-in fp16 x 3 GEMM mode (ppasr_set_gemm_mode,
-NOTES 9.8) -- the same fixtures, the same 1e-3 / greedy-id criteria."""
+NOTES 9.8) -- the same fixtures, the frozen mode's own 1e-3 and the same greedy-id criteria."""
 import os
 
 import numpy as np
@@ -15,10 +15,11 @@ import pytest
 import torch
 
 import ref_cases as rc
+from numerics import F32_BUDGET, F32_BUDGET_DS2
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-TOL = 1e-3
+TOL = {"f32": F32_BUDGET, "f16x3": 1e-3}  # per GEMM mode: the opt-in fp16 x 3 mode keeps its 1e-3 (out of scope)
 
 
 @pytest.fixture(scope="module")
@@ -89,7 +90,7 @@ def test_former_batched_matches_reference_source(ref, name, gemm):
     torch.cuda.synchronize()
     e_l, e_p = _rel(logits.cpu().numpy(), ref[f"{name}/logits"]), _rel(probs.cpu().numpy(), ref[f"{name}/probs"])
     print(f"{name} [{gemm}]: logits {e_l:.2e} probs {e_p:.2e}")
-    assert e_l < TOL and e_p < TOL
+    assert e_l < TOL[gemm] and e_p < TOL[gemm]
     got, want = probs.cpu().numpy().argmax(-1), ref[f"{name}/probs"].argmax(-1)
     if gemm == "f32":
         assert np.array_equal(got, want)
@@ -119,7 +120,7 @@ def test_former_chunks_match_reference_source(ref, name, required, gemm):
     e_a = _rel(att.cpu().numpy(), ref[k + "/att"]) if ref[k + "/att"].size else 0.0
     e_c = _rel(cnn.cpu().numpy(), ref[k + "/cnn"]) if ref[k + "/cnn"].size else 0.0  # (use_cnn_module=False: empty)
     print(f"{k} [{gemm}]: probs {e_p:.2e} att {e_a:.2e} cnn {e_c:.2e}")
-    assert e_p < TOL and e_a < TOL and e_c < TOL
+    assert e_p < TOL[gemm] and e_a < TOL[gemm] and e_c < TOL[gemm]
 
 
 @pytest.mark.parametrize("name", DS2)
@@ -131,7 +132,7 @@ def test_ds2_matches_reference_source(ref, name):
     torch.cuda.synchronize()
     e = _rel(probs.cpu().numpy(), ref[f"{name}/probs"])
     print(f"{name}: probs {e:.2e}")
-    assert e < TOL
+    assert e < F32_BUDGET_DS2
     assert np.array_equal(probs.cpu().numpy().argmax(-1), ref[f"{name}/probs"].argmax(-1))
     if case["chunk_frames"]:
         xc = rc.chunk_features(case)
@@ -146,9 +147,9 @@ def test_ds2_matches_reference_source(ref, name):
         e_p = _rel(np.concatenate(outs, 1), ref[f"{name}/chunk/probs"])
         e_h = _rel(h.cpu().numpy(), ref[f"{name}/chunk/h"])
         print(f"{name}/chunk: probs {e_p:.2e} h {e_h:.2e}")
-        assert e_p < TOL and e_h < TOL
+        assert e_p < F32_BUDGET_DS2 and e_h < F32_BUDGET_DS2
         if not case["kw"].get("use_gru"):
-            assert _rel(c.cpu().numpy(), ref[f"{name}/chunk/c"]) < TOL
+            assert _rel(c.cpu().numpy(), ref[f"{name}/chunk/c"]) < F32_BUDGET_DS2
 
 
 # ---- BASELINE.json configs at full size ------------------------------------------------------------------------------
@@ -212,7 +213,7 @@ def test_cfg1_deepspeech2_full_size_matches_reference_source(ref_full):
     torch.cuda.synchronize()
     assert tuple(probs.shape) == (1, 123, 4233)
     e_p, e_m = _check_probs_against_summary(probs.cpu().numpy()[0], ref_full, "cfg1", "cfg1")
-    assert e_p < TOL and e_m < TOL
+    assert e_p < F32_BUDGET_DS2 and e_m < F32_BUDGET_DS2
     tokens, n, _, _, _ = greedy_decode_ids(probs)
     rid = ref_full["cfg1/ids"][0]
     if (ref_full["cfg1/margin"][0] > 1e-3).all():
@@ -238,9 +239,9 @@ def test_cfg2_all_utterances_logits_and_tokens(ref_full, gemm):
                                            ref_full["cfg2/sampled"].reshape(B * Tp, -1), cols, f"cfg2 [{gemm}]",
                                            MEASURED_ERR_MODE[gemm])
     print(f"cfg2: sampled logits {e_s:.2e} lse {e_z:.2e} near-ties {near}/{B * Tp}")
-    assert e_s < TOL and e_z < TOL
+    assert e_s < TOL[gemm] and e_z < TOL[gemm]
     e_m = float(np.abs(probs.cpu().numpy().max(-1) - ref_full["cfg2/maxprob"]).max())
-    assert e_m < TOL
+    assert e_m < TOL[gemm]
     # fused greedy tokens of EVERY utterance == collapse of the HIP path's own frame ids (the fused route and the
     # materialised logits agree), and == collapse of the reference's frame ids wherever no frame of the utterance
     # differed above (near-tie utterances included: their ids were just compared frame by frame)
@@ -280,7 +281,7 @@ def test_cfg4_efficient_conformer_beam_all_utterances(ref_full, gemm):
                                       ref_full["cfg4/sampled"].reshape(B * Tp, -1), ref_full["cfg4/cols"], f"cfg4 [{gemm}]",
                                       MEASURED_ERR_MODE[gemm])
     print(f"cfg4: sampled logits {e_s:.2e} lse {e_z:.2e} near-ties {near}/{B * Tp}")
-    assert e_s < TOL and e_z < TOL
+    assert e_s < TOL[gemm] and e_z < TOL[gemm]
     toks, n, _, _ = beam_search_ids(probs, beam_size=rc.BEAM["beam_size"], cutoff_prob=rc.BEAM["cutoff_prob"],
                                     cutoff_top_n=rc.BEAM["cutoff_top_n"])
     toks, n = toks[:, 0].cpu().numpy(), n[:, 0].cpu().numpy()
@@ -347,7 +348,7 @@ def test_cfg5_squeezeformer_ragged_beam(ref_full, route, gemm):
                                        ref_full[f"{key}/sampled/{i}"], cols, f"{key}[{i}] [{gemm}]", MEASURED_ERR_MODE[gemm])
         worst = max(worst, e_s, e_z)
     print(f"cfg5/{route}: worst rel err {worst:.2e}")
-    assert worst < TOL
+    assert worst < TOL[gemm]
     if route == "buckets":
         for i in range(B):
             n = ref_full[f"cfg5/ids/{i}"].shape[0]

@@ -8,6 +8,7 @@ import torch
 
 from ppasr_amd.utils.synth import (conformer_state_dict, deepspeech2_state_dict, efficient_conformer_state_dict,
                                    squeezeformer_state_dict, synth_features)
+from numerics import F32_BUDGET, F32_BUDGET_DS2
 
 pytestmark = pytest.mark.gpu
 
@@ -90,7 +91,7 @@ def test_squeezeformer_with_15_tap_conv_modules(mode):
     torch.cuda.synchronize()
     e = _rel(logits.cpu().numpy(), ref.numpy())
     print(f"squeezeformer, 15 taps, {mode}: logits {e:.2e}")
-    assert e < 1e-3
+    assert e < F32_BUDGET
 
 
 @pytest.mark.parametrize("ks", [31, 15])
@@ -111,7 +112,7 @@ def test_squeezeformer_utterances_of_three_frames(ks):
         x, la, return_logits=True)
     torch.cuda.synchronize()
     assert tuple(logits.shape) == tuple(ref.shape) and logits.shape[1] == 3
-    assert _rel(logits.cpu().numpy(), ref.numpy()) < 1e-3
+    assert _rel(logits.cpu().numpy(), ref.numpy()) < F32_BUDGET
 
 
 def test_gru_single_utterance_step_kernel():
@@ -130,8 +131,8 @@ def test_gru_single_utterance_step_kernel():
         torch.cuda.synchronize()
         rp, rl, rh, _rc = DeepSpeech2Oracle(sd, L, H, streaming, use_gru=True).forward(x, lens)
         assert out_lens.cpu().tolist() == rl.tolist()
-        assert _rel(probs.cpu().numpy(), rp.numpy()) < 1e-3
-        assert _rel(fh.cpu().numpy(), rh.numpy()) < 1e-3
+        assert _rel(probs.cpu().numpy(), rp.numpy()) < F32_BUDGET_DS2
+        assert _rel(fh.cpu().numpy(), rh.numpy()) < F32_BUDGET_DS2
 
 
 def test_probabilities_of_a_vocabulary_beyond_5120_characters():
@@ -148,5 +149,5 @@ def test_probabilities_of_a_vocabulary_beyond_5120_characters():
     got = model.get_encoder_out(x, lens).cpu().numpy()
     want = ConformerOracle(sd, num_blocks=L).get_encoder_out(x, lens).numpy()
     assert got.shape == want.shape
-    assert _rel(got, want) < 1e-3
+    assert _rel(got, want) < F32_BUDGET
     assert np.abs(got.sum(-1) - 1.0).max() < 1e-5

@@ -8,9 +8,10 @@ import torch
 from oracle.efficient_conformer_oracle import EfficientConformerOracle
 from oracle.squeezeformer_oracle import SqueezeformerOracle
 from ppasr_amd.utils.synth import efficient_conformer_state_dict, squeezeformer_state_dict, synth_features
+from numerics import F32_BUDGET
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-3
+TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
 
 
 def _rel(a, b):

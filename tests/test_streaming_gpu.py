@@ -7,9 +7,10 @@ import torch
 
 from oracle.conformer_oracle import ConformerOracle
 from ppasr_amd.utils.synth import conformer_state_dict, synth_features
+from numerics import F32_BUDGET
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-3
+TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
 
 
 def _rel(a, b):
