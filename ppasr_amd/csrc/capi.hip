@@ -1170,9 +1170,8 @@ ppasr_status ppasr_ctc_beam_search_ws(const float* probs, const int32_t* frame_l
   }
   ppasr_status s = beam_config(V, beam_size, cutoff_prob, cutoff_top_n, blank, nbest, max_tokens, &c);
   if (s != PPASR_OK) return s;
+  c.node_table = lm && c.lm.word_based;
   {
-    const char* e = getenv("PPASR_BEAM_NODE_TABLE");
-    c.node_table = e ? (atoi(e) != 0) : (lm && c.lm.word_based);
     const char* f = getenv("PPASR_BEAM_FAST");  // (read per call: the tests run both selections in one process)
     c.fast_path = f ? (atoi(f) != 0) : 1;
   }

@@ -250,10 +250,8 @@ extern "C" ppasr_status ppasr_ds2_encode(ppasr_handle h, const float* feats, con
   //  projections then run on the step kernel's 32-row tiles instead of the dense GEMM; measured, 5 x 1024 LSTM, 5 s
   //  utterances: B = 32 6.6 ms against 9.2 per-step, B = 64 11.4 against 11.2, B = 128 21.9 against 21.0)
   // (round 4: a workgroup of the wavefront kernel takes up to 128 utterances -- 1 / 2 / 4 row tiles -- and streams its gate
-  //  columns' weights once for all of them, so the wavefront wins at every batch size; nn.GRU stacks take it too.
-  //  PPASR_DS2_WAVE_MAX_B: the per-step route above that batch size, for A/B measurements)
-  static const int wave_max_b = getenv("PPASR_DS2_WAVE_MAX_B") ? atoi(getenv("PPASR_DS2_WAVE_MAX_B")) : (1 << 30);
-  if (W.wave_tab && dirs == 1 && Tp > 0 && B >= 4 && B <= wave_max_b) {
+  //  columns' weights once for all of them, so the wavefront wins at every batch size; nn.GRU stacks take it too)
+  if (W.wave_tab && dirs == 1 && Tp > 0 && B >= 4) {
     // ---- unidirectional stack: wavefront over (layer, time), Tp + L - 1 dependent launches (k_lstm_wave) ----
     const int L = W.n_layers;
     const Ds2LayerW& L0 = h->ds2_layers[0];

@@ -474,7 +474,6 @@ __global__ void k_g_kv_append(const float* __restrict__ qkv, float* __restrict__
   vc[i] = qkv[row * 3 * D + 2 * D + c];
 }
 
-inline bool fused_ffn512() { return true; }  // width 512: the fused feed-forward kernels (other widths: LayerNorm + two GEMM launches)
 inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
 inline dim3 blocks(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
@@ -585,9 +584,8 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
     return e;
   };
   // PositionwiseFeedForward (positionwise.py:32-39) inside the layer's residual (encoder.py:380-386 / 411-417)
-  const bool fused_ffn = fused_ffn512();
   auto ffn = [&](const float* lg, const float* lb, const f32x4* w1, const float* b1, const f32x4* w2, const float* b2, float scale) {
-    if (fused_ffn && D == kD512) {  // one launch, hidden activations in LDS
+    if (D == kD512) {  // one launch, hidden activations in LDS (other widths: LayerNorm + two GEMM launches)
       PPASR_LAUNCH(k_g_ffn512, dim3((M + kRows - 1) / kRows), dim3(kThreads), kLdsFfn512, st, x, x, o.post_norm ? nullptr : lg,
                    o.post_norm ? nullptr : lb, w1, b1, w2, b2, scale, o.act, M, H / 256, ps);
       if (o.post_norm) ln(x, x, lg, lb, 1e-5f, kActNone, false, M);
@@ -613,7 +611,7 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
     // ---- (Rel)MultiHeadedAttention (attention.py:123-262) ----
     {
       const float* in = x;
-      if (fused_ffn && D == kD512 && !o.concat_after) {  // LayerNorm + QKV in one launch
+      if (D == kD512 && !o.concat_after) {  // LayerNorm + QKV in one launch
         PPASR_LAUNCH(k_g_proj512<false>, dim3((M + kRows - 1) / kRows), dim3(kThreads), kLdsProj512, st, x, big, 3 * D,
                      o.post_norm ? nullptr : L.ln_mha_g, o.post_norm ? nullptr : L.ln_mha_b, 1e-5f, (const int64_t*)nullptr, Tp, mul,
                      L.wqkv, L.bqkv, 3 * D / 32 / kWaves, M, ps);
@@ -659,7 +657,7 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
       const bool stride2 = eff && ((eff_stride_mask(h->desc) >> i) & 1u);
       float* a_new = a + (size_t)lo_s * D;
       const int rows = lo_s + M;
-      if (fused_ffn && D == kD512 && lo_s == 0) {  // (LayerNorm) + pad mask + pointwise_conv1 + GLU in one launch
+      if (D == kD512 && lo_s == 0) {  // (LayerNorm) + pad mask + pointwise_conv1 + GLU in one launch
         PPASR_LAUNCH(k_g_proj512<true>, dim3((M + kRows - 1) / kRows), dim3(kThreads), kLdsProj512, st, x, g, D,
                      o.post_norm ? nullptr : L.ln_conv_g, o.post_norm ? nullptr : L.ln_conv_b, 1e-5f, lens, Tp, mul, L.pw1,
                      L.pw1_b, 2, M, ps);
@@ -894,7 +892,7 @@ ppasr_status sq_run(ppasr_model_s* h, const float* feats, const int64_t* lens, i
     if (pre) {
       ln(x, y, W.ln1_g, W.ln1_b, 1e-5f, kActNone, false, Mi, Ti, mul);
       dense(y, D, W.wqkv, W.bqkv, big, Mi, D, 3 * D, 3 * D, 3 * D, st, 1.0f, plain_epi());
-    } else if (fused_ffn512() && D == kD512)
+    } else if (D == kD512)
       PPASR_LAUNCH(k_g_proj512<false>, dim3((Mi + kRows - 1) / kRows), dim3(kThreads), kLdsProj512, st, x, big, 3 * D,
                    (const float*)nullptr, (const float*)nullptr, 1e-5f, (const int64_t*)nullptr, Ti, mul, W.wqkv, W.bqkv,
                    3 * D / 32 / kWaves, Mi, ps);
@@ -933,7 +931,7 @@ ppasr_status sq_run(ppasr_model_s* h, const float* feats, const int64_t* lens, i
         dense(big, H, w2, b2, x, Mi, H, D, D, D, st, 1.0f, res_epi(false));
         return;
       }
-      if (fused_ffn512() && D == kD512) {
+      if (D == kD512) {
         PPASR_LAUNCH(k_g_ffn512, dim3((Mi + kRows - 1) / kRows), dim3(kThreads), kLdsFfn512, st, x, x, (const float*)nullptr,
                      (const float*)nullptr, w1, b1, w2, b2, 1.0f, h->gen.act, Mi, H / 256, ps);
         return;
@@ -949,7 +947,7 @@ ppasr_status sq_run(ppasr_model_s* h, const float* feats, const int64_t* lens, i
       const int rows = lo_s + Mi;
       if (pre) ln(x, y, W.ln3_g, W.ln3_b, 1e-5f, kActNone, false, Mi, Ti, mul);
       const float* cin = pre ? y : x;  // the conv module's input
-      if (!pre && fused_ffn512() && D == kD512 && lo_s == 0) {  // ada scale / bias + pad mask + pointwise_conv1 + GLU in one launch
+      if (!pre && D == kD512 && lo_s == 0) {  // ada scale / bias + pad mask + pointwise_conv1 + GLU in one launch
         PPASR_LAUNCH(k_g_proj512<true>, dim3((Mi + kRows - 1) / kRows), dim3(kThreads), kLdsProj512, st, x, g, D, W.cm_scale,
                      W.cm_bias, -1.0f, lens, Ti, mul, W.pw1_raw, W.pw1_b_raw, 2, Mi, ps);
       } else {

@@ -211,7 +211,6 @@ struct ppasr_stream_s {
   float* xh_hist;   // [L][lo][D]  conv-module input history
   float* g_hist;    // [L][lo][256] GLU(pointwise_conv1(history)) of every layer, recomputed at the start of each chunk (fused route)
   HistLayer* hist_tab;  // device [L]: per-layer pointwise_conv1 weights / history rows for that launch (fused route)
-  int* ticket = nullptr;  // device [16], zero between launches: arrival counters of the feed-forward slices that join in-kernel
 };
 
 // the reference's shape arithmetic for one chunk (capi_stream.hip: plan_chunk)
@@ -238,7 +237,7 @@ int wide_slices_for(const ppasr_model_s* m, int M, int units);  // embed K chunk
 // padded count decides.
 int row_block_for(const ppasr_model_s* m, int B, int Tcur, int mul, int slack, bool skip);
 bool block_tables_enabled();  // active-block lists for ragged layer kernels (PPASR_BLOCK_TABLE=0: padded grids; A/B switch)
-// the 4x front end as one launch (front_fused.hip)?  ppasr_set_front_fused, then PPASR_CONV12=0 (A/B switch)
+// the 4x front end as one launch (front_fused.hip)?  ppasr_set_front_fused
 bool conv12_enabled(const ppasr_model_s* m);
 ppasr::LayerW sq_conv_view(const ppasr::SqLayerW& W);  // capi_squeezeformer.hip
 

@@ -149,7 +149,7 @@ ppasr_status conformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* xa, f
     } else if (S > 1) {
       flush(Ti);
       launch_ffn_split(xa, L.ln_mac_g, L.ln_mac_b, Lk.ffm_w1, L.ffm_b1, Lk.ffm_w2, L.ffm_b2, 0.5f, nullptr, nullptr, partial, xb,
-                       Ti, n_chunks, S, st, PadSkip{}, false, h3, s->ticket);
+                       Ti, n_chunks, S, st, PadSkip{}, false, h3);
       launch_ln_qkv(xb, qkv, Lk, Ti, st, PadSkip{}, kc + (size_t)n_cache * kD, vc + (size_t)n_cache * kD, h3);
     } else {
       flush(Ti);
@@ -170,7 +170,7 @@ ppasr_status conformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* xa, f
       if (Ss > 1) {  // one row block: the conv half of the stride layer alone, its feed-forward module over the slices
         launch_conv_ffn_stride(g, gh, xc, xa, Lk, nullptr, 1, Ti, Ts, n_chunks, h->layer_ks[i], mul * 2, st, PadSkip{}, true, h3, ctx);
         launch_ffn_split(ctx, L.ln_ff_g, L.ln_ff_b, Lk.ff_w1, L.ff_b1, Lk.ff_w2, L.ff_b2, 0.5f, L.ln_fin_g, L.ln_fin_b, partial, xa, Ts,
-                         n_chunks, Ss, st, PadSkip{}, false, h3, s->ticket);
+                         n_chunks, Ss, st, PadSkip{}, false, h3);
       } else {
         launch_conv_ffn_stride(g, gh, xc, xa, Lk, nullptr, 1, Ti, Ts, n_chunks, h->layer_ks[i], mul * 2, st, PadSkip{}, true, h3);
       }
@@ -188,7 +188,7 @@ ppasr_status conformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* xa, f
       } else if (S > 1) {
         launch_conv_pre(g, gh, xc, ctx, Lk, nullptr, Ti, Ti, h->layer_ks[i], mul, st, true, PadSkip{}, h3);
         launch_ffn_split(ctx, L.ln_ff_g, L.ln_ff_b, Lk.ff_w1, L.ff_b1, Lk.ff_w2, L.ff_b2, 0.5f, L.ln_fin_g, L.ln_fin_b, partial,
-                         xa, Ti, n_chunks, S, st, PadSkip{}, false, h3, s->ticket);
+                         xa, Ti, n_chunks, S, st, PadSkip{}, false, h3);
       } else {
         launch_conv_ffn(g, gh, xc, xa, L, nullptr, Ti, Ti, n_chunks, h->layer_ks[i], mul, nullptr, nullptr, nullptr, st);
       }
@@ -245,7 +245,7 @@ ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* x
     float* xh = s->xh_hist + (size_t)i * s->lo * kD;
     const int S = ffn_split_for(h, Ti);  // one row block: split route (see squeezeformer_encode)
     const bool h3s = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty();  // (the FFN slices in the mode)
-    const bool r16 = S > 1 && !h3s && Ti <= split_rows16_max();
+    const bool r16 = S > 1 && !h3s && Ti <= kSplitRows16Max;
     if (!have_qkv) {
       if (r16) {
         launch_ln_qkv(x, qkv, qkv_view(W), Ti, st, PadSkip{}, kc + (size_t)n_cache * kD, vc + (size_t)n_cache * kD, false);
@@ -273,7 +273,7 @@ ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* x
         launch_sq_oproj(ctx, x, other, W, Ti, st);
       }
       launch_ffn_split(other, nullptr, nullptr, Ws.ff1_w1, W.ff1_b1, Ws.ff1_w2, W.ff1_b2, 1.0f, W.ln2_g, W.ln2_b, partial, xc,
-                       Ti, n_chunks, S, st, PadSkip{}, false, h3s, s->ticket);
+                       Ti, n_chunks, S, st, PadSkip{}, false, h3s);
       if (r16 && KS - 1 <= 30) {
         LayerW vp{};
         vp.pw1 = W.pw1; vp.pw1_b = W.pw1_b;
@@ -284,7 +284,7 @@ ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* x
       }
       launch_conv_pre(g, gh, xc, ctx, sq_conv_view(W), nullptr, Ti, Ti, KS, mul, st);
       launch_ffn_split(ctx, W.ln3_g, W.ln3_b, Ws.ff2_w1, W.ff2_b1, Ws.ff2_w2, W.ff2_b2, 1.0f, W.ln4_g, W.ln4_b, partial, other,
-                       Ti, n_chunks, S, st, PadSkip{}, /*residual_is_normed=*/true, h3s, s->ticket);
+                       Ti, n_chunks, S, st, PadSkip{}, /*residual_is_normed=*/true, h3s);
       if (Wn && r16) {  // (fuse_next: layer i + 1 runs at this layer's rate -- same rows, same cache length)
         float* kcn = s->kc + (size_t)(i + 1) * s->cap * kD;
         float* vcn = s->vc + (size_t)(i + 1) * s->cap * kD;
@@ -335,12 +335,9 @@ ppasr_status ppasr_stream_create(ppasr_handle h, ppasr_stream* out) {
   hipError_t e4 = hipMalloc(reinterpret_cast<void**>(&s->g_hist), L * lo_alloc * D * sizeof(float));
   s->hist_tab = nullptr;
   if (e4 == hipSuccess) e4 = hipMalloc(reinterpret_cast<void**>(&s->hist_tab), L * sizeof(HistLayer));
-  if (e4 == hipSuccess) e4 = hipMalloc(reinterpret_cast<void**>(&s->ticket), 16 * sizeof(int));
-  if (e4 == hipSuccess) e4 = hipMemset(s->ticket, 0, 16 * sizeof(int));
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
     (void)hipFree(s->kc); (void)hipFree(s->vc); (void)hipFree(s->xh_hist); (void)hipFree(s->g_hist);
     (void)hipFree(s->hist_tab);
-    (void)hipFree(s->ticket);
     delete s;
     return fail(PPASR_EHIP, "hipMalloc failed for the stream caches");
   }
@@ -367,7 +364,6 @@ ppasr_status ppasr_stream_destroy(ppasr_stream s) {
   if (!s) return PPASR_OK;
   (void)hipFree(s->kc); (void)hipFree(s->vc); (void)hipFree(s->xh_hist); (void)hipFree(s->g_hist);
   (void)hipFree(s->hist_tab);
-  (void)hipFree(s->ticket);
   delete s;
   return PPASR_OK;
 }

@@ -216,7 +216,7 @@ void launch_conv_pre(const float* g, const float* g_hist, const float* x2, float
 void launch_ffn_split(const float* x, const float* ln_g, const float* ln_b, const f32x4* w1, const float* b1,
                       const f32x4* w2, const float* b2, float scale, const float* out_ln_g, const float* out_ln_b,
                       float* partial, float* out, int M, int n_chunks, int S, hipStream_t st, const PadSkip& ps = PadSkip{},
-                      bool residual_is_normed = false, bool h3 = false, int* ticket = nullptr);  // h3: w1 / w2 are the re-packed weights
+                      bool residual_is_normed = false, bool h3 = false);  // h3: w1 / w2 are the re-packed weights
 // kc / vc: write the K / V thirds to these cache rows instead of qkv (single-session streaming)
 // ---- one streaming session's chunk (<= 16 rows): feed-forward slices whose partial tiles are joined by their CONSUMER ----
 // JoinIn describes a pending join  out = LN?(x + scale (sum_s partial[s] + b2))  of S partial tiles [S][M][256]: the launch
@@ -231,8 +231,11 @@ struct JoinIn {
   const float *ln_g = nullptr, *ln_b = nullptr;    // LayerNorm behind the residual sum (or nullptr)
   float* out = nullptr;
 };
-int split_rows16_max();  // rows up to which the split route runs its 16-row forms (split_route_kernels.hip)
-// true iff launch_ffn_half16 / launch_join_ln_qkv16 serve this shape (M rows, S = n_chunks slices; PPASR_* switches on)
+// Rows up to which the split route runs its 16-row forms.  512 rows = 32 blocks x 8 feed-forward slices = one round of 256
+// half-as-long workgroups.  Encoder latency of ONE utterance, same box, 16-row forms up to 16 rows (a streaming chunk only)
+// / up to 512: 5 s 1.64 / 1.23 ms, 10 s 1.69 / 1.28 ms, 20 s 1.85 / 1.47 ms (tools/experiments/r06/single_utt.py).
+constexpr int kSplitRows16Max = 512;
+// true iff launch_ffn_half16 / launch_join_ln_qkv16 serve this shape (M rows, S = n_chunks slices)
 bool ffn_half16_route(int M, int S, int n_chunks);
 // partial[2 S][M][256] <- the 2 S half-chunk slices of FFN(LN(x_in)), x_in = x or the join `jn` (then jn.out is written)
 void launch_ffn_half16(const float* x, const JoinIn& jn, const float* ln_g, const float* ln_b, const f32x4* w1, const float* b1,

@@ -42,9 +42,9 @@ struct BeamConfig {
 // recognised as its child -- upstream's trie keeps such nodes (PathTrie::remove only deletes childless nodes) and revives
 // them in get_path_trie, with the dictionary state they had; without the table the re-created prefix spawns a duplicate
 // of its own descendant.  It costs two dependent HBM round trips per frame (look-up, insertion), so it is used where
-// such revivals are frequent -- word-based scorers, whose dictionary funnels the beam into few spellings -- and on request
-// (BeamConfig::node_table; PPASR_BEAM_NODE_TABLE=1); otherwise every new prefix gets a fresh id (DOCUMENTED DEVIATION: in
-// the rare revival case the re-created prefix and the old descendant's line split their probability mass).
+// such revivals are frequent -- word-based scorers, whose dictionary funnels the beam into few spellings
+// (BeamConfig::node_table); otherwise every new prefix gets a fresh id (DOCUMENTED DEVIATION: in the rare revival case
+// the re-created prefix and the old descendant's line split their probability mass).
 __host__ __device__ inline size_t beam_fixed_words(int beam) { return ((size_t)2 + (size_t)kBeamStateArrays * beam + 1) & ~(size_t)1; }
 __host__ __device__ inline size_t beam_table_slots(int max_nodes) { return (size_t)2 * max_nodes; }
 constexpr int kArenaWords = 3;

@@ -1,7 +1,6 @@
 // split_route_kernels.hip -- the layer tail cut at its feed-forward modules for UNDER-FILLED grids (small batches,
 // half-rate layers, single streaming sessions).  (Split from conformer_kernels.hip in round 5.)
 #include <algorithm>
-#include <cstdlib>
 
 #include "conformer_kernels.h"
 #include "launch.h"
@@ -232,24 +231,11 @@ __global__ __launch_bounds__(kThreads) void k_ln_qkv(const float* __restrict__ x
 // GEMM unit is bound by one CU's matrix pipe (6.8 us for 32 rows x 256 x 256 in fp32) -- the 16-row unit takes half.
 // Round 6: the feed-forward slices and the Q / K / V thirds, 36 of a chunk's ~110 units.  Results agree with the 32-row
 // forms to the order of the sums inside a 16-wide k step.
-// In-kernel join (jn.ticket != nullptr; single stream handles): the S workgroups of a row block take a ticket when their
-// partial tile is in memory, and the LAST one to arrive runs k_ffn_join's row loop for the block -- no spinning (the others
-// have left), so nothing can deadlock; the counter goes back to 0 for the next launch.  One launch per feed-forward module
-// instead of two.
-struct FfnJoin {
-  const float* b2;
-  float scale;
-  const float *ln_g, *ln_b;  // LayerNorm behind the residual sum (or nullptr)
-  float* out;
-  const float *pre_g, *pre_b;  // the residual is LN_pre(x) (Squeezeformer's second module) or x
-  int* ticket;               // [row blocks] arrival counters, zero between launches
-};
 template <int R>
 __global__ __launch_bounds__(RBT<R>::THREADS) void k_ffn_part_t(const float* __restrict__ x, const float* __restrict__ ln_g,
                                                                 const float* __restrict__ ln_b, const f32x4* __restrict__ w1,
                                                                 const float* __restrict__ b1, const f32x4* __restrict__ w2,
-                                                                float* __restrict__ partial, int M, int n_total, PadSkip ps,
-                                                                FfnJoin jn) {
+                                                                float* __restrict__ partial, int M, int n_total, PadSkip ps) {
   using T = RBT<R>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int blk = pad_block_of(ps, T::ROWS, M);
@@ -273,32 +259,6 @@ __global__ __launch_bounds__(RBT<R>::THREADS) void k_ffn_part_t(const float* __r
 #pragma unroll
   for (int q = 0; q < T::NQ; ++q)
     if (L.row(q) < valid) *reinterpret_cast<f32x4*>(out + (size_t)(r0 + L.row(q)) * kD + L.col(q)) = T::quad(acc2, q);
-  if (!jn.ticket) return;
-  __shared__ int s_last;
-  __threadfence();  // this workgroup's partial tile is visible device-wide before its ticket is
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int S = (int)gridDim.y;
-    const int t = atomicAdd(&jn.ticket[blk], 1);
-    s_last = (t == S - 1) ? 1 : 0;
-    if (t == S - 1) jn.ticket[blk] = 0;  // (everyone has arrived: re-armed for the next launch on this stream)
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();  // (the other workgroups' tiles: no stale lines of this CU's vector cache)
-  const int S = (int)gridDim.y, lane = L.lane;
-  for (int row = r0 + L.wave; row < r0 + valid; row += T::WAVES) {  // k_ffn_join, one wave per row
-    f32x4 acc = *reinterpret_cast<const f32x4*>(partial + (size_t)row * kD + 4 * lane);
-    for (int sidx = 1; sidx < S; ++sidx)
-      acc += *reinterpret_cast<const f32x4*>(partial + ((size_t)sidx * M + row) * kD + 4 * lane);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(jn.b2 + 4 * lane);
-    f32x4 y = *reinterpret_cast<const f32x4*>(x + (size_t)row * kD + 4 * lane);
-    if (jn.pre_g) y = ln_row(y, jn.pre_g, jn.pre_b, lane);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = y[e] + jn.scale * (acc[e] + bv[e]);
-    if (jn.ln_g) y = ln_row(y, jn.ln_g, jn.ln_b, lane);
-    *reinterpret_cast<f32x4*>(jn.out + (size_t)row * kD + 4 * lane) = y;
-  }
 }
 
 template <int R>
@@ -481,25 +441,8 @@ constexpr size_t conv_cols16_lds() { return (size_t)(KS - 1 + 16 + KS + 16) * kL
 //  HIP streams the own-size allocation, 3 workgroups per CU, was 13 % slower per chunk round, same box)
 constexpr size_t kLdsFfnPart16 = kLdsExclusive, kLdsLnQkv16 = kLdsExclusive;
 static_assert(3 * 16 * kLda * sizeof(float) <= kLdsExclusive, "LDS of the 16-row feed-forward slice");
-// (up to split_rows16_max() rows -- streaming chunks, single utterances, small batches: the 16-row forms; PPASR_SPLIT_ROWS16=0
-//  switches them off)
-static bool ffn_half16_on() {  // (PPASR_FFN_HALF16=0: whole chunks per workgroup, the A/B knob of the measurement above)
-  static const bool on = !(getenv("PPASR_FFN_HALF16") && atoi(getenv("PPASR_FFN_HALF16")) == 0);
-  return on;
-}
-// Rows up to which the split route runs its 16-row forms (PPASR_SPLIT_ROWS16_MAX: tuning knob).  512 rows = 32 blocks x 8
-// feed-forward slices = one round of 256 half-as-long workgroups.  Encoder latency of ONE utterance, same box, 16-row forms up
-// to 16 rows (a streaming chunk only) / up to 512: 5 s 1.64 / 1.23 ms, 10 s 1.69 / 1.28 ms, 20 s 1.85 / 1.47 ms
-// (tools/experiments/r06/single_utt.py).
-int split_rows16_max() {
-  static const int m = [] {
-    if (getenv("PPASR_SPLIT_ROWS16") && atoi(getenv("PPASR_SPLIT_ROWS16")) == 0) return 0;
-    const char* e = getenv("PPASR_SPLIT_ROWS16_MAX");
-    return e ? atoi(e) : 512;
-  }();
-  return m;
-}
-static bool split_rows16(int M) { return M <= split_rows16_max(); }
+// (up to kSplitRows16Max rows -- streaming chunks, single utterances, small batches: the 16-row forms)
+static bool split_rows16(int M) { return M <= kSplitRows16Max; }
 
 constexpr size_t kLdsConvPre = 4 * kRows * kLda * sizeof(float);  // (the depthwise window uses the three buffers + halo)
 constexpr size_t kLdsFfnPart = 3 * kRows * kLda * sizeof(float);
@@ -548,29 +491,19 @@ void launch_conv_pre(const float* g, const float* g_hist, const float* x2, float
 void launch_ffn_split(const float* x, const float* ln_g, const float* ln_b, const f32x4* w1, const float* b1,
                       const f32x4* w2, const float* b2, float scale, const float* out_ln_g, const float* out_ln_b,
                       float* partial, float* out, int M, int n_chunks, int S, hipStream_t st, const PadSkip& ps,
-                      bool residual_is_normed, bool h3, int* ticket) {
+                      bool residual_is_normed, bool h3) {
   if (h3)  // (w1 / w2: the re-packed weights)
     PPASR_LAUNCH(k_ffn_part<true>, dim3((M + kRows - 1) / kRows, S), dim3(kThreads), kLdsFfnPart + kH3ExtraLds, st, x, ln_g, ln_b,
                  w1, b1, w2, partial, M, n_chunks, ps);
-  else if (split_rows16(M) && !ps.tab && S == n_chunks && ffn_half16_on() && ((M + 15) / 16) * 2 * S <= 256 &&
-           !(getenv("PPASR_STREAM_TICKET") && atoi(getenv("PPASR_STREAM_TICKET")) == 1)) {
+  else if (split_rows16(M) && !ps.tab && S == n_chunks && ((M + 15) / 16) * 2 * S <= 256) {
     // one chunk per workgroup already: cut the chunks in halves (k_ffn_half16), 2 S partial tiles
     PPASR_LAUNCH(k_ffn_half16, dim3((M + 15) / 16, 2 * S), dim3(kThreads), kLdsFfnPart16, st, x, ln_g, ln_b, w1, b1, w2, partial, M,
                  n_chunks, ps, JoinIn{});
     S *= 2;
-  } else if (split_rows16(M) && !ps.tab) {
-    // (out == x would let the joining workgroup overwrite rows another slice is still reading: two launches then)
-    // OPT-IN (PPASR_STREAM_TICKET=1): measured on one box, one 0.64 s chunk of one session 1.35 ms with the in-kernel join
-    // against 1.24 ms with the join as its own launch (the last slice's workgroup joins 16 rows x S partial tiles alone; the
-    // join kernel spreads them over 4 workgroups) -- four launches fewer per block, and slower.  32 sessions: 14.26 / 14.5 ms.
-    const char* tk = getenv("PPASR_STREAM_TICKET");
-    const bool join_in_kernel = tk && atoi(tk) == 1 && ticket != nullptr && out != x && (M + 15) / 16 <= 16;
+  } else if (split_rows16(M) && !ps.tab)
     PPASR_LAUNCH(k_ffn_part_t<16>, dim3((M + 15) / 16, S), dim3(kThreads), kLdsFfnPart16, st, x, ln_g, ln_b, w1, b1, w2, partial, M,
-                 n_chunks, ps,
-                 FfnJoin{b2, scale, out_ln_g, out_ln_b, out, residual_is_normed ? ln_g : nullptr, residual_is_normed ? ln_b : nullptr,
-                         join_in_kernel ? ticket : nullptr});
-    if (join_in_kernel) return;
-  } else
+                 n_chunks, ps);
+  else
     PPASR_LAUNCH(k_ffn_part<false>, dim3((M + kRows - 1) / kRows, S), dim3(kThreads), kLdsFfnPart, st, x, ln_g, ln_b, w1, b1,
                  w2, partial, M, n_chunks, ps);
   PPASR_LAUNCH(k_ffn_join, dim3((M + 3) / 4), dim3(256), 0, st, x, partial, S, b2, scale, out_ln_g, out_ln_b, out, M,
@@ -586,11 +519,7 @@ void launch_ln_qkv(const float* x1, float* qkv, const LayerW& w, int M, hipStrea
     PPASR_LAUNCH(k_ln_qkv<false>, dim3((M + kRows - 1) / kRows, 3), dim3(kThreads), kLdsLnQkv, st, x1, qkv, w, M, ps, kc, vc);
 }
 // ---- consumer-side joins of one streaming session's chunk (conformer_kernels.h JoinIn) ----
-bool ffn_half16_route(int M, int S, int n_chunks) {
-  static const bool fuse = !(getenv("PPASR_JOIN_FUSED") && atoi(getenv("PPASR_JOIN_FUSED")) == 0);  // (A/B switch)
-  return fuse && M <= 16 && S > 1 && S == n_chunks && split_rows16(M) && ffn_half16_on() &&
-         !(getenv("PPASR_STREAM_TICKET") && atoi(getenv("PPASR_STREAM_TICKET")) == 1);
-}
+bool ffn_half16_route(int M, int S, int n_chunks) { return M <= 16 && S > 1 && S == n_chunks && split_rows16(M); }
 void launch_ffn_half16(const float* x, const JoinIn& jn, const float* ln_g, const float* ln_b, const f32x4* w1, const float* b1,
                        const f32x4* w2, float* partial, int M, int n_chunks, hipStream_t st) {
   PPASR_LAUNCH(k_ffn_half16, dim3(1, 2 * n_chunks), dim3(kThreads), kLdsFfnPart16, st, x, ln_g, ln_b, w1, b1, w2, partial, M,

@@ -208,25 +208,19 @@ def _tied_probs(rng, T, V):
     return (w / w.sum(1, keepdims=True)).astype(np.float32)
 
 
-@pytest.mark.parametrize("T,V,beam,cutoff_prob,top_n", [
-    (249, 4233, 10, 0.99, 40),   # BASELINE configs[3] / [4]
-    (200, 500, 10, 0.99, 40),
-    (150, 90, 16, 0.999, 40),
-    (120, 64, 5, 0.99, 12),
-    (100, 300, 1, 0.99, 40),
-    (80, 50, 8, 1.0, 40),        # no pruning: every character of every frame
-    (60, 700, 13, 0.9, 7),
-])
-@pytest.mark.parametrize("kind", ["peaky", "flat", "tied"])
-def test_staircase_fast_path_is_bit_identical_to_the_general_selection(T, V, beam, cutoff_prob, top_n, kind):
+def _tie_probs(rng, T, V, levels=4):
+    """Probabilities drawn from a handful of exactly representable values: many hypotheses share a score exactly."""
+    vals = np.array([2.0 ** -(2 + i) for i in range(levels)], np.float32)
+    p = vals[rng.integers(0, levels, size=(T, V))].astype(np.float32)
+    p[:, 0] *= 2.0
+    return p / np.float32(V)  # (rows need not sum to one: the decoder takes the table as is)
+
+
+def _check_fast_path_against_general_selection(batch, lens, beam, cutoff_prob, top_n, with_oracle):
     """Same survivors, same order, same node ids: every n-best token sequence and every score bit for bit, with and without
     the fast path -- and the best path equal to the C oracle's."""
     from ppasr_amd.decoders.beam_search_decoder import beam_search_ids
-    lib = _oracle()
-    rng = np.random.Generator(np.random.PCG64(T * 11 + V + beam))
-    B = 4
-    batch = np.stack([_tied_probs(rng, T, V) if kind == "tied" else _probs(rng, T, V, kind) for _ in range(B)])
-    lens = np.array([T, T - 7, T // 2, 1], np.int32)
+    B = batch.shape[0]
     nbest = beam
     outs = []
     for on in (True, False):
@@ -243,13 +237,53 @@ def test_staircase_fast_path_is_bit_identical_to_the_general_selection(T, V, bea
                 continue
             assert np.array_equal(outs[0][0][b, r, :n], outs[1][0][b, r, :n]), (b, r)
             assert outs[0][2][b, r] == outs[1][2][b, r], (b, r)  # float64 scores: the same sums in the same order
+    if not with_oracle:  # (exact score ties at the cut: the oracle's container order decides there; only the two
+        return           #  selections of the kernel are compared on these tables)
+    lib = _oracle()
     tokens, ln, sc = outs[0]
-    if kind == "tied":  # (exact score ties at the cut: the oracle's container order decides there; only the two selections
-        return          #  of the kernel are compared on these tables)
     for b in range(B):
         ref = _oracle_decode(lib, batch[b, :lens[b]], beam, cutoff_prob, top_n, 0, 1)
         assert tokens[b, 0, :ln[b, 0]].tolist() == ref[0][0], b
         assert abs(sc[b, 0] - ref[0][1]) <= 1e-4 * max(1.0, abs(ref[0][1]))
+
+
+@pytest.mark.parametrize("T,V,beam,cutoff_prob,top_n", [
+    (249, 4233, 10, 0.99, 40),   # BASELINE configs[3] / [4]
+    (200, 500, 10, 0.99, 40),
+    (150, 90, 16, 0.999, 40),
+    (120, 64, 5, 0.99, 12),
+    (100, 300, 1, 0.99, 40),
+    (80, 50, 8, 1.0, 40),        # no pruning: every character of every frame
+    (60, 700, 13, 0.9, 7),
+])
+@pytest.mark.parametrize("kind", ["peaky", "flat", "tied"])
+def test_staircase_fast_path_is_bit_identical_to_the_general_selection(T, V, beam, cutoff_prob, top_n, kind):
+    rng = np.random.Generator(np.random.PCG64(T * 11 + V + beam))
+    B = 4
+    batch = np.stack([_tied_probs(rng, T, V) if kind == "tied" else _probs(rng, T, V, kind) for _ in range(B)])
+    lens = np.array([T, T - 7, T // 2, 1], np.int32)
+    _check_fast_path_against_general_selection(batch, lens, beam, cutoff_prob, top_n, with_oracle=kind != "tied")
+
+
+@pytest.mark.parametrize("T,V,beam,cutoff_prob,top_n,kind", [
+    (150, 500, 10, 0.99, 40, "peaky"),
+    (150, 4233, 10, 0.99, 40, "flat"),
+    (60, 300, 16, 0.99, 64, "flat"),
+    (60, 300, 1, 0.99, 40, "peaky"),
+    (60, 50, 2, 1.0, 40, "flat"),      # cutoff_prob 1: every character of a small vocabulary is a candidate
+    (80, 300, 5, 0.5, 3, "flat"),
+    (90, 200, 10, 0.99, 40, "ties"),
+    (90, 64, 16, 1.0, 64, "ties"),
+    (40, 30, 7, 1.0, 40, "ties"),
+])
+def test_staircase_fast_path_is_bit_identical_on_small_beams(T, V, beam, cutoff_prob, top_n, kind):
+    """The same check on small beams (<= 16, <= 64 candidates per frame): tables of exactly representable values that tie
+    many scores at the cut, and a batch that holds a 1-frame and a 0-frame utterance."""
+    rng = np.random.Generator(np.random.PCG64(T + 3 * V + 7 * beam + top_n))
+    B = 5
+    batch = np.stack([_tie_probs(rng, T, V) if kind == "ties" else _probs(rng, T, V, kind) for _ in range(B)])
+    lens = np.array([T, T - 1, max(T // 2, 1), 1, 0], np.int32)
+    _check_fast_path_against_general_selection(batch, lens, beam, cutoff_prob, top_n, with_oracle=kind != "ties")
 
 
 def test_staircase_fast_path_streaming_state_is_identical():
@@ -268,6 +302,28 @@ def test_staircase_fast_path_streaming_state_is_identical():
                 out.append(dec.decode_chunk(p[None, s0:s0 + 16], np.array([16])))
         res.append(out)
     assert res[0] == res[1]
+
+
+def test_batched_streaming_state_equals_one_shot():
+    """A batch of three decoded in 16-frame chunks through one _BeamState: the n-best tokens, lengths and scores of the
+    last chunk equal those of one call over the whole table."""
+    from ppasr_amd.decoders.beam_search_decoder import _BeamState, beam_search_ids
+    rng = np.random.Generator(np.random.PCG64(77))
+    T, V, beam, B = 96, 400, 10, 3
+    batch = np.stack([_probs(rng, T, V, "peaky") for _ in range(B)])
+    p = torch.from_numpy(batch).cuda()
+    one = beam_search_ids(p, beam, 0.99, 40, 0, nbest=2)[:3]
+    st = _BeamState(B, T, beam, p.device)
+    for lo in range(0, T, 16):
+        chunked = beam_search_ids(p[:, lo:lo + 16].contiguous(), beam, 0.99, 40, 0, nbest=2, state=st)[:3]
+    torch.cuda.synchronize()
+    L = one[0].shape[2]
+    for a, b in zip(one, chunked):
+        a, b = a.cpu().numpy(), b.cpu().numpy()
+        if a.ndim == 3:
+            b = b[:, :, :L] if b.shape[2] >= L else b
+            a = a[:, :, :b.shape[2]]
+        assert np.array_equal(a, b)
 
 
 @pytest.mark.parametrize("beam,V,T", [(10, 300, 120), (16, 90, 100), (100, 500, 80), (300, 4233, 60)])

@@ -53,6 +53,12 @@ def _oracle_lm_decode(lib, chunks, V, beam, cutoff_prob, top_n, lm, alpha, beta,
     (30, 120, 300, 3, 2.2, 4.3, "flat"),     # the reference's default beam_size
     (20, 4233, 300, 3, 2.2, 4.3, "flat"),    # ... with the full vocabulary (LDS budget of beam x candidates)
     (1, 120, 5, 3, 2.2, 4.3, "flat"),
+    (70, 200, 10, 3, 2.2, 4.3, "flat"),      # small beams (<= 16, <= 40 candidates per frame)
+    (70, 200, 10, 3, 2.2, 4.3, "peaky"),
+    (70, 200, 16, 2, 1.9, 0.3, "flat"),
+    (70, 200, 16, 2, 1.9, 0.3, "peaky"),
+    (70, 200, 8, 5, 0.5, -1.5, "flat"),
+    (70, 200, 8, 5, 0.5, -1.5, "peaky"),
 ])
 def test_beam_search_with_scorer_matches_c_oracle(tmp_path, T, V, beam, order, alpha, beta, kind):
     from ppasr_amd.decoders.beam_search_decoder import Scorer, beam_search_ids
