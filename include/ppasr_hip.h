@@ -418,14 +418,21 @@ PPASR_API ppasr_status ppasr_ctc_collapse(const int32_t* frame_argmax, const flo
                                 void* stream);
 
 /* ---- multi-session streaming (no reference counterpart: PPASR streams one session per call) -----------------------
- * A group of Conformer sessions whose K/V and conv caches live in one allocation; ppasr_encode_chunk_group advances
- * any subset of them by one chunk with ONE set of launches (rows of all listed sessions stacked).  Every session
+ * A group of Conformer (or Squeezeformer) sessions whose K/V and conv caches live in one allocation;
+ * ppasr_encode_chunk_group advances any subset of them by one chunk with ONE set of launches (rows of all listed sessions
+ * stacked).  Every session
  * follows the single-session arithmetic of ppasr_encode_chunk with required_cache_size < 0 (full history, what
  * PPASRPredictor.predict_stream passes, predict.py:306-307).  max_frames caps the per-session cache (<= max_len).
  *   sessions_host [n] distinct slot indices; feats [n][T][F]; outputs by list position: probs [n][c][V] or NULL,
  *   frame_argmax / frame_maxprob [n][c] or NULL. */
 typedef struct ppasr_stream_group_s* ppasr_stream_group;
 PPASR_API ppasr_status ppasr_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out);
+/* The same kind of group for a streaming (causal) Squeezeformer handle on the conv2d front end and the fused 256-wide
+ * route (conv kernel 31 or 15); PPASR_EUNSUPPORTED for any other handle.  ppasr_stream_group_create stays Conformer-only.
+ * Each session keeps its full-rate and half-rate caches (the reference's trim of the reduced cache, as on a stream
+ * handle) and ppasr_encode_chunk_group refuses, with PPASR_EINVAL and no session changed, a round in which any listed
+ * session would leave an odd cache length or exceed max_len / max_frames.  The other group calls take it unchanged. */
+PPASR_API ppasr_status ppasr_sq_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out);
 PPASR_API ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g);
 PPASR_API ppasr_status ppasr_stream_group_reset(ppasr_stream_group g, int session /* < 0: all */, void* stream);
 PPASR_API int          ppasr_stream_group_offset(ppasr_stream_group g, int session);

@@ -133,6 +133,7 @@ SYMBOLS = [
                                                 _vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_double,
                                                 ctypes.c_double, _vp]),
     ("ppasr_stream_group_create", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    ("ppasr_sq_stream_group_create", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     ("ppasr_stream_group_destroy", ctypes.c_int, [_vp]),
     ("ppasr_stream_group_reset", ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     ("ppasr_stream_group_offset", ctypes.c_int, [_vp, ctypes.c_int]),

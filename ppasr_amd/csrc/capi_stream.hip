@@ -47,19 +47,21 @@ void history_glu_all(ppasr_stream_s* s, hipStream_t st) {
   launch_pw1_glu_layers(s->xh_hist, s->g_hist, s->hist_tab, s->m->desc.num_blocks, s->lo, st);
 }
 
-// the reference's shape arithmetic for one chunk
-ppasr_status plan_chunk(const ppasr_stream_s* s, int c, int required_cache_size, ChunkPlan* p) {
-  const ppasr_model_s* h = s->m;
+// the reference's shape arithmetic for one chunk of c frames on a session whose caches hold cache_t (full-rate layers) /
+// cache_r (half-rate layers) frames, `offset` frames emitted so far and room for `cap` keys per layer; shared by the
+// stream handles and the Squeezeformer session groups
+ppasr_status plan_chunk_for(const ppasr_model_s* h, int cache_t, int cache_r, int offset, int cap, int c,
+                            int required_cache_size, ChunkPlan* p) {
   p->c = c;
   p->c_r = ceil_div(c, 2);  // Conv1D(k=1, s=2) / stride-2 depthwise conv + ceil-mode AvgPool
-  p->T2 = s->cache_t + c;
-  const int pos_len_r = ceil_div(s->cache_t + c, 2);  // pos_emb[:, ::2]
+  p->T2 = cache_t + c;
+  const int pos_len_r = ceil_div(cache_t + c, 2);  // pos_emb[:, ::2]
   if (is_sq(h)) {
     // att_cache[i][:, :, ::2][:, :, :pos_len - xs_len] of a cache exported as repeat_interleave(...)[:max_att_len]
-    const int avail = ceil_div(std::min(2 * s->cache_r, s->cache_t), 2);
+    const int avail = ceil_div(std::min(2 * cache_r, cache_t), 2);
     p->used_r = std::min(avail, pos_len_r - p->c_r);
   } else {
-    p->used_r = s->cache_r;  // att_cache[i][:, :, ::2], no trim
+    p->used_r = cache_r;  // att_cache[i][:, :, ::2], no trim
   }
   p->T2_r = p->used_r + p->c_r;
   const bool has_half = is_sq(h) ? h->desc.reduce_idx >= 0 : (is_eff(h) && h->desc.stride_layer_idx >= 0);
@@ -70,12 +72,15 @@ ppasr_status plan_chunk(const ppasr_stream_s* s, int c, int required_cache_size,
   else if (required_cache_size == 0) p->ncs = p->T2;
   else p->ncs = std::max(p->T2 - required_cache_size, 0);
   // efficient_conformer/encoder.py:305: offset *= calculate_downsampling_factor(num_blocks + 1)
-  const int off = is_eff(h) && h->desc.stride_layer_idx >= 0 ? 2 * s->offset : s->offset;
-  p->pos0 = off - s->cache_t;
+  const int off = is_eff(h) && h->desc.stride_layer_idx >= 0 ? 2 * offset : offset;
+  p->pos0 = off - cache_t;
   if (p->pos0 < 0) return fail(PPASR_EINVAL, "offset smaller than the attention cache length");
   if (p->pos0 + p->T2 >= h->desc.max_len) return fail(PPASR_EINVAL, "offset + chunk exceeds the positional table (max_len)");
-  if (p->T2 > s->cap) return fail(PPASR_EINVAL, "attention cache capacity exceeded");
+  if (p->T2 > cap) return fail(PPASR_EINVAL, "attention cache capacity exceeded");
   return PPASR_OK;
+}
+ppasr_status plan_chunk(const ppasr_stream_s* s, int c, int required_cache_size, ChunkPlan* p) {
+  return plan_chunk_for(s->m, s->cache_t, s->cache_r, s->offset, s->cap, c, required_cache_size, p);
 }
 
 ppasr_status finish_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* shift_tmp, hipStream_t st) {
@@ -504,8 +509,8 @@ ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* att_cache, i
 }
 
 // =====================================================================================
-// Multi-session streaming: a group of Conformer sessions whose caches live in one allocation and advance with ONE set
-// of launches per chunk round (the rows of all active sessions are stacked: n x c frames -> ceil(n*c/32) row blocks
+// Multi-session streaming: a group of Conformer (ppasr_stream_group_create) or Squeezeformer (ppasr_sq_stream_group_create)
+// sessions whose caches live in one allocation and advance with ONE set of launches per chunk round (the rows of all active sessions are stacked: n x c frames -> ceil(n*c/32) row blocks
 // per kernel instead of one).  No reference counterpart: PPASR streams one session per call
 // (predict.py:232-337, forward_chunk asserts B = 1); each session here follows exactly the single-session arithmetic
 // (required_cache_size < 0: the full history is kept, what PPASRPredictor passes, predict.py:306-307).
@@ -513,59 +518,230 @@ ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* att_cache, i
 struct ppasr_stream_group_s {
   ppasr_model_s* m;
   int n_sessions, cap, lo;
+  bool sq;            // Squeezeformer group (ppasr_sq_stream_group_create): full- and half-rate layers
   float *kc, *vc;     // [n_sessions][L][cap][256]
   float* xh_hist;     // [n_sessions][L][lo][256]
+  HistLayer* hist_tab;  // Squeezeformer: device [L], the layers' unfolded pointwise_conv1 (k_pw1_glu_layers)
   // per-call descriptors: a ring of pinned host staging buffers + device copies, each guarded by an event, so that a
-  // call never overwrites a buffer an earlier (still queued) call reads
+  // call never overwrites a buffer an earlier (still queued) call reads.  A slot holds per_slot = n_sessions descriptors
+  // (Squeezeformer: 2 n_sessions -- those of the full-rate layers, then those of the half-rate layers)
   static constexpr int kRing = 8;
-  SessDesc* desc_host;  // pinned [kRing][n_sessions]
-  SessDesc* desc_dev;   // device [kRing][n_sessions]
-  hipEvent_t ev[kRing];
+  int per_slot;
+  SessDesc* desc_host;  // pinned [kRing][per_slot]
+  SessDesc* desc_dev;   // device [kRing][per_slot]
+  hipEvent_t ev[kRing];  // (null until created)
   int slot;
-  std::vector<int> cache_t, offset;
+  std::vector<int> cache_t, cache_r, offset;
 };
+
+}  // extern "C"
+
+namespace {
+
+ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, bool sq, ppasr_stream_group* out) {
+  auto* g = new ppasr_stream_group_s();  // (value-initialised: every pointer and event null until it exists)
+  g->m = h;
+  g->n_sessions = n_sessions;
+  g->sq = sq;
+  g->cap = (max_frames > 0 && max_frames < h->desc.max_len) ? max_frames : h->desc.max_len;
+  g->lo = h->desc.cnn_module_kernel - 1;
+  g->per_slot = sq ? 2 * n_sessions : n_sessions;
+  g->slot = 0;
+  // any failure below releases whatever exists so far (ppasr_stream_group_destroy skips what does not)
+  auto bail = [g](const char* what, hipError_t e) {
+    (void)ppasr_stream_group_destroy(g);
+    return fail(PPASR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  };
+  const size_t L = h->desc.num_blocks;
+  const size_t kv = (size_t)n_sessions * L * g->cap * kD * sizeof(float);
+  const size_t hb = (size_t)n_sessions * L * g->lo * kD * sizeof(float);
+  const size_t db = (size_t)ppasr_stream_group_s::kRing * g->per_slot * sizeof(SessDesc);
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->kc), kv);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->vc), kv);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->xh_hist), hb);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->desc_dev), db);
+  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->desc_host), db, hipHostMallocDefault);
+  if (e == hipSuccess && sq) e = hipMalloc(reinterpret_cast<void**>(&g->hist_tab), L * sizeof(HistLayer));
+  if (e != hipSuccess) return bail("allocation failed for the session-group caches", e);
+  for (int i = 0; i < ppasr_stream_group_s::kRing; ++i) {
+    e = hipEventCreateWithFlags(&g->ev[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+      g->ev[i] = nullptr;
+      return bail("creating the session-group events failed", e);
+    }
+  }
+  e = hipMemset(g->xh_hist, 0, hb);
+  if (e != hipSuccess) return bail("clearing the session-group conv histories failed", e);
+  if (sq) {  // (what ppasr_stream_create puts in a Squeezeformer stream's table)
+    std::vector<HistLayer> tab(L);
+    for (size_t i = 0; i < L; ++i) tab[i] = HistLayer{h->sq_layers[i].pw1_raw, h->sq_layers[i].pw1_b_raw, g->lo, 0};
+    e = hipMemcpy(g->hist_tab, tab.data(), L * sizeof(HistLayer), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return bail("uploading the session-group history table failed", e);
+  }
+  g->cache_t.assign(n_sessions, 0);
+  g->cache_r.assign(n_sessions, 0);
+  g->offset.assign(n_sessions, 0);
+  *out = g;
+  return PPASR_OK;
+}
+
+// Squeezeformer session group: the workspace of n chunks of T frames -- the batched layout for B = n (its xs holds the
+// pre-reduction rows [n*c][256]), the conv-module input rows [n*c][256] and the GLU'd histories [L][n][lo][256]
+size_t sq_group_ws_floats(const ppasr_model_s* h, int n, int T) {
+  const size_t c = h->front_dims(T).Tp;
+  return ws_layout(h, n, T).total + (((size_t)n * c * kD + 63) & ~(size_t)63) +
+         (size_t)h->desc.num_blocks * n * (h->desc.cnn_module_kernel - 1) * kD;
+}
+
+// One round of a Squeezeformer group: squeezeformer_chunk's arithmetic for every listed session, rows stacked (n*c
+// full-rate rows, n*c_r half-rate rows).  Every session is planned (plan_chunk_for) before anything is launched or
+// changed, so a refused call leaves every session as it was.  The fp16 x3 mode covers what it covers on a stream handle:
+// the feed-forward slices of the split route.  A layer whose stacked rows leave the split route (ffn_split_for(Mi) = 1:
+// more than 4 096 rows at the default setting, ppasr_set_ffn_split(0)) runs the fused fp32 kernels in either mode, as the
+// Conformer group does; a stream handle's one-session chunk never gets there.
+ppasr_status sq_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
+                                   float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
+                                   void* workspace, hipStream_t st) {
+  ppasr_model_s* h = g->m;
+  const auto fd = h->front_dims(T);
+  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2;
+  std::vector<ChunkPlan> plans(n);
+  std::vector<char> seen(g->n_sessions, 0);
+  for (int b = 0; b < n; ++b) {
+    const int sidx = sessions_host[b];
+    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
+    seen[sidx] = 1;
+    ppasr_status r = plan_chunk_for(h, g->cache_t[sidx], g->cache_r[sidx], g->offset[sidx], g->cap, c, -1, &plans[b]);
+    if (r != PPASR_OK) return r;
+  }
+  const int c_r = plans[0].c_r;
+  const int slot = g->slot;
+  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
+  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
+  SessDesc* desc = g->desc_host + (size_t)slot * g->per_slot;
+  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->per_slot;
+  for (int b = 0; b < n; ++b) {  // full-rate layers {sess, cache_t, offset - cache_t}; half-rate {sess, used_r, same}
+    desc[b] = SessDesc{sessions_host[b], g->cache_t[sessions_host[b]], plans[b].pos0, 0};
+    desc[n + b] = SessDesc{sessions_host[b], plans[b].used_r, plans[b].pos0, 0};
+  }
+  HIP_TRY(hipMemcpyAsync(desc_dev, desc, (size_t)2 * n * sizeof(SessDesc), hipMemcpyHostToDevice, st));
+  const SessDesc* d_full = desc_dev;
+  const SessDesc* d_half = desc_dev + n;
+  const WsLayout wl = ws_layout(h, n, T);
+  float* ws = static_cast<float*>(workspace);
+  float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
+  float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g, *xs = ws + wl.xs;
+  float* xhat = ws + wl.total;                                        // [n*c][256] conv-module inputs of this chunk
+  float* g_hist = xhat + (((size_t)n * c * kD + 63) & ~(size_t)63);  // [L][n][lo][256]
+  const int lo = g->lo, M = n * c, L = h->desc.num_blocks, H = h->desc.attention_heads;
+  const int n_chunks = h->desc.linear_units / 256, KS = h->desc.cnn_module_kernel;
+  const long long kv_sess = (long long)L * g->cap * kD, hist_sess = (long long)L * lo * kD;
+  launch_conv1(feats, h->front, y1, n, T, F, T1, F1, st);
+  launch_conv2(y1, h->front, y2, n, T1, F1, c, F2, st);
+  launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), /*scale_before_bias=*/true, st, PadSkip{}, ffn_split_for(h, M), y1);
+  launch_ln_rows(xa, h->preln_g, h->preln_b, M, st);
+  launch_pw1_glu_layers_group(g->xh_hist, hist_sess, d_full, g_hist, g->hist_tab, L, n, lo, st);
+  float* x = xa;
+  float* other = xb;
+  bool reduced = false, have_qkv = false;
+  for (int i = 0; i < L; ++i) {
+    const SqLayerW& W = h->sq_layers[i];
+    if (i == h->desc.reduce_idx) {
+      HIP_TRY(hipMemcpyAsync(xs, x, (size_t)M * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
+      launch_sq_reduce(x, other, qkv, h->sq_reduce, W.wqkv, W.bqkv, nullptr, n, c, c_r, st);
+      std::swap(x, other);
+      reduced = true;
+      have_qkv = true;
+    }
+    if (i == h->desc.recover_idx && reduced) {
+      launch_sq_recover(x, xs, other, qkv, h->sq_wrec, h->sq_brec, W.wqkv, W.bqkv, n, c, c_r, st);
+      std::swap(x, other);
+      reduced = false;
+      have_qkv = true;
+    }
+    const int Ti = reduced ? c_r : c, Mi = n * Ti;
+    const int mul = reduced ? 8 : 4;
+    const SessDesc* dsc = reduced ? d_half : d_full;
+    float* kc = g->kc + (size_t)i * g->cap * kD;
+    float* vc = g->vc + (size_t)i * g->cap * kD;
+    float* xh = g->xh_hist + (size_t)i * lo * kD;
+    float* gh = g_hist + (size_t)i * n * lo * kD;
+    const int S = ffn_split_for(h, Mi);  // few sessions = an under-filled grid: split route (partial sums in y1)
+    const bool h3s = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty();  // (as squeezeformer_chunk)
+    if (!have_qkv) launch_sq_qkv(x, qkv, W.wqkv, W.bqkv, Mi, st);
+    launch_kv_append_group(qkv, kc, vc, kv_sess, dsc, n, Ti, st);
+    AttnArgs a{qkv, 768, kc, kD, vc, kD, Ti, Ti, 0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, reduced ? 2 : 1, mul, Ti, Ti, 1,
+               dsc, kv_sess};
+    launch_attention(a, n, H, st);
+    const bool fuse_next = (i + 1 < L) && (i + 1 != h->desc.reduce_idx) && !(i + 1 == h->desc.recover_idx && reduced);
+    const SqLayerW* Wn = fuse_next ? &h->sq_layers[i + 1] : nullptr;
+    if (S > 1) {
+      const SqLayerW& Ws = h3s ? h->sq_layers_h3[i] : W;
+      launch_sq_oproj(ctx, x, other, W, Mi, st);
+      launch_ffn_split(other, nullptr, nullptr, Ws.ff1_w1, W.ff1_b1, Ws.ff1_w2, W.ff1_b2, 1.0f, W.ln2_g, W.ln2_b, y1, xc, Mi,
+                       n_chunks, S, st, PadSkip{}, false, h3s);
+      launch_sq_pw1glu(xc, gg, xhat, W, nullptr, Mi, Ti, mul, st);
+      launch_conv_pre(gg, gh, xc, ctx, sq_conv_view(W), nullptr, Mi, Ti, KS, mul, st);
+      launch_ffn_split(ctx, W.ln3_g, W.ln3_b, Ws.ff2_w1, W.ff2_b1, Ws.ff2_w2, W.ff2_b2, 1.0f, W.ln4_g, W.ln4_b, y1, other, Mi,
+                       n_chunks, S, st, PadSkip{}, /*residual_is_normed=*/true, h3s);
+      if (Wn) launch_sq_qkv(other, qkv, Wn->wqkv, Wn->bqkv, Mi, st);
+    } else {
+      launch_sq_mid(ctx, x, xc, gg, xhat, W, nullptr, Mi, Ti, mul, n_chunks, st);
+      launch_sq_tail(gg, gh, xc, other, qkv, W, Wn ? Wn->wqkv : nullptr, Wn ? Wn->bqkv : nullptr, nullptr, Mi, Ti, mul,
+                     n_chunks, KS, st);
+    }
+    launch_hist_update_group(xh, hist_sess, dsc, xhat, n, Ti, lo, st);
+    std::swap(x, other);
+    have_qkv = fuse_next;
+  }
+  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
+  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
+  launch_ctc_head(x, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, M, st, PadSkip{}, ffn_split_for(h, M), y1);
+  if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, M, h->head.V, st);
+  for (int b = 0; b < n; ++b) {  // (finish_chunk with required_cache_size < 0: nothing is dropped)
+    const int sidx = sessions_host[b];
+    g->cache_t[sidx] = plans[b].T2;
+    g->cache_r[sidx] = plans[b].T2_r;
+    g->offset[sidx] += c;
+  }
+  HIP_TRY(hipEventRecord(g->ev[slot], st));
+  if (c_out_host) *c_out_host = c;
+  HIP_TRY(hipGetLastError());
+  return PPASR_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 ppasr_status ppasr_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
   if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
   if (h->desc.model_type != PPASR_MODEL_CONFORMER || !h->desc.causal)
-    return fail(PPASR_EUNSUPPORTED, "session groups are built for streaming (causal) model_type=conformer");
+    return fail(PPASR_EUNSUPPORTED, "session groups are built for streaming (causal) model_type=conformer "
+                                    "(Squeezeformer: ppasr_sq_stream_group_create)");
   if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
   if (h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
-  auto g = std::make_unique<ppasr_stream_group_s>();
-  g->m = h;
-  g->n_sessions = n_sessions;
-  g->cap = (max_frames > 0 && max_frames < h->desc.max_len) ? max_frames : h->desc.max_len;
-  g->lo = h->desc.cnn_module_kernel - 1;
-  const size_t L = h->desc.num_blocks;
-  const size_t kv = (size_t)n_sessions * L * g->cap * kD * sizeof(float);
-  const size_t hb = (size_t)n_sessions * L * g->lo * kD * sizeof(float);
-  g->kc = g->vc = g->xh_hist = nullptr;
-  g->desc_dev = g->desc_host = nullptr;
-  g->slot = 0;
-  const size_t db = (size_t)ppasr_stream_group_s::kRing * n_sessions * sizeof(SessDesc);
-  hipError_t e1 = hipMalloc(reinterpret_cast<void**>(&g->kc), kv);
-  hipError_t e2 = hipMalloc(reinterpret_cast<void**>(&g->vc), kv);
-  hipError_t e3 = hipMalloc(reinterpret_cast<void**>(&g->xh_hist), hb);
-  hipError_t e4 = hipMalloc(reinterpret_cast<void**>(&g->desc_dev), db);
-  hipError_t e5 = hipHostMalloc(reinterpret_cast<void**>(&g->desc_host), db, hipHostMallocDefault);
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess) {
-    (void)hipFree(g->kc); (void)hipFree(g->vc); (void)hipFree(g->xh_hist); (void)hipFree(g->desc_dev);
-    (void)hipHostFree(g->desc_host);
-    return fail(PPASR_EHIP, "allocation failed for the session-group caches");
-  }
-  for (int i = 0; i < ppasr_stream_group_s::kRing; ++i) HIP_TRY(hipEventCreateWithFlags(&g->ev[i], hipEventDisableTiming));
-  HIP_TRY(hipMemset(g->xh_hist, 0, hb));
-  g->cache_t.assign(n_sessions, 0);
-  g->offset.assign(n_sessions, 0);
-  *out = g.release();
-  return PPASR_OK;
+  return group_alloc(h, n_sessions, max_frames, false, out);
+}
+
+ppasr_status ppasr_sq_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
+  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
+  if (h->desc.model_type != PPASR_MODEL_SQUEEZEFORMER || !h->desc.causal)
+    return fail(PPASR_EUNSUPPORTED, "Squeezeformer session groups are built for streaming (causal) model_type=squeezeformer");
+  if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
+  if (h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
+  if (h->desc.cnn_module_kernel != 31 && h->desc.cnn_module_kernel != 15)
+    return fail(PPASR_EUNSUPPORTED, "Squeezeformer session groups: the streaming conv kernels exist for kernel sizes 31 / 15");
+  return group_alloc(h, n_sessions, max_frames, true, out);
 }
 
 ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g) {
   if (!g) return PPASR_OK;
   (void)hipFree(g->kc); (void)hipFree(g->vc); (void)hipFree(g->xh_hist); (void)hipFree(g->desc_dev);
+  (void)hipFree(g->hist_tab);
   (void)hipHostFree(g->desc_host);
-  for (int i = 0; i < ppasr_stream_group_s::kRing; ++i) (void)hipEventDestroy(g->ev[i]);
+  for (int i = 0; i < ppasr_stream_group_s::kRing; ++i)
+    if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
   delete g;
   return PPASR_OK;
 }
@@ -578,10 +754,12 @@ ppasr_status ppasr_stream_group_reset(ppasr_stream_group g, int session, void* s
   if (session < 0) {
     HIP_TRY(hipMemsetAsync(g->xh_hist, 0, per * g->n_sessions * sizeof(float), st));
     std::fill(g->cache_t.begin(), g->cache_t.end(), 0);
+    std::fill(g->cache_r.begin(), g->cache_r.end(), 0);
     std::fill(g->offset.begin(), g->offset.end(), 0);
   } else {
     HIP_TRY(hipMemsetAsync(g->xh_hist + per * session, 0, per * sizeof(float), st));
     g->cache_t[session] = 0;
+    g->cache_r[session] = 0;
     g->offset[session] = 0;
   }
   return PPASR_OK;
@@ -593,6 +771,7 @@ int ppasr_stream_group_offset(ppasr_stream_group g, int session) {
 
 size_t ppasr_group_chunk_workspace_bytes(ppasr_handle h, int n, int T) {
   if (!h || n < 1 || T < 7) return 0;
+  if (is_sq(h)) return sq_group_ws_floats(h, n, T) * sizeof(float);
   const size_t Tp = ((T - 1) / 2 - 1) / 2;
   // the batched layout for B = n, plus the conv-module input rows and the GLU'd histories of the active sessions
   return (ws_layout(h, n, T).total + (size_t)n * Tp * kD + 64 + (size_t)n * (h->desc.cnn_module_kernel - 1) * kD * 2 + 64) *
@@ -608,12 +787,15 @@ ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int* sessions_
   ppasr_model_s* h = g->m;
   if (T < 7) return fail(PPASR_EINVAL, "chunk shorter than the conv front-end's receptive field (7 frames)");
   if (workspace_bytes < ppasr_group_chunk_workspace_bytes(h, n, T)) return fail(PPASR_ENOSPACE, "workspace too small");
+  if (g->sq)
+    return sq_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
+                                 static_cast<hipStream_t>(stream));
   const int F = h->desc.input_dim, T1 = (T - 1) / 2, F1 = h->F1, c = (T1 - 1) / 2, F2 = h->F2;
   const int slot = g->slot;
   g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
   HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
-  SessDesc* desc = g->desc_host + (size_t)slot * g->n_sessions;
-  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->n_sessions;
+  SessDesc* desc = g->desc_host + (size_t)slot * g->per_slot;
+  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->per_slot;
   std::vector<char> seen(g->n_sessions, 0);
   for (int b = 0; b < n; ++b) {
     const int sidx = sessions_host[b];

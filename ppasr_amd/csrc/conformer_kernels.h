@@ -265,6 +265,10 @@ struct HistLayer {
 void launch_pw1_glu_layers(const float* xh_hist, float* g_hist, const HistLayer* tab, int n_layers, int lo_stride,
                            hipStream_t st);
 void launch_kv_append(const float* qkv, float* kc, float* vc, int n_rows, hipStream_t st);
+// session groups: every layer x every listed session in one launch; layer i of session sess[b] reads
+// xh_hist + sess[b].sess * sess_stride + i * lo * 256 in place and writes g_hist [n_layers][n][lo][256]
+void launch_pw1_glu_layers_group(const float* xh_hist, long long sess_stride, const SessDesc* sess, float* g_hist,
+                                 const HistLayer* tab, int n_layers, int n, int lo, hipStream_t st);
 // multi-session variants: row (b, t) of the chunk batch <-> session sess[b]
 void launch_kv_append_group(const float* qkv, float* kc, float* vc, long long sess_stride, const SessDesc* sess, int n, int c,
                             hipStream_t st);

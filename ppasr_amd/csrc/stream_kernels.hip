@@ -41,15 +41,19 @@ __global__ __launch_bounds__(kThreads) void k_pw1_glu(const float* __restrict__ 
     if (row < valid) g[(size_t)(r0 + row) * kD + col] = (av[0][0][r] + bval) * sigmoidf(ag[0][0][r] + bgate);
   }
 }
-// the same for every layer's history in ONE launch (single-session streaming: the histories only depend on the previous
-// chunk, so the twelve small launches need not sit between the layers): block i = layer i, tab[i] = its weights / rows
+// the same for every layer's history in ONE launch (streaming: the histories only depend on the previous chunk, so the
+// twelve small launches need not sit between the layers): block (i, b) = layer i of list position b, tab[i] = its weights /
+// rows.  One stream: sess == nullptr, gridDim.y = 1.  Session groups: the history of session sess[b].sess is read in place
+// (xh_hist + sess * sess_stride), g_hist is [layer][b][lo_stride][256] -- the per-session layout dwconv_phase reads.
 __global__ __launch_bounds__(kThreads) void k_pw1_glu_layers(const float* __restrict__ xh_hist, float* __restrict__ g_hist,
-                                                             const HistLayer* __restrict__ tab, int lo_stride) {
+                                                             const HistLayer* __restrict__ tab, int lo_stride,
+                                                             const SessDesc* __restrict__ sess, long long sess_stride) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* bufA = smem;
-  const HistLayer t = tab[blockIdx.x];
-  const float* xhat = xh_hist + (size_t)blockIdx.x * lo_stride * kD;
-  float* g = g_hist + (size_t)blockIdx.x * lo_stride * kD;
+  const int layer = blockIdx.x, b = blockIdx.y;
+  const HistLayer t = tab[layer];
+  const float* xhat = xh_hist + (sess ? (size_t)sess[b].sess * sess_stride : 0) + (size_t)layer * lo_stride * kD;
+  float* g = g_hist + ((size_t)layer * gridDim.y + b) * lo_stride * kD;
   const int lane = lane_id(), wave = wave_id();
   const int valid = min(kRows, t.rows);
   const int col = wave * 32 + (lane & 31);
@@ -75,7 +79,12 @@ __global__ __launch_bounds__(kThreads) void k_pw1_glu_layers(const float* __rest
 constexpr size_t kLdsPw1Glu = kRows * kLda * sizeof(float);
 void launch_pw1_glu_layers(const float* xh_hist, float* g_hist, const HistLayer* tab, int n_layers, int lo_stride,
                            hipStream_t st) {
-  PPASR_LAUNCH(k_pw1_glu_layers, dim3(n_layers), dim3(kThreads), kLdsPw1Glu, st, xh_hist, g_hist, tab, lo_stride);
+  PPASR_LAUNCH(k_pw1_glu_layers, dim3(n_layers), dim3(kThreads), kLdsPw1Glu, st, xh_hist, g_hist, tab, lo_stride,
+               (const SessDesc*)nullptr, 0ll);
+}
+void launch_pw1_glu_layers_group(const float* xh_hist, long long sess_stride, const SessDesc* sess, float* g_hist,
+                                 const HistLayer* tab, int n_layers, int n, int lo, hipStream_t st) {
+  PPASR_LAUNCH(k_pw1_glu_layers, dim3(n_layers, n), dim3(kThreads), kLdsPw1Glu, st, xh_hist, g_hist, tab, lo, sess, sess_stride);
 }
 void launch_pw1_glu(const float* xhat, float* g, const LayerW& w, int M, hipStream_t st) {
   PPASR_LAUNCH(k_pw1_glu, dim3((M + kRows - 1) / kRows), dim3(kThreads), kLdsPw1Glu, st, xhat, g, w, M);

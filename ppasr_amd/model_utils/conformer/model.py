@@ -397,9 +397,9 @@ class ConformerStream:
 
 class StreamHandleSet:
     """The interface of ``ConformerStreamGroup`` over per-session stream handles (``model.new_stream()``): for the handles
-    whose sessions the C-ABI cannot advance in one call (``ppasr_stream_group_create`` is built for plain Conformer
-    handles; Squeezeformer / Efficient-Conformer models keep half-rate layers, grouped attention or a stride layer per
-    session).  Same results as driving each session's own stream; N sets of launches per round instead of one."""
+    whose sessions ``make_stream_group`` builds no group for (``ppasr_stream_group_create`` is built for plain Conformer
+    handles; Squeezeformer groups are opt-in, ``SqueezeformerStreamGroup``; Efficient-Conformer models keep grouped
+    attention and a stride layer per session).  Same results as driving each session's own stream; N sets of launches per round instead of one."""
 
     def __init__(self, model, n_sessions, max_frames=0):
         self.model = model
@@ -443,14 +443,15 @@ class ConformerStreamGroup:
     (their rows are stacked), so a server's throughput is no longer bound by per-chunk launch overhead.  Every session
     follows ``ConformerStream.encode_chunk(chunk, required_cache_size=-16)`` exactly (full history)."""
 
+    _create = "ppasr_stream_group_create"  # the C-ABI call that builds the group (SqueezeformerStreamGroup: its own)
+
     def __init__(self, model, n_sessions, max_frames=0):
         self.model = model
         self.lib = model.lib
         self.n_sessions = int(n_sessions)
         self._g = ctypes.c_void_p()
         with torch.cuda.device(model.device):
-            _lib.check(self.lib.ppasr_stream_group_create(model._h, self.n_sessions, int(max_frames),
-                                                          ctypes.byref(self._g)))
+            _lib.check(getattr(self.lib, self._create)(model._h, self.n_sessions, int(max_frames), ctypes.byref(self._g)))
         self._ws = {}
 
     def __del__(self):

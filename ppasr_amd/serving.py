@@ -1,5 +1,5 @@
 """Many-session streaming recogniser built on session groups (``ppasr_encode_chunk_group``; per-session stream handles for
-the families the library has no group call for).
+the families ``make_stream_group`` builds no group for -- a ready group, e.g. ``SqueezeformerStreamGroup``, can be passed in).
 
 No reference counterpart: PPASR serves one stream per ``PPASRPredictor`` (``predict_stream``, predict.py:232-337, one
 global predictor behind its FastAPI / GUI apps).  ``StreamPool`` keeps the per-session state machine of
@@ -28,13 +28,19 @@ class _Session:
 
 
 class StreamPool:
-    def __init__(self, model, vocab_list, n_sessions, preprocess_conf=None, max_seconds=200.0, blank_index=0):
+    def __init__(self, model, vocab_list, n_sessions, preprocess_conf=None, max_seconds=200.0, blank_index=0, group=None):
+        """group: a ready session group for `model` with `n_sessions` slots (e.g. ``SqueezeformerStreamGroup``); None =
+        ``make_stream_group``'s choice."""
         self.model = model
         self.vocab = list(vocab_list)
         self.blank = blank_index
-        # (one set of launches per round for plain Conformer handles; per-session stream handles behind the same interface
-        #  for the Squeezeformer and the Efficient-Conformer)
-        self.group = make_stream_group(model, n_sessions, max_frames=min(model.max_len, int(max_seconds * 25) + 32))
+        if group is None:
+            # (one set of launches per round for plain Conformer handles; per-session stream handles behind the same
+            #  interface for the Squeezeformer and the Efficient-Conformer)
+            group = make_stream_group(model, n_sessions, max_frames=min(model.max_len, int(max_seconds * 25) + 32))
+        elif getattr(group, "model", None) is not model or int(getattr(group, "n_sessions", -1)) != int(n_sessions):
+            raise ValueError("StreamPool(group=...): the group must be built for the same model and session count")
+        self.group = group
         self.featurizer = AudioFeaturizer(**(preprocess_conf or {}))
         self.sessions = [_Session() for _ in range(n_sessions)]
 
