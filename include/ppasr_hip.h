@@ -418,7 +418,7 @@ PPASR_API ppasr_status ppasr_ctc_collapse(const int32_t* frame_argmax, const flo
                                 void* stream);
 
 /* ---- multi-session streaming (no reference counterpart: PPASR streams one session per call) -----------------------
- * A group of Conformer (or Squeezeformer) sessions whose K/V and conv caches live in one allocation;
+ * A group of Conformer (or Squeezeformer, or Efficient-Conformer) sessions whose K/V and conv caches live in one allocation;
  * ppasr_encode_chunk_group advances any subset of them by one chunk with ONE set of launches (rows of all listed sessions
  * stacked).  Every session
  * follows the single-session arithmetic of ppasr_encode_chunk with required_cache_size < 0 (full history, what
@@ -433,6 +433,14 @@ PPASR_API ppasr_status ppasr_stream_group_create(ppasr_handle h, int n_sessions,
  * handle) and ppasr_encode_chunk_group refuses, with PPASR_EINVAL and no session changed, a round in which any listed
  * session would leave an odd cache length or exceed max_len / max_frames.  The other group calls take it unchanged. */
 PPASR_API ppasr_status ppasr_sq_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out);
+/* The same kind of group for a streaming (causal) Efficient-Conformer handle on the conv2d front end and the fused
+ * 256-wide route with at most one stride layer (grouped-attention layers of group size 2 / 3 / 4 included): what
+ * ppasr_stream_create runs on that route.  PPASR_EUNSUPPORTED for any other handle (several stride layers, the general
+ * route, the 6x / 8x front ends, non-causal models); ppasr_stream_group_create and ppasr_sq_stream_group_create refuse
+ * Efficient-Conformer handles.  Each session keeps its full-rate and half-rate caches and its offset; a round emits
+ * ppasr_out_frames(h, T) frames per session, and ppasr_encode_chunk_group refuses, with PPASR_EINVAL and no session
+ * changed, a round in which any listed session would leave an odd cache length or exceed max_len / max_frames. */
+PPASR_API ppasr_status ppasr_eff_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out);
 PPASR_API ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g);
 PPASR_API ppasr_status ppasr_stream_group_reset(ppasr_stream_group g, int session /* < 0: all */, void* stream);
 PPASR_API int          ppasr_stream_group_offset(ppasr_stream_group g, int session);

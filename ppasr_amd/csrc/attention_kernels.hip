@@ -126,7 +126,11 @@ __global__ __launch_bounds__(64 * AttnT<DK>::WV, DK == 64 ? PPASR_ATTN_OCC : 2) 
   const float* __restrict__ ptab = a.ptab + (size_t)a.pos0 * dm;
   if (a.sess) {  // multi-session streaming: per-session cache slot, length and position
     const SessDesc d = a.sess[b];
-    T2 = F2 = d.cache_t + T1;
+    // grouped heads: the session's key frames (its cache + this chunk's query frames) are re-cut into tokens of G frames
+    // from the start of its cache (pad4group on the concatenated keys); the resources below are bounded at F2, so the
+    // zero-padded tail group reads zeros, never rows of the session's cache slot behind its own frames
+    F2 = d.cache_t + (G == 1 ? T1 : F1);
+    T2 = G == 1 ? F2 : (F2 + G - 1) / G;
     kbp = a.k + (size_t)d.sess * a.sess_stride;
     vbp = a.v + (size_t)d.sess * a.sess_stride;
     ptab = a.ptab + (size_t)d.pos0 * dm;

@@ -49,7 +49,7 @@ void history_glu_all(ppasr_stream_s* s, hipStream_t st) {
 
 // the reference's shape arithmetic for one chunk of c frames on a session whose caches hold cache_t (full-rate layers) /
 // cache_r (half-rate layers) frames, `offset` frames emitted so far and room for `cap` keys per layer; shared by the
-// stream handles and the Squeezeformer session groups
+// stream handles and the Squeezeformer / Efficient-Conformer session groups
 ppasr_status plan_chunk_for(const ppasr_model_s* h, int cache_t, int cache_r, int offset, int cap, int c,
                             int required_cache_size, ChunkPlan* p) {
   p->c = c;
@@ -311,6 +311,9 @@ ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* x
   return PPASR_OK;
 }
 
+// which of the chunk-round paths a session group takes (the family of the handle it was built for)
+enum class GroupFamily { kConformer, kSqueezeformer, kEfficientConformer };
+
 }  // namespace
 
 extern "C" {
@@ -509,8 +512,9 @@ ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* att_cache, i
 }
 
 // =====================================================================================
-// Multi-session streaming: a group of Conformer (ppasr_stream_group_create) or Squeezeformer (ppasr_sq_stream_group_create)
-// sessions whose caches live in one allocation and advance with ONE set of launches per chunk round (the rows of all active sessions are stacked: n x c frames -> ceil(n*c/32) row blocks
+// Multi-session streaming: a group of Conformer (ppasr_stream_group_create), Squeezeformer (ppasr_sq_stream_group_create)
+// or Efficient-Conformer (ppasr_eff_stream_group_create) sessions whose caches live in one allocation and advance with ONE
+// set of launches per chunk round (the rows of all active sessions are stacked: n x c frames -> ceil(n*c/32) row blocks
 // per kernel instead of one).  No reference counterpart: PPASR streams one session per call
 // (predict.py:232-337, forward_chunk asserts B = 1); each session here follows exactly the single-session arithmetic
 // (required_cache_size < 0: the full history is kept, what PPASRPredictor passes, predict.py:306-307).
@@ -518,13 +522,14 @@ ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* att_cache, i
 struct ppasr_stream_group_s {
   ppasr_model_s* m;
   int n_sessions, cap, lo;
-  bool sq;            // Squeezeformer group (ppasr_sq_stream_group_create): full- and half-rate layers
+  GroupFamily family;  // Squeezeformer / Efficient-Conformer: full- and half-rate layers, per-layer histories
   float *kc, *vc;     // [n_sessions][L][cap][256]
-  float* xh_hist;     // [n_sessions][L][lo][256]
-  HistLayer* hist_tab;  // Squeezeformer: device [L], the layers' unfolded pointwise_conv1 (k_pw1_glu_layers)
+  float* xh_hist;     // [n_sessions][L][lo][256] (layer i uses its first kernel_i - 1 rows)
+  HistLayer* hist_tab;  // Squeezeformer / Efficient-Conformer: device [L], the layers' pointwise_conv1 (k_pw1_glu_layers)
   // per-call descriptors: a ring of pinned host staging buffers + device copies, each guarded by an event, so that a
   // call never overwrites a buffer an earlier (still queued) call reads.  A slot holds per_slot = n_sessions descriptors
-  // (Squeezeformer: 2 n_sessions -- those of the full-rate layers, then those of the half-rate layers)
+  // (Squeezeformer / Efficient-Conformer: 2 n_sessions -- those of the full-rate layers, then those of the half-rate
+  // layers)
   static constexpr int kRing = 8;
   int per_slot;
   SessDesc* desc_host;  // pinned [kRing][per_slot]
@@ -538,14 +543,15 @@ struct ppasr_stream_group_s {
 
 namespace {
 
-ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, bool sq, ppasr_stream_group* out) {
+ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFamily family, ppasr_stream_group* out) {
   auto* g = new ppasr_stream_group_s();  // (value-initialised: every pointer and event null until it exists)
   g->m = h;
   g->n_sessions = n_sessions;
-  g->sq = sq;
+  g->family = family;
   g->cap = (max_frames > 0 && max_frames < h->desc.max_len) ? max_frames : h->desc.max_len;
   g->lo = h->desc.cnn_module_kernel - 1;
-  g->per_slot = sq ? 2 * n_sessions : n_sessions;
+  const bool layered = family != GroupFamily::kConformer;  // (per-layer history table, two descriptor sets)
+  g->per_slot = layered ? 2 * n_sessions : n_sessions;
   g->slot = 0;
   // any failure below releases whatever exists so far (ppasr_stream_group_destroy skips what does not)
   auto bail = [g](const char* what, hipError_t e) {
@@ -561,7 +567,7 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, bool sq
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->xh_hist), hb);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->desc_dev), db);
   if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->desc_host), db, hipHostMallocDefault);
-  if (e == hipSuccess && sq) e = hipMalloc(reinterpret_cast<void**>(&g->hist_tab), L * sizeof(HistLayer));
+  if (e == hipSuccess && layered) e = hipMalloc(reinterpret_cast<void**>(&g->hist_tab), L * sizeof(HistLayer));
   if (e != hipSuccess) return bail("allocation failed for the session-group caches", e);
   for (int i = 0; i < ppasr_stream_group_s::kRing; ++i) {
     e = hipEventCreateWithFlags(&g->ev[i], hipEventDisableTiming);
@@ -572,9 +578,12 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, bool sq
   }
   e = hipMemset(g->xh_hist, 0, hb);
   if (e != hipSuccess) return bail("clearing the session-group conv histories failed", e);
-  if (sq) {  // (what ppasr_stream_create puts in a Squeezeformer stream's table)
+  if (layered) {  // (what ppasr_stream_create puts in the family's stream table: rows = kernel_i - 1)
     std::vector<HistLayer> tab(L);
-    for (size_t i = 0; i < L; ++i) tab[i] = HistLayer{h->sq_layers[i].pw1_raw, h->sq_layers[i].pw1_b_raw, g->lo, 0};
+    for (size_t i = 0; i < L; ++i)
+      tab[i] = family == GroupFamily::kSqueezeformer
+                   ? HistLayer{h->sq_layers[i].pw1_raw, h->sq_layers[i].pw1_b_raw, g->lo, 0}
+                   : HistLayer{h->layers[i].pw1, h->layers[i].pw1_b, layer_lo(h, (int)i), 0};
     e = hipMemcpy(g->hist_tab, tab.data(), L * sizeof(HistLayer), hipMemcpyHostToDevice);
     if (e != hipSuccess) return bail("uploading the session-group history table failed", e);
   }
@@ -585,9 +594,10 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, bool sq
   return PPASR_OK;
 }
 
-// Squeezeformer session group: the workspace of n chunks of T frames -- the batched layout for B = n (its xs holds the
-// pre-reduction rows [n*c][256]), the conv-module input rows [n*c][256] and the GLU'd histories [L][n][lo][256]
-size_t sq_group_ws_floats(const ppasr_model_s* h, int n, int T) {
+// Squeezeformer / Efficient-Conformer session group: the workspace of n chunks of T frames -- the batched layout for
+// B = n (Squeezeformer: its xs holds the pre-reduction rows [n*c][256]), the conv-module input rows [n*c][256] and the GLU'd
+// histories [L][n][lo][256] (lo = cnn_module_kernel - 1, the widest layer's)
+size_t layered_group_ws_floats(const ppasr_model_s* h, int n, int T) {
   const size_t c = h->front_dims(T).Tp;
   return ws_layout(h, n, T).total + (((size_t)n * c * kD + 63) & ~(size_t)63) +
          (size_t)h->desc.num_blocks * n * (h->desc.cnn_module_kernel - 1) * kD;
@@ -710,6 +720,128 @@ ppasr_status sq_encode_chunk_group(ppasr_stream_group g, const int* sessions_hos
   return PPASR_OK;
 }
 
+// One round of an Efficient-Conformer group: conformer_chunk's arithmetic for every listed session, rows stacked (n*c
+// full-rate rows up to and including the stride layer, n*c_r half-rate rows behind it).  Every session is planned
+// (plan_chunk_for: offset doubled, no trim of the half-rate cache, odd cache lengths refused) before anything is launched
+// or changed, so a refused call leaves every session as it was.  The descriptors of the full-rate layers carry
+// {sess, cache_t, pos0}, those of the half-rate layers {sess, cache_r, pos0}, pos0 = 2 offset - cache_t (the half-rate
+// layers read every second positional row).  Grouped-attention layers re-cut each session's cache + chunk frames into
+// tokens from the start of its cache (k_attention_t's per-session branch).  The conv histories of every layer and
+// session are GLU'd in one launch; layer i's are kernel_i - 1 rows per session (7-tap convs behind the stride layer).
+// fp16 x3 follows the stream handle's rule per launch, as in the other groups: the split route's units on the layers' h3
+// views, the fused kernels (stacked rows beyond the split route) in fp32.  The consumer-side joins of a stream handle's
+// chunk (ffn_half16 / join16) are single-session and not used here.
+ppasr_status eff_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
+                                    float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
+                                    void* workspace, hipStream_t st) {
+  ppasr_model_s* h = g->m;
+  const auto fd = h->front_dims(T);
+  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2;
+  std::vector<ChunkPlan> plans(n);
+  std::vector<char> seen(g->n_sessions, 0);
+  for (int b = 0; b < n; ++b) {
+    const int sidx = sessions_host[b];
+    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
+    seen[sidx] = 1;
+    ppasr_status r = plan_chunk_for(h, g->cache_t[sidx], g->cache_r[sidx], g->offset[sidx], g->cap, c, -1, &plans[b]);
+    if (r != PPASR_OK) return r;
+  }
+  const int c_r = plans[0].c_r;
+  const int slot = g->slot;
+  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
+  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
+  SessDesc* desc = g->desc_host + (size_t)slot * g->per_slot;
+  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->per_slot;
+  for (int b = 0; b < n; ++b) {  // full-rate layers {sess, cache_t, 2 offset - cache_t}; half-rate {sess, cache_r, same}
+    desc[b] = SessDesc{sessions_host[b], g->cache_t[sessions_host[b]], plans[b].pos0, 0};
+    desc[n + b] = SessDesc{sessions_host[b], plans[b].used_r, plans[b].pos0, 0};
+  }
+  HIP_TRY(hipMemcpyAsync(desc_dev, desc, (size_t)2 * n * sizeof(SessDesc), hipMemcpyHostToDevice, st));
+  const WsLayout wl = ws_layout(h, n, T);
+  float* ws = static_cast<float*>(workspace);
+  float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
+  float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g;
+  float* xhat = ws + wl.total;                                        // [n*c][256] conv-module inputs of this chunk
+  float* g_hist = xhat + (((size_t)n * c * kD + 63) & ~(size_t)63);  // [L][n * lo][256]
+  const int lo = g->lo, M = n * c, L = h->desc.num_blocks, H = h->desc.attention_heads;
+  const int n_chunks = h->desc.linear_units / 256;
+  const long long kv_sess = (long long)L * g->cap * kD, hist_sess = (long long)L * lo * kD;
+  const bool h3_mode = h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty();
+  launch_conv1(feats, h->front, y1, n, T, F, T1, F1, st);
+  launch_conv2(y1, h->front, y2, n, T1, F1, c, F2, st);
+  launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), /*scale_before_bias=*/false, st, PadSkip{}, ffn_split_for(h, M),
+               y1);
+  launch_pw1_glu_layers_group(g->xh_hist, hist_sess, desc_dev, g_hist, g->hist_tab, L, n, lo, st);
+  int Ti = c, mul = 4, pstride = 1;
+  const SessDesc* dsc = desc_dev;  // (the half-rate descriptors behind the stride layer)
+  for (int i = 0; i < L; ++i) {
+    const LayerW& W = h->layers[i];
+    const int grp = h->layer_group[i], KS = h->layer_ks[i], lo_i = layer_lo(h, i), Mi = n * Ti;
+    float* kc = g->kc + (size_t)i * g->cap * kD;
+    float* vc = g->vc + (size_t)i * g->cap * kD;
+    float* xh = g->xh_hist + (size_t)i * lo * kD;
+    float* gh = g_hist + (size_t)i * n * lo * kD;  // list position b at row b * lo_i (k_pw1_glu_layers)
+    const int S = ffn_split_for(h, Mi);  // few sessions = an under-filled grid: split route (partial sums in y1)
+    const bool h3 = S > 1 && h3_mode;
+    const LayerW& Wk = h3 ? h->layers_h3[i] : W;
+    if (S > 1) {
+      launch_ffn_split(xa, W.ln_mac_g, W.ln_mac_b, Wk.ffm_w1, W.ffm_b1, Wk.ffm_w2, W.ffm_b2, 0.5f, nullptr, nullptr, y1, xb, Mi,
+                       n_chunks, S, st, PadSkip{}, false, h3);
+      launch_ln_qkv(xb, qkv, Wk, Mi, st, PadSkip{}, nullptr, nullptr, h3);
+    } else {
+      launch_ffn_qkv(xa, xb, qkv, W, Mi, n_chunks, st);
+    }
+    launch_kv_append_group(qkv, kc, vc, kv_sess, dsc, n, Ti, st);
+    // (T2 / kv_frames: per session from dsc -- cache + Ti frames, ceil(/ grp) tokens)
+    const int Tq = ceil_div(Ti, grp);
+    AttnArgs a{qkv, 768, kc, kD, vc, kD, Tq, Tq, 0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, pstride, mul * grp, Ti, Ti, grp,
+               dsc, kv_sess};
+    launch_attention(a, n, H, st);
+    launch_out_glu(ctx, xb, xc, gg, xhat, Wk, nullptr, Mi, Ti, mul, st, PadSkip{}, S > 1 ? xhat : nullptr, h3);
+    if (i == h->desc.stride_layer_idx) {
+      const int Ms = n * c_r, Ss = ffn_split_for(h, Ms);
+      const bool h3s = Ss > 1 && h3_mode;
+      const LayerW& Ws = h3s ? h->layers_h3[i] : W;
+      if (Ss > 1) {  // the conv half alone (x3 -> ctx), its feed-forward module over the slices
+        launch_conv_ffn_stride(gg, gh, xc, xa, Ws, nullptr, n, Ti, c_r, n_chunks, KS, mul * 2, st, PadSkip{}, true, h3s, ctx);
+        launch_ffn_split(ctx, W.ln_ff_g, W.ln_ff_b, Ws.ff_w1, W.ff_b1, Ws.ff_w2, W.ff_b2, 0.5f, W.ln_fin_g, W.ln_fin_b, y1, xa,
+                         Ms, n_chunks, Ss, st, PadSkip{}, false, h3s);
+      } else {
+        launch_conv_ffn_stride(gg, gh, xc, xa, W, nullptr, n, Ti, c_r, n_chunks, KS, mul * 2, st);
+      }
+      launch_hist_update_group(xh, hist_sess, dsc, xhat, n, Ti, lo_i, st);
+      Ti = c_r;  // masks[:, :, ::2], pos_emb[:, ::2]  (efficient_conformer/encoder.py:252-257)
+      mul *= 2;
+      pstride *= 2;
+      dsc = desc_dev + n;
+    } else {
+      if (S > 1) {
+        launch_conv_pre(gg, gh, xc, ctx, Wk, nullptr, Mi, Ti, KS, mul, st, true, PadSkip{}, h3);
+        launch_ffn_split(ctx, W.ln_ff_g, W.ln_ff_b, Wk.ff_w1, W.ff_b1, Wk.ff_w2, W.ff_b2, 0.5f, W.ln_fin_g, W.ln_fin_b, y1, xa, Mi,
+                         n_chunks, S, st, PadSkip{}, false, h3);
+      } else {
+        launch_conv_ffn(gg, gh, xc, xa, W, nullptr, Mi, Ti, n_chunks, KS, mul, nullptr, nullptr, nullptr, st);
+      }
+      launch_hist_update_group(xh, hist_sess, dsc, xhat, n, Ti, lo_i, st);
+    }
+  }
+  const int Mo = n * Ti;  // (Ti = c_r behind a stride layer, c without one: ppasr_out_frames)
+  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
+  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
+  launch_ctc_head(xa, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, Mo, st, PadSkip{}, ffn_split_for(h, Mo), y1);
+  if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, Mo, h->head.V, st);
+  for (int b = 0; b < n; ++b) {  // (finish_chunk with required_cache_size < 0: nothing is dropped)
+    const int sidx = sessions_host[b];
+    g->cache_t[sidx] = plans[b].T2;
+    g->cache_r[sidx] = plans[b].T2_r;
+    g->offset[sidx] += Ti;
+  }
+  HIP_TRY(hipEventRecord(g->ev[slot], st));
+  if (c_out_host) *c_out_host = Ti;
+  HIP_TRY(hipGetLastError());
+  return PPASR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -721,7 +853,7 @@ ppasr_status ppasr_stream_group_create(ppasr_handle h, int n_sessions, int max_f
                                     "(Squeezeformer: ppasr_sq_stream_group_create)");
   if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
   if (h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
-  return group_alloc(h, n_sessions, max_frames, false, out);
+  return group_alloc(h, n_sessions, max_frames, GroupFamily::kConformer, out);
 }
 
 ppasr_status ppasr_sq_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
@@ -732,7 +864,19 @@ ppasr_status ppasr_sq_stream_group_create(ppasr_handle h, int n_sessions, int ma
   if (h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
   if (h->desc.cnn_module_kernel != 31 && h->desc.cnn_module_kernel != 15)
     return fail(PPASR_EUNSUPPORTED, "Squeezeformer session groups: the streaming conv kernels exist for kernel sizes 31 / 15");
-  return group_alloc(h, n_sessions, max_frames, true, out);
+  return group_alloc(h, n_sessions, max_frames, GroupFamily::kSqueezeformer, out);
+}
+
+ppasr_status ppasr_eff_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
+  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
+  if (h->desc.model_type != PPASR_MODEL_EFFICIENT_CONFORMER || !h->desc.causal)
+    return fail(PPASR_EUNSUPPORTED,
+                "Efficient-Conformer session groups are built for streaming (causal) model_type=efficient_conformer");
+  if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
+  if (h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
+  if (__builtin_popcount(eff_stride_mask(h->desc)) > 1)
+    return fail(PPASR_EUNSUPPORTED, "Efficient-Conformer session groups are built for at most one stride layer");
+  return group_alloc(h, n_sessions, max_frames, GroupFamily::kEfficientConformer, out);
 }
 
 ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g) {
@@ -771,7 +915,7 @@ int ppasr_stream_group_offset(ppasr_stream_group g, int session) {
 
 size_t ppasr_group_chunk_workspace_bytes(ppasr_handle h, int n, int T) {
   if (!h || n < 1 || T < 7) return 0;
-  if (is_sq(h)) return sq_group_ws_floats(h, n, T) * sizeof(float);
+  if (is_sq(h) || is_eff(h)) return layered_group_ws_floats(h, n, T) * sizeof(float);
   const size_t Tp = ((T - 1) / 2 - 1) / 2;
   // the batched layout for B = n, plus the conv-module input rows and the GLU'd histories of the active sessions
   return (ws_layout(h, n, T).total + (size_t)n * Tp * kD + 64 + (size_t)n * (h->desc.cnn_module_kernel - 1) * kD * 2 + 64) *
@@ -787,9 +931,12 @@ ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int* sessions_
   ppasr_model_s* h = g->m;
   if (T < 7) return fail(PPASR_EINVAL, "chunk shorter than the conv front-end's receptive field (7 frames)");
   if (workspace_bytes < ppasr_group_chunk_workspace_bytes(h, n, T)) return fail(PPASR_ENOSPACE, "workspace too small");
-  if (g->sq)
+  if (g->family == GroupFamily::kSqueezeformer)
     return sq_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
                                  static_cast<hipStream_t>(stream));
+  if (g->family == GroupFamily::kEfficientConformer)
+    return eff_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
+                                  static_cast<hipStream_t>(stream));
   const int F = h->desc.input_dim, T1 = (T - 1) / 2, F1 = h->F1, c = (T1 - 1) / 2, F2 = h->F2;
   const int slot = g->slot;
   g->slot = (slot + 1) % ppasr_stream_group_s::kRing;

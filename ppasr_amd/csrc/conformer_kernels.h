@@ -69,8 +69,9 @@ struct AttnArgs {
   int mask_mul;         // key j is PAD iff mask_mul*j >= len (4; 8 on time-reduced layers; x3 when grouped)
   int q_frames, kv_frames;  // valid frames behind the query / key tokens (== T1 / T2 unless grouped)
   int group;            // 1, or 3 = GroupedRelPositionMultiHeadedAttention (pos_u / pos_v are then [h][192])
-  // multi-session streaming (plain heads only): utterance b = session sess[b]: keys / values at k + sess*sess_stride,
-  // T2 = cache_t + T1 keys, positional rows from pos0; nullptr otherwise
+  // multi-session streaming: utterance b = session sess[b]: keys / values at k + sess*sess_stride, kv_frames =
+  // cache_t + q_frames key frames (T2 = ceil(kv_frames / group) tokens; T2 / kv_frames here are not read), positional rows
+  // from pos0; nullptr otherwise
   const SessDesc* sess;
   long long sess_stride;
   // ragged batches: 0 = every query row / key block is computed; n > 0 = query rows behind the valid frames + (n - 1)
@@ -246,6 +247,7 @@ void launch_join_ln_qkv16(const JoinIn& jn, float* qkv, const LayerW& w, int M, 
 void launch_join16(const JoinIn& jn, int M, hipStream_t st);
 void launch_ln_qkv(const float* x1, float* qkv, const LayerW& w, int M, hipStream_t st, const PadSkip& ps = PadSkip{},
                    float* kc = nullptr, float* vc = nullptr, bool h3 = false);
+// g_hist (streaming): the GLU'd conv histories [B][ksize - 1][256] of the B chunks' sessions, or nullptr
 void launch_conv_ffn_stride(const float* g, const float* g_hist, const float* x2, float* x_out, const LayerW& w, const int64_t* lens, int B,
                             int Tp, int Ts, int n_chunks, int ksize, int mask_mul_out, hipStream_t st,
                             const PadSkip& ps = PadSkip{}, bool causal = true, bool h3 = false,
@@ -266,7 +268,8 @@ void launch_pw1_glu_layers(const float* xh_hist, float* g_hist, const HistLayer*
                            hipStream_t st);
 void launch_kv_append(const float* qkv, float* kc, float* vc, int n_rows, hipStream_t st);
 // session groups: every layer x every listed session in one launch; layer i of session sess[b] reads
-// xh_hist + sess[b].sess * sess_stride + i * lo * 256 in place and writes g_hist [n_layers][n][lo][256]
+// xh_hist + sess[b].sess * sess_stride + i * lo * 256 in place and writes the layer's slab of g_hist [n_layers][n * lo][256]
+// at row b * tab[i].rows (= b * (kernel_i - 1), where the conv kernels read it)
 void launch_pw1_glu_layers_group(const float* xh_hist, long long sess_stride, const SessDesc* sess, float* g_hist,
                                  const HistLayer* tab, int n_layers, int n, int lo, hipStream_t st);
 // multi-session variants: row (b, t) of the chunk batch <-> session sess[b]

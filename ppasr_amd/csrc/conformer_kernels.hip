@@ -1129,7 +1129,8 @@ __global__ __launch_bounds__(kThreads) void k_conv_ffn_stride(const float* __res
           const f32x4 wj = *reinterpret_cast<const f32x4*>(w.dw_w + t * kD + 4 * lane);
           f32x4 v = causal ? gp : f32x4{0.f, 0.f, 0.f, 0.f};
           if (f >= 0 && f < Tp) v = *reinterpret_cast<const f32x4*>(gb + (size_t)f * kD);
-          else if (f < 0 && g_hist) v = *reinterpret_cast<const f32x4*>(g_hist + (size_t)(LO + f) * kD + 4 * lane);  // streaming, B = 1
+          // streaming: the left context of output row (b, j) is the history of list position b, g_hist [B][LO][256]
+          else if (f < 0 && g_hist) v = *reinterpret_cast<const f32x4*>(g_hist + ((size_t)b * LO + LO + f) * kD + 4 * lane);
           out += wj * v;
         }
       }

@@ -44,7 +44,9 @@ __global__ __launch_bounds__(kThreads) void k_pw1_glu(const float* __restrict__ 
 // the same for every layer's history in ONE launch (streaming: the histories only depend on the previous chunk, so the
 // twelve small launches need not sit between the layers): block (i, b) = layer i of list position b, tab[i] = its weights /
 // rows.  One stream: sess == nullptr, gridDim.y = 1.  Session groups: the history of session sess[b].sess is read in place
-// (xh_hist + sess * sess_stride), g_hist is [layer][b][lo_stride][256] -- the per-session layout dwconv_phase reads.
+// (xh_hist + sess * sess_stride); layer i's slab of g_hist holds gridDim.y x lo_stride rows, list position b at
+// b * tab[i].rows -- the per-session layout dwconv_phase / k_conv_ffn_stride read (b * (KS_i - 1)), also when the layers'
+// kernel sizes differ (Efficient-Conformer: 7 taps behind the stride layer).
 __global__ __launch_bounds__(kThreads) void k_pw1_glu_layers(const float* __restrict__ xh_hist, float* __restrict__ g_hist,
                                                              const HistLayer* __restrict__ tab, int lo_stride,
                                                              const SessDesc* __restrict__ sess, long long sess_stride) {
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void k_pw1_glu_layers(const float* __rest
   const int layer = blockIdx.x, b = blockIdx.y;
   const HistLayer t = tab[layer];
   const float* xhat = xh_hist + (sess ? (size_t)sess[b].sess * sess_stride : 0) + (size_t)layer * lo_stride * kD;
-  float* g = g_hist + ((size_t)layer * gridDim.y + b) * lo_stride * kD;
+  float* g = g_hist + ((size_t)layer * gridDim.y * lo_stride + (size_t)b * t.rows) * kD;
   const int lane = lane_id(), wave = wave_id();
   const int valid = min(kRows, t.rows);
   const int col = wave * 32 + (lane & 31);

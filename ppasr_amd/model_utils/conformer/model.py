@@ -398,8 +398,8 @@ class ConformerStream:
 class StreamHandleSet:
     """The interface of ``ConformerStreamGroup`` over per-session stream handles (``model.new_stream()``): for the handles
     whose sessions ``make_stream_group`` builds no group for (``ppasr_stream_group_create`` is built for plain Conformer
-    handles; Squeezeformer groups are opt-in, ``SqueezeformerStreamGroup``; Efficient-Conformer models keep grouped
-    attention and a stride layer per session).  Same results as driving each session's own stream; N sets of launches per round instead of one."""
+    handles; Squeezeformer and Efficient-Conformer groups are opt-in, ``SqueezeformerStreamGroup`` /
+    ``EfficientConformerStreamGroup``).  Same results as driving each session's own stream; N sets of launches per round instead of one."""
 
     def __init__(self, model, n_sessions, max_frames=0):
         self.model = model
@@ -443,7 +443,7 @@ class ConformerStreamGroup:
     (their rows are stacked), so a server's throughput is no longer bound by per-chunk launch overhead.  Every session
     follows ``ConformerStream.encode_chunk(chunk, required_cache_size=-16)`` exactly (full history)."""
 
-    _create = "ppasr_stream_group_create"  # the C-ABI call that builds the group (SqueezeformerStreamGroup: its own)
+    _create = "ppasr_stream_group_create"  # the C-ABI call that builds the group (the other families' groups: their own)
 
     def __init__(self, model, n_sessions, max_frames=0):
         self.model = model

@@ -10,9 +10,9 @@ import numpy as np
 import torch
 
 from ppasr_amd import _lib
-from ppasr_amd.model_utils.conformer.model import ConformerModel, _pe_table
+from ppasr_amd.model_utils.conformer.model import ConformerModel, ConformerStreamGroup, _pe_table
 
-__all__ = ["EfficientConformerModel"]
+__all__ = ["EfficientConformerModel", "EfficientConformerStreamGroup"]
 
 
 class EfficientConformerModel(ConformerModel):
@@ -106,3 +106,15 @@ class EfficientConformerModel(ConformerModel):
         self._h = handle
         self._ws = None
         self._taps = None
+
+
+class EfficientConformerStreamGroup(ConformerStreamGroup):
+    """``ConformerStreamGroup``'s interface for a streaming Efficient-Conformer model with at most one stride layer
+    (``ppasr_eff_stream_group_create``): the listed sessions advance by one chunk each with ONE set of kernel launches per
+    round, their full-rate and half-rate layers' rows stacked.  Every session follows
+    ``new_stream().encode_chunk(chunk, required_cache_size=-16)`` (full history); a round that any listed session's stream
+    would refuse (odd cache length, ``max_len``, capacity) raises and leaves every session as it was.  Not what
+    ``make_stream_group`` picks (that stays ``StreamHandleSet`` for this family); pass it to
+    ``serving.StreamPool(..., group=...)``."""
+
+    _create = "ppasr_eff_stream_group_create"

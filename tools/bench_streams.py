@@ -5,7 +5,12 @@ streams from one host thread.  Prints the aggregate audio-seconds/s and the sing
                              PPASR: 12 blocks, reduce before 5, recover before 11, kernel 31), SqueezeformerStreamGroup
                              against StreamHandleSet at n = 1 / 8 / 64 / 256, measured alternately in this process
   --sq-rounds R --sessions N only R group rounds of N sessions (after model set-up, nothing else): run it under
-                             `rocprofv3 --kernel-trace --stats` at two R and subtract for the dispatches per round"""
+                             `rocprofv3 --kernel-trace --stats` at two R and subtract for the dispatches per round
+  --efficient-conformer      the same section for the Efficient-Conformer: the shipped configuration
+                             (configs/efficient_conformer.yml of PPASR: 12 blocks, stride layer 3, grouped attention on
+                             layers 0-3 with group size 3, kernel 15 -> 7), EfficientConformerStreamGroup against
+                             StreamHandleSet
+  --eff-rounds R --sessions N  R Efficient-Conformer group rounds of N sessions, for the dispatch count as above"""
 import json, os, sys, time
 import numpy as np
 import torch
@@ -28,19 +33,28 @@ def squeezeformer_model():
     return SqueezeformerModel(80, V, streaming=True, encoder_conf=conf, state_dict=sd, device="cuda:0")
 
 
-def squeezeformer_section(n_chunks=8, sizes=(1, 8, 64, 256), reps=3):
+def efficient_conformer_model():
+    from ppasr_amd.model_utils.efficient_conformer.model import EfficientConformerModel
+    from ppasr_amd.utils.synth import efficient_conformer_state_dict
+    V = DEFAULT_VOCAB_SIZE
+    conf = dict(output_size=256, attention_heads=4, linear_units=2048, num_blocks=12, cnn_module_kernel=15,
+                cnn_module_norm="layer_norm",
+                efficient_conf=dict(stride_layer_idx=[3], stride=[2], group_layer_idx=[0, 1, 2, 3], group_size=3))
+    sd = efficient_conformer_state_dict(vocab_size=V, seed=1234)
+    return EfficientConformerModel(80, V, streaming=True, encoder_conf=conf, state_dict=sd, device="cuda:0")
+
+
+def group_section(family, model, group_cls, n_chunks=8, sizes=(1, 8, 64, 256), reps=3):
     """ms per round and audio-s/s of one 0.64 s chunk per session per round: the group (one set of launches per round)
     and StreamHandleSet (one stream handle per session, what make_stream_group gives this family) at the same n,
     measured alternately (warm-up, then `reps` timed passes of each; the median is printed)."""
     from ppasr_amd.model_utils.conformer.model import StreamHandleSet
-    from ppasr_amd.model_utils.squeezeformer.model import SqueezeformerStreamGroup
-    model = squeezeformer_model()
     x, _ = synth_features(1, 67, seed=5)
     chunk = torch.from_numpy(x).cuda()
     for n in sizes:
         batch = chunk.repeat(n, 1, 1).contiguous()
         ids = list(range(n))
-        kinds = {"group": SqueezeformerStreamGroup(model, n, max_frames=16 * (n_chunks + 2)),
+        kinds = {"group": group_cls(model, n, max_frames=16 * (n_chunks + 2)),
                  "handle_set": StreamHandleSet(model, n)}
         times = {k: [] for k in kinds}
         for rep in range(reps + 1):  # rep 0 = warm-up
@@ -55,26 +69,36 @@ def squeezeformer_section(n_chunks=8, sizes=(1, 8, 64, 256), reps=3):
                     times[k].append(time.perf_counter() - t)
         for k in kinds:
             dt = float(np.median(times[k]))
-            print(json.dumps({"family": "squeezeformer", "route": k, "sessions": n,
+            print(json.dumps({"family": family, "route": k, "sessions": n,
                               "ms_per_chunk_round": round(dt / n_chunks * 1e3, 3),
                               "audio_s_per_s": round(n * n_chunks * 0.64 / dt, 1)}), flush=True)
         del kinds
 
 
-if "--sq-rounds" in sys.argv:
-    from ppasr_amd.model_utils.squeezeformer.model import SqueezeformerStreamGroup
-    _model = squeezeformer_model()
-    _n, _R = _arg("--sessions", 1), _arg("--sq-rounds", 10)
-    _g = SqueezeformerStreamGroup(_model, _n, max_frames=16 * (_R + 2))
-    _batch = torch.from_numpy(synth_features(1, 67, seed=5)[0]).cuda().repeat(_n, 1, 1).contiguous()
-    torch.cuda.synchronize()
-    for _ in range(_R):
-        _g.encode_chunks(list(range(_n)), _batch)
-    torch.cuda.synchronize()
-    print(json.dumps({"sq_rounds": _R, "sessions": _n}), flush=True)
-    sys.exit(0)
+for _flag in ("--sq-rounds", "--eff-rounds"):
+    if _flag in sys.argv:
+        if _flag == "--sq-rounds":
+            from ppasr_amd.model_utils.squeezeformer.model import SqueezeformerStreamGroup as _cls
+            _model = squeezeformer_model()
+        else:
+            from ppasr_amd.model_utils.efficient_conformer.model import EfficientConformerStreamGroup as _cls
+            _model = efficient_conformer_model()
+        _n, _R = _arg("--sessions", 1), _arg(_flag, 10)
+        _g = _cls(_model, _n, max_frames=16 * (_R + 2))
+        _batch = torch.from_numpy(synth_features(1, 67, seed=5)[0]).cuda().repeat(_n, 1, 1).contiguous()
+        torch.cuda.synchronize()
+        for _ in range(_R):
+            _g.encode_chunks(list(range(_n)), _batch)
+        torch.cuda.synchronize()
+        print(json.dumps({_flag[2:].replace("-", "_"): _R, "sessions": _n}), flush=True)
+        sys.exit(0)
 if "--squeezeformer" in sys.argv:
-    squeezeformer_section()
+    from ppasr_amd.model_utils.squeezeformer.model import SqueezeformerStreamGroup
+    group_section("squeezeformer", squeezeformer_model(), SqueezeformerStreamGroup)
+    sys.exit(0)
+if "--efficient-conformer" in sys.argv:
+    from ppasr_amd.model_utils.efficient_conformer.model import EfficientConformerStreamGroup
+    group_section("efficient_conformer", efficient_conformer_model(), EfficientConformerStreamGroup)
     sys.exit(0)
 
 V = DEFAULT_VOCAB_SIZE
