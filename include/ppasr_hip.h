@@ -449,6 +449,42 @@ PPASR_API ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int*
                                       float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
                                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- beam-search session pools (no reference counterpart as a pool) ---------------------------------------------
+ * Replaces N x CtcBeamSearchDecoderBatch.next() + decode() (swig_wrapper.py:106-121, beam_search_decoder.py:75-96: one
+ * streaming decoder object per session) for a server that decodes many streams: n_sessions independent streaming CTC
+ * prefix beam searches with one configuration (V, beam_size, cutoff_prob / cutoff_top_n, blank, optional scorer with
+ * alpha / beta; lm must outlive the pool).  ppasr_beam_pool_decode advances any subset of the sessions by one chunk with
+ * ONE pruning launch and ONE search launch; each listed session's result is the one its own
+ * ppasr_ctc_beam_search_ws(init_state = 1, then 0, ...) sequence on the same chunks gives.  Refused configurations
+ * (vocabulary, beam, LDS fit): the codes of ppasr_ctc_beam_search_ws, at create.
+ * The pool owns its device memory: each session a state block sized for its own frame capacity, init_frames at first.
+ * A call whose chunk would take a session past its capacity first moves that session's block into one twice the size
+ * (doubling until it fits; the other sessions' blocks are not touched) and SYNCHRONISES `stream` once before freeing the
+ * replaced blocks.  Calls on one pool are serialised on one stream. */
+typedef struct ppasr_beam_pool_s* ppasr_beam_pool;
+PPASR_API ppasr_status ppasr_beam_pool_create(int n_sessions, int V, int beam_size, double cutoff_prob, int cutoff_top_n,
+                                              int blank, ppasr_lm_handle lm /* or NULL */, double alpha, double beta,
+                                              int init_frames, ppasr_beam_pool* out);
+PPASR_API ppasr_status ppasr_beam_pool_destroy(ppasr_beam_pool pool);
+/* A new search for one session (session < 0: all): one small launch per session on `stream`. */
+PPASR_API ppasr_status ppasr_beam_pool_reset(ppasr_beam_pool pool, int session, void* stream);
+/* Cumulative frames a session decoded since its last reset; its current frame capacity (-1: bad argument). */
+PPASR_API long long    ppasr_beam_pool_frames(ppasr_beam_pool pool, int session);
+PPASR_API long long    ppasr_beam_pool_capacity(ppasr_beam_pool pool, int session);
+/* Reads back the n_sessions status words (non-zero: a prefix arena ran out -- growth is planned so that it does not);
+ * PPASR_ENOSPACE if any is set.  Synchronises `stream`. */
+PPASR_API ppasr_status ppasr_beam_pool_status(ppasr_beam_pool pool, int32_t* status_host, void* stream);
+/* Device workspace of a call listing n sessions with chunks of T frames: the pruning records and, for cutoff_prob >= 1
+ * or element lists that do not fit LDS, the search's scratch (ppasr_ctc_beam_scratch_bytes).  May be 0. */
+PPASR_API size_t       ppasr_beam_pool_workspace_bytes(ppasr_beam_pool pool, int n, int T);
+/* sessions_host [n] distinct indices; probs device [n][T][V] f32; frame_lens_host [n] in [0, T] or NULL (all T).  Outputs
+ * by list position, the n-best = 1 hypothesis: tokens [n][max_tokens] (-1 padded), lens [n], scores [n] f64 = -log P
+ * (approx_ctc with a scorer).  Every argument is checked before any device work; a refused call (PPASR_EINVAL,
+ * PPASR_ENOSPACE) changes no session. */
+PPASR_API ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool pool, const int* sessions_host, int n, const float* probs, int T,
+                                              const int32_t* frame_lens_host, int max_tokens, int32_t* tokens, int32_t* lens,
+                                              double* scores, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Kaldi-compatible fbank front-end --------------------------------------------
  * Replaces AudioFeaturizer.featurize (ppasr/data_utils/featurizer/audio_featurizer.py:37-67,120-138):
  * AudioSegment.normalize(target_dB) (data_utils/audio.py:287-304) -> .to('int16') (audio.py:244) ->

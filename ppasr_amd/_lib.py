@@ -141,6 +141,17 @@ SYMBOLS = [
     ("ppasr_group_chunk_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int]),
     ("ppasr_encode_chunk_group", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _vp, ctypes.c_int, _vp,
                                                 _vp, _vp, ctypes.POINTER(ctypes.c_int), _vp, ctypes.c_size_t, _vp]),
+    ("ppasr_beam_pool_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                              ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                              ctypes.POINTER(_vp)]),
+    ("ppasr_beam_pool_destroy", ctypes.c_int, [_vp]),
+    ("ppasr_beam_pool_reset", ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    ("ppasr_beam_pool_frames", ctypes.c_longlong, [_vp, ctypes.c_int]),
+    ("ppasr_beam_pool_capacity", ctypes.c_longlong, [_vp, ctypes.c_int]),
+    ("ppasr_beam_pool_status", ctypes.c_int, [_vp, _vp, _vp]),
+    ("ppasr_beam_pool_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int]),
+    ("ppasr_beam_pool_decode", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _vp, ctypes.c_int, _vp,
+                                              ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     ("ppasr_fbank_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                           ctypes.POINTER(_vp)]),
     ("ppasr_fbank_destroy", ctypes.c_int, [_vp]),

@@ -1251,6 +1251,234 @@ ppasr_status ppasr_ctc_beam_status(const void* state, size_t state_bytes, int B,
   return PPASR_OK;
 }
 
+// ---- beam-search session pools (include/ppasr_hip.h: ppasr_beam_pool_*) ----
+// Every session owns its state block (ctc_beam.h layout, sized for its own frame capacity) and a status word; a decode
+// call builds a slot table of the listed sessions' blocks (by list position) and runs the pruning pre-pass and the search
+// once for all of them.  Growth is planned on the host from the sessions' frame counters before anything is launched.
+struct ppasr_beam_pool_s {
+  BeamConfig cfg;  // shared configuration (max_nodes / max_tokens / fast_path set per call)
+  int n_sessions;
+  std::vector<int32_t*> block;   // device state block of each session
+  std::vector<size_t> cap;       // frames each block is sized for
+  std::vector<long long> frames; // cumulative frames decoded since the session's last reset
+  int32_t* status;               // device [n_sessions]
+  // per-call slot tables + frame counts: a ring of pinned host staging buffers and device copies, each guarded by an
+  // event, so that a call never overwrites a buffer an earlier (still queued) call reads
+  static constexpr int kRing = 8;
+  size_t ring_bytes;  // per ring entry: [n_sessions] BeamSlot, then [n_sessions] int32 frame counts
+  char* ring_host;
+  char* ring_dev;
+  hipEvent_t ev[kRing];
+  int ring;
+};
+
+namespace {
+size_t pool_block_bytes(size_t F, int beam) { return 4 * beam_state_words(beam, (int)beam_max_nodes(F, beam)); }
+size_t pool_rec_bytes(const BeamConfig& c, int n, int T) {  // narrow pruning records (wide ones live in the scratch)
+  return c.n_cand_max > kSmallCand ? 0 : (((size_t)n * T * prune_rec_words(c.n_cand_max) * 4 + 255) & ~(size_t)255);
+}
+// largest capacity whose arena node count still fits the kernel's int arithmetic
+bool pool_cap_ok(size_t F, int beam) { return F <= (size_t)(0x3fffffff / beam) - 2; }
+}  // namespace
+
+ppasr_status ppasr_beam_pool_create(int n_sessions, int V, int beam_size, double cutoff_prob, int cutoff_top_n, int blank,
+                                    ppasr_lm_handle lm, double alpha, double beta, int init_frames, ppasr_beam_pool* out) {
+  if (!out) return fail(PPASR_EINVAL, "null argument");
+  *out = nullptr;
+  if (n_sessions < 1 || init_frames < 1) return fail(PPASR_EINVAL, "beam pool: n_sessions and init_frames must be >= 1");
+  BeamConfig c{};
+  if (lm) {  // before beam_config: the LDS budget depends on it
+    c.lm = *ppasr::lm_device_view(lm);
+    c.alpha = alpha;
+    c.beta = beta;
+  }
+  ppasr_status s = beam_config(V, beam_size, cutoff_prob, cutoff_top_n, blank, 1, 1, &c);
+  if (s != PPASR_OK) return s;
+  if (!pool_cap_ok((size_t)init_frames, beam_size)) return fail(PPASR_EINVAL, "beam pool: init_frames too large");
+  c.node_table = lm && c.lm.word_based;
+  auto* p = new ppasr_beam_pool_s();  // (value-initialised: every pointer and event null until it exists)
+  p->cfg = c;
+  p->n_sessions = n_sessions;
+  p->block.assign(n_sessions, nullptr);
+  p->cap.assign(n_sessions, (size_t)init_frames);
+  p->frames.assign(n_sessions, 0);
+  p->ring_bytes = ((size_t)n_sessions * (sizeof(BeamSlot) + 4) + 255) & ~(size_t)255;
+  auto bail = [p](const char* what, hipError_t e) {
+    (void)ppasr_beam_pool_destroy(p);
+    return fail(PPASR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  };
+  const size_t bb = pool_block_bytes((size_t)init_frames, beam_size);
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->status), (size_t)n_sessions * 4);
+  for (int i = 0; i < n_sessions && e == hipSuccess; ++i) e = hipMalloc(reinterpret_cast<void**>(&p->block[i]), bb);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->ring_dev), ppasr_beam_pool_s::kRing * p->ring_bytes);
+  if (e == hipSuccess)
+    e = hipHostMalloc(reinterpret_cast<void**>(&p->ring_host), ppasr_beam_pool_s::kRing * p->ring_bytes, hipHostMallocDefault);
+  if (e != hipSuccess) return bail("allocation failed for the beam pool", e);
+  for (int i = 0; i < ppasr_beam_pool_s::kRing; ++i) {
+    e = hipEventCreateWithFlags(&p->ev[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+      p->ev[i] = nullptr;
+      return bail("creating the beam-pool events failed", e);
+    }
+  }
+  for (int i = 0; i < n_sessions; ++i) {
+    e = launch_beam_reset(p->block[i], p->status + i, beam_size, (int)beam_max_nodes(p->cap[i], beam_size), c.lm.bos,
+                          c.node_table != 0, nullptr);
+    if (e != hipSuccess) return bail("initialising the beam-pool sessions failed", e);
+  }
+  e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) return bail("initialising the beam-pool sessions failed", e);
+  *out = p;
+  return PPASR_OK;
+}
+
+ppasr_status ppasr_beam_pool_destroy(ppasr_beam_pool p) {
+  if (!p) return fail(PPASR_EINVAL, "null pool");
+  for (hipEvent_t ev : p->ev)
+    if (ev) (void)hipEventSynchronize(ev);
+  for (int32_t* b : p->block)
+    if (b) (void)hipFree(b);
+  if (p->status) (void)hipFree(p->status);
+  if (p->ring_dev) (void)hipFree(p->ring_dev);
+  if (p->ring_host) (void)hipHostFree(p->ring_host);
+  for (hipEvent_t ev : p->ev)
+    if (ev) (void)hipEventDestroy(ev);
+  delete p;
+  return PPASR_OK;
+}
+
+ppasr_status ppasr_beam_pool_reset(ppasr_beam_pool p, int session, void* stream) {
+  if (!p) return fail(PPASR_EINVAL, "null pool");
+  if (session >= p->n_sessions) return fail(PPASR_EINVAL, "beam pool: session out of range");
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const int lo = session < 0 ? 0 : session, hi = session < 0 ? p->n_sessions : session + 1;
+  for (int i = lo; i < hi; ++i) {
+    HIP_TRY(launch_beam_reset(p->block[i], p->status + i, p->cfg.beam, (int)beam_max_nodes(p->cap[i], p->cfg.beam),
+                              p->cfg.lm.bos, p->cfg.node_table != 0, hs));
+    p->frames[i] = 0;
+  }
+  return PPASR_OK;
+}
+
+long long ppasr_beam_pool_frames(ppasr_beam_pool p, int session) {
+  if (!p || session < 0 || session >= p->n_sessions) return -1;
+  return p->frames[session];
+}
+
+long long ppasr_beam_pool_capacity(ppasr_beam_pool p, int session) {
+  if (!p || session < 0 || session >= p->n_sessions) return -1;
+  return (long long)p->cap[session];
+}
+
+ppasr_status ppasr_beam_pool_status(ppasr_beam_pool p, int32_t* status_host, void* stream) {
+  if (!p || !status_host) return fail(PPASR_EINVAL, "null argument");
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemcpyAsync(status_host, p->status, (size_t)p->n_sessions * 4, hipMemcpyDeviceToHost, hs));
+  HIP_TRY(hipStreamSynchronize(hs));
+  for (int i = 0; i < p->n_sessions; ++i)
+    if (status_host[i] != 0) return fail(PPASR_ENOSPACE, "beam pool: the prefix arena of at least one session is exhausted");
+  return PPASR_OK;
+}
+
+size_t ppasr_beam_pool_workspace_bytes(ppasr_beam_pool p, int n, int T) {
+  if (!p || n < 1 || T < 0) return 0;
+  return pool_rec_bytes(p->cfg, n, T) + beam_scratch_bytes(p->cfg, n, T);
+}
+
+ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host, int n, const float* probs, int T,
+                                    const int32_t* frame_lens_host, int max_tokens, int32_t* tokens, int32_t* lens,
+                                    double* scores, void* workspace, size_t workspace_bytes, void* stream) {
+  // ---- every check before any device work: a refused call changes no session ----
+  if (!p || !sessions_host || !tokens || !lens || !scores || (!probs && T > 0)) return fail(PPASR_EINVAL, "null argument");
+  if (n < 1 || n > p->n_sessions || T < 0 || max_tokens < 1) return fail(PPASR_EINVAL, "beam pool: bad n / T / max_tokens");
+  std::vector<char> seen(p->n_sessions, 0);
+  std::vector<int> fl(n);
+  for (int b = 0; b < n; ++b) {
+    const int s = sessions_host[b];
+    if (s < 0 || s >= p->n_sessions || seen[s]) return fail(PPASR_EINVAL, "beam pool: session index out of range or repeated");
+    seen[s] = 1;
+    fl[b] = frame_lens_host ? frame_lens_host[b] : T;
+    if (fl[b] < 0 || fl[b] > T) return fail(PPASR_EINVAL, "beam pool: frame_lens must lie in [0, T]");
+  }
+  const size_t need = ppasr_beam_pool_workspace_bytes(p, n, T);
+  if (workspace_bytes < need || (need > 0 && !workspace))
+    return fail(PPASR_ENOSPACE, "beam pool: workspace smaller than ppasr_beam_pool_workspace_bytes(pool, n, T)");
+  const int beam = p->cfg.beam;
+  std::vector<size_t> new_cap(n, 0);  // 0: no growth
+  for (int b = 0; b < n; ++b) {
+    const int s = sessions_host[b];
+    const size_t want = (size_t)p->frames[s] + (size_t)fl[b];
+    if (want <= p->cap[s]) continue;
+    size_t c = p->cap[s];
+    while (c < want) c *= 2;
+    if (!pool_cap_ok(c, beam)) return fail(PPASR_ENOSPACE, "beam pool: a session's stream is too long for one prefix arena");
+    new_cap[b] = c;
+  }
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  // ---- growth: the session's block moves into one sized for twice the frames (doubling until the chunk fits).  Header,
+  // beam arrays and arena keep their offsets (ppasr_ctc_beam_state_grow); the node table, where the search uses one, is
+  // rebuilt for its new size.  The replaced blocks are freed after ONE stream synchronisation that covers every copy of
+  // this call (growth is rare: a session's capacity doubles, so a stream of F frames grows log2(F / init_frames) times).
+  std::vector<int32_t*> retired;
+  for (int b = 0; b < n; ++b) {
+    if (!new_cap[b]) continue;
+    const int s = sessions_host[b];
+    const int mo = (int)beam_max_nodes(p->cap[s], beam), mn = (int)beam_max_nodes(new_cap[b], beam);
+    int32_t* nb = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&nb), pool_block_bytes(new_cap[b], beam)));
+    const size_t head_words = beam_fixed_words(beam) + beam_arena_words(mo);
+    hipError_t e = hipMemcpyAsync(nb, p->block[s], head_words * 4, hipMemcpyDeviceToDevice, hs);
+    if (e == hipSuccess && p->cfg.node_table) {
+      const size_t tab_off = (beam_fixed_words(beam) + beam_arena_words(mn)) * 4, tab_bytes = 12 * beam_table_slots(mn);
+      e = hipMemsetAsync(reinterpret_cast<char*>(nb) + tab_off, 0, tab_bytes, hs);
+      if (e == hipSuccess) e = launch_beam_rehash(nb, 1, beam, mn, hs);
+    }
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(hs);
+      (void)hipFree(nb);
+      return fail(PPASR_EHIP, std::string("beam pool: growing a session failed: ") + hipGetErrorString(e));
+    }
+    retired.push_back(p->block[s]);
+    p->block[s] = nb;
+    p->cap[s] = new_cap[b];
+  }
+  if (!retired.empty()) {
+    HIP_TRY(hipStreamSynchronize(hs));
+    for (int32_t* o : retired) (void)hipFree(o);
+  }
+  // ---- the slot table and frame counts of this call ----
+  const int slot = p->ring;
+  p->ring = (slot + 1) % ppasr_beam_pool_s::kRing;
+  HIP_TRY(hipEventSynchronize(p->ev[slot]));  // the call that last used this entry has consumed it (no-op when unused)
+  char* host = p->ring_host + (size_t)slot * p->ring_bytes;
+  char* dev = p->ring_dev + (size_t)slot * p->ring_bytes;
+  BeamSlot* tab = reinterpret_cast<BeamSlot*>(host);
+  int32_t* fl_host = reinterpret_cast<int32_t*>(host + (size_t)n * sizeof(BeamSlot));
+  for (int b = 0; b < n; ++b) {
+    const int s = sessions_host[b];
+    tab[b] = BeamSlot{p->block[s], p->status + s, (int)beam_max_nodes(p->cap[s], beam), 0};
+    fl_host[b] = fl[b];
+  }
+  const size_t used = (size_t)n * (sizeof(BeamSlot) + 4);
+  HIP_TRY(hipMemcpyAsync(dev, host, used, hipMemcpyHostToDevice, hs));
+  BeamConfig c = p->cfg;
+  c.max_tokens = max_tokens;
+  c.max_nodes = 0;  // (per session: the slot table)
+  {
+    const char* f = getenv("PPASR_BEAM_FAST");  // (read per call, as ppasr_ctc_beam_search_ws does)
+    c.fast_path = f ? (atoi(f) != 0) : 1;
+  }
+  char* ws = static_cast<char*>(workspace);
+  const size_t rec_bytes = pool_rec_bytes(c, n, T), scratch_bytes = beam_scratch_bytes(c, n, T);
+  int32_t* recs = rec_bytes ? reinterpret_cast<int32_t*>(ws) : nullptr;
+  void* scratch = scratch_bytes ? ws + rec_bytes : nullptr;
+  HIP_TRY(launch_ctc_beam(probs, reinterpret_cast<const int32_t*>(dev + (size_t)n * sizeof(BeamSlot)), n, T, c, recs, nullptr,
+                          0, 1, tokens, lens, scores, nullptr, scratch, hs, reinterpret_cast<const BeamSlot*>(dev)));
+  HIP_TRY(hipEventRecord(p->ev[slot], hs));
+  for (int b = 0; b < n; ++b) p->frames[sessions_host[b]] += fl[b];
+  return PPASR_OK;
+}
+
 // ---- kernel-name profiler: every PPASR_LAUNCH of the calling thread between begin and end carries its own dispatch-attached
 // event pair (launch.h); entries are keyed by the kernel's function pointer and named from the code object, so the names
 // are the ones rocprofv3's kernel trace prints.  Covers every model family and the decoders (bench.py roofline leg). ----

@@ -68,11 +68,25 @@ size_t beam_state_bytes(const BeamConfig& c);  // per utterance
 // HBM scratch a call needs beyond the state buffer (0 for the shipped configurations): wide pruning records
 // (n_cand_max > kSmallCand) and / or per-utterance element lists that do not fit LDS
 size_t beam_scratch_bytes(const BeamConfig& c, int B, int T);
+// Per-session entry of a session pool's search (ppasr_beam_pool_decode): the session's own state block (sized for
+// max_nodes arena nodes, ctc_beam.h layout) and status word.  A launch with a slot table reads entry u for workgroup u
+// instead of state + u * beam_state_words(beam, cfg.max_nodes) / cfg.max_nodes / status[u].
+struct BeamSlot {
+  int32_t* state;
+  int32_t* status;
+  int max_nodes;
+  int pad;
+};
 // prune_recs: the state buffer's record area, B * T * prune_rec_words(cfg.n_cand_max) words (narrow records); wide records
 // are written to `scratch`.  `scratch`: beam_scratch_bytes(cfg, B, T) bytes or nullptr when that is 0
 hipError_t launch_ctc_beam(const float* probs, const int32_t* frame_lens, int B, int T, const BeamConfig& cfg,
                            int32_t* prune_recs, int32_t* state, int init_state, int finalize, int32_t* out_tokens, int32_t* out_lens,
-                           double* out_scores, int32_t* status, void* scratch, hipStream_t st);
+                           double* out_scores, int32_t* status, void* scratch, hipStream_t st,
+                           const BeamSlot* slots = nullptr);  // slots: device table [B] (state / status unused then)
+// writes the root state of ONE state block (what init_state = 1 starts from), zeroes its status word and, when
+// clear_table, its node table: a session of a pool starts a new search with init_state = 0
+hipError_t launch_beam_reset(int32_t* state, int32_t* status, int beam, int max_nodes, int bos, bool clear_table,
+                             hipStream_t st);
 
 // rebuilds the node tables of B state blocks (cleared by the caller) from their arenas: after a streaming state buffer grew
 hipError_t launch_beam_rehash(int32_t* state, int B, int beam, int max_nodes, hipStream_t st);

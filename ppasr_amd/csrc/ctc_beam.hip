@@ -28,6 +28,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "ctc_beam.h"
@@ -581,14 +582,16 @@ __global__ __launch_bounds__(kWideThreads) void k_ctc_prune_wide(const float* __
 // with full rows.  The result is therefore the full-row result bit for bit: same survivors, same order, same node ids.
 // LM: 0 no scorer, 1 character-based, 2 word-based (compile-time: the scorer's look-ups cost ~80 registers, which a
 // 1 024-thread workgroup -- 128 per lane -- does not have to spare on the scorer-less path)
-template <int BT, int LM, bool WIDE>
+// SLOTS (session pools, ppasr_beam_pool_decode): workgroup u takes its state block, arena capacity and status word from
+// slots[u] instead of state + u * words / cfg.max_nodes / status[u]; everything else is indexed by list position as before
+template <int BT, int LM, bool WIDE, bool SLOTS>
 __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ probs, const int32_t* __restrict__ frame_lens,
                                                   int T, BeamConfig cfg, const int32_t* __restrict__ recs,
                                                   int32_t* __restrict__ state, int init_state,
                                                   int finalize, int32_t* __restrict__ out_tokens,
                                                   int32_t* __restrict__ out_lens, double* __restrict__ out_scores,
                                                   int32_t* __restrict__ status, char* __restrict__ scratch_lists,
-                                                  size_t scratch_list_stride) {
+                                                  size_t scratch_list_stride, const BeamSlot* __restrict__ slots) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NW = BT / 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -649,11 +652,17 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
   for (uint32_t i = tid; i < plan.total / 4; i += BT) reinterpret_cast<uint32_t*>(smem)[i] = (uint32_t)(PPASR_BEAM_POISON);
   __syncthreads();
 #endif
-  int32_t* st = state + (size_t)u * beam_state_words(beam, cfg.max_nodes);
+  const int max_nodes = SLOTS ? slots[u].max_nodes : cfg.max_nodes;
+  int32_t* st = SLOTS ? slots[u].state : state + (size_t)u * beam_state_words(beam, max_nodes);
+  int32_t* status_u = SLOTS ? slots[u].status : status;  // (the contiguous form indexes status[u], as it always did)
+  auto set_status = [&](int v) {
+    if (SLOTS) *status_u = v;
+    else if (status) status[u] = v;
+  };
   int32_t* g_arr = st + 2;
   int32_t* arena = st + beam_fixed_words(beam);
-  const size_t tslots = beam_table_slots(cfg.max_nodes);
-  unsigned long long* tkeys = reinterpret_cast<unsigned long long*>(arena + beam_arena_words(cfg.max_nodes));  // (8-byte aligned)
+  const size_t tslots = beam_table_slots(max_nodes);
+  unsigned long long* tkeys = reinterpret_cast<unsigned long long*>(arena + beam_arena_words(max_nodes));  // (8-byte aligned)
   int32_t* tids = reinterpret_cast<int32_t*>(tkeys + tslots);
   int nb, n_nodes;
   if (init_state) {
@@ -1024,7 +1033,7 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
       } else {
         const int i = (code >> 14) & 0xFFFF, kk = code & 0x3FFF;
         const int c = cand_c(kk);
-        if (!cfg.node_table && id < cfg.max_nodes) { arena[kArenaWords * (size_t)id] = cur.node[i]; arena[kArenaWords * (size_t)id + 1] = c; }
+        if (!cfg.node_table && id < max_nodes) { arena[kArenaWords * (size_t)id] = cur.node[i]; arena[kArenaWords * (size_t)id + 1] = c; }
         if (word_lm) {
           // the LM context holds WORDS: it moves on when a space completes one.  The dictionary state belongs to the trie
           // node: a new node starts where the arc leads, a revived one is where it was left (a final state may have been
@@ -1032,7 +1041,7 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
           const int to = lm_dict_arc(cfg.lm, new_dst[i], c);
           if (fresh) {
             nxt.dst[pos] = to;
-            if (id < cfg.max_nodes) arena[kArenaWords * (size_t)id + 2] = to;
+            if (id < max_nodes) arena[kArenaWords * (size_t)id + 2] = to;
           } else {
             nxt.dst[pos] = arena[kArenaWords * (size_t)id + 2];
           }
@@ -1259,7 +1268,7 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
       ts_n += NL; ts_c += C; ts_nb += nb;
 #endif
       if (!in_lds && !lkey_g) {  // (the host refuses configurations that can get here without scratch; defensive)
-        if (tid == 0 && status) status[u] = 2;
+        if (tid == 0) set_status(2);
         clip = false;
         k_sel = -1;
         break;
@@ -1313,7 +1322,7 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
               }
               if (kr >= 0) {
                 nd = 0;
-                if (cur.node[q] < cfg.max_nodes) arena[kArenaWords * (size_t)cur.node[q] + 2] = 0;  // (the node's own state)
+                if (cur.node[q] < max_nodes) arena[kArenaWords * (size_t)cur.node[q] + 2] = 0;  // (the node's own state)
               }
             }
             k_reset[q] = kr;
@@ -1624,7 +1633,7 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
       const int before = block_excl_scan<NW>(miss, wave_tot + 3 * NW, n_miss);
       if (miss) {
         my_id = n_nodes + before;
-        if (my_id < cfg.max_nodes) {
+        if (my_id < max_nodes) {
           arena[kArenaWords * (size_t)my_id] = my_parent;
           arena[kArenaWords * (size_t)my_id + 1] = my_char;
           const unsigned long long key = beam_node_key(my_parent, my_char);
@@ -1648,8 +1657,8 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
     nb = __builtin_amdgcn_readfirstlane(k_sel);
     n_nodes = n_nodes_next;
     if (cfg.node_table) __threadfence_block();  // its entries are looked up by other threads of this block in later frames
-    if (n_nodes + beam > cfg.max_nodes) {  // arena exhausted: report, stop consuming frames
-      if (tid == 0 && status) status[u] = 1;
+    if (n_nodes + beam > max_nodes) {  // arena exhausted: report, stop consuming frames
+      if (tid == 0) set_status(1);
       Beam tmp = cur; cur = nxt; nxt = tmp;
       break;
     }
@@ -1809,9 +1818,43 @@ hipError_t launch_beam_rehash(int32_t* state, int B, int beam, int max_nodes, hi
   return hipGetLastError();
 }
 
+// Root state of one session (session pools): what k_ctc_beam's init_state branch puts in LDS, written to the state block
+// instead -- one hypothesis (node 0, no character, no parent, log P_b = 0, log P_nb = -inf, score 0, <s>-padded LM
+// context, dictionary start state), the root node in the arena -- plus a zero status word and, for searches that use it
+// (BeamConfig::node_table), an empty node table.  A search with init_state = 0 then starts exactly where one with
+// init_state = 1 starts.
+__global__ __launch_bounds__(256) void k_beam_reset(int32_t* __restrict__ st, int32_t* __restrict__ status, int beam,
+                                                    int max_nodes, int bos, int clear_table) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    int32_t* g_arr = st + 2;
+    int32_t* arena = st + beam_fixed_words(beam);
+    st[0] = 1;
+    st[1] = 1;
+    g_arr[0] = 0; g_arr[beam] = -1; g_arr[2 * beam] = -1;
+    g_arr[3 * beam] = __float_as_int(0.f); g_arr[4 * beam] = __float_as_int(kNegInf); g_arr[5 * beam] = __float_as_int(0.f);
+    for (int j = 0; j < kLmCtx; ++j) g_arr[(6 + j) * beam] = bos;
+    g_arr[(6 + kLmCtx) * beam] = 0;
+    arena[0] = -1; arena[1] = -1; arena[2] = 0;
+    *status = 0;
+  }
+  if (clear_table) {
+    int32_t* tab = st + beam_fixed_words(beam) + beam_arena_words(max_nodes);
+    const size_t words = 3 * beam_table_slots(max_nodes);  // uint64 keys, then int32 ids
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) tab[i] = 0;
+  }
+}
+hipError_t launch_beam_reset(int32_t* state, int32_t* status, int beam, int max_nodes, int bos, bool clear_table,
+                             hipStream_t st) {
+  const size_t words = clear_table ? 3 * beam_table_slots(max_nodes) : 0;
+  const int blocks = (int)std::min<size_t>(std::max<size_t>((words + 255) / 256, 1), 1024);
+  PPASR_LAUNCH(k_beam_reset, dim3(blocks), dim3(256), 0, st, state, status, beam, max_nodes, bos, clear_table ? 1 : 0);
+  return hipGetLastError();
+}
+
 hipError_t launch_ctc_beam(const float* probs, const int32_t* frame_lens, int B, int T, const BeamConfig& cfg,
                            int32_t* prune_recs, int32_t* state, int init_state, int finalize, int32_t* out_tokens,
-                           int32_t* out_lens, double* out_scores, int32_t* status, void* scratch, hipStream_t st) {
+                           int32_t* out_lens, double* out_scores, int32_t* status, void* scratch, hipStream_t st,
+                           const BeamSlot* slots) {
   const size_t lds = beam_lds_bytes(cfg);
   const bool wide = cfg.n_cand_max > kSmallCand;
   // threads per utterance by the number of (hypothesis, candidate) elements a frame can have: every phase is a chain of
@@ -1853,15 +1896,20 @@ hipError_t launch_ctc_beam(const float* probs, const int32_t* frame_lens, int B,
       PPASR_LAUNCH(k_ctc_prune<kPruneThreads>, dim3(T, B), dim3(kPruneThreads), plds, st, probs, frame_lens, T, cfg, recs);
     }
   }
-#define PPASR_LAUNCH_BEAM(BT, LMK, WIDE)                                                                                \
+#define PPASR_LAUNCH_BEAM_S(BT, LMK, WIDE, SL)                                                                          \
   do {                                                                                                                  \
-    const void* fn = reinterpret_cast<const void*>(k_ctc_beam<BT, LMK, WIDE>);                                          \
+    const void* fn = reinterpret_cast<const void*>(k_ctc_beam<BT, LMK, WIDE, SL>);                                      \
     if (lds > 48 * 1024) {                                                                                              \
       hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
       if (e != hipSuccess) return e;                                                                                    \
     }                                                                                                                   \
-    PPASR_LAUNCH((k_ctc_beam<BT, LMK, WIDE>), dim3(B), dim3(BT), lds, st, probs, frame_lens, T, cfg, recs, state,       \
-                 init_state, finalize, out_tokens, out_lens, out_scores, status, lists, list_stride);                   \
+    PPASR_LAUNCH((k_ctc_beam<BT, LMK, WIDE, SL>), dim3(B), dim3(BT), lds, st, probs, frame_lens, T, cfg, recs, state,   \
+                 init_state, finalize, out_tokens, out_lens, out_scores, status, lists, list_stride, slots);            \
+  } while (0)
+#define PPASR_LAUNCH_BEAM(BT, LMK, WIDE)                                                                                \
+  do {                                                                                                                  \
+    if (slots) PPASR_LAUNCH_BEAM_S(BT, LMK, WIDE, true);                                                                \
+    else PPASR_LAUNCH_BEAM_S(BT, LMK, WIDE, false);                                                                     \
   } while (0)
 #define PPASR_LAUNCH_BEAM_LM(BT, WIDE)                                                                                  \
   do {                                                                                                                  \
@@ -1874,6 +1922,7 @@ hipError_t launch_ctc_beam(const float* probs, const int32_t* frame_lens, int B,
   else PPASR_LAUNCH_BEAM_LM(512, false);
 #undef PPASR_LAUNCH_BEAM_LM
 #undef PPASR_LAUNCH_BEAM
+#undef PPASR_LAUNCH_BEAM_S
   return hipGetLastError();
 }
 

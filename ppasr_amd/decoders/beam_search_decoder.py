@@ -17,8 +17,8 @@ import torch
 
 from ppasr_amd import _lib
 
-__all__ = ["BeamSearchDecoder", "Scorer", "ctc_beam_search_decoding", "ctc_beam_search_decoding_batch",
-           "beam_search_ids"]
+__all__ = ["BeamSearchDecoder", "BeamSearchSessions", "Scorer", "ctc_beam_search_decoding",
+           "ctc_beam_search_decoding_batch", "beam_search_ids"]
 
 
 class Scorer:
@@ -256,3 +256,118 @@ class BeamSearchDecoder:
     def reset_decoder(self):
         """beam_search_decoder.py:93-96"""
         self._state = None
+
+
+class BeamSearchSessions:
+    """Many streaming beam searches with one configuration (``ppasr_beam_pool_*``; no reference counterpart as a pool --
+    the reference keeps one ``CtcBeamSearchDecoderBatch`` per stream, beam_search_decoder.py:75-96).  Built from
+    ``BeamSearchDecoder``'s arguments (``scorer``: share an existing ``Scorer`` instead of loading
+    ``language_model_path`` again; its alpha / beta at construction hold).  ``decode_chunks(sessions, probs)`` advances
+    the listed sessions by one chunk each with one pruning and one search launch; each session's (score, text) equals
+    what its own ``BeamSearchDecoder.decode_chunk`` sequence returns.  Sessions start with room for ``init_frames``
+    frames and double on demand."""
+
+    def __init__(self, n_sessions, alpha, beta, beam_size, cutoff_prob, cutoff_top_n, vocab_list, num_processes=10,
+                 blank_id=0, language_model_path=None, scorer=None, init_frames=256, device=None):
+        self.n_sessions, self.beam_size, self.init_frames = int(n_sessions), int(beam_size), int(init_frames)
+        self.vocab_list = list(vocab_list)
+        self.alpha, self.beta = alpha, beta
+        self.cutoff_prob, self.cutoff_top_n, self.blank_id = float(cutoff_prob), int(cutoff_top_n), int(blank_id)
+        self.num_processes = num_processes
+        if self.n_sessions < 1:
+            raise ValueError("BeamSearchSessions: n_sessions must be >= 1")
+        if self.init_frames < 1:
+            raise ValueError("BeamSearchSessions: init_frames must be >= 1")
+        if self.beam_size < 1 or self.cutoff_top_n < 1:
+            raise ValueError("BeamSearchSessions: beam_size and cutoff_top_n must be >= 1")
+        if len(self.vocab_list) < 2 or not 0 <= self.blank_id < len(self.vocab_list):
+            raise ValueError("BeamSearchSessions: the vocabulary needs two entries and must hold blank_id")
+        if scorer is not None and language_model_path:
+            raise ValueError("BeamSearchSessions: pass either scorer or language_model_path, not both")
+        if not torch.cuda.is_available():
+            raise _lib.PPASRHipError("no HIP device visible: ppasr_amd has no CPU fallback")
+        self._lib = _lib.load()
+        self._device = torch.device(device or f"cuda:{torch.cuda.current_device()}")
+        self._ext_scorer = scorer if scorer is not None else (
+            Scorer(alpha, beta, language_model_path, self.vocab_list, device=self._device) if language_model_path else None)
+        sc = self._ext_scorer
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self._device):
+            _lib.check(self._lib.ppasr_beam_pool_create(self.n_sessions, len(self.vocab_list), self.beam_size,
+                                                        self.cutoff_prob, self.cutoff_top_n, self.blank_id,
+                                                        None if sc is None else sc._h, 0.0 if sc is None else sc.alpha,
+                                                        0.0 if sc is None else sc.beta, self.init_frames, ctypes.byref(h)))
+        self._h = h
+        self._ws = {}
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self._lib.ppasr_beam_pool_destroy(h)
+            self._h = None
+
+    def _stream(self):
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    def reset(self, session=-1):
+        """A new search for one session (-1: every session)."""
+        if int(session) >= self.n_sessions:
+            raise ValueError(f"BeamSearchSessions.reset: session {session} out of range")
+        with torch.cuda.device(self._device):
+            _lib.check(self._lib.ppasr_beam_pool_reset(self._h, int(session), self._stream()))
+
+    def frames(self, session):
+        """Cumulative frames the session decoded since its last reset."""
+        if not 0 <= int(session) < self.n_sessions:
+            raise ValueError(f"BeamSearchSessions.frames: session {session} out of range")
+        return int(self._lib.ppasr_beam_pool_frames(self._h, int(session)))
+
+    def capacity(self, session):
+        """Frames the session's state block is currently sized for."""
+        if not 0 <= int(session) < self.n_sessions:
+            raise ValueError(f"BeamSearchSessions.capacity: session {session} out of range")
+        return int(self._lib.ppasr_beam_pool_capacity(self._h, int(session)))
+
+    def status(self):
+        """Status words of every session (non-zero: a prefix arena ran out).  Synchronises."""
+        out = np.zeros(self.n_sessions, np.int32)
+        with torch.cuda.device(self._device):
+            self._lib.ppasr_beam_pool_status(self._h, out.ctypes.data_as(ctypes.c_void_p), self._stream())
+        return out
+
+    def decode_chunks(self, sessions, probs, lens=None):
+        """sessions: distinct indices (n); probs [n,c,V] (device tensor or array); lens [n] frames of each chunk (None:
+        all c).  -> [(score, text)] by list position: each session's current best after this chunk.  One device-to-host
+        copy per call."""
+        ids = [int(s) for s in sessions]
+        n = len(ids)
+        if n < 1 or len(set(ids)) != n or any(not 0 <= s < self.n_sessions for s in ids):
+            raise ValueError("BeamSearchSessions.decode_chunks: sessions must be distinct indices in [0, n_sessions)")
+        p = torch.as_tensor(probs, dtype=torch.float32)
+        if p.dim() != 3 or int(p.shape[0]) != n or int(p.shape[2]) != len(self.vocab_list):
+            raise ValueError(f"BeamSearchSessions.decode_chunks: probs must be [{n}, c, {len(self.vocab_list)}], "
+                             f"got {tuple(p.shape)}")
+        T = int(p.shape[1])
+        fl = np.full(n, T, np.int32) if lens is None else np.asarray(lens).astype(np.int32).reshape(-1)
+        if fl.shape[0] != n or (fl < 0).any() or (fl > T).any():
+            raise ValueError("BeamSearchSessions.decode_chunks: lens must hold n values in [0, c]")
+        p = p.to(self._device).contiguous()
+        L = max(max(self.frames(s) for s in ids) + T, 1)
+        # one buffer for every output, so that the results come back with one copy: scores f64 [n], lens i32 [n], tokens
+        out = torch.empty(8 * n + 4 * n + 4 * n * L, dtype=torch.uint8, device=self._device)
+        base = out.data_ptr()
+        with torch.cuda.device(self._device):
+            stream = self._stream()
+            need = int(self._lib.ppasr_beam_pool_workspace_bytes(self._h, n, T))
+            ws = self._ws.get(stream)
+            if need and (ws is None or ws.numel() < need):
+                ws = self._ws[stream] = torch.empty(need, dtype=torch.uint8, device=self._device)
+            c_ids = (ctypes.c_int * n)(*ids)
+            _lib.check(self._lib.ppasr_beam_pool_decode(self._h, c_ids, n, p.data_ptr() if T > 0 else None, T,
+                                                        fl.ctypes.data_as(ctypes.c_void_p), L, base + 12 * n, base + 8 * n,
+                                                        base, None if not need else ws.data_ptr(), need, stream))
+        host = out.cpu().numpy()
+        scores = host[:8 * n].view(np.float64)
+        ln = host[8 * n:12 * n].view(np.int32)
+        tk = host[12 * n:].view(np.int32).reshape(n, L)
+        return [(float(scores[k]), _text(tk[k, :max(int(ln[k]), 0)].tolist(), self.vocab_list)) for k in range(n)]

@@ -6,7 +6,9 @@ global predictor behind its FastAPI / GUI apps).  ``StreamPool`` keeps the per-s
 ``predict_stream`` (audio remainder, cached feature frames, 67-frame windows with stride 64 = 16 output frames,
 greedy_decoder_chunk's running lists) for N sessions and advances every session that has a full window buffered with ONE
 set of kernel launches per round.  Each session's result equals what its own ``PPASRPredictor.predict_stream`` returns
-(ctc_greedy decoder)."""
+with the same decoder: ``ctc_greedy`` (the default), or ``ctc_beam_search``, where every round's CTC probabilities go to a
+``BeamSearchSessions`` pool -- one beam-search launch for all sessions of the round, on the same stream as the encoder, with
+no host synchronisation in between."""
 import numpy as np
 import torch
 
@@ -16,6 +18,10 @@ from ppasr_amd.model_utils.conformer.model import make_stream_group
 __all__ = ["StreamPool"]
 
 _WINDOW, _STRIDE, _CONTEXT, _KEEP = 67, 64, 7, 3  # predict.py:277-283
+_DECODERS = ("ctc_greedy", "ctc_beam_search")
+# keys of ctc_beam_search_decoder_conf (configs/conformer.yml); the shipped values except the language model
+_BEAM_DEFAULTS = dict(alpha=2.2, beta=4.3, beam_size=300, num_processes=10, cutoff_prob=0.99, cutoff_top_n=40,
+                      language_model_path=None)
 
 
 class _Session:
@@ -28,9 +34,21 @@ class _Session:
 
 
 class StreamPool:
-    def __init__(self, model, vocab_list, n_sessions, preprocess_conf=None, max_seconds=200.0, blank_index=0, group=None):
+    def __init__(self, model, vocab_list, n_sessions, preprocess_conf=None, max_seconds=200.0, blank_index=0, group=None,
+                 decoder="ctc_greedy", decoder_conf=None):
         """group: a ready session group for `model` with `n_sessions` slots (e.g. ``SqueezeformerStreamGroup``); None =
-        ``make_stream_group``'s choice."""
+        ``make_stream_group``'s choice.  decoder: "ctc_greedy" or "ctc_beam_search"; decoder_conf: keys of
+        ``ctc_beam_search_decoder_conf`` (alpha, beta, beam_size, num_processes, cutoff_prob, cutoff_top_n,
+        language_model_path), over the shipped values without a language model."""
+        if decoder not in _DECODERS:
+            raise ValueError(f"StreamPool: unknown decoder {decoder!r} (one of {', '.join(_DECODERS)})")
+        conf = dict(decoder_conf or {})
+        unknown = sorted(set(conf) - set(_BEAM_DEFAULTS))
+        if unknown:
+            raise ValueError(f"StreamPool: unknown decoder_conf keys {unknown} (known: {sorted(_BEAM_DEFAULTS)})")
+        if conf and decoder != "ctc_beam_search":
+            raise ValueError("StreamPool: decoder_conf applies to decoder='ctc_beam_search' only")
+        self.decoder = decoder
         self.model = model
         self.vocab = list(vocab_list)
         self.blank = blank_index
@@ -43,6 +61,11 @@ class StreamPool:
         self.group = group
         self.featurizer = AudioFeaturizer(**(preprocess_conf or {}))
         self.sessions = [_Session() for _ in range(n_sessions)]
+        self.beam = None
+        if decoder == "ctc_beam_search":
+            from ppasr_amd.decoders.beam_search_decoder import BeamSearchSessions
+            self.beam = BeamSearchSessions(n_sessions, vocab_list=self.vocab, blank_id=blank_index,
+                                           **{**_BEAM_DEFAULTS, **conf})
 
     def feed(self, session, audio_data, channels=1, samp_width=2):
         """Append PCM bytes or float samples to a session's buffer (what predict_stream does with each packet)."""
@@ -71,18 +94,31 @@ class StreamPool:
             if not ready:
                 break
             chunks = np.concatenate([self.sessions[i].cached_feat[:, :_WINDOW] for i in ready], axis=0)
-            fa, fp = self.group.encode_chunks(ready, chunks)
-            fa, fp = fa.cpu().numpy(), fp.cpu().numpy()
+            results = self._advance(ready, chunks)
             for k, i in enumerate(ready):
                 s = self.sessions[i]
-                s.frame_ids.extend(fa[k].tolist())
-                s.frame_probs.extend(fp[k][fa[k] != self.blank].tolist())
                 # windows advance by the stride; predict_stream keeps `end - 3` frames once no full window is left,
                 # which is the same position because the next window starts at cur + 64 = end - 3
                 s.cached_feat = s.cached_feat[:, _STRIDE:]
-                s.result = self._result(s)
+                s.result = results[k]
                 updated[i] = s.result
         return updated
+
+    def _advance(self, ids, chunks):
+        """One encoder round for the listed sessions, then their decoder step -> result dicts by list position."""
+        if self.beam is not None:
+            # the probabilities stay on the device: the search is queued behind the encoder on the same stream
+            _, _, probs = self.group.encode_chunks(ids, chunks, want_probs=True)
+            return [{"text": text, "score": score} for score, text in self.beam.decode_chunks(ids, probs)]
+        fa, fp = self.group.encode_chunks(ids, chunks)
+        fa, fp = fa.cpu().numpy(), fp.cpu().numpy()
+        out = []
+        for k, i in enumerate(ids):
+            s = self.sessions[i]
+            s.frame_ids.extend(fa[k].tolist())
+            s.frame_probs.extend(fp[k][fa[k] != self.blank].tolist())
+            out.append(self._result(s))
+        return out
 
     def finish(self, session):
         """End of a session's audio (``predict_stream(..., is_end=True)``, predict.py:291-298): run the buffered full
@@ -92,12 +128,8 @@ class StreamPool:
         self.step()
         s = self.sessions[session]
         if s.cached_feat is not None and s.cached_feat.shape[1] >= _CONTEXT:
-            fa, fp = self.group.encode_chunks([session], s.cached_feat)
-            fa, fp = fa.cpu().numpy(), fp.cpu().numpy()
-            s.frame_ids.extend(fa[0].tolist())
-            s.frame_probs.extend(fp[0][fa[0] != self.blank].tolist())
+            s.result = self._advance([session], s.cached_feat)[0]
             s.cached_feat = s.cached_feat[:, s.cached_feat.shape[1] - _KEEP:]
-            s.result = self._result(s)
         return s.result
 
     def _result(self, s):
@@ -112,4 +144,6 @@ class StreamPool:
 
     def reset(self, session):
         self.group.reset(session)
+        if self.beam is not None:
+            self.beam.reset(session)
         self.sessions[session] = _Session()

@@ -10,7 +10,12 @@ streams from one host thread.  Prints the aggregate audio-seconds/s and the sing
                              (configs/efficient_conformer.yml of PPASR: 12 blocks, stride layer 3, grouped attention on
                              layers 0-3 with group size 3, kernel 15 -> 7), EfficientConformerStreamGroup against
                              StreamHandleSet
-  --eff-rounds R --sessions N  R Efficient-Conformer group rounds of N sessions, for the dispatch count as above"""
+  --eff-rounds R --sessions N  R Efficient-Conformer group rounds of N sessions, for the dispatch count as above
+  --decoder beam             the beam-search session pool (BeamSearchSessions, one pruning + one search launch per round)
+                             against N BeamSearchDecoder objects: the decode stage of one 16-frame round at n = 8 / 64 /
+                             256 / 300, beam 10 and the shipped beam 300 (cutoff 0.99 / 40), without and with a synthetic
+                             character ARPA scorer; then pool rounds end to end (Conformer group + beam pool)
+  --beam-rounds R --sessions N  R pool decode rounds of N sessions at beam 300 (no scorer), for a rocprofv3 kernel trace"""
 import json, os, sys, time
 import numpy as np
 import torch
@@ -74,6 +79,123 @@ def group_section(family, model, group_cls, n_chunks=8, sizes=(1, 8, 64, 256), r
                               "audio_s_per_s": round(n * n_chunks * 0.64 / dt, 1)}), flush=True)
         del kinds
 
+
+def _beam_probs(n, T, V, seed):
+    """peaky synthetic posteriors (a character held for 3 frames, blank-heavy), [n, T, V] on the device"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    logits = torch.randn(n, T, V, device="cuda", generator=g)
+    idx = torch.randint(0, V, (n, (T + 2) // 3), device="cuda", generator=g).repeat_interleave(3, 1)[:, :T]
+    logits.scatter_add_(2, idx[..., None], torch.full((n, T, 1), 6.0, device="cuda"))
+    logits[..., 0] += 7.0 * (torch.rand(n, T, device="cuda", generator=g) < 0.4)
+    return torch.softmax(logits, -1).contiguous()
+
+
+def _beam_scorer(V):
+    import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from lm_util import write_synthetic_arpa
+    from ppasr_amd.decoders.beam_search_decoder import Scorer
+    vocab = [chr(0x4E00 + i) for i in range(V)]
+    path = os.path.join(tempfile.mkdtemp(), "bench.arpa")
+    write_synthetic_arpa(path, vocab[2:400], order=3, seed=1)
+    return vocab, path, Scorer
+
+
+def beam_section(sizes=(8, 64, 256, 300), rounds=4, reps=2, T=16):
+    """ms per round of the decode stage (one 16-frame chunk per session): the session pool against N decoder objects,
+    measured alternately (warm-up, then `reps` timed passes of `rounds` rounds each; the median is printed)."""
+    from ppasr_amd.decoders.beam_search_decoder import BeamSearchDecoder, BeamSearchSessions
+    V = DEFAULT_VOCAB_SIZE
+    vocab, arpa, Scorer = _beam_scorer(V)
+    for beam, lm in ((10, False), (300, False), (10, True), (300, True)):
+        scorer = Scorer(2.2, 4.3, arpa, vocab) if lm else None
+        for n in sizes:
+            probs = _beam_probs(n, T, V, seed=n)
+            pool = BeamSearchSessions(n, 2.2, 4.3, beam, 0.99, 40, vocab, scorer=scorer, init_frames=T * (rounds + 1))
+            decs = [BeamSearchDecoder(2.2, 4.3, beam, 0.99, 40, vocab, max_stream_frames=T * (rounds + 1)) for _ in range(n)]
+            for d in decs:
+                d._ext_scorer = scorer
+            ids, lens = list(range(n)), np.full(1, T, np.int32)
+            times = {"pool": [], "decoders": []}
+            for rep in range(reps + 1):  # rep 0 = warm-up
+                pool.reset()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(rounds):
+                    pool.decode_chunks(ids, probs)
+                torch.cuda.synchronize()
+                if rep:
+                    times["pool"].append(time.perf_counter() - t)
+                for d in decs:
+                    d.reset_decoder()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(rounds):
+                    for k, d in enumerate(decs):
+                        d.decode_chunk(probs[k:k + 1], lens)
+                torch.cuda.synchronize()
+                if rep:
+                    times["decoders"].append(time.perf_counter() - t)
+            out = {k: round(float(np.median(v)) / rounds * 1e3, 3) for k, v in times.items()}
+            print(json.dumps({"section": "beam_decode", "beam": beam, "cutoff": [0.99, 40], "scorer": "arpa3" if lm else None,
+                              "sessions": n, "pool_ms_per_round": out["pool"], "decoders_ms_per_round": out["decoders"],
+                              "speedup": round(out["decoders"] / out["pool"], 2)}), flush=True)
+            del pool, decs
+
+
+def beam_end_to_end(sizes=(8, 64, 256), n_chunks=8, reps=2):
+    """ms per round of one 0.64 s chunk per session: Conformer group + beam pool (beam 300, cutoff 0.99 / 40, no scorer)
+    against the group alone; the chunk's probabilities go to the pool on the same stream."""
+    from ppasr_amd.decoders.beam_search_decoder import BeamSearchSessions
+    from ppasr_amd.model_utils.conformer.model import ConformerStreamGroup
+    model = ConformerModel(80, DEFAULT_VOCAB_SIZE, streaming=True, device="cuda:0",
+                           encoder_conf=dict(output_size=256, attention_heads=4, linear_units=2048, num_blocks=12,
+                                             cnn_module_kernel=15),
+                           state_dict=conformer_state_dict(vocab_size=DEFAULT_VOCAB_SIZE, num_blocks=12, seed=1234))
+    vocab = [chr(0x4E00 + i) for i in range(DEFAULT_VOCAB_SIZE)]
+    x, _ = synth_features(1, 67, seed=5)
+    chunk = torch.from_numpy(x).cuda()
+    for n in sizes:
+        batch = chunk.repeat(n, 1, 1).contiguous()
+        ids = list(range(n))
+        g = ConformerStreamGroup(model, n, max_frames=16 * (n_chunks + 2))
+        pool = BeamSearchSessions(n, 2.2, 4.3, 300, 0.99, 40, vocab, init_frames=16 * (n_chunks + 2))
+        times = {"group": [], "group+beam": []}
+        for rep in range(reps + 1):
+            for k in times:
+                g.reset()
+                pool.reset()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(n_chunks):
+                    if k == "group":
+                        g.encode_chunks(ids, batch)[0].cpu()  # (the greedy pool's copy-back)
+                    else:
+                        pool.decode_chunks(ids, g.encode_chunks(ids, batch, want_probs=True)[2])
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(time.perf_counter() - t)
+        print(json.dumps({"section": "beam_end_to_end", "sessions": n, **{
+            f"{k}_ms_per_round": round(float(np.median(v)) / n_chunks * 1e3, 3) for k, v in times.items()}}), flush=True)
+        del g, pool
+
+
+if "--beam-rounds" in sys.argv:
+    from ppasr_amd.decoders.beam_search_decoder import BeamSearchSessions
+    _n, _R = _arg("--sessions", 64), _arg("--beam-rounds", 4)
+    _vocab = [chr(0x4E00 + i) for i in range(DEFAULT_VOCAB_SIZE)]
+    _pool = BeamSearchSessions(_n, 2.2, 4.3, 300, 0.99, 40, _vocab, init_frames=16 * (_R + 1))
+    _p = _beam_probs(_n, 16, DEFAULT_VOCAB_SIZE, seed=3)
+    for _ in range(_R):
+        _pool.decode_chunks(list(range(_n)), _p)
+    torch.cuda.synchronize()
+    print(json.dumps({"beam_rounds": _R, "sessions": _n}))
+    sys.exit(0)
+
+if "--decoder" in sys.argv and _arg("--decoder", "greedy") == "beam":
+    beam_section()
+    beam_end_to_end()
+    sys.exit(0)
 
 for _flag in ("--sq-rounds", "--eff-rounds"):
     if _flag in sys.argv:
