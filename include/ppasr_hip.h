@@ -418,7 +418,8 @@ PPASR_API ppasr_status ppasr_ctc_collapse(const int32_t* frame_argmax, const flo
                                 void* stream);
 
 /* ---- multi-session streaming (no reference counterpart: PPASR streams one session per call) -----------------------
- * A group of Conformer (or Squeezeformer, or Efficient-Conformer) sessions whose K/V and conv caches live in one allocation;
+ * A group of Conformer (or Squeezeformer, or Efficient-Conformer) sessions whose K/V and conv caches live in one allocation
+ * (DeepSpeech2 groups: the sessions' recurrent states, ppasr_ds2_stream_group_create);
  * ppasr_encode_chunk_group advances any subset of them by one chunk with ONE set of launches (rows of all listed sessions
  * stacked).  Every session
  * follows the single-session arithmetic of ppasr_encode_chunk with required_cache_size < 0 (full history, what
@@ -441,6 +442,18 @@ PPASR_API ppasr_status ppasr_sq_stream_group_create(ppasr_handle h, int n_sessio
  * ppasr_out_frames(h, T) frames per session, and ppasr_encode_chunk_group refuses, with PPASR_EINVAL and no session
  * changed, a round in which any listed session would leave an odd cache length or exceed max_len / max_frames. */
 PPASR_API ppasr_status ppasr_eff_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out);
+/* The same kind of group for a streaming (causal = 1, unidirectional) DeepSpeech2 handle, LSTM or GRU, rnn_size 1024 or
+ * 2048.  Each session keeps its recurrent state on the device -- h [L][H], and c [L][H] for the LSTM (a GRU has none: the
+ * reference hands its c box through unchanged) -- and its output-frame offset; max_frames is accepted and ignored (the
+ * state does not grow with the stream).  PPASR_EUNSUPPORTED for a bidirectional handle (the reference streams no such
+ * model) and any other model type; the three create calls above refuse DeepSpeech2 handles.  A round is what
+ * ppasr_ds2_encode computes for the n stacked windows with every length T and those sessions' states as the h / c boxes
+ * (the (layer, time) wavefront route whatever n, bit for bit, with no stream synchronisation; the launches do not depend
+ * on n except for the CTC head's K-split join, which ppasr_ds2_encode adds up to 512 stacked frames), c =
+ * ((T-1)/2-1)/2 frames per session; the states move between the sessions' slots and the recurrence by one launch each way.
+ * ppasr_stream_group_reset zeroes a session's state and offset.  ppasr_group_chunk_workspace_bytes(h, n, T) gives the
+ * round's workspace for such a handle. */
+PPASR_API ppasr_status ppasr_ds2_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out);
 PPASR_API ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g);
 PPASR_API ppasr_status ppasr_stream_group_reset(ppasr_stream_group g, int session /* < 0: all */, void* stream);
 PPASR_API int          ppasr_stream_group_offset(ppasr_stream_group g, int session);

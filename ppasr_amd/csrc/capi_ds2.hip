@@ -349,6 +349,50 @@ extern "C" ppasr_status ppasr_ds2_encode(ppasr_handle h, const float* feats, con
   return PPASR_OK;
 }
 
+// Session groups (capi_stream.hip ppasr_ds2_stream_group_create): the batched layout for B = n, the probabilities when
+// the caller wants none, the frame argmax / max-prob when the caller wants none
+size_t ds2_group_ws_floats(const ppasr_model_s* m, int n, int T) {
+  const size_t M = (size_t)n * (((T - 1) / 2 - 1) / 2);
+  return ds2_ws(m, n, T).total + al64(M * m->ds2.V) + 2 * al64(M);
+}
+
+// One round of a DeepSpeech2 session group: the wavefront route of ppasr_ds2_encode for the n listed sessions stacked, every
+// length T, the initial states gathered from the sessions' slots and the final ones scattered back to them (slots: device
+// [n], distinct, checked by the caller).  No per-session launch and no persistent route whatever n.
+ppasr_status ds2_group_round(ppasr_model_s* h, const int* slots, int n, const float* feats, int T, float* state_h,
+                             float* state_c, float* probs, int32_t* frame_argmax, float* frame_maxprob, float* ws,
+                             hipStream_t st) {
+  const Ds2W& W = h->ds2;
+  const Ds2Ws wl = ds2_ws(h, n, T);
+  const int F = h->desc.input_dim, T1 = (T - 1) / 2, F1 = h->F1, Tp = (T1 - 1) / 2, F2 = h->F2;
+  const int M = n * Tp, H = W.H, G = W.gates, L = W.n_layers;
+  float *y1 = ws + wl.y1, *x = ws + wl.x, *gx = ws + wl.gx, *out = ws + wl.ya;
+  float *hbuf = ws + wl.hbuf, *cbuf = ws + wl.cbuf, *yring = ws + wl.yring;
+  float* part = wl.part_floats ? ws + wl.part : nullptr;
+  int32_t* lens32 = reinterpret_cast<int32_t*>(ws + wl.lens32);
+  float* pr = probs ? probs : ws + wl.total;
+  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.total + al64((size_t)M * W.V));
+  float* fp = frame_maxprob ? frame_maxprob : ws + wl.total + al64((size_t)M * W.V) + al64(M);
+  launch_ds2_conv1(feats, W.cmvn_mean, W.cmvn_istd, W.c1_w, W.c1_b, y1, n, T, F, T1, F1, st);
+  launch_ds2_conv2(y1, W.c2_w, W.c2_b, x, n, T1, F1, Tp, F2, W.ldx, st);
+  const Ds2LayerW& L0 = h->ds2_layers[0];
+  launch_dense(x, W.ldx, L0.w_ih, L0.b_sum, gx, M, L0.in_dim_padded, G * H, G * H, G * H, st, 1.0f, part, wl.part_floats);
+  launch_ds2_state_gather(state_h, state_c, slots, hbuf, G == 4 ? cbuf : nullptr, lens32, n, L, H, Tp, st);
+  // (every row runs all Tp steps, so the last layer writes every row of `out`: no memset)
+  for (int s = 0; s < Tp + L - 1; ++s) {
+    const int l_lo = s - (Tp - 1) > 0 ? s - (Tp - 1) : 0, l_hi = s < L - 1 ? s : L - 1;
+    launch_lstm_wave(gx, W.wave_tab, hbuf, cbuf, yring, out, lens32, n, Tp, H, L, s, l_lo, l_hi - l_lo + 1, st, G == 3);
+  }
+  launch_ds2_state_scatter(hbuf, G == 4 ? cbuf : nullptr, slots, state_h, state_c, n, L, H, Tp, st);
+  const Ds2LayerW& Ll = h->ds2_layers[L - 1];
+  launch_ln_wide(out, Ll.ln_g, Ll.ln_b, M, H, st);
+  launch_dense(out, H, W.ctc_w, W.ctc_b, pr, M, H, W.Vpad, W.V, W.V, st, 1.0f, part, wl.part_floats);
+  launch_softmax_from_stats(pr, nullptr, nullptr, M, W.V, st);
+  launch_frame_argmax(pr, fa, fp, M, W.V, st);
+  HIP_TRY(hipGetLastError());
+  return PPASR_OK;
+}
+
 // Test hook (not used by any product path): holds `n_workgroups` whole CUs for `milliseconds` on `stream` (ds2_kernels.hip
 // k_occupy).  tests/test_deepspeech2_gpu.py forces the persistent recurrence's give-up path with it.
 extern "C" ppasr_status ppasr_debug_occupy_cus(int n_workgroups, int milliseconds, void* stream) {

@@ -262,6 +262,11 @@ ppasr_status generic_sq_encode(ppasr_model_s* h, const float* feats, const int64
 
 // model-family back ends
 ppasr_status ds2_create(ppasr_model_s* m, BlobMap& sd);
+// DeepSpeech2 session groups (capi_ds2.hip): workspace of a round of n windows of T frames, and the round itself
+size_t ds2_group_ws_floats(const ppasr_model_s* m, int n, int T);
+ppasr_status ds2_group_round(ppasr_model_s* h, const int* slots, int n, const float* feats, int T, float* state_h,
+                             float* state_c, float* probs, int32_t* frame_argmax, float* frame_maxprob, float* ws,
+                             hipStream_t st);
 ppasr_status squeezeformer_create(ppasr_model_s* m, BlobMap& sd, const float* pe_dev);
 ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const int64_t* lens, int B, int T, float* probs,
                                   float* logits, int32_t* frame_argmax, float* frame_maxprob, float* ws,

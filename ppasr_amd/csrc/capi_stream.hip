@@ -312,7 +312,7 @@ ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* x
 }
 
 // which of the chunk-round paths a session group takes (the family of the handle it was built for)
-enum class GroupFamily { kConformer, kSqueezeformer, kEfficientConformer };
+enum class GroupFamily { kConformer, kSqueezeformer, kEfficientConformer, kDeepSpeech2 };
 
 }  // namespace
 
@@ -518,6 +518,9 @@ ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* att_cache, i
 // per kernel instead of one).  No reference counterpart: PPASR streams one session per call
 // (predict.py:232-337, forward_chunk asserts B = 1); each session here follows exactly the single-session arithmetic
 // (required_cache_size < 0: the full history is kept, what PPASRPredictor passes, predict.py:306-307).
+// DeepSpeech2 groups (ppasr_ds2_stream_group_create) keep each session's LSTM / GRU state [L][H] (h, and c for the LSTM)
+// instead of caches: a round is the wavefront route of ppasr_ds2_encode over the n stacked windows (capi_ds2.hip
+// ds2_group_round), with the states gathered from and scattered back to the sessions' slots by one launch each.
 // =====================================================================================
 struct ppasr_stream_group_s {
   ppasr_model_s* m;
@@ -525,11 +528,12 @@ struct ppasr_stream_group_s {
   GroupFamily family;  // Squeezeformer / Efficient-Conformer: full- and half-rate layers, per-layer histories
   float *kc, *vc;     // [n_sessions][L][cap][256]
   float* xh_hist;     // [n_sessions][L][lo][256] (layer i uses its first kernel_i - 1 rows)
+  float* ds2_state;   // DeepSpeech2: h [n_sessions][L][H], then (LSTM) c of the same shape; one allocation
   HistLayer* hist_tab;  // Squeezeformer / Efficient-Conformer: device [L], the layers' pointwise_conv1 (k_pw1_glu_layers)
   // per-call descriptors: a ring of pinned host staging buffers + device copies, each guarded by an event, so that a
   // call never overwrites a buffer an earlier (still queued) call reads.  A slot holds per_slot = n_sessions descriptors
   // (Squeezeformer / Efficient-Conformer: 2 n_sessions -- those of the full-rate layers, then those of the half-rate
-  // layers)
+  // layers; DeepSpeech2: n_sessions plain slot indices)
   static constexpr int kRing = 8;
   int per_slot;
   SessDesc* desc_host;  // pinned [kRing][per_slot]
@@ -543,6 +547,12 @@ struct ppasr_stream_group_s {
 
 namespace {
 
+// DeepSpeech2 group: bytes of every session's h (and, LSTM, c) state, [n_sessions][L][H] each
+size_t ds2_state_bytes(const ppasr_model_s* h, int n_sessions) {
+  const Ds2W& W = h->ds2;
+  return (W.gates == 4 ? 2 : 1) * (size_t)n_sessions * W.n_layers * W.H * sizeof(float);
+}
+
 ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFamily family, ppasr_stream_group* out) {
   auto* g = new ppasr_stream_group_s();  // (value-initialised: every pointer and event null until it exists)
   g->m = h;
@@ -550,7 +560,8 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFa
   g->family = family;
   g->cap = (max_frames > 0 && max_frames < h->desc.max_len) ? max_frames : h->desc.max_len;
   g->lo = h->desc.cnn_module_kernel - 1;
-  const bool layered = family != GroupFamily::kConformer;  // (per-layer history table, two descriptor sets)
+  const bool layered = family == GroupFamily::kSqueezeformer || family == GroupFamily::kEfficientConformer;
+  // (layered: per-layer history table, two descriptor sets)
   g->per_slot = layered ? 2 * n_sessions : n_sessions;
   g->slot = 0;
   // any failure below releases whatever exists so far (ppasr_stream_group_destroy skips what does not)
@@ -559,12 +570,14 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFa
     return fail(PPASR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
   };
   const size_t L = h->desc.num_blocks;
-  const size_t kv = (size_t)n_sessions * L * g->cap * kD * sizeof(float);
-  const size_t hb = (size_t)n_sessions * L * g->lo * kD * sizeof(float);
+  const bool ds2 = family == GroupFamily::kDeepSpeech2;  // (no caches: the recurrent states)
+  const size_t kv = ds2 ? 0 : (size_t)n_sessions * L * g->cap * kD * sizeof(float);
+  const size_t hb = ds2 ? ds2_state_bytes(h, n_sessions) : (size_t)n_sessions * L * g->lo * kD * sizeof(float);
   const size_t db = (size_t)ppasr_stream_group_s::kRing * g->per_slot * sizeof(SessDesc);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->kc), kv);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->vc), kv);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->xh_hist), hb);
+  hipError_t e = hipSuccess;
+  if (!ds2) e = hipMalloc(reinterpret_cast<void**>(&g->kc), kv);
+  if (e == hipSuccess && !ds2) e = hipMalloc(reinterpret_cast<void**>(&g->vc), kv);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(ds2 ? &g->ds2_state : &g->xh_hist), hb);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->desc_dev), db);
   if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->desc_host), db, hipHostMallocDefault);
   if (e == hipSuccess && layered) e = hipMalloc(reinterpret_cast<void**>(&g->hist_tab), L * sizeof(HistLayer));
@@ -576,7 +589,7 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFa
       return bail("creating the session-group events failed", e);
     }
   }
-  e = hipMemset(g->xh_hist, 0, hb);
+  e = hipMemset(ds2 ? g->ds2_state : g->xh_hist, 0, hb);
   if (e != hipSuccess) return bail("clearing the session-group conv histories failed", e);
   if (layered) {  // (what ppasr_stream_create puts in the family's stream table: rows = kernel_i - 1)
     std::vector<HistLayer> tab(L);
@@ -842,9 +855,52 @@ ppasr_status eff_encode_chunk_group(ppasr_stream_group g, const int* sessions_ho
   return PPASR_OK;
 }
 
+// One round of a DeepSpeech2 group: ds2_group_round on the listed sessions' slots.  Every argument is checked before the
+// slot table is written or anything is launched, so a refused call leaves every session as it was.  The only host wait is
+// the descriptor ring's event (a slot table still read by a queued round is not overwritten).
+ppasr_status ds2_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
+                                    float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
+                                    void* workspace, hipStream_t st) {
+  ppasr_model_s* h = g->m;
+  std::vector<char> seen(g->n_sessions, 0);
+  for (int b = 0; b < n; ++b) {
+    const int sidx = sessions_host[b];
+    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
+    seen[sidx] = 1;
+  }
+  const int c = ((T - 1) / 2 - 1) / 2;
+  const int slot = g->slot;
+  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
+  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
+  int* slots = reinterpret_cast<int*>(g->desc_host + (size_t)slot * g->per_slot);
+  int* slots_dev = reinterpret_cast<int*>(g->desc_dev + (size_t)slot * g->per_slot);
+  std::copy(sessions_host, sessions_host + n, slots);
+  HIP_TRY(hipMemcpyAsync(slots_dev, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  const Ds2W& W = h->ds2;
+  float* state_h = g->ds2_state;
+  float* state_c = W.gates == 4 ? g->ds2_state + (size_t)g->n_sessions * W.n_layers * W.H : nullptr;
+  ppasr_status r = ds2_group_round(h, slots_dev, n, feats, T, state_h, state_c, probs, frame_argmax, frame_maxprob,
+                                   static_cast<float*>(workspace), st);
+  if (r != PPASR_OK) return r;
+  for (int b = 0; b < n; ++b) g->offset[sessions_host[b]] += c;
+  HIP_TRY(hipEventRecord(g->ev[slot], st));
+  if (c_out_host) *c_out_host = c;
+  return PPASR_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+ppasr_status ppasr_ds2_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
+  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
+  if (h->desc.model_type != PPASR_MODEL_DEEPSPEECH2 || !h->desc.causal)
+    return fail(PPASR_EUNSUPPORTED, "DeepSpeech2 session groups are built for streaming (unidirectional) model_type=deepspeech2 "
+                                    "(the reference streams no bidirectional model)");
+  if (!h->ds2.wave_tab) return fail(PPASR_EUNSUPPORTED, "DeepSpeech2 session groups run on the wavefront recurrence");
+  // (max_frames: no cache grows with the stream -- the state is [L][H] per session whatever its length)
+  return group_alloc(h, n_sessions, max_frames, GroupFamily::kDeepSpeech2, out);
+}
 
 ppasr_status ppasr_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
   if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
@@ -882,7 +938,7 @@ ppasr_status ppasr_eff_stream_group_create(ppasr_handle h, int n_sessions, int m
 ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g) {
   if (!g) return PPASR_OK;
   (void)hipFree(g->kc); (void)hipFree(g->vc); (void)hipFree(g->xh_hist); (void)hipFree(g->desc_dev);
-  (void)hipFree(g->hist_tab);
+  (void)hipFree(g->hist_tab); (void)hipFree(g->ds2_state);
   (void)hipHostFree(g->desc_host);
   for (int i = 0; i < ppasr_stream_group_s::kRing; ++i)
     if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
@@ -894,6 +950,18 @@ ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g) {
 ppasr_status ppasr_stream_group_reset(ppasr_stream_group g, int session, void* stream) {
   if (!g || session >= g->n_sessions) return fail(PPASR_EINVAL, "bad session");
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (g->family == GroupFamily::kDeepSpeech2) {  // zero state (h, c), offset 0
+    const Ds2W& W = g->m->ds2;
+    const size_t per = (size_t)W.n_layers * W.H, planes = W.gates == 4 ? 2 : 1;
+    for (size_t p = 0; p < planes; ++p) {
+      float* base = g->ds2_state + p * per * g->n_sessions;
+      if (session < 0) HIP_TRY(hipMemsetAsync(base, 0, per * g->n_sessions * sizeof(float), st));
+      else HIP_TRY(hipMemsetAsync(base + per * session, 0, per * sizeof(float), st));
+    }
+    if (session < 0) std::fill(g->offset.begin(), g->offset.end(), 0);
+    else g->offset[session] = 0;
+    return PPASR_OK;
+  }
   const size_t per = (size_t)g->m->desc.num_blocks * g->lo * kD;
   if (session < 0) {
     HIP_TRY(hipMemsetAsync(g->xh_hist, 0, per * g->n_sessions * sizeof(float), st));
@@ -915,6 +983,7 @@ int ppasr_stream_group_offset(ppasr_stream_group g, int session) {
 
 size_t ppasr_group_chunk_workspace_bytes(ppasr_handle h, int n, int T) {
   if (!h || n < 1 || T < 7) return 0;
+  if (h->desc.model_type == PPASR_MODEL_DEEPSPEECH2) return ds2_group_ws_floats(h, n, T) * sizeof(float);
   if (is_sq(h) || is_eff(h)) return layered_group_ws_floats(h, n, T) * sizeof(float);
   const size_t Tp = ((T - 1) / 2 - 1) / 2;
   // the batched layout for B = n, plus the conv-module input rows and the GLU'd histories of the active sessions
@@ -934,6 +1003,9 @@ ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int* sessions_
   if (g->family == GroupFamily::kSqueezeformer)
     return sq_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
                                  static_cast<hipStream_t>(stream));
+  if (g->family == GroupFamily::kDeepSpeech2)
+    return ds2_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
+                                  static_cast<hipStream_t>(stream));
   if (g->family == GroupFamily::kEfficientConformer)
     return eff_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
                                   static_cast<hipStream_t>(stream));

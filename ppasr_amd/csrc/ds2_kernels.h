@@ -70,6 +70,13 @@ void launch_lstm_wave(const float* gx0, const Ds2WaveLayer* tab, float* hbuf, fl
                       const int32_t* lens, int B, int T, int H, int L, int s, int l_lo, int n_l, hipStream_t st, bool gru = false);
 // [B][H] row-major <-> the MFMA-fragment order of the wavefront kernel's state buffers (hbuf / yring)
 void launch_state_reorder(const float* src, float* dst, int B, int H, bool to_frag, hipStream_t st);
+// Session groups: state_h / state_c [slots][L][H] (state_c / cbuf NULL: GRU), slots [n] device, T = the wavefront's time
+// steps.  gather: the listed sessions' states -> slot 0 of hbuf [L][2][Bp][H] (fragment order, pad rows of the last 32-row
+// tile zeroed) and cbuf [L][n][H], lens32 [n] = T.  scatter: hbuf[l][T & 1] and cbuf[l] -> the listed sessions' states.
+void launch_ds2_state_gather(const float* state_h, const float* state_c, const int* slots, float* hbuf, float* cbuf,
+                             int32_t* lens32, int n, int L, int H, int T, hipStream_t st);
+void launch_ds2_state_scatter(const float* hbuf, const float* cbuf, const int* slots, float* state_h, float* state_c, int n,
+                              int L, int H, int T, hipStream_t st);
 void launch_ln_wide(float* x, const float* g, const float* b, int M, int N, hipStream_t st);
 
 }  // namespace ppasr

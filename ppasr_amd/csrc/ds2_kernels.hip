@@ -810,6 +810,59 @@ __global__ __launch_bounds__(256) void k_state_reorder(const float* __restrict__
 void launch_state_reorder(const float* src, float* dst, int B, int H, bool to_frag, hipStream_t st) {
   PPASR_LAUNCH(k_state_reorder, dim3((unsigned)(((size_t)B * H + 255) / 256)), dim3(256), 0, st, src, dst, B, H, to_frag ? 1 : 0);
 }
+
+// ---- session groups (ppasr_ds2_stream_group_create): the sessions' states [slot][L][H] <-> the wavefront buffers of the
+// listed sessions (row b = list position b), every layer in one launch.  A thread moves one quad of 4 consecutive units
+// of one row: 16 bytes in the row-major state and, in k_state_reorder's fragment order, 16 contiguous bytes of hbuf.
+__device__ __forceinline__ size_t frag_quad(int bb, int q, int H) {  // fragment index of row bb, units 4q .. 4q + 3
+  return ((size_t)(bb >> 5) * (H / 8) + (q >> 1)) * 256 + ((bb & 31) + 32 * (q & 1)) * 4;
+}
+// gather: slot 0 of hbuf[l] (the state before time 0; rows n .. Bp - 1 of the last 32-row tile zero), cbuf[l] row b (LSTM),
+// lens32[b] = T (every listed session runs the whole window)
+__global__ __launch_bounds__(256) void k_ds2_state_gather(const float* __restrict__ state_h, const float* __restrict__ state_c,
+                                                          const int* __restrict__ slots, float* __restrict__ hbuf,
+                                                          float* __restrict__ cbuf, int32_t* __restrict__ lens32, int n, int L,
+                                                          int H, int T) {
+  const int Bp = (n + 31) / 32 * 32, nq = H / 4;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)L * Bp * nq) return;
+  const int q = (int)(i % nq), bb = (int)((i / nq) % Bp), l = (int)(i / ((size_t)nq * Bp));
+  const size_t BHp = (size_t)Bp * H;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (bb < n) {
+    const size_t si = ((size_t)slots[bb] * L + l) * H + 4 * q;
+    v = *reinterpret_cast<const f32x4*>(state_h + si);
+    if (cbuf) *reinterpret_cast<f32x4*>(cbuf + ((size_t)l * n + bb) * H + 4 * q) = *reinterpret_cast<const f32x4*>(state_c + si);
+    if (l == 0 && q == 0) lens32[bb] = T;
+  }
+  *reinterpret_cast<f32x4*>(hbuf + (size_t)l * 2 * BHp + frag_quad(bb, q, H)) = v;
+}
+// scatter: the final states -- h from hbuf[l][slot T & 1], c from cbuf[l] (LSTM) -- back to the listed sessions' slots
+__global__ __launch_bounds__(256) void k_ds2_state_scatter(const float* __restrict__ hbuf, const float* __restrict__ cbuf,
+                                                           const int* __restrict__ slots, float* __restrict__ state_h,
+                                                           float* __restrict__ state_c, int n, int L, int H, int T) {
+  const int Bp = (n + 31) / 32 * 32, nq = H / 4;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)L * n * nq) return;
+  const int q = (int)(i % nq), bb = (int)((i / nq) % n), l = (int)(i / ((size_t)nq * n));
+  const size_t BHp = (size_t)Bp * H;
+  const size_t si = ((size_t)slots[bb] * L + l) * H + 4 * q;
+  *reinterpret_cast<f32x4*>(state_h + si) =
+      *reinterpret_cast<const f32x4*>(hbuf + ((size_t)l * 2 + (T & 1)) * BHp + frag_quad(bb, q, H));
+  if (cbuf) *reinterpret_cast<f32x4*>(state_c + si) = *reinterpret_cast<const f32x4*>(cbuf + ((size_t)l * n + bb) * H + 4 * q);
+}
+void launch_ds2_state_gather(const float* state_h, const float* state_c, const int* slots, float* hbuf, float* cbuf,
+                             int32_t* lens32, int n, int L, int H, int T, hipStream_t st) {
+  const size_t threads = (size_t)L * ((n + 31) / 32 * 32) * (H / 4);
+  PPASR_LAUNCH(k_ds2_state_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, state_h, state_c, slots, hbuf,
+               cbuf, lens32, n, L, H, T);
+}
+void launch_ds2_state_scatter(const float* hbuf, const float* cbuf, const int* slots, float* state_h, float* state_c, int n,
+                              int L, int H, int T, hipStream_t st) {
+  const size_t threads = (size_t)L * n * (H / 4);
+  PPASR_LAUNCH(k_ds2_state_scatter, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, hbuf, cbuf, slots, state_h,
+               state_c, n, L, H, T);
+}
 void launch_ln_wide(float* x, const float* g, const float* b, int M, int N, hipStream_t st) {
   PPASR_LAUNCH(k_ln_wide, dim3((M + 3) / 4), dim3(256), 0, st, x, g, b, M, N);
 }

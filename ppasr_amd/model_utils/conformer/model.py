@@ -427,7 +427,11 @@ class StreamHandleSet:
 
 
 def make_stream_group(model, n_sessions, max_frames=0):
-    """``ConformerStreamGroup`` where the library builds session groups for the handle, else ``StreamHandleSet``."""
+    """``ConformerStreamGroup`` where the library builds session groups for the handle, else ``StreamHandleSet``
+    (a streaming DeepSpeech2 model: ``DeepSpeech2StreamGroup``, the only many-session path of that family)."""
+    from ppasr_amd.model_utils.deepspeech2.model import DeepSpeech2Model, DeepSpeech2StreamGroup
+    if isinstance(model, DeepSpeech2Model):
+        return DeepSpeech2StreamGroup(model, n_sessions, max_frames=max_frames)
     try:
         return ConformerStreamGroup(model, n_sessions, max_frames=max_frames)
     except _lib.PPASRHipError as e:

@@ -6,8 +6,9 @@ import numpy as np
 import torch
 
 from ppasr_amd import _lib
+from ppasr_amd.model_utils.conformer.model import ConformerStreamGroup
 
-__all__ = ["DeepSpeech2Model"]
+__all__ = ["DeepSpeech2Model", "DeepSpeech2StreamGroup"]
 
 
 class DeepSpeech2Model:
@@ -88,3 +89,14 @@ class DeepSpeech2Model:
     def get_encoder_out_chunk(self, speech, speech_lengths, init_state_h_box=None, init_state_c_box=None):
         """-> (ctc_probs, eouts_len, final_h_box, final_c_box).  deepspeech2/model.py:67-72"""
         return self._run(speech, speech_lengths, init_state_h_box, init_state_c_box, want_states=True)
+
+
+class DeepSpeech2StreamGroup(ConformerStreamGroup):
+    """``ConformerStreamGroup``'s interface for a streaming DeepSpeech2 model, LSTM or GRU (``ppasr_ds2_stream_group_create``):
+    each session's recurrent state stays on the device, and ``encode_chunks(sessions, feats)`` advances the listed
+    sessions by one window each with ONE set of kernel launches (their windows stacked).  Every session gets what
+    ``get_encoder_out_chunk`` returns for its window with its own state boxes (what ``predict_chunk_deepspeech`` carries
+    between calls).  ``make_stream_group`` picks it for a streaming DeepSpeech2 model; ``max_frames`` is ignored (the
+    state does not grow)."""
+
+    _create = "ppasr_ds2_stream_group_create"

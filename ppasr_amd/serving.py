@@ -53,9 +53,13 @@ class StreamPool:
         self.vocab = list(vocab_list)
         self.blank = blank_index
         if group is None:
-            # (one set of launches per round for plain Conformer handles; per-session stream handles behind the same
-            #  interface for the Squeezeformer and the Efficient-Conformer)
-            group = make_stream_group(model, n_sessions, max_frames=min(model.max_len, int(max_seconds * 25) + 32))
+            # (one set of launches per round for plain Conformer and streaming DeepSpeech2 handles; per-session stream
+            #  handles behind the same interface for the Squeezeformer and the Efficient-Conformer)
+            # (DeepSpeech2: session states that do not grow, no max_len)
+            max_frames = int(max_seconds * 25) + 32
+            if hasattr(model, "max_len"):
+                max_frames = min(model.max_len, max_frames)
+            group = make_stream_group(model, n_sessions, max_frames=max_frames)
         elif getattr(group, "model", None) is not model or int(getattr(group, "n_sessions", -1)) != int(n_sessions):
             raise ValueError("StreamPool(group=...): the group must be built for the same model and session count")
         self.group = group

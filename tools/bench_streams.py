@@ -11,6 +11,11 @@ streams from one host thread.  Prints the aggregate audio-seconds/s and the sing
                              layers 0-3 with group size 3, kernel 15 -> 7), EfficientConformerStreamGroup against
                              StreamHandleSet
   --eff-rounds R --sessions N  R Efficient-Conformer group rounds of N sessions, for the dispatch count as above
+  --deepspeech2 [--gru]      the same section for DeepSpeech2: the shipped configuration (configs/deepspeech2.yml of PPASR:
+                             streaming, 5 x 1024 LSTM; --gru: nn.GRU layers), DeepSpeech2StreamGroup against one
+                             get_encoder_out_chunk call per session that carries its own h / c boxes (what
+                             predict_chunk_deepspeech does), one 67-frame window per session per round
+  --ds2-rounds R --sessions N [--gru]  R DeepSpeech2 group rounds of N sessions, for the dispatch count as above
   --decoder beam             the beam-search session pool (BeamSearchSessions, one pruning + one search launch per round)
                              against N BeamSearchDecoder objects: the decode stage of one 16-frame round at n = 8 / 64 /
                              256 / 300, beam 10 and the shipped beam 300 (cutoff 0.99 / 40), without and with a synthetic
@@ -49,18 +54,51 @@ def efficient_conformer_model():
     return EfficientConformerModel(80, V, streaming=True, encoder_conf=conf, state_dict=sd, device="cuda:0")
 
 
-def group_section(family, model, group_cls, n_chunks=8, sizes=(1, 8, 64, 256), reps=3):
+def deepspeech2_model(gru=False):
+    from ppasr_amd.model_utils.deepspeech2.model import DeepSpeech2Model
+    from ppasr_amd.utils.synth import deepspeech2_state_dict
+    V = DEFAULT_VOCAB_SIZE
+    sd = deepspeech2_state_dict(vocab_size=V, num_rnn_layers=5, rnn_size=1024, streaming=True, seed=1234, use_gru=gru)
+    return DeepSpeech2Model(80, V, streaming=True, encoder_conf=dict(num_rnn_layers=5, rnn_size=1024, use_gru=gru),
+                            state_dict=sd, device="cuda:0")
+
+
+class Ds2BoxSessions:
+    """The group's interface over per-session get_encoder_out_chunk calls, each with its own h / c boxes (the only way to
+    serve N DeepSpeech2 streams without a group: N single-utterance calls per round)."""
+
+    def __init__(self, model, n_sessions, max_frames=0):
+        self.model, self.n_sessions = model, int(n_sessions)
+        self.boxes = [(None, None)] * self.n_sessions
+
+    def reset(self, session=-1):
+        for i in (range(self.n_sessions) if int(session) < 0 else [int(session)]):
+            self.boxes[i] = (None, None)
+
+    def encode_chunks(self, sessions, speech, want_probs=False):
+        lens = np.full(1, int(speech.shape[1]), np.int64)
+        out = []
+        for k, s in enumerate(sessions):
+            probs, _, h, c = self.model.get_encoder_out_chunk(speech[k:k + 1], lens, *self.boxes[s])
+            self.boxes[s] = (h, c)
+            out.append(probs)
+        return out
+
+
+def group_section(family, model, group_cls, n_chunks=8, sizes=(1, 8, 64, 256), reps=3, baseline=None):
     """ms per round and audio-s/s of one 0.64 s chunk per session per round: the group (one set of launches per round)
-    and StreamHandleSet (one stream handle per session, what make_stream_group gives this family) at the same n,
-    measured alternately (warm-up, then `reps` timed passes of each; the median is printed)."""
+    and StreamHandleSet (one stream handle per session, what make_stream_group gives this family; `baseline`: another
+    per-session class with its interface) at the same n, measured alternately (warm-up, then `reps` timed passes of each;
+    the median is printed)."""
     from ppasr_amd.model_utils.conformer.model import StreamHandleSet
+    baseline = baseline or ("handle_set", StreamHandleSet)
     x, _ = synth_features(1, 67, seed=5)
     chunk = torch.from_numpy(x).cuda()
     for n in sizes:
         batch = chunk.repeat(n, 1, 1).contiguous()
         ids = list(range(n))
         kinds = {"group": group_cls(model, n, max_frames=16 * (n_chunks + 2)),
-                 "handle_set": StreamHandleSet(model, n)}
+                 baseline[0]: baseline[1](model, n)}
         times = {k: [] for k in kinds}
         for rep in range(reps + 1):  # rep 0 = warm-up
             for k, g in kinds.items():
@@ -197,11 +235,14 @@ if "--decoder" in sys.argv and _arg("--decoder", "greedy") == "beam":
     beam_end_to_end()
     sys.exit(0)
 
-for _flag in ("--sq-rounds", "--eff-rounds"):
+for _flag in ("--sq-rounds", "--eff-rounds", "--ds2-rounds"):
     if _flag in sys.argv:
         if _flag == "--sq-rounds":
             from ppasr_amd.model_utils.squeezeformer.model import SqueezeformerStreamGroup as _cls
             _model = squeezeformer_model()
+        elif _flag == "--ds2-rounds":
+            from ppasr_amd.model_utils.deepspeech2.model import DeepSpeech2StreamGroup as _cls
+            _model = deepspeech2_model(gru="--gru" in sys.argv)
         else:
             from ppasr_amd.model_utils.efficient_conformer.model import EfficientConformerStreamGroup as _cls
             _model = efficient_conformer_model()
@@ -217,6 +258,12 @@ for _flag in ("--sq-rounds", "--eff-rounds"):
 if "--squeezeformer" in sys.argv:
     from ppasr_amd.model_utils.squeezeformer.model import SqueezeformerStreamGroup
     group_section("squeezeformer", squeezeformer_model(), SqueezeformerStreamGroup)
+    sys.exit(0)
+if "--deepspeech2" in sys.argv:
+    from ppasr_amd.model_utils.deepspeech2.model import DeepSpeech2StreamGroup
+    _gru = "--gru" in sys.argv
+    group_section("deepspeech2_gru" if _gru else "deepspeech2", deepspeech2_model(_gru), DeepSpeech2StreamGroup, n_chunks=4,
+                  baseline=("per_session_calls", Ds2BoxSessions))
     sys.exit(0)
 if "--efficient-conformer" in sys.argv:
     from ppasr_amd.model_utils.efficient_conformer.model import EfficientConformerStreamGroup
