@@ -60,6 +60,18 @@ inline std::vector<float> pack_b(int K, int N, Acc w) {
   return out;
 }
 
+// conv2 of Conv2dSubsampling4 in the pair form (front_fused.hip): K = 6 stages (kw, 128-channel half) x 4 slabs
+// (g0 = W[kh=0], W[kh=1], g0 + g1, g1 = W[kh=2]) x 128 channels, packed like pack_b.  w(k, n) is the direct form's
+// accessor (k = (kh * 3 + kw) * 256 + cin, as conv2_w).
+template <typename Acc>
+inline std::vector<float> pack_conv2_pair(int d, Acc w) {
+  return pack_b(24 * 128, d, [&](int k, int n) {
+    const int s = k / 512, slab = (k / 128) & 3, kw = s >> 1, c = (s & 1) * 128 + (k & 127);
+    const float g0 = w(kw * d + c, n), w1 = w((3 + kw) * d + c, n), g1 = w((6 + kw) * d + c, n);
+    return slab == 0 ? g0 : slab == 1 ? w1 : slab == 2 ? g0 + g1 : g1;
+  });
+}
+
 typedef std::unordered_map<std::string, Blob> BlobMap;
 
 // Efficient-Conformer: bit i = layer i is a stride-2 layer (ppasr_model_desc::stride_layer_mask, or the single

@@ -1,27 +1,41 @@
-// front_fused.hip -- Conv2dSubsampling4's two convolutions as ONE launch (conformer/subsampling.py:84-88):
+// front_fused.hip -- Conv2dSubsampling4's second convolution in the pair form, with conv1 fused in (conformer/subsampling.py:84-88):
 //   y2[b][t'][f2][c2] = relu(b2 + sum_{kh,kw,c} W2[c2][c][kh][kw] * y1[b][2t'+kh][2f2+kw][c]),
 //   y1[b][t1][f1][c]  = relu(b1 + sum_{i,j} W1[c][i][j] * cmvn(x)[b][2t1+i][2f1+j]).
-// k_conv1 wrote y1 to HBM (B*T1*F1*256 floats: 638 MB for 32 x 10 s, 1.27 GB for cfg4's 64 x 10 s -- at 5 - 6 TB/s the
-// largest HBM stream of a step) and conv2 (k_gemm_stream<.., Conv2Src>) gathered its implicit-GEMM A rows from it.  Here
-// the A tile of chunk kc + 1 (tap (kh, kw), 128 input channels) is COMPUTED from the features while the matrix pipe works
-// on chunk kc: the tile's features (<= 8 output frames x 7 input frames x F, normalised once) sit in LDS, every thread
-// owns 4 input channels (its 9 + 1 conv1 weight quads are re-requested per chunk: L1 hits) and 2 MT rows, and the 36
-// multiply-adds of a row quad are sliced into the k-groups of the running GEMM (rb_gemm Side) -- vector-ALU work in the
-// shadow of the MFMAs.  Each y1 element is recomputed for the ~2.25 output positions x that read it: +2.5 % FLOPs on the
-// vector ALU, no y1 traffic at all, one launch less.
-// Same arithmetic as k_conv1 followed by k_gemm_stream (same fmaf chain per y1 element, same MFMA order): bit-identical.
+//
+// Pair form (Winograd F(2,2) over time).  Output frames t0 = 2p and t0 + 1 read y1 frames 4p .. 4p + 4.  With
+// d0, d1, d2 = y1 frames 4p, 4p + 2, 4p + 4, o0, o1 = y1 frames 4p + 1, 4p + 3 and g0, g1 = W2[kh=0], W2[kh=2]:
+//   A = (d0 - d1) g0 + o0 W2[kh=1],   S = d1 (g0 + g1),   B = (d2 - d1) g1 + o1 W2[kh=1],
+//   y2[t0] = relu(A + S + b2),        y2[t0 + 1] = relu(S + B + b2)
+// (each product a K = 3 x 256 contraction over (kw, c)): 5 K=256 tap-GEMMs per pair of output frames instead of 6, and
+// 5 y1 frames instead of 6.  The transform constants are +-1; g0 + g1 is folded into the weights at load
+// (capi_internal.h pack_conv2_pair).  A GEMM row is a (pair, f2) position; pairs never straddle utterances (an odd Tp
+// leaves the last pair's second frame dead: computed from clamped inputs, never written).
+//
+// The contraction runs in 6 stages (kw, 128-channel half), each as 4 chunks with their own LDS A tile and weight slab:
+//   D01 = d0 - d1 (x g0 -> A),  O = [o0; o1] (x W2[kh=1] -> A and B: one weight slab, two row tiles),
+//   D1 = d1 (x (g0 + g1) -> S), D21 = d2 - d1 (x g1 -> B).
+// The tile of chunk j + 1 is produced while the matrix pipe works on chunk j (rb_gemm Side; double-buffered LDS).
+//
+// k_conv12 computes the y1 values from the features held in LDS (the tile's input frames, normalised once; each thread
+// owns 4 channels and 2 MT rows, d1 is kept in registers between the chunks that use it) -- y1 never leaves the chip.
+// k_conv2_pair is its two-launch twin (behind k_conv1, ppasr_set_front_fused(0)): the same body with the y1 values read
+// from HBM.  k_conv1 runs the same fmaf chain per y1 element, and the chunk / MFMA / epilogue order is shared: the two
+// routes are bit-identical.
 #include "conformer_kernels.h"
 #include "launch.h"
 
 namespace ppasr {
 
-template <int MT>
-__global__ __launch_bounds__(kThreads) void k_conv12(const float* __restrict__ feats, FrontW fw, float* __restrict__ out,
-                                                     int T, int F, int Tp, int F2, int M, int m0, PadSkip ps,
-                                                     const int* __restrict__ tile_tab) {
-  constexpr int BM = 32 * MT, KC = 128, LD = KC + 4, G = KC / 8, NL = 2 * MT, STEP = G / NL, N_CHUNKS = 18;
+// FROM_Y1 = false: src = features [B][T][F] (T, F: feature frames / bins); true: src = y1 [B][T][F][256] (T1, F1)
+template <int MT, bool FROM_Y1>
+__device__ __forceinline__ void conv2_pair_body(const float* __restrict__ src, const FrontW& fw, float* __restrict__ out,
+                                                int T, int F, int Tp, int F2, int M, int m0, const PadSkip& ps,
+                                                const int* __restrict__ tile_tab) {
+  constexpr int BP = 32 * MT, KC = 128, LD = KC + 4, G = KC / 8, NL = 2 * MT, N_STAGES = 6, N_CHUNKS = 4 * N_STAGES;
+  constexpr int SLOT = 2 * BP * LD;  // one A buffer: the O chunk's 2 BP rows
+  const int P = (Tp + 1) >> 1;       // pairs per utterance; M = B * P * F2 rows
   // tile -> rows: as k_gemm_stream (ragged batches: the t-th ACTIVE tile of the table, cut per utterance)
-  int r0 = m0 + blockIdx.x * BM, Mlim = M;
+  int r0 = m0 + blockIdx.x * BP, Mlim = M;
   if (tile_tab) {
     const int t = blockIdx.x, nb = tile_tab[0];
     const int* pre = tile_tab + 1;
@@ -33,101 +47,167 @@ __global__ __launch_bounds__(kThreads) void k_conv12(const float* __restrict__ f
       else hi = mid;
     }
     const int S = ps.Tp * ps.unit;
-    r0 = lo * S + (t - pre[lo]) * BM;
+    r0 = lo * S + (t - pre[lo]) * BP;
     Mlim = min(M, (lo + 1) * S);
-  } else if (pad_block_skippable(ps, r0, BM, M)) {
+  } else if (pad_block_skippable(ps, r0, BP, M)) {
     return;
   }
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* xs = smem + 2 * BM * LD;  // [output frame of the tile][7 input frames][F] normalised features
+  float* const slot0 = smem;
+  float* const slot1 = smem + SLOT;
   const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
   constexpr int tile_stride = N_CHUNKS * G * 64;
-  const f32x4* wbase = fw.conv2_w + (size_t)wave * tile_stride;
+  const f32x4* wbase = fw.conv2_wp + (size_t)wave * tile_stride;
   BRing<1> ring;
   ring_prime(ring, wbase, 0);
-  // ---- the tile's features: output frames bt0 .. bt0 + nbt - 1 of the flattened [B][Tp] frame space, input frames
-  // 4 t' .. 4 t' + 6 each (conv1 frame 2 t' + kh reads input frames 4 t' + 2 kh + i) ----
-  const int bt0 = r0 / F2, nbt = (min(r0 + BM, Mlim) - 1) / F2 - bt0 + 1;
-  for (int idx = tid; idx < nbt * 7 * F; idx += kThreads) {
-    const int p = idx / F, f = idx - p * F;
-    const int btl = p / 7, fr = p - 7 * btl;
-    const int bt = bt0 + btl, b = bt / Tp, tp = bt - b * Tp;
-    const int t = min(4 * tp + fr, T - 1);  // (always < T for rows < M)
-    xs[idx] = (feats[((size_t)b * T + t) * F + f] - fw.cmvn_mean[f]) * fw.cmvn_istd[f];
-  }
-  // ---- this thread's rows (2 MT of them, 16 apart) and input-channel quad ----
-  const int c4 = tid & 31, rbase = tid >> 5;
-  // the rows' windows inside xs, two 16-bit offsets per register (0xffff: a zero row; the 128-row kernel is 2 registers
-  // short of spilling)
+  const int c4 = tid & 31, rbase = tid >> 5;  // this thread's channel quad and first row (rows rbase + 16 i, i < NL)
+  const int bp0 = r0 / F2;                    // first (utterance, pair) of the tile
+  // ---- per-row state: where row i's y1 values come from ----
+  // fused: the row's window inside xs (the tile's input frames 8p .. 8p + 10 of each pair), two 16-bit offsets per
+  // register (0xffff: a zero row); twin: the row's first y1 frame b T1 + 4p, the frame 4p and 2 f2 (-1: a zero row)
+  float* xs = smem + 2 * SLOT;
   uint32_t pb[MT];
+  int yrow[FROM_Y1 ? NL : 1], yp4[FROM_Y1 ? NL : 1], yf[FROM_Y1 ? NL : 1];
+  if constexpr (!FROM_Y1) {
+    const int nbp = (min(r0 + BP, Mlim) - 1) / F2 - bp0 + 1;
+    for (int idx = tid; idx < nbp * 11 * F; idx += kThreads) {
+      const int q = idx / F, f = idx - q * F;
+      const int bpl = q / 11, fr = q - 11 * bpl;
+      const int bp = bp0 + bpl, b = bp / P, p = bp - b * P;
+      const int t = min(8 * p + fr, T - 1);  // (< T except for the dead second frame of an odd Tp's last pair)
+      xs[idx] = (src[((size_t)b * T + t) * F + f] - fw.cmvn_mean[f]) * fw.cmvn_istd[f];
+    }
 #pragma unroll
-  for (int i = 0; i < NL; ++i) {
-    const int m = r0 + rbase + 16 * i;
-    const int bt = m / F2, f2 = m - bt * F2;
-    const uint32_t v = m < Mlim ? (uint32_t)((bt - bt0) * 7 * F + 4 * f2) : 0xffffu;
-    pb[i >> 1] = (i & 1) ? (pb[i >> 1] | (v << 16)) : v;
+    for (int i = 0; i < NL; ++i) {
+      const int m = r0 + rbase + 16 * i;
+      const int bp = m / F2, f2 = m - bp * F2;
+      const uint32_t v = m < Mlim ? (uint32_t)((bp - bp0) * 11 * F + 4 * f2) : 0xffffu;
+      pb[i >> 1] = (i & 1) ? (pb[i >> 1] | (v << 16)) : v;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const int m = r0 + rbase + 16 * i;
+      const int bp = m / F2, f2 = m - bp * F2, b = bp / P, p = bp - b * P;
+      yrow[i] = b * T + 4 * p;
+      yp4[i] = 4 * p;
+      yf[i] = m < Mlim ? 2 * f2 : -1;
+    }
   }
   auto pbase = [&](int i) { return (int)((i & 1) ? (pb[i >> 1] >> 16) : (pb[i >> 1] & 0xffffu)); };
   const int lds_off0 = rbase * LD + 4 * c4;  // row i of this thread: + i * 16 * LD
-  f32x4 wv[9], bv;
+  f32x4 wv[FROM_Y1 ? 1 : 9], bv;
   float xv[9];
-  auto load_w = [&](int kc) {  // conv1 weights of the 4 channels this thread produces for chunk kc
-    const int c = (kc & 1) * 128 + 4 * c4;
+  f32x4 yv;
+  auto load_w = [&](int s) {  // conv1 weights of the 4 channels this thread produces in stage s
+    if constexpr (!FROM_Y1) {
+      const int c = (s & 1) * 128 + 4 * c4;
 #pragma unroll
-    for (int j = 0; j < 9; ++j) wv[j] = *reinterpret_cast<const f32x4*>(fw.conv1_w + j * 256 + c);
-    bv = *reinterpret_cast<const f32x4*>(fw.conv1_b + c);
+      for (int j = 0; j < 9; ++j) wv[j] = *reinterpret_cast<const f32x4*>(fw.conv1_w + j * 256 + c);
+      bv = *reinterpret_cast<const f32x4*>(fw.conv1_b + c);
+    }
   };
-  auto read_x = [&](int i, int toff) {  // toff = 2 kh F + 2 kw: the tap's corner inside a row's window
-    const int o = pbase(i);
-    const float* p = xs + (o == 0xffff ? 0 : o) + toff;
+  // y1 frame 4p + j of row i at column 2 f2 + kw, channels (s & 1) * 128 + 4 c4 .. + 3, in two steps: the request
+  // (LDS window / HBM) during one k-group, the value during the next
+  auto y1_read = [&](int i, int s, int j) {
+    const int kw = s >> 1;
+    if constexpr (!FROM_Y1) {
+      const int o = pbase(i);
+      const float* p = xs + (o == 0xffff ? 0 : o) + 2 * j * F + 2 * kw;
 #pragma unroll
-    for (int ii = 0; ii < 3; ++ii)
+      for (int ii = 0; ii < 3; ++ii)
 #pragma unroll
-      for (int jj = 0; jj < 3; ++jj) xv[ii * 3 + jj] = p[ii * F + jj];
+        for (int jj = 0; jj < 3; ++jj) xv[ii * 3 + jj] = p[ii * F + jj];
+    } else {
+      // (zero rows, and the frames behind T1 that only the dead second frame of an odd Tp's last pair reads)
+      yv = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (yf[i] >= 0 && yp4[i] + j < T)
+        yv = *reinterpret_cast<const f32x4*>(src + ((size_t)(yrow[i] + j) * F + yf[i] + kw) * 256 + (s & 1) * 128 + 4 * c4);
+    }
   };
-  // k_conv1's arithmetic for (row i, 4 channels), written straight into the A buffer of the NEXT chunk (free since the
-  // barrier that ended the previous chunk: nobody reads it during this chunk's GEMM)
-  auto fma_row = [&](int i, float* buf) {
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+  auto y1_value = [&](int i) {  // k_conv1's arithmetic (fused) / the value read (twin)
+    if constexpr (!FROM_Y1) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int j = 0; j < 9; ++j)
+      for (int j = 0; j < 9; ++j)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) a[e] = fmaf(wv[j][e], xv[j], a[e]);
-    a += bv;
+        for (int e = 0; e < 4; ++e) a[e] = fmaf(wv[j][e], xv[j], a[e]);
+      a += bv;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) a[e] = pbase(i) != 0xffff ? fmaxf(a[e], 0.f) : 0.f;
-    *reinterpret_cast<f32x4*>(buf + lds_off0 + i * 16 * LD) = a;
+      for (int e = 0; e < 4; ++e) a[e] = pbase(i) != 0xffff ? fmaxf(a[e], 0.f) : 0.f;
+      return a;
+    } else {
+      return yv;
+    }
   };
-  auto tap_off = [&](int kc) {
-    const int tap = kc >> 1, kh = tap / 3, kw = tap - 3 * kh;
-    return 2 * kh * F + 2 * kw;
+  auto put = [&](float* buf, int row16, const f32x4& v) {  // row16: this thread's row index (+ NL for O's second half)
+    *reinterpret_cast<f32x4*>(buf + lds_off0 + row16 * 16 * LD) = v;
   };
-  f32x16 acc[MT][1];
-  acc_zero(acc);
+  f32x4 d1c[NL], d0;  // d1 of the stage's rows (used by D01, D1 and D21); d0 until its d1 is there
+  // the chunks' tiles; y1 value number e (read during k-group 2e, used during 2e + 1)
+  auto side_d01 = [&](int s, int g) {  // D01 of stage s into slot 0
+    const int e = g >> 1, i = e >> 1;
+    if (e >= 2 * NL) return;
+    if ((g & 1) == 0) {
+      y1_read(i, s, (e & 1) ? 2 : 0);
+    } else if ((e & 1) == 0) {
+      d0 = y1_value(i);
+    } else {
+      d1c[i] = y1_value(i);
+      put(slot0, i, d0 - d1c[i]);
+    }
+  };
+  auto side_o = [&](int s, int g) {  // O of stage s into slot 1: o0 in rows [0, BP), o1 in rows [BP, 2 BP)
+    const int e = g >> 1, hi = e >= NL, i = e - (hi ? NL : 0);
+    if (e >= 2 * NL) return;
+    if ((g & 1) == 0) y1_read(i, s, hi ? 3 : 1);
+    else put(slot1, hi ? NL + i : i, y1_value(i));
+  };
+  auto side_d1 = [&](int g) {  // D1 into slot 0
+    if (g < NL) put(slot0, g, d1c[g]);
+  };
+  auto side_d21 = [&](int s, int g) {  // D21 of stage s into slot 1
+    const int e = g >> 1;
+    if (e >= NL) return;
+    if ((g & 1) == 0) y1_read(e, s, 4);
+    else put(slot1, e, y1_value(e) - d1c[e]);
+  };
   load_w(0);
   __syncthreads();  // xs complete
 #pragma unroll
-  for (int i = 0; i < NL; ++i) {
-    read_x(i, 0);
-    fma_row(i, smem);
+  for (int g = 0; g < 2 * G; ++g) {
+    side_d01(0, g);
+    __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();
-  for (int kc = 0; kc < N_CHUNKS; ++kc) {
-    float* cur = smem + (kc & 1) * BM * LD;
-    float* nxt = smem + ((kc + 1) & 1) * BM * LD;
-    const f32x4* seg = wbase + (size_t)kc * G * 64;
-    if (kc + 1 < N_CHUNKS) {
-      load_w(kc + 1);
-      const int toff = tap_off(kc + 1);
-      // row i of the next A tile: window read during k-group STEP i, multiply-adds during k-group STEP i + 1
-      auto side = [&](int g) {
-        const int i = g / STEP, ph = g - i * STEP;
-        if (i < NL && ph == 0) read_x(i, toff);
-        if (i < NL && ph == 1) fma_row(i, nxt);
-      };
-      rb_gemm<MT, 1, G, kPF, decltype(side)>(cur, LD, seg, 0, seg + G * 64, 0, ring, acc, side);
+  f32x16 accA[MT][1], accB[MT][1], accS[MT][1];
+  acc_zero(accA);
+  acc_zero(accB);
+  acc_zero(accS);
+  for (int s = 0; s < N_STAGES; ++s) {
+    const f32x4* seg = wbase + (size_t)(4 * s) * G * 64;
+    {
+      auto side = [&](int g) { side_o(s, g); };
+      rb_gemm<MT, 1, G, kPF, decltype(side)>(slot0, LD, seg, 0, seg + G * 64, 0, ring, accA, side);
+    }
+    __syncthreads();
+    {  // (the W2[kh=1] slab is streamed twice: o0 -> A, then o1 -> B)
+      auto side = [&](int g) { side_d1(g); };
+      rb_gemm<MT, 1, G, kPF, decltype(side)>(slot1, LD, seg + G * 64, 0, seg + G * 64, 0, ring, accA, side);
+      rb_gemm<MT, 1, G>(slot1 + BP * LD, LD, seg + G * 64, 0, seg + 2 * G * 64, 0, ring, accB);
+    }
+    __syncthreads();
+    {
+      auto side = [&](int g) { side_d21(s, g); };
+      rb_gemm<MT, 1, G, kPF, decltype(side)>(slot0, LD, seg + 2 * G * 64, 0, seg + 3 * G * 64, 0, ring, accS, side);
+    }
+    __syncthreads();
+    if (s + 1 < N_STAGES) {
+      load_w(s + 1);
+      auto side = [&](int g) { side_d01(s + 1, g); };
+      rb_gemm<MT, 1, G, kPF, decltype(side)>(slot1, LD, seg + 3 * G * 64, 0, seg + 4 * G * 64, 0, ring, accB, side);
     } else {
-      rb_gemm<MT, 1, G>(cur, LD, seg, 0, nullptr, 0, ring, acc);
+      rb_gemm<MT, 1, G>(slot1, LD, seg + 3 * G * 64, 0, nullptr, 0, ring, accB);
     }
     __syncthreads();
   }
@@ -138,64 +218,82 @@ __global__ __launch_bounds__(kThreads) void k_conv12(const float* __restrict__ f
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = r0 + mt * 32 + acc_row(r, lane);
-      const float v = fmaxf((acc[mt][0][r] + b2) * 1.0f, 0.f);
-      if (m < Mlim) out[(size_t)m * 256 + col] = v;
+      if (m >= Mlim) continue;
+      const int bp = m / F2, f2 = m - bp * F2, b = bp / P, t0 = 2 * (bp - b * P);
+      const float s = accS[mt][0][r];
+      float* o = out + ((size_t)(b * Tp + t0) * F2 + f2) * 256 + col;
+      o[0] = fmaxf(accA[mt][0][r] + s + b2, 0.f);
+      if (t0 + 1 < Tp) o[(size_t)F2 * 256] = fmaxf(s + accB[mt][0][r] + b2, 0.f);
     }
 }
 
-static size_t conv12_lds(int mt, int F, int F2) {
-  const int bm = 32 * mt, nbt = (bm - 1) / F2 + 2;
-  return ((size_t)2 * bm * 132 + (size_t)nbt * 7 * F) * sizeof(float);
+template <int MT>
+__global__ __launch_bounds__(kThreads) void k_conv12(const float* __restrict__ feats, FrontW fw, float* __restrict__ out,
+                                                     int T, int F, int Tp, int F2, int M, int m0, PadSkip ps,
+                                                     const int* __restrict__ tile_tab) {
+  conv2_pair_body<MT, false>(feats, fw, out, T, F, Tp, F2, M, m0, ps, tile_tab);
 }
+template <int MT>
+__global__ __launch_bounds__(kThreads) void k_conv2_pair(const float* __restrict__ y1, FrontW fw, float* __restrict__ out,
+                                                         int T1, int F1, int Tp, int F2, int M, int m0, PadSkip ps,
+                                                         const int* __restrict__ tile_tab) {
+  conv2_pair_body<MT, true>(y1, fw, out, T1, F1, Tp, F2, M, m0, ps, tile_tab);
+}
+
+static size_t pair_lds(int mt, bool fused, int F, int F2) {
+  const int bp = 32 * mt, nbp = (bp - 1) / F2 + 2;
+  return ((size_t)2 * 2 * bp * 132 + (fused ? (size_t)nbp * 11 * F : 0)) * sizeof(float);
+}
+bool conv2_pair_supported(const FrontW& fw) { return fw.conv2_wp && fw.conv2_k == 3 && fw.conv2_s == 2; }
 bool conv12_supported(const FrontW& fw, int F, int F2) {
-  // Conv2dSubsampling4 only (3x3 / 2 twice), and the 128-row tile's features + A double buffer must fit the CU's LDS
-  return fw.conv2_k == 3 && fw.conv2_s == 2 && F2 >= 1 && conv12_lds(4, F, F2) <= 160 * 1024 &&
-         (size_t)((127 / F2) + 2) * 7 * F < 0xffff;  // (16-bit window offsets)
+  // the pair form's weights, and the tile's features + A double buffer must fit the CU's LDS
+  return conv2_pair_supported(fw) && F2 >= 1 && pair_lds(1, true, F, F2) <= 160 * 1024 &&
+         (size_t)((31 / F2) + 2) * 11 * F < 0xffff;  // (16-bit window offsets)
 }
 
 // tile_prefix_launch: the ragged launch's tile table (front_kernels.hip k_tile_prefix)
 void launch_tile_prefix(const PadSkip& ps, int B, int BM, int* tab, hipStream_t st);
 
+// rows are (utterance, pair, f2): B * ceil(Tp / 2) * F2 of them.  Pair p holds frames 2p, 2p + 1 = input frames 8p ..,
+// so the ragged-batch rule of the frames (need = ceil(len / 4) + slack frames) becomes ceil(len / 8) + ceil(slack / 2)
+// pairs (a superset: ceil((a + s) / 2) <= ceil(a / 2) + ceil(s / 2)).
+static void launch_pair(bool fused, const float* src, const FrontW& fw, float* y2, int B, int T, int F, int Tp, int F2,
+                        hipStream_t st, const PadSkip& ps_frames, int* tile_scratch) {
+  const int P = (Tp + 1) / 2;
+  PadSkip ps = ps_frames;
+  ps.Tp = P;
+  ps.mul = 2 * ps_frames.mul;
+  ps.slack = (ps_frames.slack + 1) / 2;
+  ps.unit = F2;
+  const int M = B * P * F2;
+  const int* no_tab = nullptr;
+#define PAIR(MTA, GRID, M0, TAB)                                                                                        \
+  do {                                                                                                                 \
+    if (fused)                                                                                                         \
+      PPASR_LAUNCH(k_conv12<MTA>, dim3(GRID), dim3(kThreads), pair_lds(MTA, true, F, F2), st, src, fw, y2, T, F, Tp, F2, \
+                   M, M0, ps, TAB);                                                                                    \
+    else                                                                                                               \
+      PPASR_LAUNCH(k_conv2_pair<MTA>, dim3(GRID), dim3(kThreads), pair_lds(MTA, false, F, F2), st, src, fw, y2, T, F,   \
+                   Tp, F2, M, M0, ps, TAB);                                                                            \
+  } while (0)
+  // 32-row tiles (MT = 2 would need 96 accumulator registers besides conv1's weights and operands: more than the 256 a
+  // lane of a two-waves-per-SIMD workgroup has).  Ragged batches: the active tiles in front of one grid.
+  if (ps.lens && tile_scratch) {
+    launch_tile_prefix(ps, B, 32, tile_scratch, st);
+    PAIR(1, B * ((P * F2 + 31) / 32), 0, (const int*)tile_scratch);
+    return;
+  }
+  PAIR(1, (M + 31) / 32, 0, no_tab);
+#undef PAIR
+}
+
 void launch_conv12(const float* feats, const FrontW& fw, float* y2, int B, int T, int F, int Tp, int F2, hipStream_t st,
                    const PadSkip& ps_frames, int* tile_scratch) {
-  PadSkip ps = ps_frames;
-  ps.unit = F2;  // rows are (frame, f2) pairs
-  const int M = B * Tp * F2;
-  constexpr int kCUs = 256;
-  const int* no_tab = nullptr;
-#define CONV12(MTA, GRID, M0, TAB)                                                                                      \
-  PPASR_LAUNCH(k_conv12<MTA>, dim3(GRID), dim3(kThreads), conv12_lds(MTA, F, F2), st, feats, fw, y2, T, F, Tp, F2, M, M0, \
-               ps, TAB)
-  // (the same cut of the row space into launches as launch_conv_stage: whole rounds of 128-row tiles, the remainder
-  //  re-cut into <= 256 shorter tiles; ragged batches: the active tiles in front of one grid)
-  if (ps.lens && tile_scratch && M > 128 * kCUs) {
-    launch_tile_prefix(ps, B, 128, tile_scratch, st);
-    const int per_utt = (Tp * F2 + 127) / 128;
-    CONV12(4, B * per_utt, 0, (const int*)tile_scratch);
-    return;
-  }
-  const int tiles4 = (M + 127) / 128;
-  const int full = (tiles4 / kCUs) * kCUs;
-  const int rem_rows = M - full * 128;
-  const int mt_rem = (rem_rows + 32 * kCUs - 1) / (32 * kCUs);
-  if (full == 0) {
-    const int mt = (M + 32 * kCUs - 1) / (32 * kCUs);
-    if (mt <= 1) CONV12(1, (M + 31) / 32, 0, no_tab);
-    else if (mt == 2) CONV12(2, (M + 63) / 64, 0, no_tab);
-    else if (mt == 3) CONV12(3, (M + 95) / 96, 0, no_tab);
-    else CONV12(4, (M + 127) / 128, 0, no_tab);
-    return;
-  }
-  if (rem_rows <= 0 || mt_rem >= 4) {
-    CONV12(4, tiles4, 0, no_tab);
-    return;
-  }
-  CONV12(4, full, 0, no_tab);
-  const int m0 = full * 128;
-  if (mt_rem <= 1) CONV12(1, (rem_rows + 31) / 32, m0, no_tab);
-  else if (mt_rem == 2) CONV12(2, (rem_rows + 63) / 64, m0, no_tab);
-  else CONV12(3, (rem_rows + 95) / 96, m0, no_tab);
-#undef CONV12
+  launch_pair(true, feats, fw, y2, B, T, F, Tp, F2, st, ps_frames, tile_scratch);
+}
+void launch_conv2_pair(const float* y1, const FrontW& fw, float* y2, int B, int T1, int F1, int Tp, int F2, hipStream_t st,
+                       const PadSkip& ps_frames, int* tile_scratch) {
+  launch_pair(false, y1, fw, y2, B, T1, F1, Tp, F2, st, ps_frames, tile_scratch);
 }
 
 hipError_t configure_front_fused_kernels() {
@@ -204,9 +302,7 @@ hipError_t configure_front_fused_kernels() {
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
   if (e != hipSuccess) return e;
   SET_LDS(k_conv12<1>);
-  SET_LDS(k_conv12<2>);
-  SET_LDS(k_conv12<3>);
-  SET_LDS(k_conv12<4>);
+  SET_LDS(k_conv2_pair<1>);
 #undef SET_LDS
   return hipSuccess;
 }
