@@ -20,11 +20,16 @@ collective other than that gather).
     python bench.py --gpus 2 --dry-run-cpu   # plumbing check without a GPU: gloo, 2 ranks, stub kernels (value is null)
     python bench.py --dump-outputs DIR       # + the last timed step's token ids / counts / scores as DIR/*.npy: the inputs
                                              #   are seeded, so two builds can be compared output for output
+    python bench.py --full                   # + every leg after the timed steps (below); a plain run sets up, warms up,
+                                             #   times the steps, dumps and prints, and nothing else
 
 Prints ONE JSON line on rank 0 (contract in the task statement): `value` comes from the wall time of EXACTLY K steps
 bracketed by barrier + synchronize (max over ranks).  Extra fields:
   median_ms_per_step - median of the K per-step durations measured with HIP events on the launch stream
   n_ranks_seen       - torch.distributed world size as RCCL saw it (asserted == --gpus), `backend`
+With --full (null without it):
+  config.serial      - cfg4 / cfg5: the same steps with the beam search on the encoder's stream (no overlap)
+  config.f16x3       - cfg2 / cfg4 / cfg5: the same steps in the opt-in fp16 x3 GEMM mode, and whether its tokens agree
   roofline           - dominant kernel's algorithmic FLOP/s (or bytes/s) vs the chip peak; its launch duration is measured
                        live with HIP events attached to every dispatch (ppasr_kprof_* in the C-ABI); `traffic` = HBM bytes
                        per launch from the committed rocprofv3 PMC passes, used only when they were collected for THIS
@@ -214,7 +219,10 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU")
     ap.add_argument("--frames", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs the headline does not need: the serial figure (cfg4 / "
+                         "cfg5), the roofline, the fp16 x3 mode's figure and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--gemm", default="f32", choices=["f32", "f16x3"],
                     help="f16x3: the WHOLE line in the opt-in fp16 x 3 GEMM mode (ppasr_set_gemm_mode; cfg2 / cfg4 / cfg5), dtype "
                          "'f16x3-split', its own roofline denominator; never the headline (default f32: exact fp32 MFMA)")
@@ -957,9 +965,9 @@ def main():
     # Pipelined workloads (cfg4 / cfg5): the same steps once more with the overlap switched off -- encoder, then its beam
     # search, then the next step -- so that the line carries BOTH figures: `value` = the pipelined rate (a caller with a
     # stream of batches), config.serial = what a caller with ONE batch at a time gets.  Every rank runs it (N > 1: a
-    # step ends in the all-gather).
+    # step ends in the all-gather).  This and every leg below run with --full only.
     serial = None
-    if w.pipelined and not dry:
+    if args.full and w.pipelined and not dry:
         holder, attr = (w.plan, "pipeline") if hasattr(w, "plan") else (w.pipe, "enable")
         setattr(holder, attr, False)
         try:
@@ -989,23 +997,24 @@ def main():
     # EVERY rank runs the leg (each profiles its own kernels; rank 0's figures are reported) -- a rank-0-only leg would
     # leave rank 0 waiting in a collective the other ranks never enter.  The dry run mirrors the extra steps.
     roofline = None
-    if dry:
-        for _ in range(ROOFLINE_REPS):
-            w.step()
-        w.finish()
-    else:
-        roofline = build_roofline(w, args, ms_per_step)
-        if rank != 0:
-            roofline = None
-    if world > 1:
-        dist.barrier()
+    if args.full:
+        if dry:
+            for _ in range(ROOFLINE_REPS):
+                w.step()
+            w.finish()
+        else:
+            roofline = build_roofline(w, args, ms_per_step)
+            if rank != 0:
+                roofline = None
+        if world > 1:
+            dist.barrier()
 
     # cfg2 / cfg4 / cfg5: the same steps once more with the large GEMMs on the opt-in fp16 x3 route (ppasr_set_gemm_mode, csrc/h3.h).
     # NOT the headline: `value` above is the default fp32-MFMA mode; this figure goes to config.f16x3 together with whether
     # the token ids of the batch (greedy / beam search) are the default mode's.  Every rank runs it (a step ends in the
     # all-gather).
     f16x3 = None
-    if not dry and args.config in ("cfg2", "cfg4", "cfg5") and args.gemm == "f32":
+    if args.full and not dry and args.config in ("cfg2", "cfg4", "cfg5") and args.gemm == "f32":
         ref_out = w.step()
         sync()
         ref_ids = [t.clone() for t in ref_out[:2]]
@@ -1049,7 +1058,7 @@ def main():
             w.model.set_gemm_mode("f32")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
         cpu = w.cpu_baseline()
 
     if rank == 0:

@@ -31,6 +31,13 @@ def test_under_the_drivers_launcher():
     assert line["n_ranks_seen"] == 2 and line["scaling"] == "weak"
 
 
+def test_full_runs_its_legs_under_both_launch_forms():
+    """--full: the legs after the timed steps (in a dry run, the roofline leg's extra steps) on every rank, one line."""
+    line = _run([sys.executable, "bench.py", "--gpus", "2", "--dry-run-cpu", "--steps", "2", "--warmup", "1", "--full"])
+    assert line["n_ranks_seen"] == 2 and line["steps"] == 2 and line["value"] is None
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+
+
 def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
     """--dump-outputs DIR: the last timed step's gathered (tokens, n_tokens, scores) as float32 / float64 .npy files, the
     same for two runs with the same arguments; --steps sets the timed steps and the line carries ms_per_step."""

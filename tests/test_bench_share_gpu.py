@@ -1,7 +1,8 @@
 """GPU: `bench.py --gpus 2 --share-gpu` -- the REAL workload of every BASELINE config under the driver's launcher with two
 ranks on the one visible GPU (gloo backend, host-staged collectives): the whole N > 1 flow (model creation per rank, the
 hypothesis all-gather at the end of every step, the barrier-bracketed timing, the roofline leg on every rank, ONE JSON
-line) that the dry-run test cannot reach because its steps launch nothing.  Not a measurement."""
+line) that the dry-run test cannot reach because its steps launch nothing.  Run with --full, so that the legs after the
+timed steps take part too.  Not a measurement."""
 import json
 import os
 import subprocess
@@ -26,8 +27,16 @@ def _run(cmd):
 def test_two_ranks_share_the_gpu(cfg, rows):
     line = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                  "127.0.0.1", "--master-port", str(29900 + os.getpid() % 90), "bench.py", "--config", cfg, "--gpus", "2",
-                 "--share-gpu", "--steps", "3", "--warmup", "1"])
+                 "--share-gpu", "--steps", "3", "--warmup", "1", "--full"])
     assert line["n_gpus"] == 2 and line["n_ranks_seen"] == 2 and line["backend"] == "gloo"
     assert line["config"]["global_batch"] == rows and line["steps"] == 3
     assert "plumbing check" in line["data"] and line["value"] > 0
     assert line["roofline"] and line["roofline"]["kernel"] and line["cpu_baseline"] is None
+
+
+def test_plain_run_leaves_the_full_legs_out():
+    """Without --full a run times its steps and prints: no serial, fp16 x3, roofline or CPU-baseline leg."""
+    line = _run([sys.executable, "bench.py", "--config", "cfg4", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["config"]["pipelined"]
+    assert line["config"]["serial"] is None and line["config"]["f16x3"] is None
+    assert line["roofline"] is None and line["cpu_baseline"] is None
