@@ -168,7 +168,9 @@ PPASR_API ppasr_status ppasr_set_skip_padding(ppasr_handle h, int enable);
  * session) the Conformer-family layer tail is cut at its two feed-forward modules and each module's hidden dimension is
  * split over 2 / 4 / 8 workgroups per row block (partial sums joined by the next launch).  Same arithmetic up to the
  * order of the final sum over hidden chunks.  mode: -1 = decide by grid size (default), 0 = never (always the fused
- * kernels, the fused attention kernel included), 2 / 4 / 8 = always that many slices. */
+ * kernels, the fused attention kernel included), 2 / 4 / 8 = always that many slices.  The partial sums live in the
+ * workspace: ppasr_workspace_bytes / ppasr_chunk_workspace_bytes / ppasr_group_chunk_workspace_bytes follow the mode, so
+ * query them again after changing it (a call with a smaller workspace returns PPASR_ENOSPACE). */
 PPASR_API ppasr_status ppasr_set_ffn_split(ppasr_handle h, int mode);
 
 /* Conv2dSubsampling4 (conformer/subsampling.py:84-88) as ONE launch (csrc/front_fused.hip: conv1's output is computed
@@ -347,8 +349,10 @@ PPASR_API ppasr_status ppasr_stream_destroy(ppasr_stream s);
 PPASR_API ppasr_status ppasr_stream_reset(ppasr_stream s, void* stream);
 PPASR_API int ppasr_stream_offset(ppasr_stream s);        /* encoder frames emitted so far */
 PPASR_API int ppasr_stream_cache_frames(ppasr_stream s);  /* cache_t1: key/value frames currently cached */
-PPASR_API size_t ppasr_chunk_workspace_bytes(ppasr_handle h, int T);  /* (query it per T: it holds the chunk's activations, the
-                                                                         cache-trim scratch and the front end's K-split tiles) */
+PPASR_API size_t ppasr_chunk_workspace_bytes(ppasr_handle h, int T);  /* (the chunk's activations, the cache-trim scratch and
+                                                                         the front end's K-split tiles; never decreases as T
+                                                                         grows, so a workspace sized for the longest chunk
+                                                                         serves every shorter one) */
 /*   feats [1,T,F] f32; required_cache_size as in encoder.py:255-260 (<0 keep everything, the value
  *   predict_stream uses; 0 none; >0 last n frames); probs [1,c,V] or NULL; c = ((T-1)/2-1)/2 is also
  *   written to *c_out_host (host int, may be NULL). */
@@ -373,7 +377,7 @@ PPASR_API ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* at
  * synchronisation and a 4-byte read-back of the kernels' give-up flag; when a launch gave up (the chip was shared with
  * another stream / process) the call re-runs on the per-step kernels before it returns, and the handle stays on those for
  * the next 64 .. 1 024 calls before it tries the persistent route again.  PPASR_DS2_PERSIST=0 switches the route off. */
-PPASR_API size_t ppasr_ds2_workspace_bytes(ppasr_handle h, int B, int T);
+PPASR_API size_t ppasr_ds2_workspace_bytes(ppasr_handle h, int B, int T);  /* (never decreases as B or T grows) */
 /* Test hook, not part of any product path: `n_workgroups` workgroups that each take a whole CU (1 024 threads, 128
  * registers per lane) and spin for `milliseconds` on `stream`.  With part of the chip held like this the persistent
  * recurrence above cannot become fully resident and gives up: the tests check that the call then returns the per-step

@@ -54,7 +54,7 @@ ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob*
     g2->desc = *desc;
     g2->F1 = (desc->input_dim - 1) / 2;
     g2->F2 = (g2->F1 - 1) / 2;
-    if (g2->F1 > 40) return fail(PPASR_EUNSUPPORTED, "deepspeech2: input_dim <= 81");
+    if (g2->F1 > 40) return fail(PPASR_EUNSUPPORTED, "deepspeech2: input_dim <= 82 ((input_dim - 1) / 2 <= 40)");
     ppasr_status s2 = ds2_create(g2.get(), sd2);
     if (s2 != PPASR_OK) return s2;
     HIP_TRY(hipDeviceSynchronize());
@@ -161,6 +161,9 @@ ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob*
   if (il != 0 && desc->model_type == PPASR_MODEL_SQUEEZEFORMER)
     return fail(PPASR_EUNSUPPORTED, "squeezeformer: only the conv2d front end is built");
   m->F1 = (F - 1) / 2;
+  // conv2d6's 5-wide kernel needs F1 >= 5: below that (F1 - 5) / 3 truncates toward zero to F2 = 1, and the conv would
+  // read past the end of each conv1 row (the reference's conv2d raises)
+  if (il == 6 && m->F1 < 5) return fail(PPASR_EINVAL, "input_dim too small for this input_layer (conv2d6: >= 11)");
   m->F2 = il == 6 ? (m->F1 - 5) / 3 + 1 : (m->F1 - 1) / 2;
   m->F3 = il == 8 ? (m->F2 - 1) / 2 : 0;
   if (il != 1 && m->F_last() < 1) return fail(PPASR_EINVAL, "input_dim too small for this input_layer");
@@ -439,8 +442,19 @@ WsLayout ws_layout(const ppasr_model_s* m, int B, int T) {
   auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
   WsLayout w;
   size_t o = 0;
-  w.y1 = o; o += al((size_t)B * T1 * m->F1 * kD);  // (conv2d8: the third conv's output reuses it)
-  w.y2 = o; o += al((size_t)B * (fd.T2 ? fd.T2 : Tp) * m->F2 * kD);
+  // Partial-sum tiles of the under-filled launches (ffn_split_for: S slices of Mi <= M rows): the default split keeps
+  // S x blocks <= 256, so S Mi <= 256 x 32 rows; one forced by ppasr_set_ffn_split is S = ffn_split at any Mi.
+  const size_t split_rows = m->ffn_split > 1 ? (size_t)m->ffn_split * M
+                          : m->ffn_split == 0 ? 0 : std::min((size_t)8 * M, (size_t)256 * kRows);
+  // (conv2d8: the third conv's output reuses it.)  Once the front end has read it, the conv1 buffer is the partial-sum
+  // scratch of the layers and the head: up to 4 S tiles (the streaming chunk's two fused FFN joins of 2 S tiles each).
+  // conv1's own output (T1 >= 2 T' + 1 frames of F1 bins) covers that from F1 = 16 on; at fewer bins the buffer is
+  // sized for the scratch.
+  w.y1 = o; o += al(std::max((size_t)B * T1 * m->F1 * kD, 4 * split_rows * kD));
+  // conv2d8: once the third conv has read it, conv2's output buffer is the embed's K-split scratch (S tiles); conv2's
+  // own output (T2 >= 2 T' + 1 frames of F2 bins) covers that from F2 = 4 on
+  const size_t y2_floats = (size_t)B * (fd.T2 ? fd.T2 : Tp) * m->F2 * kD;
+  w.y2 = o; o += al(m->desc.input_layer == 8 ? std::max(y2_floats, split_rows * kD) : y2_floats);
   w.xa = o; o += al(M * kD);
   w.xb = o; o += al(M * kD);
   w.xc = o; o += al(M * kD);

@@ -205,8 +205,10 @@ static Ds2Ws ds2_ws(const ppasr_model_s* m, int B, int T) {
   w.cbuf = o; o += al64((size_t)W.n_layers * B * W.H);
   w.yring = o; o += al64((size_t)W.n_layers * 2 * Bp * W.H);
   // K-slice partial sums of the dense layers when the launch is under-filled (few frames: single utterances)
-  w.part_floats = M <= 512 ? (size_t)8 * M * std::max((size_t)W.gates * W.H, (size_t)W.Vpad) : 0;
-  w.part = o; o += al64(w.part_floats);
+  // (reserved for up to 512 rows even past them: the workspace size never decreases with B or T)
+  const size_t part_cols = std::max((size_t)W.gates * W.H, (size_t)W.Vpad);
+  w.part_floats = M <= 512 ? (size_t)8 * M * part_cols : 0;
+  w.part = o; o += al64((size_t)8 * std::min(M, (size_t)512) * part_cols);
   // persistent recurrence of single utterances (k_lstm_persist): exchange granules [2][dirs][H] x 8 bytes, abort flag
   w.xbuf = o; o += al64((size_t)4 * W.dirs * W.H);
   w.pflag = o; o += 64;

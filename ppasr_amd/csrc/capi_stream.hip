@@ -395,8 +395,9 @@ size_t ppasr_chunk_workspace_bytes(ppasr_handle h, int T) {
   const size_t Tp = h->front_dims(T).Tp;
   if (h->generic) return (generic_ws_floats(h, 1, T) + (size_t)h->desc.max_len * h->desc.output_size) * sizeof(float);
   // the full-utterance layout for B=1, plus the conv-module input rows and a cache-shift scratch
-  // (+ the K-split scratch of the chunk's conv2 launch)
-  return (ws_layout(h, 1, T).total + Tp * kD + 64 + (size_t)h->desc.max_len * kD + conv_stage_part_floats((int)Tp * h->F2)) *
+  // (+ the K-split scratch of the chunk's conv2 launch, reserved for up to its row limit even past it: the size never
+  // decreases with T, so one workspace sized for the longest chunk serves every shorter one)
+  return (ws_layout(h, 1, T).total + Tp * kD + 64 + (size_t)h->desc.max_len * kD + conv_stage_part_reserve((int)Tp * h->F2)) *
          sizeof(float);
 }
 

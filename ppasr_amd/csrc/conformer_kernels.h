@@ -165,6 +165,9 @@ void launch_conv_stage(const float* y_in, const f32x4* w, const float* bias, flo
                        float* part = nullptr, size_t part_floats = 0);  // scratch: under-filled launches split the taps (K)
 // floats of `part` that let launch_conv_stage split a launch of M output rows over its K chunks (0: it would not split)
 size_t conv_stage_part_floats(int M, int channels = 256);
+// the largest conv_stage_part_floats(m) over m <= M (channels 256): what a workspace for up to M rows reserves, so that the
+// workspace size never drops where M passes the split's row limit
+size_t conv_stage_part_reserve(int M);
 // tile_scratch (ragged batches): device scratch of B + 2 ints for the active-tile table (k_tile_prefix)
 void launch_conv2(const float* y1, const FrontW& fw, float* y2, int B, int T1, int F1, int Tp, int F2, hipStream_t st,
                   const PadSkip& ps = PadSkip{}, int* tile_scratch = nullptr, const f32x4* w_h3 = nullptr, float* part = nullptr,

@@ -3,6 +3,7 @@
 // and the plain dense layers (DenseSrc), their fp16 x3 instantiations, the active-tile / active-block tables of ragged
 // batches.  (Split from conformer_kernels.hip in round 5; the one-launch conv1 + conv2 is front_fused.hip.)
 // Reference: ppasr/model_utils/conformer/{subsampling,embedding}.py, model_utils/utils/cmvn.py (file:line per kernel).
+#include <algorithm>
 #include <cstdlib>
 
 #include "conformer_kernels.h"
@@ -371,9 +372,11 @@ __global__ __launch_bounds__(256) void k_gemm_join(const float* __restrict__ par
   *reinterpret_cast<f32x4*>(out + (size_t)row * kD + 4 * lane) = y;
 }
 constexpr int kConvSplitMax = 9;  // K slices of an under-filled convolution stage (3 x 3 taps x 2 chunks = 18 chunks: 2 each)
+constexpr int kConvSplitRows = 32 * 28;  // rows up to which an under-filled stage takes the K split
 size_t conv_stage_part_floats(int M, int channels) {
-  return (channels == 256 && M <= 32 * 28) ? (size_t)kConvSplitMax * M * 256 : 0;
+  return (channels == 256 && M <= kConvSplitRows) ? (size_t)kConvSplitMax * M * 256 : 0;
 }
+size_t conv_stage_part_reserve(int M) { return conv_stage_part_floats(std::min(M, kConvSplitRows)); }
 
 void launch_conv2(const float* y1, const FrontW& fw, float* y2, int B, int T1, int F1, int Tp, int F2, hipStream_t st,
                   const PadSkip& ps_frames, int* tile_scratch, const f32x4* w_h3, float* part, size_t part_floats) {

@@ -58,6 +58,7 @@ class DeepSpeech2Model:
     def _run(self, speech, speech_lengths, init_h=None, init_c=None, want_states=False):
         x = torch.as_tensor(speech, dtype=torch.float32).to(self.device).contiguous()
         lens = torch.as_tensor(speech_lengths, dtype=torch.int64).to(self.device).contiguous()
+        assert x.dim() == 3 and x.shape[2] == self.input_dim and lens.shape[0] == x.shape[0]
         B, T, _ = x.shape
         Tp = self.out_frames(T)
         need = int(self.lib.ppasr_ds2_workspace_bytes(self._h, B, T))

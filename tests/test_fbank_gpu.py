@@ -17,16 +17,24 @@ def _audio(seconds, seed=0, sr=16000):
     return x.astype(np.float32)
 
 
-@pytest.mark.parametrize("seconds,use_db", [(2.0, True), (2.0, False), (0.0251, True), (10.0, True), (0.5123, True), (1.0240625, True),
-                                            (29.97, True)])
-def test_fbank_matches_oracle(seconds, use_db):
+# (seconds, use_db) at 80 mels / 16 kHz; other banks: 64 and 128 mels at 16 kHz (128: one empty filter and 24 that cover
+# one FFT bin), 80 mels at 8 kHz (14 one-bin filters) -- the empty and one-bin rows take the bank_lo == bank_hi path and
+# the floor
+FBANK_CASES = ([pytest.param(s, db, 80, 16000, id=f"{s}-{db}") for s, db in
+                [(2.0, True), (2.0, False), (0.0251, True), (10.0, True), (0.5123, True), (1.0240625, True), (29.97, True)]]
+               + [pytest.param(s, True, n, sr, id=f"{s}-True-{n}mel-{sr // 1000}k")
+                  for n, sr in ((64, 16000), (128, 16000), (80, 8000)) for s in (2.0, 0.5123, 10.0)])
+
+
+@pytest.mark.parametrize("seconds,use_db,n_mels,sr", FBANK_CASES)
+def test_fbank_matches_oracle(seconds, use_db, n_mels, sr):
     from ppasr_amd.data_utils.featurizer import AudioFeaturizer
-    wav = _audio(seconds, seed=int(seconds * 10))
-    f = AudioFeaturizer(feature_method="fbank", n_mels=80, sample_rate=16000, use_dB_normalization=use_db, target_dB=-20)
-    got = f.featurize(wav)
-    ref = fbank_oracle.featurize(wav, 16000, 80, use_db, -20.0)
-    assert got.shape == ref.shape and got.dtype == np.float32
-    assert got.shape[0] == 1 + (len(wav) - 400) // 160
+    wav = _audio(seconds, seed=int(seconds * 10), sr=sr)
+    f = AudioFeaturizer(feature_method="fbank", n_mels=n_mels, sample_rate=sr, use_dB_normalization=use_db, target_dB=-20)
+    got = f.featurize(wav, sr)
+    ref = fbank_oracle.featurize(wav, sr, n_mels, use_db, -20.0)
+    assert got.shape == ref.shape and got.dtype == np.float32 and got.shape[1] == n_mels
+    assert got.shape[0] == 1 + (len(wav) - sr // 40) // (sr // 100)  # 25 ms windows, 10 ms hop
     # The gain is bit-exact (the kernel sums the squares in numpy's order: pairwise, 8192-element chunks), so every int16
     # sample equals the oracle's; what is left is fp32 arithmetic (window, radix-2 FFT, mel sums) against the oracle's
     # float64.  Its error scales with the frame's LARGEST spectral amplitude, so a mel bin that sits e_max / e below the

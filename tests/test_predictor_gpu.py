@@ -55,6 +55,35 @@ def test_predict_and_predict_stream_conformer(decoder):
     assert p.predictor.offset[0] == 0 and p.predictor.att_cache.shape == (0, 0, 0, 0)
 
 
+def test_predictor_builds_the_handle_at_the_configured_n_mels():
+    """preprocess_conf.n_mels = 64 (inference_predictor.py: the handle's input_dim comes from the config): the handle is
+    built at 64 bins, predict's text is the model's on AudioFeaturizer(n_mels=64) output, and on that output the float64
+    oracle's greedy ids are the model's"""
+    import numerics as nm
+    from ppasr_amd.data_utils.featurizer import AudioFeaturizer
+    from ppasr_amd.predict import PPASRPredictor
+    V, L = 300, 2
+    vocab = synth_vocabulary(V)
+    sd = conformer_state_dict(input_dim=64, vocab_size=V, num_blocks=L, seed=31, perturb_norm=True)
+    cfg = _cfg(L=L)
+    cfg["preprocess_conf"]["n_mels"] = 64
+    p = PPASRPredictor(configs=cfg, state_dict=sd, vocab_list=vocab, warmup=False)
+    model = p.predictor.model
+    assert model.input_dim == 64
+    wav = _audio(2.3, seed=4)
+    res = p.predict(audio_data=wav)
+    feat = AudioFeaturizer(**cfg["preprocess_conf"]).featurize(wav)
+    assert feat.shape[1] == 64
+    x, lens = feat[None].astype(np.float32), np.array([feat.shape[0]], np.int64)
+    probs, logits = model.get_encoder_out(x, lens, return_logits=True)
+    torch.cuda.synchronize()
+    assert p.decode(probs[0])[1] == res["text"]
+    ref = nm.oracle64("conformer", sd, num_blocks=L).get_encoder_out(x, lens, return_logits=True)[1]
+    ok, near = nm.frame_ids_ok(logits, ref, nm.F32_BUDGET)
+    print(f"n_mels=64: logits {nm.utt_rel(logits, ref):.2e}, near-ties {near}, text {res['text']!r}")
+    assert ok
+
+
 def test_inference_predictor_matches_model_and_numpy_io():
     from ppasr_amd.infer_utils.inference_predictor import InferencePredictor
     V = 200
