@@ -223,7 +223,7 @@ ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob*
     auto c2 = [&](int k, int n) { return c2w[((size_t)n * d + (k % d)) * taps2 + (k / d)]; };
     UP4(pack_b(taps2 * d, d, c2), m->front.conv2_w);
     m->front.conv2_wp = nullptr;
-    if (il == 0 && d == kD) UP4(pack_conv2_pair(d, c2), m->front.conv2_wp);  // (batched calls: front_fused.hip)
+    if (il == 0 && d == kD) UP4(pack_conv2_quad(d, c2), m->front.conv2_wp);  // (batched calls: front_fused.hip)
     UP(vec_of(c2b, d), m->front.conv2_b);
     m->front.conv2_k = k2;
     m->front.conv2_s = il == 6 ? 3 : 2;
@@ -863,8 +863,8 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
       // (ragged batches: the active-tile table of conv2 lives in the CTC head's statistics buffer, unused until the head)
       int* tile_tab = (size_t)B + 2 <= ((size_t)M + 63) / 64 * 64 ? reinterpret_cast<int*>(ws + wl.rmax) : nullptr;
       if (conv12) launch_conv12(feats, h->front, y2, B, T, F, Tp, F2, st, ps_front, tile_tab);
-      else if (h->desc.input_layer == 0 && !conv2_h3 && conv2_pair_supported(h->front))
-        launch_conv2_pair(y1, h->front, y2, B, T1, F1, Tp, F2, st, ps_front, tile_tab);
+      else if (h->desc.input_layer == 0 && !conv2_h3 && conv2_quad_supported(h->front))
+        launch_conv2_quad(y1, h->front, y2, B, T1, F1, Tp, F2, st, ps_front, tile_tab);
       else launch_conv2(y1, h->front, y2, B, T1, F1, Tp, F2, st, ps_front, tile_tab, h->desc.input_layer == 0 ? conv2_h3 : nullptr);
     });
     timed(2, [&] {

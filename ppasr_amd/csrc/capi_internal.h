@@ -60,15 +60,21 @@ inline std::vector<float> pack_b(int K, int N, Acc w) {
   return out;
 }
 
-// conv2 of Conv2dSubsampling4 in the pair form (front_fused.hip): K = 6 stages (kw, 128-channel half) x 4 slabs
-// (g0 = W[kh=0], W[kh=1], g0 + g1, g1 = W[kh=2]) x 128 channels, packed like pack_b.  w(k, n) is the direct form's
-// accessor (k = (kh * 3 + kw) * 256 + cin, as conv2_w).
+// conv2 of Conv2dSubsampling4 in the quad form (front_fused.hip): K = 2 stages (128-channel half) x 16 slabs x 128
+// channels, packed like pack_b.  Slab 4 ft + ff is the kh factor ft times the kw factor ff, each of w0, w1, w0 + w2, w2
+// (the taps {0}, {1}, {0, 2}, {2}), summed in double.  w(k, n) is the direct form's accessor (k = (kh * 3 + kw) * 256 +
+// cin, as conv2_w).
 template <typename Acc>
-inline std::vector<float> pack_conv2_pair(int d, Acc w) {
-  return pack_b(24 * 128, d, [&](int k, int n) {
-    const int s = k / 512, slab = (k / 128) & 3, kw = s >> 1, c = (s & 1) * 128 + (k & 127);
-    const float g0 = w(kw * d + c, n), w1 = w((3 + kw) * d + c, n), g1 = w((6 + kw) * d + c, n);
-    return slab == 0 ? g0 : slab == 1 ? w1 : slab == 2 ? g0 + g1 : g1;
+inline std::vector<float> pack_conv2_quad(int d, Acc w) {
+  static const int taps[4][2] = {{0, -1}, {1, -1}, {0, 2}, {2, -1}};
+  return pack_b(32 * 128, d, [&](int k, int n) {
+    const int h = k / 2048, slab = (k / 128) & 15, c = h * 128 + (k & 127);
+    const int* th = taps[slab >> 2];
+    const int* tw = taps[slab & 3];
+    double v = 0.0;
+    for (int a = 0; a < 2 && th[a] >= 0; ++a)
+      for (int e = 0; e < 2 && tw[e] >= 0; ++e) v += (double)w((th[a] * 3 + tw[e]) * d + c, n);
+    return (float)v;
   });
 }
 

@@ -79,7 +79,7 @@ ppasr_status squeezeformer_create(ppasr_model_s* m, BlobMap& sd, const float* pe
       return c2w[((size_t)n * d + (k % d)) * 9 + (k / d)];
     };
     UP4(pack_b(9 * d, d, c2), m->front.conv2_w);
-    if (d == kD) UP4(pack_conv2_pair(d, c2), m->front.conv2_wp);  // (batched calls: front_fused.hip)
+    if (d == kD) UP4(pack_conv2_quad(d, c2), m->front.conv2_wp);  // (batched calls: front_fused.hip)
     UP(vec_of(c2b, d), m->front.conv2_b);
     UP4(pack_b(F2 * d, d, [&](int k, int n) { return ew[((size_t)(k % d) * F2 + (k / d)) * d + n]; }), m->front.embed_w);
     UP(vec_of(eb, d), m->front.embed_b);
@@ -385,7 +385,7 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
     launch_conv12(feats, h->front, y2, B, T, F, Tp, F2, st, psF, tile_tab);
   } else {
     launch_conv1(feats, h->front, y1, B, T, F, T1, F1, st, psF);
-    if (!conv2_h3 && conv2_pair_supported(h->front)) launch_conv2_pair(y1, h->front, y2, B, T1, F1, Tp, F2, st, psF, tile_tab);
+    if (!conv2_h3 && conv2_quad_supported(h->front)) launch_conv2_quad(y1, h->front, y2, B, T1, F1, Tp, F2, st, psF, tile_tab);
     else launch_conv2(y1, h->front, y2, B, T1, F1, Tp, F2, st, psF, tile_tab, conv2_h3);
   }
   // (the embed GEMM works on 32-row blocks: it takes the full-rate list when that is the 32-row one)

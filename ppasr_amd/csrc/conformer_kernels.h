@@ -26,7 +26,7 @@ struct FrontW {
   const float *cmvn_mean, *cmvn_istd;  // [F]
   const float *conv1_w, *conv1_b;      // [9][256] tap-major, [256]
   const f32x4 *conv2_w;                // packed, K = k*k*256 ordered (kh,kw,cin)
-  const f32x4 *conv2_wp = nullptr;     // Conv2dSubsampling4 only: conv2 in the pair form (front_fused.hip, pack_conv2_pair)
+  const f32x4 *conv2_wp = nullptr;     // Conv2dSubsampling4 only: conv2 in the quad form (front_fused.hip, pack_conv2_quad)
   const float *conv2_b;
   int conv2_k = 3, conv2_s = 2;        // 3, 2 (conv2d / conv2d8, Squeezeformer) or 5, 3 (conv2d6)
   const f32x4 *conv3_w = nullptr;      // conv2d8 only: third 3x3 / 2 conv, packed like conv2_w
@@ -111,13 +111,13 @@ hipError_t configure_attention_kernels();
 // the list of active R-row blocks of a ragged batch (rowblock.h PadSkip::tab): 1 + ceil(M / R) ints at `tab`
 void launch_block_table(const PadSkip& ps, int M, int R, int* tab, hipStream_t st);
 
-// front_fused.hip: conv2 of Conv2dSubsampling4 in the pair form (Winograd F(2,2) over time), with conv1 fused in
-// (launch_conv12: y1 is never written) or behind k_conv1 (launch_conv2_pair); the two are bit-identical
-bool conv2_pair_supported(const FrontW& fw);
+// front_fused.hip: conv2 of Conv2dSubsampling4 in the quad form (Winograd F(2x2, 2x2)), with conv1 fused in
+// (launch_conv12: y1 is never written) or behind k_conv1 (launch_conv2_quad); the two are bit-identical
+bool conv2_quad_supported(const FrontW& fw);
 bool conv12_supported(const FrontW& fw, int F, int F2);
 void launch_conv12(const float* feats, const FrontW& fw, float* y2, int B, int T, int F, int Tp, int F2, hipStream_t st,
                    const PadSkip& ps_frames, int* tile_scratch);
-void launch_conv2_pair(const float* y1, const FrontW& fw, float* y2, int B, int T1, int F1, int Tp, int F2, hipStream_t st,
+void launch_conv2_quad(const float* y1, const FrontW& fw, float* y2, int B, int T1, int F1, int Tp, int F2, hipStream_t st,
                        const PadSkip& ps_frames, int* tile_scratch);
 hipError_t configure_front_fused_kernels();
 
