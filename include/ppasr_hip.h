@@ -422,7 +422,8 @@ PPASR_API ppasr_status ppasr_ctc_collapse(const int32_t* frame_argmax, const flo
                                 void* stream);
 
 /* ---- multi-session streaming (no reference counterpart: PPASR streams one session per call) -----------------------
- * A group of Conformer (or Squeezeformer, or Efficient-Conformer) sessions whose K/V and conv caches live in one allocation
+ * A group of Conformer (fused or general route, ppasr_gen_stream_group_create), Squeezeformer or Efficient-Conformer
+ * sessions whose K/V and conv caches live in one allocation
  * (DeepSpeech2 groups: the sessions' recurrent states, ppasr_ds2_stream_group_create);
  * ppasr_encode_chunk_group advances any subset of them by one chunk with ONE set of launches (rows of all listed sessions
  * stacked).  Every session
@@ -458,6 +459,18 @@ PPASR_API ppasr_status ppasr_eff_stream_group_create(ppasr_handle h, int n_sessi
  * ppasr_stream_group_reset zeroes a session's state and offset.  ppasr_group_chunk_workspace_bytes(h, n, T) gives the
  * round's workspace for such a handle. */
 PPASR_API ppasr_status ppasr_ds2_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out);
+/* The same kind of group for a streaming (causal) Conformer handle on the general layer route with the conv2d front end:
+ * output_size 512 / 768 / 1024, or any of the ConformerEncoder options that route streams (abs_pos / no_pos,
+ * normalize_before = False, concat_after, macaron_style = False, use_cnn_module = False, any activation, any causal
+ * cnn_module_kernel).  Each session keeps K / V caches [L][cap][D] (cap = max_frames, or max_len), its conv-module input
+ * history [L][cnn_module_kernel - 1][D] (none without a conv module), its cache length and offset.  A round runs the
+ * general route's pieces once over the n stacked chunks; per-session kernels append the keys / values, assemble each
+ * session's [history | chunk] conv input, move the histories on and, with abs_pos, add each session's positional rows.
+ * ppasr_encode_chunk_group refuses, with PPASR_EINVAL and no session changed, a round in which any listed session would
+ * exceed max_len / max_frames.  PPASR_EUNSUPPORTED for every other handle (the fused 256-wide route, Squeezeformer /
+ * Efficient-Conformer, the 6x / 8x and linear front ends, non-causal models, DeepSpeech2); the four create calls above
+ * keep refusing general-route handles. */
+PPASR_API ppasr_status ppasr_gen_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out);
 PPASR_API ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g);
 PPASR_API ppasr_status ppasr_stream_group_reset(ppasr_stream_group g, int session /* < 0: all */, void* stream);
 PPASR_API int          ppasr_stream_group_offset(ppasr_stream_group g, int session);

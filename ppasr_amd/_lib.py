@@ -136,6 +136,7 @@ SYMBOLS = [
     ("ppasr_sq_stream_group_create", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     ("ppasr_eff_stream_group_create", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     ("ppasr_ds2_stream_group_create", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    ("ppasr_gen_stream_group_create", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     ("ppasr_stream_group_destroy", ctypes.c_int, [_vp]),
     ("ppasr_stream_group_reset", ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     ("ppasr_stream_group_offset", ctypes.c_int, [_vp, ctypes.c_int]),

@@ -6,7 +6,10 @@
 //   * every activation_type of utils/common.py:189-206;
 //   * input_layer = linear (LinearNoSubsampling) besides conv2d / conv2d6 / conv2d8;
 //   * any cnn_module_kernel;
-// batched (ConformerEncoder.forward) and chunk by chunk (forward_chunk, encoder.py:208-283).
+// batched (ConformerEncoder.forward), chunk by chunk (forward_chunk, encoder.py:208-283) and, for session groups
+// (ppasr_gen_stream_group_create), one chunk of each of n sessions over their stacked rows: per-session kernels append
+// the keys / values, assemble every session's [conv history | chunk] rows, move the histories on and add abs_pos rows;
+// everything else runs as for one chunk.
 //
 // The fused kernels (conformer_kernels.hip) keep a 32 x 256 row block in four LDS buffers per workgroup; a 512-wide row
 // block, a post-norm layer or a layer without its macaron half does not fit that scheme.  This route runs the same layer
@@ -337,21 +340,9 @@ __global__ __launch_bounds__(kThreads) void k_g_proj512(const float* __restrict_
 // mask, convolution.py:104-106).  eps < 0: per-channel affine only (folded BatchNorm, see capi.hip).  g == nullptr:
 // identity (mask / activation only).  The result is multiplied by post_scale (1 everywhere but behind
 // LinearNoSubsampling, where the positional encoding's x * sqrt(d) follows the ReLU).  (x and out may be the same buffer, so neither is __restrict__)
-__global__ __launch_bounds__(256) void k_g_ln(const float* x, float* out, const float* __restrict__ g,
-                                              const float* __restrict__ b, int M, int D, float eps, int act,
-                                              const int64_t* __restrict__ lens, int Tp, int mul, float post_scale, PadSkip ps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= M) return;
-  if (pad_block_skippable(ps, row, 1, M)) return;  // ragged batches: a row behind its utterance's needed frames
-  const float* xr = x + (size_t)row * D;
-  float* o = out + (size_t)row * D;
-  if (lens) {
-    const int bb = row / Tp, t = row - bb * Tp;
-    if ((int64_t)mul * t >= lens[bb]) {
-      for (int c = lane; c < D; c += 64) o[c] = 0.f;
-      return;
-    }
-  }
+// g_ln_row: one row, wave-wide (lane 0 .. 63); the session groups' conv-input kernel runs the same arithmetic
+__device__ __forceinline__ void g_ln_row(const float* xr, float* o, const float* __restrict__ g, const float* __restrict__ b,
+                                         int D, float eps, int act, float post_scale, int lane) {
   float mean = 0.f, rstd = 1.f;
   if (g && eps >= 0.f) {
     float s = 0.f;
@@ -369,6 +360,23 @@ __global__ __launch_bounds__(256) void k_g_ln(const float* x, float* out, const 
     if (act != kActNone) y = act_apply(act, y);
     o[c] = y * post_scale;
   }
+}
+__global__ __launch_bounds__(256) void k_g_ln(const float* x, float* out, const float* __restrict__ g,
+                                              const float* __restrict__ b, int M, int D, float eps, int act,
+                                              const int64_t* __restrict__ lens, int Tp, int mul, float post_scale, PadSkip ps) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  if (pad_block_skippable(ps, row, 1, M)) return;  // ragged batches: a row behind its utterance's needed frames
+  const float* xr = x + (size_t)row * D;
+  float* o = out + (size_t)row * D;
+  if (lens) {
+    const int bb = row / Tp, t = row - bb * Tp;
+    if ((int64_t)mul * t >= lens[bb]) {
+      for (int c = lane; c < D; c += 64) o[c] = 0.f;
+      return;
+    }
+  }
+  g_ln_row(xr, o, g, b, D, eps, act, post_scale, lane);
 }
 
 // GLU over the channel halves of pointwise_conv1's output: g[m][c] = pg[m][c] * sigmoid(pg[m][D + c])  (convolution.py:126)
@@ -474,17 +482,76 @@ __global__ void k_g_kv_append(const float* __restrict__ qkv, float* __restrict__
   vc[i] = qkv[row * 3 * D + 2 * D + c];
 }
 
+// ---- session groups (ppasr_gen_stream_group_create): the per-session parts of a round over B sessions' stacked chunks
+// of Tp rows; chunk b belongs to session sess[b].sess, whose slot is sess_stride floats into each group array ----
+// abs_pos: x[b][t] += pe[offset_b + t], offset_b = the session's emitted frames (SessDesc::offset)
+__global__ void k_g_add_pe_group(float* __restrict__ x, const float* __restrict__ pe, int M, int D, int Tp,
+                                 const SessDesc* __restrict__ sess) {
+  const int D4 = D / 4;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // f32x4 index
+  if (i >= (size_t)M * D4) return;
+  const int row = (int)(i / D4), c4 = (int)(i - (size_t)row * D4);
+  const int b = row / Tp, t = row - b * Tp;
+  f32x4* xp = reinterpret_cast<f32x4*>(x) + i;
+  *xp = *xp + *reinterpret_cast<const f32x4*>(pe + (size_t)(sess[b].offset + t) * D + 4 * c4);
+}
+// keys / values of chunk row (b, t) (columns D.. / 2D.. of qkv, contiguous) -> cache row cache_t_b + t of the session;
+// kc / vc = this layer's rows of slot 0.  One workgroup per row.
+__global__ __launch_bounds__(256) void k_g_kv_append_group(const float* __restrict__ qkv, float* __restrict__ kc,
+                                                           float* __restrict__ vc, long long sess_stride,
+                                                           const SessDesc* __restrict__ sess, int Tp, int D) {
+  const int row = blockIdx.x, b = row / Tp, t = row - b * Tp;
+  const SessDesc d = sess[b];
+  const size_t dst = (size_t)d.sess * sess_stride + (size_t)(d.cache_t + t) * D;
+  const float* src = qkv + (size_t)row * 3 * D + D;
+  for (int j = 4 * threadIdx.x; j < 2 * D; j += 4 * 256) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src + j);
+    *reinterpret_cast<f32x4*>(j < D ? kc + dst + j : vc + dst + (j - D)) = v;
+  }
+}
+// the conv module's input rows of a round, [b][lo + Tp]: the session's history of this layer (hist = its rows in slot 0),
+// then LayerNorm(chunk row (b, t)) (g == nullptr: the row as it is, post-norm layers).  One wave per output row, the
+// LayerNorm arithmetic of k_g_ln (streaming has no PAD frames: no mask).
+__global__ __launch_bounds__(256) void k_g_conv_in_group(const float* __restrict__ x, float* __restrict__ out,
+                                                         const float* __restrict__ hist, long long sess_stride,
+                                                         const SessDesc* __restrict__ sess, const float* __restrict__ g,
+                                                         const float* __restrict__ bb, int B, int Tp, int lo, int D) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int per = lo + Tp;
+  if (row >= B * per) return;
+  const int b = row / per, j = row - b * per;
+  float* o = out + (size_t)row * D;
+  if (j < lo) {
+    const float* hr = hist + (size_t)sess[b].sess * sess_stride + (size_t)j * D;
+    for (int c = 4 * lane; c < D; c += 256) *reinterpret_cast<f32x4*>(o + c) = *reinterpret_cast<const f32x4*>(hr + c);
+    return;
+  }
+  g_ln_row(x + ((size_t)b * Tp + (j - lo)) * D, o, g, bb, D, 1e-5f, kActNone, 1.0f, lane);
+}
+// new history = the last lo rows of each session's [history | chunk] rows of k_g_conv_in_group's output
+// (convolution.py:110-116); grid (B, lo), one workgroup per row
+__global__ __launch_bounds__(256) void k_g_hist_update_group(const float* __restrict__ in, float* __restrict__ hist,
+                                                             long long sess_stride, const SessDesc* __restrict__ sess, int Tp,
+                                                             int lo, int D) {
+  const int b = blockIdx.x, j = blockIdx.y;
+  const float* src = in + ((size_t)b * (lo + Tp) + Tp + j) * D;
+  float* dst = hist + (size_t)sess[b].sess * sess_stride + (size_t)j * D;
+  for (int c = 4 * threadIdx.x; c < D; c += 4 * 256)
+    *reinterpret_cast<f32x4*>(dst + c) = *reinterpret_cast<const f32x4*>(src + c);
+}
+
 inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
 inline dim3 blocks(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 struct GenWs {
   size_t y1, y2, x, a, big, y, g, ctx, cat, lg, xs, xr, total;
 };
-GenWs gen_layout(const ppasr_model_s* m, int B, int T) {
+// n_hist: utterances with cached conv rows in front of their chunk (1 for a stream handle, B for a session group)
+GenWs gen_layout(const ppasr_model_s* m, int B, int T, int n_hist = 1) {
   const int D = m->desc.output_size, H = m->desc.linear_units, V = m->desc.vocab_size;
   const auto fd = m->front_dims(T);
   const size_t M = (size_t)B * fd.Tp;
-  const size_t lo = m->desc.cnn_module_kernel > 0 ? m->desc.cnn_module_kernel - 1 : 0;  // streaming: cached conv rows in front
+  const size_t lo = m->desc.cnn_module_kernel > 0 ? (size_t)n_hist * (m->desc.cnn_module_kernel - 1) : 0;  // streaming: cached conv rows in front
   const size_t wide = (size_t)std::max(3 * D, H);
   GenWs w{};
   size_t o = 0;
@@ -521,6 +588,12 @@ struct GenRun {
   int pos0 = 0;
   int used_r = 0;               // cached frames of the half-rate layers that take part (Efficient-Conformer, ChunkPlan)
   int* frames_out = nullptr;    // encoder frames this call produced (half of the chunk's behind a stride layer)
+  // session group (ppasr_gen_stream_group_create): chunk b of the B stacked ones belongs to session sess[b] (device
+  // descriptors: slot, cached frames, first positional row); its caches sit g_kv floats into gkc / gvc ([L][cap][D] per
+  // session), its conv histories g_hist floats into ghist ([L][glo][D] per session)
+  const SessDesc* sess = nullptr;
+  float *gkc = nullptr, *gvc = nullptr, *ghist = nullptr;
+  int gcap = 0, glo = 0;
 };
 
 ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* frame_argmax, float* frame_maxprob) {
@@ -605,7 +678,7 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
     const LayerW& L = h->layers[i];
     // streaming: cached conv-input rows in front of the chunk (this layer's kernel - 1: the slot's first rows, like the
     // fused route) and cached key / value frames (the half-rate layers hold each cached frame once, capi_stream.hip)
-    const int lo_s = (r.s && o.use_cnn) ? h->layer_ks[i] - 1 : 0;
+    const int lo_s = ((r.s || r.sess) && o.use_cnn) ? h->layer_ks[i] - 1 : 0;
     const int n_cache = r.s ? (half ? r.used_r : r.s->cache_t) : 0;
     if (o.macaron) ffn(L.ln_mac_g, L.ln_mac_b, L.ffm_w1, L.ffm_b1, L.ffm_w2, L.ffm_b2, ff_scale);
     // ---- (Rel)MultiHeadedAttention (attention.py:123-262) ----
@@ -637,6 +710,16 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
         // concatenated keys, efficient_conformer/attention.py:160-175)
         at.kv_frames = n_cache + Tp;
         at.T2 = (n_cache + Tp + grp - 1) / grp;
+      } else if (r.sess) {  // session group: each session's [cache | chunk] in its own slot (k_attention's SessDesc branch)
+        const long long kv_sess = (long long)h->desc.num_blocks * r.gcap * D;
+        float* kc = r.gkc + (size_t)i * r.gcap * D;
+        float* vc = r.gvc + (size_t)i * r.gcap * D;
+        PPASR_LAUNCH(k_g_kv_append_group, dim3(M), dim3(256), 0, st, big, kc, vc, kv_sess, r.sess, Tp, D);
+        at.k = kc;
+        at.v = vc;
+        at.k_stride = at.v_stride = D;
+        at.sess = r.sess;
+        at.sess_stride = kv_sess;
       }
       at.pad_skip = skip ? ps.slack + 1 : 0;
       at.dm = D;
@@ -656,11 +739,19 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
       const int left = h->desc.causal ? KS - 1 : (KS - 1) / 2;
       const bool stride2 = eff && ((eff_stride_mask(h->desc) >> i) & 1u);
       float* a_new = a + (size_t)lo_s * D;
-      const int rows = lo_s + M;
+      const int rows = (r.sess ? B : 1) * lo_s + M;
       if (D == kD512 && lo_s == 0) {  // (LayerNorm) + pad mask + pointwise_conv1 + GLU in one launch
         PPASR_LAUNCH(k_g_proj512<true>, dim3((M + kRows - 1) / kRows), dim3(kThreads), kLdsProj512, st, x, g, D,
                      o.post_norm ? nullptr : L.ln_conv_g, o.post_norm ? nullptr : L.ln_conv_b, 1e-5f, lens, Tp, mul, L.pw1,
                      L.pw1_b, 2, M, ps);
+      } else if (r.sess) {  // session group: [history | LN_conv(chunk)] of every session, then its new history
+        const long long h_sess = (long long)h->desc.num_blocks * r.glo * D;
+        float* hist = r.ghist + (size_t)i * r.glo * D;
+        PPASR_LAUNCH(k_g_conv_in_group, dim3((rows + 3) / 4), dim3(256), 0, st, x, a, hist, h_sess, r.sess,
+                     o.post_norm ? nullptr : L.ln_conv_g, o.post_norm ? nullptr : L.ln_conv_b, B, Tp, lo_s, D);
+        if (lo_s) PPASR_LAUNCH(k_g_hist_update_group, dim3(B, lo_s), dim3(256), 0, st, a, hist, h_sess, r.sess, Tp, lo_s, D);
+        dense(a, D, L.pw1, L.pw1_b, big, rows, D, 2 * D, 2 * D, 2 * D, st, 1.0f, GemmEpi{});
+        PPASR_LAUNCH(k_g_glu, blocks((size_t)rows * D), dim3(256), 0, st, big, g, rows, D);
       } else {
         if (!o.post_norm) ln(x, a_new, L.ln_conv_g, L.ln_conv_b, 1e-5f, kActNone, true, M);  // LN_conv, PAD frames -> 0
         else ln(x, a_new, nullptr, nullptr, 0.f, kActNone, true, M);                           // PAD frames -> 0 only
@@ -723,8 +814,9 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
 
 // front end: GlobalCMVN + the subsampling class + the positional encoding's scaling (subsampling.py, embedding.py)
 // -> x [B * Tp][D]; pe_off = position of the first output frame (abs_pos)
+// (sess: a session group's descriptors -- utterance b's first frame sits at position sess[b].offset instead)
 ppasr_status gen_front(ppasr_model_s* h, const float* feats, int B, int T, float* ws, const GenWs& wl, int pe_off,
-                       hipStream_t st) {
+                       hipStream_t st, const SessDesc* sess = nullptr) {
   const int D = h->desc.output_size, F = h->desc.input_dim;
   const auto fd = h->front_dims(T);
   const int Tp = fd.Tp, M = B * Tp, il = h->desc.input_layer;
@@ -750,7 +842,9 @@ ppasr_status gen_front(ppasr_model_s* h, const float* feats, int B, int T, float
       dense(y2, h->F2 * D, h->front.embed_w, h->front.embed_b, x, M, h->F2 * D, D, D, D, st, xscale);
     }
   }
-  if (h->gen.pos == PPASR_OPT_POS_ABS)
+  if (h->gen.pos == PPASR_OPT_POS_ABS && sess)
+    PPASR_LAUNCH(k_g_add_pe_group, blocks((size_t)M * D / 4), dim3(256), 0, st, x, h->pe_dev, M, D, Tp, sess);
+  else if (h->gen.pos == PPASR_OPT_POS_ABS)
     PPASR_LAUNCH(k_g_add_pe, blocks((size_t)M * D), dim3(256), 0, st, x, h->pe_dev, M, D, Tp, pe_off);
   return PPASR_OK;
 }
@@ -1043,5 +1137,24 @@ ppasr_status generic_chunk(ppasr_stream_s* s, const ChunkPlan& p, const float* f
   r.pos0 = p.pos0;
   r.used_r = p.used_r;
   r.frames_out = frames_out;
+  return gen_layers(r, probs, nullptr, frame_argmax, frame_maxprob);
+}
+
+size_t generic_group_ws_floats(const ppasr_model_s* m, int n, int T) { return gen_layout(m, n, T, n).total; }
+
+ppasr_status generic_group_chunk(ppasr_model_s* h, const SessDesc* sess, int n, float* kc, float* vc, int cap,
+                                 float* xh_hist, int lo, const float* feats, int T, float* probs, int32_t* frame_argmax,
+                                 float* frame_maxprob, float* ws, hipStream_t st) {
+  const GenWs wl = gen_layout(h, n, T, n);
+  ppasr_status rs = gen_front(h, feats, n, T, ws, wl, 0, st, sess);
+  if (rs != PPASR_OK) return rs;
+  GenRun r{h, st, n, h->front_dims(T).Tp, nullptr, ws + wl.x, ws + wl.a, ws + wl.big, ws + wl.y, ws + wl.g, ws + wl.ctx,
+           ws + wl.cat, ws + wl.lg};
+  r.sess = sess;
+  r.gkc = kc;
+  r.gvc = vc;
+  r.ghist = xh_hist;
+  r.gcap = cap;
+  r.glo = lo;
   return gen_layers(r, probs, nullptr, frame_argmax, frame_maxprob);
 }

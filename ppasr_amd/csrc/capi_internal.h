@@ -273,6 +273,13 @@ ppasr_status generic_chunk(ppasr_stream_s* s, const ChunkPlan& p, const float* f
 // SqueezeformerEncoder.forward_chunk (squeezeformer/encoder.py:260-381) on the general route
 ppasr_status generic_sq_chunk(ppasr_stream_s* s, const ChunkPlan& p, const float* feats, int T, float* probs,
                               int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st);
+// session groups on the general route (ppasr_gen_stream_group_create): workspace of a round of n chunks of T frames, and the
+// round itself -- gen_front + gen_layers over the n stacked chunks, session sess[b] (device) for chunk b; caches kc / vc
+// [n_sessions][L][cap][D], conv histories xh_hist [n_sessions][L][lo][D]
+size_t generic_group_ws_floats(const ppasr_model_s* m, int n, int T);
+ppasr_status generic_group_chunk(ppasr_model_s* h, const SessDesc* sess, int n, float* kc, float* vc, int cap,
+                                 float* xh_hist, int lo, const float* feats, int T, float* probs, int32_t* frame_argmax,
+                                 float* frame_maxprob, float* ws, hipStream_t st);
 hipError_t configure_generic_kernels();
 // SqueezeformerEncoder.forward (squeezeformer/encoder.py:172-236) on the general route (encoder_dim 512 / 768 / 1024)
 ppasr_status generic_sq_encode(ppasr_model_s* h, const float* feats, const int64_t* lens, int B, int T, float* probs,

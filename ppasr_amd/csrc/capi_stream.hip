@@ -312,7 +312,8 @@ ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* x
 }
 
 // which of the chunk-round paths a session group takes (the family of the handle it was built for)
-enum class GroupFamily { kConformer, kSqueezeformer, kEfficientConformer, kDeepSpeech2 };
+// (kGeneral: a Conformer handle on the general layer route, capi_generic.hip)
+enum class GroupFamily { kConformer, kSqueezeformer, kEfficientConformer, kDeepSpeech2, kGeneral };
 
 }  // namespace
 
@@ -522,13 +523,16 @@ ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* att_cache, i
 // DeepSpeech2 groups (ppasr_ds2_stream_group_create) keep each session's LSTM / GRU state [L][H] (h, and c for the LSTM)
 // instead of caches: a round is the wavefront route of ppasr_ds2_encode over the n stacked windows (capi_ds2.hip
 // ds2_group_round), with the states gathered from and scattered back to the sessions' slots by one launch each.
+// General-route Conformer groups (ppasr_gen_stream_group_create) hold the same caches at the model's width D; a round is
+// gen_front + gen_layers over the stacked chunks (capi_generic.hip generic_group_chunk).
 // =====================================================================================
 struct ppasr_stream_group_s {
   ppasr_model_s* m;
   int n_sessions, cap, lo;
+  int D;               // row width of the caches: 256, or the general route's model width
   GroupFamily family;  // Squeezeformer / Efficient-Conformer: full- and half-rate layers, per-layer histories
-  float *kc, *vc;     // [n_sessions][L][cap][256]
-  float* xh_hist;     // [n_sessions][L][lo][256] (layer i uses its first kernel_i - 1 rows)
+  float *kc, *vc;     // [n_sessions][L][cap][D]
+  float* xh_hist;     // [n_sessions][L][lo][D] (layer i uses its first kernel_i - 1 rows)
   float* ds2_state;   // DeepSpeech2: h [n_sessions][L][H], then (LSTM) c of the same shape; one allocation
   HistLayer* hist_tab;  // Squeezeformer / Efficient-Conformer: device [L], the layers' pointwise_conv1 (k_pw1_glu_layers)
   // per-call descriptors: a ring of pinned host staging buffers + device copies, each guarded by an event, so that a
@@ -560,7 +564,9 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFa
   g->n_sessions = n_sessions;
   g->family = family;
   g->cap = (max_frames > 0 && max_frames < h->desc.max_len) ? max_frames : h->desc.max_len;
-  g->lo = h->desc.cnn_module_kernel - 1;
+  g->D = family == GroupFamily::kGeneral ? h->desc.output_size : kD;
+  // (the general route without a conv module keeps no history: lo = 0, a one-row allocation as on a stream handle)
+  g->lo = (family == GroupFamily::kGeneral && !h->gen.use_cnn) ? 0 : h->desc.cnn_module_kernel - 1;
   const bool layered = family == GroupFamily::kSqueezeformer || family == GroupFamily::kEfficientConformer;
   // (layered: per-layer history table, two descriptor sets)
   g->per_slot = layered ? 2 * n_sessions : n_sessions;
@@ -572,8 +578,8 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFa
   };
   const size_t L = h->desc.num_blocks;
   const bool ds2 = family == GroupFamily::kDeepSpeech2;  // (no caches: the recurrent states)
-  const size_t kv = ds2 ? 0 : (size_t)n_sessions * L * g->cap * kD * sizeof(float);
-  const size_t hb = ds2 ? ds2_state_bytes(h, n_sessions) : (size_t)n_sessions * L * g->lo * kD * sizeof(float);
+  const size_t kv = ds2 ? 0 : (size_t)n_sessions * L * g->cap * g->D * sizeof(float);
+  const size_t hb = ds2 ? ds2_state_bytes(h, n_sessions) : (size_t)n_sessions * L * std::max(g->lo, 1) * g->D * sizeof(float);
   const size_t db = (size_t)ppasr_stream_group_s::kRing * g->per_slot * sizeof(SessDesc);
   hipError_t e = hipSuccess;
   if (!ds2) e = hipMalloc(reinterpret_cast<void**>(&g->kc), kv);
@@ -856,6 +862,48 @@ ppasr_status eff_encode_chunk_group(ppasr_stream_group g, const int* sessions_ho
   return PPASR_OK;
 }
 
+// One round of a general-route Conformer group: generic_group_chunk over the listed sessions.  Every session is planned
+// (plan_chunk_for: what ppasr_encode_chunk checks -- cache capacity, max_len) before anything is launched or changed, so a
+// refused call leaves every session as it was.  Descriptors {sess, cache_t, pos0, offset}: pos0 = offset - cache_t picks
+// the relative positional rows; without relative positions the attention's one-row zero table is read at row 0.
+ppasr_status gen_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
+                                    float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
+                                    void* workspace, hipStream_t st) {
+  ppasr_model_s* h = g->m;
+  const int c = h->front_dims(T).Tp;
+  std::vector<ChunkPlan> plans(n);
+  std::vector<char> seen(g->n_sessions, 0);
+  for (int b = 0; b < n; ++b) {
+    const int sidx = sessions_host[b];
+    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
+    seen[sidx] = 1;
+    ppasr_status r = plan_chunk_for(h, g->cache_t[sidx], g->cache_r[sidx], g->offset[sidx], g->cap, c, -1, &plans[b]);
+    if (r != PPASR_OK) return r;
+  }
+  const bool rel = h->gen.pos == PPASR_OPT_POS_REL;
+  const int slot = g->slot;
+  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
+  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
+  SessDesc* desc = g->desc_host + (size_t)slot * g->per_slot;
+  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->per_slot;
+  for (int b = 0; b < n; ++b) {
+    const int sidx = sessions_host[b];
+    desc[b] = SessDesc{sidx, g->cache_t[sidx], rel ? plans[b].pos0 : 0, g->offset[sidx]};
+  }
+  HIP_TRY(hipMemcpyAsync(desc_dev, desc, (size_t)n * sizeof(SessDesc), hipMemcpyHostToDevice, st));
+  ppasr_status r = generic_group_chunk(h, desc_dev, n, g->kc, g->vc, g->cap, g->xh_hist, g->lo, feats, T, probs, frame_argmax,
+                                       frame_maxprob, static_cast<float*>(workspace), st);
+  if (r != PPASR_OK) return r;
+  for (int b = 0; b < n; ++b) {  // (finish_chunk with required_cache_size < 0: nothing is dropped)
+    const int sidx = sessions_host[b];
+    g->cache_t[sidx] = plans[b].T2;
+    g->offset[sidx] += c;
+  }
+  HIP_TRY(hipEventRecord(g->ev[slot], st));
+  if (c_out_host) *c_out_host = c;
+  return PPASR_OK;
+}
+
 // One round of a DeepSpeech2 group: ds2_group_round on the listed sessions' slots.  Every argument is checked before the
 // slot table is written or anything is launched, so a refused call leaves every session as it was.  The only host wait is
 // the descriptor ring's event (a slot table still read by a queued round is not overwritten).
@@ -913,6 +961,17 @@ ppasr_status ppasr_stream_group_create(ppasr_handle h, int n_sessions, int max_f
   return group_alloc(h, n_sessions, max_frames, GroupFamily::kConformer, out);
 }
 
+ppasr_status ppasr_gen_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
+  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
+  if (h->desc.model_type != PPASR_MODEL_CONFORMER || !h->desc.causal)
+    return fail(PPASR_EUNSUPPORTED, "general-route session groups are built for streaming (causal) model_type=conformer");
+  if (!h->generic)
+    return fail(PPASR_EUNSUPPORTED, "general-route session groups are built for the general layer route "
+                                    "(the fused 256-wide route: ppasr_stream_group_create)");
+  if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
+  return group_alloc(h, n_sessions, max_frames, GroupFamily::kGeneral, out);
+}
+
 ppasr_status ppasr_sq_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
   if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
   if (h->desc.model_type != PPASR_MODEL_SQUEEZEFORMER || !h->desc.causal)
@@ -963,14 +1022,16 @@ ppasr_status ppasr_stream_group_reset(ppasr_stream_group g, int session, void* s
     else g->offset[session] = 0;
     return PPASR_OK;
   }
-  const size_t per = (size_t)g->m->desc.num_blocks * g->lo * kD;
+  const size_t per = (size_t)g->m->desc.num_blocks * g->lo * g->D;
+  if (per > 0) {  // (no conv history on a general-route model without a conv module)
+    if (session < 0) HIP_TRY(hipMemsetAsync(g->xh_hist, 0, per * g->n_sessions * sizeof(float), st));
+    else HIP_TRY(hipMemsetAsync(g->xh_hist + per * session, 0, per * sizeof(float), st));
+  }
   if (session < 0) {
-    HIP_TRY(hipMemsetAsync(g->xh_hist, 0, per * g->n_sessions * sizeof(float), st));
     std::fill(g->cache_t.begin(), g->cache_t.end(), 0);
     std::fill(g->cache_r.begin(), g->cache_r.end(), 0);
     std::fill(g->offset.begin(), g->offset.end(), 0);
   } else {
-    HIP_TRY(hipMemsetAsync(g->xh_hist + per * session, 0, per * sizeof(float), st));
     g->cache_t[session] = 0;
     g->cache_r[session] = 0;
     g->offset[session] = 0;
@@ -985,6 +1046,7 @@ int ppasr_stream_group_offset(ppasr_stream_group g, int session) {
 size_t ppasr_group_chunk_workspace_bytes(ppasr_handle h, int n, int T) {
   if (!h || n < 1 || T < 7) return 0;
   if (h->desc.model_type == PPASR_MODEL_DEEPSPEECH2) return ds2_group_ws_floats(h, n, T) * sizeof(float);
+  if (h->generic) return generic_group_ws_floats(h, n, T) * sizeof(float);
   if (is_sq(h) || is_eff(h)) return layered_group_ws_floats(h, n, T) * sizeof(float);
   const size_t Tp = ((T - 1) / 2 - 1) / 2;
   // the batched layout for B = n, plus the conv-module input rows and the GLU'd histories of the active sessions
@@ -1006,6 +1068,9 @@ ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int* sessions_
                                  static_cast<hipStream_t>(stream));
   if (g->family == GroupFamily::kDeepSpeech2)
     return ds2_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
+                                  static_cast<hipStream_t>(stream));
+  if (g->family == GroupFamily::kGeneral)
+    return gen_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
                                   static_cast<hipStream_t>(stream));
   if (g->family == GroupFamily::kEfficientConformer)
     return eff_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,

@@ -398,8 +398,8 @@ class ConformerStream:
 class StreamHandleSet:
     """The interface of ``ConformerStreamGroup`` over per-session stream handles (``model.new_stream()``): for the handles
     whose sessions ``make_stream_group`` builds no group for (``ppasr_stream_group_create`` is built for plain Conformer
-    handles; Squeezeformer and Efficient-Conformer groups are opt-in, ``SqueezeformerStreamGroup`` /
-    ``EfficientConformerStreamGroup``).  Same results as driving each session's own stream; N sets of launches per round instead of one."""
+    handles; Squeezeformer, Efficient-Conformer and general-route Conformer groups are opt-in, ``SqueezeformerStreamGroup`` /
+    ``EfficientConformerStreamGroup`` / ``GeneralConformerStreamGroup``).  Same results as driving each session's own stream; N sets of launches per round instead of one."""
 
     def __init__(self, model, n_sessions, max_frames=0):
         self.model = model
@@ -498,3 +498,16 @@ class ConformerStreamGroup:
                                                          fp.data_ptr(), ctypes.byref(c_out), ws.data_ptr(), ws.numel(),
                                                          key))
         return (fa, fp, probs) if want_probs else (fa, fp)
+
+
+class GeneralConformerStreamGroup(ConformerStreamGroup):
+    """``ConformerStreamGroup``'s interface for a streaming Conformer model on the general layer route
+    (``ppasr_gen_stream_group_create``): output_size 512 / 768 / 1024, or the ConformerEncoder options the fused 256-wide
+    kernels do not cover (abs_pos / no_pos, post-norm, concat_after, no macaron half, no conv module, any activation, any
+    causal conv kernel), conv2d front end.  The listed sessions advance by one chunk each with ONE set of kernel launches
+    per round, their rows stacked.  Every session follows ``new_stream().encode_chunk(chunk, required_cache_size=-16)``
+    (full history); a round that any listed session's stream would refuse (``max_len``, capacity) raises and leaves every
+    session as it was.  Not what ``make_stream_group`` picks (that stays ``StreamHandleSet`` for these models); pass it
+    to ``serving.StreamPool(..., group=...)``."""
+
+    _create = "ppasr_gen_stream_group_create"

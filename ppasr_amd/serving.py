@@ -36,7 +36,8 @@ class _Session:
 class StreamPool:
     def __init__(self, model, vocab_list, n_sessions, preprocess_conf=None, max_seconds=200.0, blank_index=0, group=None,
                  decoder="ctc_greedy", decoder_conf=None):
-        """group: a ready session group for `model` with `n_sessions` slots (e.g. ``SqueezeformerStreamGroup``); None =
+        """group: a ready session group for `model` with `n_sessions` slots (e.g. ``SqueezeformerStreamGroup``,
+        ``GeneralConformerStreamGroup``); None =
         ``make_stream_group``'s choice.  decoder: "ctc_greedy" or "ctc_beam_search"; decoder_conf: keys of
         ``ctc_beam_search_decoder_conf`` (alpha, beta, beam_size, num_processes, cutoff_prob, cutoff_top_n,
         language_model_path), over the shipped values without a language model."""
@@ -54,7 +55,7 @@ class StreamPool:
         self.blank = blank_index
         if group is None:
             # (one set of launches per round for plain Conformer and streaming DeepSpeech2 handles; per-session stream
-            #  handles behind the same interface for the Squeezeformer and the Efficient-Conformer)
+            #  handles behind the same interface for the Squeezeformer, the Efficient-Conformer and the general route)
             # (DeepSpeech2: session states that do not grow, no max_len)
             max_frames = int(max_seconds * 25) + 32
             if hasattr(model, "max_len"):

@@ -16,6 +16,10 @@ streams from one host thread.  Prints the aggregate audio-seconds/s and the sing
                              get_encoder_out_chunk call per session that carries its own h / c boxes (what
                              predict_chunk_deepspeech does), one 67-frame window per session per round
   --ds2-rounds R --sessions N [--gru]  R DeepSpeech2 group rounds of N sessions, for the dispatch count as above
+  --general                  the same section for the general layer route: the shipped configs/conformer.yml, streaming,
+                             with output_size 512 and attention_heads 8 (the YAML's own suggestion for large datasets),
+                             GeneralConformerStreamGroup against StreamHandleSet (one stream handle per session)
+  --gen-rounds R --sessions N  R general-route group rounds of N sessions, for the dispatch count as above
   --decoder beam             the beam-search session pool (BeamSearchSessions, one pruning + one search launch per round)
                              against N BeamSearchDecoder objects: the decode stage of one 16-frame round at n = 8 / 64 /
                              256 / 300, beam 10 and the shipped beam 300 (cutoff 0.99 / 40), without and with a synthetic
@@ -61,6 +65,18 @@ def deepspeech2_model(gru=False):
     sd = deepspeech2_state_dict(vocab_size=V, num_rnn_layers=5, rnn_size=1024, streaming=True, seed=1234, use_gru=gru)
     return DeepSpeech2Model(80, V, streaming=True, encoder_conf=dict(num_rnn_layers=5, rnn_size=1024, use_gru=gru),
                             state_dict=sd, device="cuda:0")
+
+
+def general_model():
+    """configs/conformer.yml (12 blocks, kernel 15, rel_pos, swish) at output_size 512 / 8 heads: the general layer route."""
+    import yaml
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "configs", "conformer.yml")) as f:
+        conf = dict(yaml.safe_load(f)["encoder_conf"], output_size=512, attention_heads=8)
+    V = DEFAULT_VOCAB_SIZE
+    sd = conformer_state_dict(vocab_size=V, num_blocks=conf["num_blocks"], seed=1234, output_size=512, attention_heads=8,
+                              cnn_module_kernel=conf["cnn_module_kernel"])
+    return ConformerModel(80, V, streaming=True, encoder_conf=conf, state_dict=sd, device="cuda:0")
 
 
 class Ds2BoxSessions:
@@ -235,7 +251,7 @@ if "--decoder" in sys.argv and _arg("--decoder", "greedy") == "beam":
     beam_end_to_end()
     sys.exit(0)
 
-for _flag in ("--sq-rounds", "--eff-rounds", "--ds2-rounds"):
+for _flag in ("--sq-rounds", "--eff-rounds", "--ds2-rounds", "--gen-rounds"):
     if _flag in sys.argv:
         if _flag == "--sq-rounds":
             from ppasr_amd.model_utils.squeezeformer.model import SqueezeformerStreamGroup as _cls
@@ -243,6 +259,9 @@ for _flag in ("--sq-rounds", "--eff-rounds", "--ds2-rounds"):
         elif _flag == "--ds2-rounds":
             from ppasr_amd.model_utils.deepspeech2.model import DeepSpeech2StreamGroup as _cls
             _model = deepspeech2_model(gru="--gru" in sys.argv)
+        elif _flag == "--gen-rounds":
+            from ppasr_amd.model_utils.conformer.model import GeneralConformerStreamGroup as _cls
+            _model = general_model()
         else:
             from ppasr_amd.model_utils.efficient_conformer.model import EfficientConformerStreamGroup as _cls
             _model = efficient_conformer_model()
@@ -264,6 +283,12 @@ if "--deepspeech2" in sys.argv:
     _gru = "--gru" in sys.argv
     group_section("deepspeech2_gru" if _gru else "deepspeech2", deepspeech2_model(_gru), DeepSpeech2StreamGroup, n_chunks=4,
                   baseline=("per_session_calls", Ds2BoxSessions))
+    sys.exit(0)
+if "--general" in sys.argv:
+    # (caches: the group holds 16 x (8 + 2) frames per session -- 12 layers x K + V x 512 floats = 48 KB per frame; a
+    #  stream handle holds max_len = 5 000 frames, 245 MB, so 256 handles take 63 GB)
+    from ppasr_amd.model_utils.conformer.model import GeneralConformerStreamGroup
+    group_section("conformer_512", general_model(), GeneralConformerStreamGroup)
     sys.exit(0)
 if "--efficient-conformer" in sys.argv:
     from ppasr_amd.model_utils.efficient_conformer.model import EfficientConformerStreamGroup
