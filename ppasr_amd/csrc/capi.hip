@@ -1281,14 +1281,7 @@ struct ppasr_beam_pool_s {
   std::vector<size_t> cap;       // frames each block is sized for
   std::vector<long long> frames; // cumulative frames decoded since the session's last reset
   int32_t* status;               // device [n_sessions]
-  // per-call slot tables + frame counts: a ring of pinned host staging buffers and device copies, each guarded by an
-  // event, so that a call never overwrites a buffer an earlier (still queued) call reads
-  static constexpr int kRing = 8;
-  size_t ring_bytes;  // per ring entry: [n_sessions] BeamSlot, then [n_sessions] int32 frame counts
-  char* ring_host;
-  char* ring_dev;
-  hipEvent_t ev[kRing];
-  int ring;
+  StagingRing ring;  // per-call slot tables + frame counts: [n_sessions] BeamSlot, then [n_sessions] int32 per entry
 };
 
 namespace {
@@ -1321,7 +1314,6 @@ ppasr_status ppasr_beam_pool_create(int n_sessions, int V, int beam_size, double
   p->block.assign(n_sessions, nullptr);
   p->cap.assign(n_sessions, (size_t)init_frames);
   p->frames.assign(n_sessions, 0);
-  p->ring_bytes = ((size_t)n_sessions * (sizeof(BeamSlot) + 4) + 255) & ~(size_t)255;
   auto bail = [p](const char* what, hipError_t e) {
     (void)ppasr_beam_pool_destroy(p);
     return fail(PPASR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
@@ -1329,17 +1321,8 @@ ppasr_status ppasr_beam_pool_create(int n_sessions, int V, int beam_size, double
   const size_t bb = pool_block_bytes((size_t)init_frames, beam_size);
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->status), (size_t)n_sessions * 4);
   for (int i = 0; i < n_sessions && e == hipSuccess; ++i) e = hipMalloc(reinterpret_cast<void**>(&p->block[i]), bb);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->ring_dev), ppasr_beam_pool_s::kRing * p->ring_bytes);
-  if (e == hipSuccess)
-    e = hipHostMalloc(reinterpret_cast<void**>(&p->ring_host), ppasr_beam_pool_s::kRing * p->ring_bytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = p->ring.alloc(((size_t)n_sessions * (sizeof(BeamSlot) + 4) + 255) & ~(size_t)255);
   if (e != hipSuccess) return bail("allocation failed for the beam pool", e);
-  for (int i = 0; i < ppasr_beam_pool_s::kRing; ++i) {
-    e = hipEventCreateWithFlags(&p->ev[i], hipEventDisableTiming);
-    if (e != hipSuccess) {
-      p->ev[i] = nullptr;
-      return bail("creating the beam-pool events failed", e);
-    }
-  }
   for (int i = 0; i < n_sessions; ++i) {
     e = launch_beam_reset(p->block[i], p->status + i, beam_size, (int)beam_max_nodes(p->cap[i], beam_size), c.lm.bos,
                           c.node_table != 0, nullptr);
@@ -1353,15 +1336,10 @@ ppasr_status ppasr_beam_pool_create(int n_sessions, int V, int beam_size, double
 
 ppasr_status ppasr_beam_pool_destroy(ppasr_beam_pool p) {
   if (!p) return fail(PPASR_EINVAL, "null pool");
-  for (hipEvent_t ev : p->ev)
-    if (ev) (void)hipEventSynchronize(ev);
+  p->ring.destroy();
   for (int32_t* b : p->block)
     if (b) (void)hipFree(b);
   if (p->status) (void)hipFree(p->status);
-  if (p->ring_dev) (void)hipFree(p->ring_dev);
-  if (p->ring_host) (void)hipHostFree(p->ring_host);
-  for (hipEvent_t ev : p->ev)
-    if (ev) (void)hipEventDestroy(ev);
   delete p;
   return PPASR_OK;
 }
@@ -1410,12 +1388,10 @@ ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host,
   // ---- every check before any device work: a refused call changes no session ----
   if (!p || !sessions_host || !tokens || !lens || !scores || (!probs && T > 0)) return fail(PPASR_EINVAL, "null argument");
   if (n < 1 || n > p->n_sessions || T < 0 || max_tokens < 1) return fail(PPASR_EINVAL, "beam pool: bad n / T / max_tokens");
-  std::vector<char> seen(p->n_sessions, 0);
+  if (!session_list_ok(sessions_host, n, p->n_sessions))
+    return fail(PPASR_EINVAL, "beam pool: session index out of range or repeated");
   std::vector<int> fl(n);
   for (int b = 0; b < n; ++b) {
-    const int s = sessions_host[b];
-    if (s < 0 || s >= p->n_sessions || seen[s]) return fail(PPASR_EINVAL, "beam pool: session index out of range or repeated");
-    seen[s] = 1;
     fl[b] = frame_lens_host ? frame_lens_host[b] : T;
     if (fl[b] < 0 || fl[b] > T) return fail(PPASR_EINVAL, "beam pool: frame_lens must lie in [0, T]");
   }
@@ -1466,20 +1442,17 @@ ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host,
     for (int32_t* o : retired) (void)hipFree(o);
   }
   // ---- the slot table and frame counts of this call ----
-  const int slot = p->ring;
-  p->ring = (slot + 1) % ppasr_beam_pool_s::kRing;
-  HIP_TRY(hipEventSynchronize(p->ev[slot]));  // the call that last used this entry has consumed it (no-op when unused)
-  char* host = p->ring_host + (size_t)slot * p->ring_bytes;
-  char* dev = p->ring_dev + (size_t)slot * p->ring_bytes;
-  BeamSlot* tab = reinterpret_cast<BeamSlot*>(host);
-  int32_t* fl_host = reinterpret_cast<int32_t*>(host + (size_t)n * sizeof(BeamSlot));
+  StagingRing::Entry en;
+  HIP_TRY(p->ring.acquire(&en));
+  BeamSlot* tab = reinterpret_cast<BeamSlot*>(en.host);
+  int32_t* fl_host = reinterpret_cast<int32_t*>(en.host + (size_t)n * sizeof(BeamSlot));
   for (int b = 0; b < n; ++b) {
     const int s = sessions_host[b];
     tab[b] = BeamSlot{p->block[s], p->status + s, (int)beam_max_nodes(p->cap[s], beam), 0};
     fl_host[b] = fl[b];
   }
   const size_t used = (size_t)n * (sizeof(BeamSlot) + 4);
-  HIP_TRY(hipMemcpyAsync(dev, host, used, hipMemcpyHostToDevice, hs));
+  HIP_TRY(hipMemcpyAsync(en.dev, en.host, used, hipMemcpyHostToDevice, hs));
   BeamConfig c = p->cfg;
   c.max_tokens = max_tokens;
   c.max_nodes = 0;  // (per session: the slot table)
@@ -1491,9 +1464,9 @@ ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host,
   const size_t rec_bytes = pool_rec_bytes(c, n, T), scratch_bytes = beam_scratch_bytes(c, n, T);
   int32_t* recs = rec_bytes ? reinterpret_cast<int32_t*>(ws) : nullptr;
   void* scratch = scratch_bytes ? ws + rec_bytes : nullptr;
-  HIP_TRY(launch_ctc_beam(probs, reinterpret_cast<const int32_t*>(dev + (size_t)n * sizeof(BeamSlot)), n, T, c, recs, nullptr,
-                          0, 1, tokens, lens, scores, nullptr, scratch, hs, reinterpret_cast<const BeamSlot*>(dev)));
-  HIP_TRY(hipEventRecord(p->ev[slot], hs));
+  HIP_TRY(launch_ctc_beam(probs, reinterpret_cast<const int32_t*>(en.dev + (size_t)n * sizeof(BeamSlot)), n, T, c, recs,
+                          nullptr, 0, 1, tokens, lens, scores, nullptr, scratch, hs, reinterpret_cast<const BeamSlot*>(en.dev)));
+  HIP_TRY(p->ring.release(en, hs));
   for (int b = 0; b < n; ++b) p->frames[sessions_host[b]] += fl[b];
   return PPASR_OK;
 }

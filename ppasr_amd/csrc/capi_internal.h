@@ -31,6 +31,64 @@ inline ppasr_status fail(ppasr_status s, const std::string& msg) {
     if (_e != hipSuccess) return fail(PPASR_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+// the session list of a many-session call (session groups, beam pools): every index in [0, n_sessions), none twice
+inline bool session_list_ok(const int* sessions, int n, int n_sessions) {
+  std::vector<char> seen(n_sessions, 0);
+  for (int b = 0; b < n; ++b) {
+    const int s = sessions[b];
+    if (s < 0 || s >= n_sessions || seen[s]) return false;
+    seen[s] = 1;
+  }
+  return true;
+}
+
+// Per-call staging of a many-session call (session-group descriptors, beam-pool slot tables): a ring of pinned host
+// buffers and their device copies, each guarded by an event, so that a call never overwrites an entry an earlier (still
+// queued) call reads.  A call acquires the next entry, fills its host side, copies it to the device, launches and then
+// releases the entry behind its launches; a call that fails before its launches leaves the entry unreleased (nothing
+// queued reads it).
+struct StagingRing {
+  static constexpr int kRing = 8;
+  struct Entry {
+    int i;
+    char* host;
+    char* dev;
+  };
+  size_t entry_bytes = 0;
+  char* host = nullptr;   // pinned [kRing][entry_bytes]
+  char* dev = nullptr;    // device [kRing][entry_bytes]
+  hipEvent_t ev[kRing] = {};  // (null until created)
+  int next = 0;
+
+  hipError_t alloc(size_t bytes) {
+    entry_bytes = bytes;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), kRing * bytes);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&host), kRing * bytes, hipHostMallocDefault);
+    for (int i = 0; i < kRing && e == hipSuccess; ++i) {
+      e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+      if (e != hipSuccess) ev[i] = nullptr;
+    }
+    return e;
+  }
+  // the next entry, once the call that last used it has consumed it (no wait when it was never used)
+  hipError_t acquire(Entry* out) {
+    const int i = next;
+    next = (i + 1) % kRing;
+    *out = Entry{i, host + (size_t)i * entry_bytes, dev + (size_t)i * entry_bytes};
+    return hipEventSynchronize(ev[i]);
+  }
+  hipError_t release(const Entry& en, hipStream_t st) { return hipEventRecord(ev[en.i], st); }
+  // waits for every queued call, then frees whatever exists
+  void destroy() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventSynchronize(e);
+    (void)hipFree(dev);
+    (void)hipHostFree(host);
+    for (hipEvent_t& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct Blob {
   const float* p;
   int ndim;

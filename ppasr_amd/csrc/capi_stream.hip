@@ -311,9 +311,22 @@ ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* x
   return PPASR_OK;
 }
 
+// every layer's pointwise_conv1 and history rows (kernel_i - 1) for k_pw1_glu_layers -> tab_dev [L] (the general route
+// recomputes the history's GLU inside the layer: null entries)
+hipError_t upload_hist_table(const ppasr_model_s* h, HistLayer* tab_dev) {
+  const int L = h->desc.num_blocks;
+  std::vector<HistLayer> tab(L, HistLayer{nullptr, nullptr, 0, 0});
+  for (int i = 0; i < L && !h->generic; ++i)
+    tab[i] = is_sq(h) ? HistLayer{h->sq_layers[i].pw1_raw, h->sq_layers[i].pw1_b_raw, layer_lo(h, i), 0}
+                      : HistLayer{h->layers[i].pw1, h->layers[i].pw1_b, layer_lo(h, i), 0};
+  return hipMemcpy(tab_dev, tab.data(), L * sizeof(HistLayer), hipMemcpyHostToDevice);
+}
+
 // which of the chunk-round paths a session group takes (the family of the handle it was built for)
 // (kGeneral: a Conformer handle on the general layer route, capi_generic.hip)
 enum class GroupFamily { kConformer, kSqueezeformer, kEfficientConformer, kDeepSpeech2, kGeneral };
+// families with full- and half-rate layers and per-layer conv histories
+inline bool is_layered(GroupFamily f) { return f == GroupFamily::kSqueezeformer || f == GroupFamily::kEfficientConformer; }
 
 }  // namespace
 
@@ -354,13 +367,7 @@ ppasr_status ppasr_stream_create(ppasr_handle h, ppasr_stream* out) {
   s->cache_r = 0;
   s->offset = 0;
   hipError_t e5 = hipMemset(s->xh_hist, 0, L * lo_alloc * D * sizeof(float));
-  std::vector<HistLayer> tab(L);
-  for (size_t i = 0; i < L; ++i) {
-    if (h->generic) tab[i] = HistLayer{nullptr, nullptr, 0, 0};  // (the general route recomputes the history's GLU inside the layer)
-    else if (is_sq(h)) tab[i] = HistLayer{h->sq_layers[i].pw1_raw, h->sq_layers[i].pw1_b_raw, layer_lo(h, (int)i), 0};
-    else tab[i] = HistLayer{h->layers[i].pw1, h->layers[i].pw1_b, layer_lo(h, (int)i), 0};
-  }
-  if (e5 == hipSuccess) e5 = hipMemcpy(s->hist_tab, tab.data(), L * sizeof(HistLayer), hipMemcpyHostToDevice);
+  if (e5 == hipSuccess) e5 = upload_hist_table(h, s->hist_tab);
   if (e5 != hipSuccess) {
     (void)ppasr_stream_destroy(s);
     return fail(PPASR_EHIP, "initialising the stream caches failed");
@@ -514,37 +521,38 @@ ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* att_cache, i
 }
 
 // =====================================================================================
-// Multi-session streaming: a group of Conformer (ppasr_stream_group_create), Squeezeformer (ppasr_sq_stream_group_create)
-// or Efficient-Conformer (ppasr_eff_stream_group_create) sessions whose caches live in one allocation and advance with ONE
-// set of launches per chunk round (the rows of all active sessions are stacked: n x c frames -> ceil(n*c/32) row blocks
-// per kernel instead of one).  No reference counterpart: PPASR streams one session per call
-// (predict.py:232-337, forward_chunk asserts B = 1); each session here follows exactly the single-session arithmetic
-// (required_cache_size < 0: the full history is kept, what PPASRPredictor passes, predict.py:306-307).
-// DeepSpeech2 groups (ppasr_ds2_stream_group_create) keep each session's LSTM / GRU state [L][H] (h, and c for the LSTM)
-// instead of caches: a round is the wavefront route of ppasr_ds2_encode over the n stacked windows (capi_ds2.hip
-// ds2_group_round), with the states gathered from and scattered back to the sessions' slots by one launch each.
-// General-route Conformer groups (ppasr_gen_stream_group_create) hold the same caches at the model's width D; a round is
-// gen_front + gen_layers over the stacked chunks (capi_generic.hip generic_group_chunk).
+// Multi-session streaming: a session group holds the streaming state of n_sessions sessions of one model in one
+// allocation and advances any listed subset of them with ONE set of launches per chunk round (the rows of all listed
+// sessions are stacked: n x c frames -> ceil(n*c/32) row blocks per kernel instead of one).  No reference counterpart:
+// PPASR streams one session per call (predict.py:232-337, forward_chunk asserts B = 1); each session here follows exactly
+// the single-session arithmetic (required_cache_size < 0: the full history is kept, what PPASRPredictor passes,
+// predict.py:306-307).  Each family has its own create call and launch body:
+//   Conformer            ppasr_stream_group_create      conformer_group_body
+//   Squeezeformer        ppasr_sq_stream_group_create   sq_group_body
+//   Efficient-Conformer  ppasr_eff_stream_group_create  eff_group_body
+//   general route        ppasr_gen_stream_group_create  gen_group_body: the same caches at the model's width D;
+//                                                       gen_front + gen_layers (capi_generic.hip generic_group_chunk)
+//   DeepSpeech2          ppasr_ds2_stream_group_create  ds2_group_body: each session's LSTM / GRU state [L][H] (h, and
+//                        c for the LSTM) instead of caches; the wavefront route of ppasr_ds2_encode over the n stacked
+//                        windows, states gathered from and scattered back to the slots (capi_ds2.hip ds2_group_round)
+// One round, ppasr_encode_chunk_group, is the same for every family: check the arguments and the session list, plan
+// every listed session's chunk (plan_chunk_for; DeepSpeech2 carries no cache) -- a refused call leaves every session as it
+// was; take the next staging-ring entry and stage the descriptors in it; run the family's body; commit cache_t = T2,
+// cache_r = T2_r, offset += frames (finish_chunk with required_cache_size < 0: nothing is dropped) and release the entry
+// behind the launches.  A body that fails commits nothing.  Descriptors: {sess, cache_t, pos0, offset} per listed session
+// (pos0 = 0 on the general route without relative positions: its one-row zero table); Squeezeformer and
+// Efficient-Conformer append their half-rate layers' {sess, used_r, pos0, offset}; DeepSpeech2 stages plain slot indices.
 // =====================================================================================
 struct ppasr_stream_group_s {
   ppasr_model_s* m;
   int n_sessions, cap, lo;
   int D;               // row width of the caches: 256, or the general route's model width
-  GroupFamily family;  // Squeezeformer / Efficient-Conformer: full- and half-rate layers, per-layer histories
+  GroupFamily family;
   float *kc, *vc;     // [n_sessions][L][cap][D]
   float* xh_hist;     // [n_sessions][L][lo][D] (layer i uses its first kernel_i - 1 rows)
   float* ds2_state;   // DeepSpeech2: h [n_sessions][L][H], then (LSTM) c of the same shape; one allocation
   HistLayer* hist_tab;  // Squeezeformer / Efficient-Conformer: device [L], the layers' pointwise_conv1 (k_pw1_glu_layers)
-  // per-call descriptors: a ring of pinned host staging buffers + device copies, each guarded by an event, so that a
-  // call never overwrites a buffer an earlier (still queued) call reads.  A slot holds per_slot = n_sessions descriptors
-  // (Squeezeformer / Efficient-Conformer: 2 n_sessions -- those of the full-rate layers, then those of the half-rate
-  // layers; DeepSpeech2: n_sessions plain slot indices)
-  static constexpr int kRing = 8;
-  int per_slot;
-  SessDesc* desc_host;  // pinned [kRing][per_slot]
-  SessDesc* desc_dev;   // device [kRing][per_slot]
-  hipEvent_t ev[kRing];  // (null until created)
-  int slot;
+  StagingRing ring;   // per-call descriptors, room for n_sessions per entry (is_layered: 2 n_sessions)
   std::vector<int> cache_t, cache_r, offset;
 };
 
@@ -567,10 +575,7 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFa
   g->D = family == GroupFamily::kGeneral ? h->desc.output_size : kD;
   // (the general route without a conv module keeps no history: lo = 0, a one-row allocation as on a stream handle)
   g->lo = (family == GroupFamily::kGeneral && !h->gen.use_cnn) ? 0 : h->desc.cnn_module_kernel - 1;
-  const bool layered = family == GroupFamily::kSqueezeformer || family == GroupFamily::kEfficientConformer;
-  // (layered: per-layer history table, two descriptor sets)
-  g->per_slot = layered ? 2 * n_sessions : n_sessions;
-  g->slot = 0;
+  const bool layered = is_layered(family);  // (per-layer history table, two descriptor sets)
   // any failure below releases whatever exists so far (ppasr_stream_group_destroy skips what does not)
   auto bail = [g](const char* what, hipError_t e) {
     (void)ppasr_stream_group_destroy(g);
@@ -580,31 +585,17 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFa
   const bool ds2 = family == GroupFamily::kDeepSpeech2;  // (no caches: the recurrent states)
   const size_t kv = ds2 ? 0 : (size_t)n_sessions * L * g->cap * g->D * sizeof(float);
   const size_t hb = ds2 ? ds2_state_bytes(h, n_sessions) : (size_t)n_sessions * L * std::max(g->lo, 1) * g->D * sizeof(float);
-  const size_t db = (size_t)ppasr_stream_group_s::kRing * g->per_slot * sizeof(SessDesc);
   hipError_t e = hipSuccess;
   if (!ds2) e = hipMalloc(reinterpret_cast<void**>(&g->kc), kv);
   if (e == hipSuccess && !ds2) e = hipMalloc(reinterpret_cast<void**>(&g->vc), kv);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(ds2 ? &g->ds2_state : &g->xh_hist), hb);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->desc_dev), db);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->desc_host), db, hipHostMallocDefault);
+  if (e == hipSuccess) e = g->ring.alloc((size_t)(layered ? 2 : 1) * n_sessions * sizeof(SessDesc));
   if (e == hipSuccess && layered) e = hipMalloc(reinterpret_cast<void**>(&g->hist_tab), L * sizeof(HistLayer));
   if (e != hipSuccess) return bail("allocation failed for the session-group caches", e);
-  for (int i = 0; i < ppasr_stream_group_s::kRing; ++i) {
-    e = hipEventCreateWithFlags(&g->ev[i], hipEventDisableTiming);
-    if (e != hipSuccess) {
-      g->ev[i] = nullptr;
-      return bail("creating the session-group events failed", e);
-    }
-  }
   e = hipMemset(ds2 ? g->ds2_state : g->xh_hist, 0, hb);
   if (e != hipSuccess) return bail("clearing the session-group conv histories failed", e);
-  if (layered) {  // (what ppasr_stream_create puts in the family's stream table: rows = kernel_i - 1)
-    std::vector<HistLayer> tab(L);
-    for (size_t i = 0; i < L; ++i)
-      tab[i] = family == GroupFamily::kSqueezeformer
-                   ? HistLayer{h->sq_layers[i].pw1_raw, h->sq_layers[i].pw1_b_raw, g->lo, 0}
-                   : HistLayer{h->layers[i].pw1, h->layers[i].pw1_b, layer_lo(h, (int)i), 0};
-    e = hipMemcpy(g->hist_tab, tab.data(), L * sizeof(HistLayer), hipMemcpyHostToDevice);
+  if (layered) {
+    e = upload_hist_table(h, g->hist_tab);
     if (e != hipSuccess) return bail("uploading the session-group history table failed", e);
   }
   g->cache_t.assign(n_sessions, 0);
@@ -623,42 +614,83 @@ size_t layered_group_ws_floats(const ppasr_model_s* h, int n, int T) {
          (size_t)h->desc.num_blocks * n * (h->desc.cnn_module_kernel - 1) * kD;
 }
 
-// One round of a Squeezeformer group: squeezeformer_chunk's arithmetic for every listed session, rows stacked (n*c
-// full-rate rows, n*c_r half-rate rows).  Every session is planned (plan_chunk_for) before anything is launched or
-// changed, so a refused call leaves every session as it was.  The fp16 x3 mode covers what it covers on a stream handle:
-// the feed-forward slices of the split route.  A layer whose stacked rows leave the split route (ffn_split_for(Mi) = 1:
-// more than 4 096 rows at the default setting, ppasr_set_ffn_split(0)) runs the fused fp32 kernels in either mode, as the
-// Conformer group does; a stream handle's one-session chunk never gets there.
-ppasr_status sq_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
-                                   float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
-                                   void* workspace, hipStream_t st) {
+// ---- launch bodies of a round (ppasr_encode_chunk_group): the launches over the n listed sessions' stacked chunks,
+// with the descriptors `desc` the round staged (device) and the workspace ws; *frames = the encoder frames each session
+// emitted.  A body that fails returns before the round commits anything. ----
+typedef ppasr_status (*GroupBody)(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
+                                  int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames);
+
+// Conformer: conformer_chunk's arithmetic for every listed session, rows stacked (n*c rows).  Each layer gathers the
+// listed sessions' conv histories and GLUs them (hist_gather + pw1_glu).  fp16 x3 as on a stream handle: the split
+// route's feed-forward slices on the layers' h3 views, the fused kernels (stacked rows beyond the split route) in fp32.
+ppasr_status conformer_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
+                                  int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
+  ppasr_model_s* h = g->m;
+  const int F = h->desc.input_dim, T1 = (T - 1) / 2, F1 = h->F1, c = (T1 - 1) / 2, F2 = h->F2;
+  const WsLayout wl = ws_layout(h, n, T);
+  float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
+  float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g;
+  float* xhat = ws + wl.total;
+  const int lo = g->lo;
+  float* xh_act = xhat + (((size_t)n * c * kD + 63) & ~(size_t)63);  // [n][lo][256] gathered histories
+  float* g_hist = xh_act + (size_t)n * lo * kD;                       // [n][lo][256] GLU(pointwise_conv1(history))
+  const int M = n * c, L = h->desc.num_blocks, H = h->desc.attention_heads;
+  const int n_chunks = h->desc.linear_units / 256;
+  const long long kv_sess = (long long)L * g->cap * kD, hist_sess = (long long)L * lo * kD;
+  launch_conv1(feats, h->front, y1, n, T, F, T1, F1, st);
+  launch_conv2(y1, h->front, y2, n, T1, F1, c, F2, st);
+  launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), false, st, PadSkip{}, ffn_split_for(h, M), y1);
+  for (int i = 0; i < L; ++i) {
+    const LayerW& W = h->layers[i];
+    float* kc = g->kc + (size_t)i * g->cap * kD;
+    float* vc = g->vc + (size_t)i * g->cap * kD;
+    float* xh = g->xh_hist + (size_t)i * lo * kD;
+    const int S = ffn_split_for(h, M);  // few sessions = an under-filled grid: split route (partial sums in y1)
+    const bool h3 = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty();  // (see conformer_chunk)
+    const LayerW& Wk = h3 ? h->layers_h3[i] : W;
+    if (S > 1) {
+      launch_ffn_split(xa, W.ln_mac_g, W.ln_mac_b, Wk.ffm_w1, W.ffm_b1, Wk.ffm_w2, W.ffm_b2, 0.5f, nullptr, nullptr, y1, xb, M,
+                       n_chunks, S, st, PadSkip{}, false, h3);
+      launch_ln_qkv(xb, qkv, Wk, M, st, PadSkip{}, nullptr, nullptr, h3);
+    } else {
+      launch_ffn_qkv(xa, xb, qkv, W, M, n_chunks, st);
+    }
+    launch_kv_append_group(qkv, kc, vc, kv_sess, desc, n, c, st);
+    AttnArgs a{qkv, 768, kc, kD, vc, kD, c, c, 0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, 1, 4, c, c, 1, desc, kv_sess};
+    launch_attention(a, n, H, st);
+    launch_hist_gather(xh, hist_sess, desc, xh_act, n, lo, st);
+    launch_pw1_glu(xh_act, g_hist, W, n * lo, st);
+    launch_out_glu(ctx, xb, xc, gg, xhat, Wk, nullptr, M, c, 4, st, PadSkip{}, S > 1 ? xhat : nullptr, h3);
+    if (S > 1) {
+      launch_conv_pre(gg, g_hist, xc, ctx, Wk, nullptr, M, c, h->desc.cnn_module_kernel, 4, st, true, PadSkip{}, h3);
+      launch_ffn_split(ctx, W.ln_ff_g, W.ln_ff_b, Wk.ff_w1, W.ff_b1, Wk.ff_w2, W.ff_b2, 0.5f, W.ln_fin_g, W.ln_fin_b, y1, xa, M,
+                       n_chunks, S, st, PadSkip{}, false, h3);
+    } else {
+      launch_conv_ffn(gg, g_hist, xc, xa, W, nullptr, M, c, n_chunks, h->desc.cnn_module_kernel, 4, nullptr, nullptr, nullptr, st);
+    }
+    launch_hist_update_group(xh, hist_sess, desc, xhat, n, c, lo, st);
+  }
+  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
+  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
+  launch_ctc_head(xa, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, M, st, PadSkip{}, ffn_split_for(h, M), y1);
+  if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, M, h->head.V, st);
+  *frames = c;
+  return PPASR_OK;
+}
+
+// Squeezeformer: squeezeformer_chunk's arithmetic for every listed session, rows stacked (n*c full-rate rows, n*c_r
+// half-rate rows).  The fp16 x3 mode covers what it covers on a stream handle: the feed-forward slices of the split
+// route.  A layer whose stacked rows leave the split route (ffn_split_for(Mi) = 1: more than 4 096 rows at the default
+// setting, ppasr_set_ffn_split(0)) runs the fused fp32 kernels in either mode, as the Conformer group does; a stream
+// handle's one-session chunk never gets there.
+ppasr_status sq_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
+                           int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
   ppasr_model_s* h = g->m;
   const auto fd = h->front_dims(T);
-  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2;
-  std::vector<ChunkPlan> plans(n);
-  std::vector<char> seen(g->n_sessions, 0);
-  for (int b = 0; b < n; ++b) {
-    const int sidx = sessions_host[b];
-    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
-    seen[sidx] = 1;
-    ppasr_status r = plan_chunk_for(h, g->cache_t[sidx], g->cache_r[sidx], g->offset[sidx], g->cap, c, -1, &plans[b]);
-    if (r != PPASR_OK) return r;
-  }
-  const int c_r = plans[0].c_r;
-  const int slot = g->slot;
-  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
-  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
-  SessDesc* desc = g->desc_host + (size_t)slot * g->per_slot;
-  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->per_slot;
-  for (int b = 0; b < n; ++b) {  // full-rate layers {sess, cache_t, offset - cache_t}; half-rate {sess, used_r, same}
-    desc[b] = SessDesc{sessions_host[b], g->cache_t[sessions_host[b]], plans[b].pos0, 0};
-    desc[n + b] = SessDesc{sessions_host[b], plans[b].used_r, plans[b].pos0, 0};
-  }
-  HIP_TRY(hipMemcpyAsync(desc_dev, desc, (size_t)2 * n * sizeof(SessDesc), hipMemcpyHostToDevice, st));
-  const SessDesc* d_full = desc_dev;
-  const SessDesc* d_half = desc_dev + n;
+  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2, c_r = ceil_div(c, 2);
+  const SessDesc* d_full = desc;
+  const SessDesc* d_half = desc + n;
   const WsLayout wl = ws_layout(h, n, T);
-  float* ws = static_cast<float*>(workspace);
   float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
   float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g, *xs = ws + wl.xs;
   float* xhat = ws + wl.total;                                        // [n*c][256] conv-module inputs of this chunk
@@ -728,22 +760,13 @@ ppasr_status sq_encode_chunk_group(ppasr_stream_group g, const int* sessions_hos
   float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
   launch_ctc_head(x, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, M, st, PadSkip{}, ffn_split_for(h, M), y1);
   if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, M, h->head.V, st);
-  for (int b = 0; b < n; ++b) {  // (finish_chunk with required_cache_size < 0: nothing is dropped)
-    const int sidx = sessions_host[b];
-    g->cache_t[sidx] = plans[b].T2;
-    g->cache_r[sidx] = plans[b].T2_r;
-    g->offset[sidx] += c;
-  }
-  HIP_TRY(hipEventRecord(g->ev[slot], st));
-  if (c_out_host) *c_out_host = c;
-  HIP_TRY(hipGetLastError());
+  *frames = c;
   return PPASR_OK;
 }
 
-// One round of an Efficient-Conformer group: conformer_chunk's arithmetic for every listed session, rows stacked (n*c
-// full-rate rows up to and including the stride layer, n*c_r half-rate rows behind it).  Every session is planned
-// (plan_chunk_for: offset doubled, no trim of the half-rate cache, odd cache lengths refused) before anything is launched
-// or changed, so a refused call leaves every session as it was.  The descriptors of the full-rate layers carry
+// Efficient-Conformer: conformer_chunk's arithmetic for every listed session, rows stacked (n*c full-rate rows up to and
+// including the stride layer, n*c_r half-rate rows behind it).  The session plans (plan_chunk_for) double the offset, do
+// not trim the half-rate cache and refuse odd cache lengths.  The descriptors of the full-rate layers carry
 // {sess, cache_t, pos0}, those of the half-rate layers {sess, cache_r, pos0}, pos0 = 2 offset - cache_t (the half-rate
 // layers read every second positional row).  Grouped-attention layers re-cut each session's cache + chunk frames into
 // tokens from the start of its cache (k_attention_t's per-session branch).  The conv histories of every layer and
@@ -751,34 +774,12 @@ ppasr_status sq_encode_chunk_group(ppasr_stream_group g, const int* sessions_hos
 // fp16 x3 follows the stream handle's rule per launch, as in the other groups: the split route's units on the layers' h3
 // views, the fused kernels (stacked rows beyond the split route) in fp32.  The consumer-side joins of a stream handle's
 // chunk (ffn_half16 / join16) are single-session and not used here.
-ppasr_status eff_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
-                                    float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
-                                    void* workspace, hipStream_t st) {
+ppasr_status eff_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
+                            int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
   ppasr_model_s* h = g->m;
   const auto fd = h->front_dims(T);
-  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2;
-  std::vector<ChunkPlan> plans(n);
-  std::vector<char> seen(g->n_sessions, 0);
-  for (int b = 0; b < n; ++b) {
-    const int sidx = sessions_host[b];
-    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
-    seen[sidx] = 1;
-    ppasr_status r = plan_chunk_for(h, g->cache_t[sidx], g->cache_r[sidx], g->offset[sidx], g->cap, c, -1, &plans[b]);
-    if (r != PPASR_OK) return r;
-  }
-  const int c_r = plans[0].c_r;
-  const int slot = g->slot;
-  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
-  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
-  SessDesc* desc = g->desc_host + (size_t)slot * g->per_slot;
-  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->per_slot;
-  for (int b = 0; b < n; ++b) {  // full-rate layers {sess, cache_t, 2 offset - cache_t}; half-rate {sess, cache_r, same}
-    desc[b] = SessDesc{sessions_host[b], g->cache_t[sessions_host[b]], plans[b].pos0, 0};
-    desc[n + b] = SessDesc{sessions_host[b], plans[b].used_r, plans[b].pos0, 0};
-  }
-  HIP_TRY(hipMemcpyAsync(desc_dev, desc, (size_t)2 * n * sizeof(SessDesc), hipMemcpyHostToDevice, st));
+  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2, c_r = ceil_div(c, 2);
   const WsLayout wl = ws_layout(h, n, T);
-  float* ws = static_cast<float*>(workspace);
   float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
   float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g;
   float* xhat = ws + wl.total;                                        // [n*c][256] conv-module inputs of this chunk
@@ -791,9 +792,9 @@ ppasr_status eff_encode_chunk_group(ppasr_stream_group g, const int* sessions_ho
   launch_conv2(y1, h->front, y2, n, T1, F1, c, F2, st);
   launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), /*scale_before_bias=*/false, st, PadSkip{}, ffn_split_for(h, M),
                y1);
-  launch_pw1_glu_layers_group(g->xh_hist, hist_sess, desc_dev, g_hist, g->hist_tab, L, n, lo, st);
+  launch_pw1_glu_layers_group(g->xh_hist, hist_sess, desc, g_hist, g->hist_tab, L, n, lo, st);
   int Ti = c, mul = 4, pstride = 1;
-  const SessDesc* dsc = desc_dev;  // (the half-rate descriptors behind the stride layer)
+  const SessDesc* dsc = desc;  // (the half-rate descriptors behind the stride layer)
   for (int i = 0; i < L; ++i) {
     const LayerW& W = h->layers[i];
     const int grp = h->layer_group[i], KS = h->layer_ks[i], lo_i = layer_lo(h, i), Mi = n * Ti;
@@ -833,7 +834,7 @@ ppasr_status eff_encode_chunk_group(ppasr_stream_group g, const int* sessions_ho
       Ti = c_r;  // masks[:, :, ::2], pos_emb[:, ::2]  (efficient_conformer/encoder.py:252-257)
       mul *= 2;
       pstride *= 2;
-      dsc = desc_dev + n;
+      dsc = desc + n;
     } else {
       if (S > 1) {
         launch_conv_pre(gg, gh, xc, ctx, Wk, nullptr, Mi, Ti, KS, mul, st, true, PadSkip{}, h3);
@@ -850,91 +851,73 @@ ppasr_status eff_encode_chunk_group(ppasr_stream_group g, const int* sessions_ho
   float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
   launch_ctc_head(xa, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, Mo, st, PadSkip{}, ffn_split_for(h, Mo), y1);
   if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, Mo, h->head.V, st);
-  for (int b = 0; b < n; ++b) {  // (finish_chunk with required_cache_size < 0: nothing is dropped)
-    const int sidx = sessions_host[b];
-    g->cache_t[sidx] = plans[b].T2;
-    g->cache_r[sidx] = plans[b].T2_r;
-    g->offset[sidx] += Ti;
-  }
-  HIP_TRY(hipEventRecord(g->ev[slot], st));
-  if (c_out_host) *c_out_host = Ti;
-  HIP_TRY(hipGetLastError());
+  *frames = Ti;
   return PPASR_OK;
 }
 
-// One round of a general-route Conformer group: generic_group_chunk over the listed sessions.  Every session is planned
-// (plan_chunk_for: what ppasr_encode_chunk checks -- cache capacity, max_len) before anything is launched or changed, so a
-// refused call leaves every session as it was.  Descriptors {sess, cache_t, pos0, offset}: pos0 = offset - cache_t picks
-// the relative positional rows; without relative positions the attention's one-row zero table is read at row 0.
-ppasr_status gen_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
-                                    float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
-                                    void* workspace, hipStream_t st) {
-  ppasr_model_s* h = g->m;
-  const int c = h->front_dims(T).Tp;
-  std::vector<ChunkPlan> plans(n);
-  std::vector<char> seen(g->n_sessions, 0);
-  for (int b = 0; b < n; ++b) {
-    const int sidx = sessions_host[b];
-    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
-    seen[sidx] = 1;
-    ppasr_status r = plan_chunk_for(h, g->cache_t[sidx], g->cache_r[sidx], g->offset[sidx], g->cap, c, -1, &plans[b]);
-    if (r != PPASR_OK) return r;
-  }
-  const bool rel = h->gen.pos == PPASR_OPT_POS_REL;
-  const int slot = g->slot;
-  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
-  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
-  SessDesc* desc = g->desc_host + (size_t)slot * g->per_slot;
-  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->per_slot;
-  for (int b = 0; b < n; ++b) {
-    const int sidx = sessions_host[b];
-    desc[b] = SessDesc{sidx, g->cache_t[sidx], rel ? plans[b].pos0 : 0, g->offset[sidx]};
-  }
-  HIP_TRY(hipMemcpyAsync(desc_dev, desc, (size_t)n * sizeof(SessDesc), hipMemcpyHostToDevice, st));
-  ppasr_status r = generic_group_chunk(h, desc_dev, n, g->kc, g->vc, g->cap, g->xh_hist, g->lo, feats, T, probs, frame_argmax,
-                                       frame_maxprob, static_cast<float*>(workspace), st);
-  if (r != PPASR_OK) return r;
-  for (int b = 0; b < n; ++b) {  // (finish_chunk with required_cache_size < 0: nothing is dropped)
-    const int sidx = sessions_host[b];
-    g->cache_t[sidx] = plans[b].T2;
-    g->offset[sidx] += c;
-  }
-  HIP_TRY(hipEventRecord(g->ev[slot], st));
-  if (c_out_host) *c_out_host = c;
-  return PPASR_OK;
+// general route: generic_group_chunk over the listed sessions.  pos0 = offset - cache_t picks the relative positional
+// rows; abs_pos adds row offset + t.
+ppasr_status gen_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
+                            int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
+  *frames = g->m->front_dims(T).Tp;
+  return generic_group_chunk(g->m, desc, n, g->kc, g->vc, g->cap, g->xh_hist, g->lo, feats, T, probs, frame_argmax,
+                             frame_maxprob, ws, st);
 }
 
-// One round of a DeepSpeech2 group: ds2_group_round on the listed sessions' slots.  Every argument is checked before the
-// slot table is written or anything is launched, so a refused call leaves every session as it was.  The only host wait is
-// the descriptor ring's event (a slot table still read by a queued round is not overwritten).
-ppasr_status ds2_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
-                                    float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
-                                    void* workspace, hipStream_t st) {
-  ppasr_model_s* h = g->m;
-  std::vector<char> seen(g->n_sessions, 0);
-  for (int b = 0; b < n; ++b) {
-    const int sidx = sessions_host[b];
-    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
-    seen[sidx] = 1;
-  }
-  const int c = ((T - 1) / 2 - 1) / 2;
-  const int slot = g->slot;
-  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
-  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
-  int* slots = reinterpret_cast<int*>(g->desc_host + (size_t)slot * g->per_slot);
-  int* slots_dev = reinterpret_cast<int*>(g->desc_dev + (size_t)slot * g->per_slot);
-  std::copy(sessions_host, sessions_host + n, slots);
-  HIP_TRY(hipMemcpyAsync(slots_dev, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-  const Ds2W& W = h->ds2;
+// DeepSpeech2: ds2_group_round on the listed sessions' slots (desc holds plain slot indices)
+ppasr_status ds2_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
+                            int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
+  const Ds2W& W = g->m->ds2;
   float* state_h = g->ds2_state;
   float* state_c = W.gates == 4 ? g->ds2_state + (size_t)g->n_sessions * W.n_layers * W.H : nullptr;
-  ppasr_status r = ds2_group_round(h, slots_dev, n, feats, T, state_h, state_c, probs, frame_argmax, frame_maxprob,
-                                   static_cast<float*>(workspace), st);
-  if (r != PPASR_OK) return r;
-  for (int b = 0; b < n; ++b) g->offset[sessions_host[b]] += c;
-  HIP_TRY(hipEventRecord(g->ev[slot], st));
-  if (c_out_host) *c_out_host = c;
-  return PPASR_OK;
+  *frames = ((T - 1) / 2 - 1) / 2;
+  return ds2_group_round(g->m, reinterpret_cast<const int*>(desc), n, feats, T, state_h, state_c, probs, frame_argmax,
+                         frame_maxprob, ws, st);
+}
+
+// what a family's groups are built for: the model type (with the refusal of another type, or of a non-streaming handle)
+// and the launch body of its rounds; in GroupFamily order
+const struct {
+  int model_type;
+  const char* refusal;
+  GroupBody body;
+} kGroupKinds[] = {
+    {PPASR_MODEL_CONFORMER,
+     "session groups are built for streaming (causal) model_type=conformer (Squeezeformer: ppasr_sq_stream_group_create)",
+     conformer_group_body},
+    {PPASR_MODEL_SQUEEZEFORMER, "Squeezeformer session groups are built for streaming (causal) model_type=squeezeformer",
+     sq_group_body},
+    {PPASR_MODEL_EFFICIENT_CONFORMER,
+     "Efficient-Conformer session groups are built for streaming (causal) model_type=efficient_conformer", eff_group_body},
+    {PPASR_MODEL_DEEPSPEECH2,
+     "DeepSpeech2 session groups are built for streaming (unidirectional) model_type=deepspeech2 "
+     "(the reference streams no bidirectional model)",
+     ds2_group_body},
+    {PPASR_MODEL_CONFORMER, "general-route session groups are built for streaming (causal) model_type=conformer",
+     gen_group_body},
+};
+
+// the checks every create call shares, then each family's requirements (in the order each create call has made them)
+ppasr_status group_create(ppasr_handle h, int n_sessions, int max_frames, GroupFamily family, ppasr_stream_group* out) {
+  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
+  const auto& kind = kGroupKinds[(int)family];
+  if (h->desc.model_type != kind.model_type || !h->desc.causal) return fail(PPASR_EUNSUPPORTED, kind.refusal);
+  if (family == GroupFamily::kDeepSpeech2) {
+    if (!h->ds2.wave_tab) return fail(PPASR_EUNSUPPORTED, "DeepSpeech2 session groups run on the wavefront recurrence");
+    // (max_frames: no cache grows with the stream -- the state is [L][H] per session whatever its length)
+    return group_alloc(h, n_sessions, max_frames, family, out);
+  }
+  const bool general = family == GroupFamily::kGeneral;
+  if (general && !h->generic)
+    return fail(PPASR_EUNSUPPORTED, "general-route session groups are built for the general layer route "
+                                    "(the fused 256-wide route: ppasr_stream_group_create)");
+  if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
+  if (!general && h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
+  if (family == GroupFamily::kSqueezeformer && h->desc.cnn_module_kernel != 31 && h->desc.cnn_module_kernel != 15)
+    return fail(PPASR_EUNSUPPORTED, "Squeezeformer session groups: the streaming conv kernels exist for kernel sizes 31 / 15");
+  if (family == GroupFamily::kEfficientConformer && __builtin_popcount(eff_stride_mask(h->desc)) > 1)
+    return fail(PPASR_EUNSUPPORTED, "Efficient-Conformer session groups are built for at most one stride layer");
+  return group_alloc(h, n_sessions, max_frames, family, out);
 }
 
 }  // namespace
@@ -942,66 +925,26 @@ ppasr_status ds2_encode_chunk_group(ppasr_stream_group g, const int* sessions_ho
 extern "C" {
 
 ppasr_status ppasr_ds2_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
-  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
-  if (h->desc.model_type != PPASR_MODEL_DEEPSPEECH2 || !h->desc.causal)
-    return fail(PPASR_EUNSUPPORTED, "DeepSpeech2 session groups are built for streaming (unidirectional) model_type=deepspeech2 "
-                                    "(the reference streams no bidirectional model)");
-  if (!h->ds2.wave_tab) return fail(PPASR_EUNSUPPORTED, "DeepSpeech2 session groups run on the wavefront recurrence");
-  // (max_frames: no cache grows with the stream -- the state is [L][H] per session whatever its length)
-  return group_alloc(h, n_sessions, max_frames, GroupFamily::kDeepSpeech2, out);
+  return group_create(h, n_sessions, max_frames, GroupFamily::kDeepSpeech2, out);
 }
-
 ppasr_status ppasr_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
-  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
-  if (h->desc.model_type != PPASR_MODEL_CONFORMER || !h->desc.causal)
-    return fail(PPASR_EUNSUPPORTED, "session groups are built for streaming (causal) model_type=conformer "
-                                    "(Squeezeformer: ppasr_sq_stream_group_create)");
-  if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
-  if (h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
-  return group_alloc(h, n_sessions, max_frames, GroupFamily::kConformer, out);
+  return group_create(h, n_sessions, max_frames, GroupFamily::kConformer, out);
 }
-
 ppasr_status ppasr_gen_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
-  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
-  if (h->desc.model_type != PPASR_MODEL_CONFORMER || !h->desc.causal)
-    return fail(PPASR_EUNSUPPORTED, "general-route session groups are built for streaming (causal) model_type=conformer");
-  if (!h->generic)
-    return fail(PPASR_EUNSUPPORTED, "general-route session groups are built for the general layer route "
-                                    "(the fused 256-wide route: ppasr_stream_group_create)");
-  if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
-  return group_alloc(h, n_sessions, max_frames, GroupFamily::kGeneral, out);
+  return group_create(h, n_sessions, max_frames, GroupFamily::kGeneral, out);
 }
-
 ppasr_status ppasr_sq_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
-  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
-  if (h->desc.model_type != PPASR_MODEL_SQUEEZEFORMER || !h->desc.causal)
-    return fail(PPASR_EUNSUPPORTED, "Squeezeformer session groups are built for streaming (causal) model_type=squeezeformer");
-  if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
-  if (h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
-  if (h->desc.cnn_module_kernel != 31 && h->desc.cnn_module_kernel != 15)
-    return fail(PPASR_EUNSUPPORTED, "Squeezeformer session groups: the streaming conv kernels exist for kernel sizes 31 / 15");
-  return group_alloc(h, n_sessions, max_frames, GroupFamily::kSqueezeformer, out);
+  return group_create(h, n_sessions, max_frames, GroupFamily::kSqueezeformer, out);
 }
-
 ppasr_status ppasr_eff_stream_group_create(ppasr_handle h, int n_sessions, int max_frames, ppasr_stream_group* out) {
-  if (!h || !out || n_sessions < 1) return fail(PPASR_EINVAL, "bad argument");
-  if (h->desc.model_type != PPASR_MODEL_EFFICIENT_CONFORMER || !h->desc.causal)
-    return fail(PPASR_EUNSUPPORTED,
-                "Efficient-Conformer session groups are built for streaming (causal) model_type=efficient_conformer");
-  if (h->desc.input_layer != 0) return fail(PPASR_EUNSUPPORTED, "session groups are built for the conv2d front end only");
-  if (h->generic) return fail(PPASR_EUNSUPPORTED, "session groups are built for the fused 256-wide route");
-  if (__builtin_popcount(eff_stride_mask(h->desc)) > 1)
-    return fail(PPASR_EUNSUPPORTED, "Efficient-Conformer session groups are built for at most one stride layer");
-  return group_alloc(h, n_sessions, max_frames, GroupFamily::kEfficientConformer, out);
+  return group_create(h, n_sessions, max_frames, GroupFamily::kEfficientConformer, out);
 }
 
 ppasr_status ppasr_stream_group_destroy(ppasr_stream_group g) {
   if (!g) return PPASR_OK;
-  (void)hipFree(g->kc); (void)hipFree(g->vc); (void)hipFree(g->xh_hist); (void)hipFree(g->desc_dev);
+  g->ring.destroy();
+  (void)hipFree(g->kc); (void)hipFree(g->vc); (void)hipFree(g->xh_hist);
   (void)hipFree(g->hist_tab); (void)hipFree(g->ds2_state);
-  (void)hipHostFree(g->desc_host);
-  for (int i = 0; i < ppasr_stream_group_s::kRing; ++i)
-    if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
   delete g;
   return PPASR_OK;
 }
@@ -1063,89 +1006,46 @@ ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int* sessions_
   ppasr_model_s* h = g->m;
   if (T < 7) return fail(PPASR_EINVAL, "chunk shorter than the conv front-end's receptive field (7 frames)");
   if (workspace_bytes < ppasr_group_chunk_workspace_bytes(h, n, T)) return fail(PPASR_ENOSPACE, "workspace too small");
-  if (g->family == GroupFamily::kSqueezeformer)
-    return sq_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
-                                 static_cast<hipStream_t>(stream));
-  if (g->family == GroupFamily::kDeepSpeech2)
-    return ds2_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
-                                  static_cast<hipStream_t>(stream));
-  if (g->family == GroupFamily::kGeneral)
-    return gen_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
-                                  static_cast<hipStream_t>(stream));
-  if (g->family == GroupFamily::kEfficientConformer)
-    return eff_encode_chunk_group(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
-                                  static_cast<hipStream_t>(stream));
-  const int F = h->desc.input_dim, T1 = (T - 1) / 2, F1 = h->F1, c = (T1 - 1) / 2, F2 = h->F2;
-  const int slot = g->slot;
-  g->slot = (slot + 1) % ppasr_stream_group_s::kRing;
-  HIP_TRY(hipEventSynchronize(g->ev[slot]));  // the call that last used this slot has consumed it (no-op when unused)
-  SessDesc* desc = g->desc_host + (size_t)slot * g->per_slot;
-  SessDesc* desc_dev = g->desc_dev + (size_t)slot * g->per_slot;
-  std::vector<char> seen(g->n_sessions, 0);
-  for (int b = 0; b < n; ++b) {
-    const int sidx = sessions_host[b];
-    if (sidx < 0 || sidx >= g->n_sessions || seen[sidx]) return fail(PPASR_EINVAL, "session index out of range or repeated");
-    seen[sidx] = 1;
-    if (g->cache_t[sidx] + c > g->cap) return fail(PPASR_EINVAL, "attention cache capacity exceeded");
-    if (g->offset[sidx] + c >= h->desc.max_len) return fail(PPASR_EINVAL, "offset + chunk exceeds the positional table (max_len)");
-    desc[b] = SessDesc{sidx, g->cache_t[sidx], g->offset[sidx] - g->cache_t[sidx], 0};
+  if (!session_list_ok(sessions_host, n, g->n_sessions)) return fail(PPASR_EINVAL, "session index out of range or repeated");
+  const bool ds2 = g->family == GroupFamily::kDeepSpeech2, layered = is_layered(g->family);
+  const int c = h->front_dims(T).Tp;
+  std::vector<ChunkPlan> plans(ds2 ? 0 : n);  // (DeepSpeech2 carries no cache)
+  for (size_t b = 0; b < plans.size(); ++b) {
+    const int s = sessions_host[b];
+    ppasr_status r = plan_chunk_for(h, g->cache_t[s], g->cache_r[s], g->offset[s], g->cap, c, -1, &plans[b]);
+    if (r != PPASR_OK) return r;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  HIP_TRY(hipMemcpyAsync(desc_dev, desc, (size_t)n * sizeof(SessDesc), hipMemcpyHostToDevice, st));
-  const WsLayout wl = ws_layout(h, n, T);
-  float* ws = static_cast<float*>(workspace);
-  float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
-  float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g;
-  float* xhat = ws + wl.total;
-  const int lo = g->lo;
-  float* xh_act = xhat + (((size_t)n * c * kD + 63) & ~(size_t)63);  // [n][lo][256] gathered histories
-  float* g_hist = xh_act + (size_t)n * lo * kD;                       // [n][lo][256] GLU(pointwise_conv1(history))
-  const int M = n * c, L = h->desc.num_blocks, H = h->desc.attention_heads;
-  const int n_chunks = h->desc.linear_units / 256;
-  const long long kv_sess = (long long)L * g->cap * kD, hist_sess = (long long)L * lo * kD;
-  launch_conv1(feats, h->front, y1, n, T, F, T1, F1, st);
-  launch_conv2(y1, h->front, y2, n, T1, F1, c, F2, st);
-  launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), false, st, PadSkip{}, ffn_split_for(h, M), y1);
-  for (int i = 0; i < L; ++i) {
-    const LayerW& W = h->layers[i];
-    float* kc = g->kc + (size_t)i * g->cap * kD;
-    float* vc = g->vc + (size_t)i * g->cap * kD;
-    float* xh = g->xh_hist + (size_t)i * lo * kD;
-    const int S = ffn_split_for(h, M);  // few sessions = an under-filled grid: split route (partial sums in y1)
-    const bool h3 = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty();  // (see conformer_chunk)
-    const LayerW& Wk = h3 ? h->layers_h3[i] : W;
-    if (S > 1) {
-      launch_ffn_split(xa, W.ln_mac_g, W.ln_mac_b, Wk.ffm_w1, W.ffm_b1, Wk.ffm_w2, W.ffm_b2, 0.5f, nullptr, nullptr, y1, xb, M,
-                       n_chunks, S, st, PadSkip{}, false, h3);
-      launch_ln_qkv(xb, qkv, Wk, M, st, PadSkip{}, nullptr, nullptr, h3);
-    } else {
-      launch_ffn_qkv(xa, xb, qkv, W, M, n_chunks, st);
+  StagingRing::Entry en;
+  HIP_TRY(g->ring.acquire(&en));
+  size_t staged = (size_t)n * sizeof(int);
+  if (ds2) {
+    std::copy(sessions_host, sessions_host + n, reinterpret_cast<int*>(en.host));
+  } else {
+    const bool zero_pos = g->family == GroupFamily::kGeneral && h->gen.pos != PPASR_OPT_POS_REL;
+    SessDesc* desc = reinterpret_cast<SessDesc*>(en.host);
+    for (int b = 0; b < n; ++b) {
+      const int s = sessions_host[b];
+      desc[b] = SessDesc{s, g->cache_t[s], zero_pos ? 0 : plans[b].pos0, g->offset[s]};
+      if (layered) desc[n + b] = SessDesc{s, plans[b].used_r, plans[b].pos0, g->offset[s]};
     }
-    launch_kv_append_group(qkv, kc, vc, kv_sess, desc_dev, n, c, st);
-    AttnArgs a{qkv, 768, kc, kD, vc, kD, c, c, 0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, 1, 4, c, c, 1, desc_dev, kv_sess};
-    launch_attention(a, n, H, st);
-    launch_hist_gather(xh, hist_sess, desc_dev, xh_act, n, lo, st);
-    launch_pw1_glu(xh_act, g_hist, W, n * lo, st);
-    launch_out_glu(ctx, xb, xc, gg, xhat, Wk, nullptr, M, c, 4, st, PadSkip{}, S > 1 ? xhat : nullptr, h3);
-    if (S > 1) {
-      launch_conv_pre(gg, g_hist, xc, ctx, Wk, nullptr, M, c, h->desc.cnn_module_kernel, 4, st, true, PadSkip{}, h3);
-      launch_ffn_split(ctx, W.ln_ff_g, W.ln_ff_b, Wk.ff_w1, W.ff_b1, Wk.ff_w2, W.ff_b2, 0.5f, W.ln_fin_g, W.ln_fin_b, y1, xa, M,
-                       n_chunks, S, st, PadSkip{}, false, h3);
-    } else {
-      launch_conv_ffn(gg, g_hist, xc, xa, W, nullptr, M, c, n_chunks, h->desc.cnn_module_kernel, 4, nullptr, nullptr, nullptr, st);
-    }
-    launch_hist_update_group(xh, hist_sess, desc_dev, xhat, n, c, lo, st);
+    staged = (size_t)(layered ? 2 : 1) * n * sizeof(SessDesc);
   }
-  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
-  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
-  launch_ctc_head(xa, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, M, st, PadSkip{}, ffn_split_for(h, M), y1);
-  if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, M, h->head.V, st);
+  HIP_TRY(hipMemcpyAsync(en.dev, en.host, staged, hipMemcpyHostToDevice, st));
+  int frames = 0;
+  ppasr_status r = kGroupKinds[(int)g->family].body(g, reinterpret_cast<const SessDesc*>(en.dev), n, feats, T, probs,
+                                                    frame_argmax, frame_maxprob, static_cast<float*>(workspace), st, &frames);
+  if (r != PPASR_OK) return r;
   for (int b = 0; b < n; ++b) {
-    g->cache_t[sessions_host[b]] += c;
-    g->offset[sessions_host[b]] += c;
+    const int s = sessions_host[b];
+    if (!ds2) {
+      g->cache_t[s] = plans[b].T2;
+      g->cache_r[s] = plans[b].T2_r;
+    }
+    g->offset[s] += frames;
   }
-  HIP_TRY(hipEventRecord(g->ev[slot], st));
-  if (c_out_host) *c_out_host = c;
+  HIP_TRY(g->ring.release(en, st));
+  if (c_out_host) *c_out_host = frames;
   HIP_TRY(hipGetLastError());
   return PPASR_OK;
 }

@@ -48,7 +48,7 @@ struct SessDesc {
   int sess;     // slot in the group's cache arrays
   int cache_t;  // cached frames before this chunk
   int pos0;     // offset - cache_t  (encoder.py:253)
-  int offset;   // encoder frames the session has emitted (general-route groups: abs_pos rows); 0 elsewhere
+  int offset;   // encoder frames the session has emitted; only the general route reads it (k_g_add_pe_group: abs_pos rows)
 };
 
 // Attention operands: queries / keys / values may live in different buffers (streaming reads K/V from

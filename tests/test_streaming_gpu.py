@@ -125,3 +125,41 @@ def test_session_group_equals_independent_streams():
     assert group.offset(2) == 16 and _rel(probs[0].cpu().numpy(), ref2[0].cpu().numpy()) < 3e-5
     with pytest.raises(Exception):
         group.encode_chunks([1, 1], np.concatenate([feats[1][:, :67]] * 2))
+
+
+def test_session_group_refusals_leave_every_session_as_it_was():
+    """A round that one listed session's own stream would refuse -- its attention cache is full (max_frames), or its next
+    chunk runs past the positional table (max_len) -- raises EINVAL and changes no session: the rounds after it give bit
+    for bit what they give when it was never asked for."""
+    from ppasr_amd import _lib
+    from ppasr_amd.model_utils.conformer.model import ConformerModel, ConformerStreamGroup
+    L, V = 2, 150
+    sd = conformer_state_dict(vocab_size=V, num_blocks=L, seed=62, perturb_norm=True)
+    conf = dict(output_size=256, attention_heads=4, linear_units=2048, num_blocks=L, cnn_module_kernel=15, max_len=64)
+    model = ConformerModel(80, V, streaming=True, encoder_conf=conf, state_dict=sd, device="cuda:0")
+    feats = [synth_features(1, 64 * 4 + 3, seed=90 + s)[0] for s in range(2)]
+
+    def win(s, k):
+        return feats[s][:, 64 * k:64 * k + 67]
+
+    # 16 encoder frames per chunk.  max_frames 32: the caches hold two chunks.  max_frames 0 (cap = max_len = 64): offsets
+    # 0, 16 and 32 fit, 48 + 16 >= max_len does not.
+    for max_frames, full in ((32, 2), (0, 3)):
+        runs = []
+        for with_refusals in (False, True):
+            group = ConformerStreamGroup(model, 2, max_frames=max_frames)
+            for k in range(full):  # session 0 full, session 1 one chunk behind
+                active = [0, 1] if k < full - 1 else [0]
+                group.encode_chunks(active, np.concatenate([win(s, k) for s in active]))
+            if with_refusals:
+                for active, chunks in (([0], [win(0, full)]), ([1, 0], [win(1, full - 1), win(0, full)])):
+                    with pytest.raises(_lib.PPASRHipError) as e:
+                        group.encode_chunks(active, np.concatenate(chunks))
+                    assert e.value.status == _lib.PPASR_EINVAL, (max_frames, active)
+                assert (group.offset(0), group.offset(1)) == (16 * full, 16 * (full - 1))
+            _, _, p1 = group.encode_chunks([1], win(1, full - 1), want_probs=True)
+            group.reset(0)
+            _, _, p0 = group.encode_chunks([0], win(0, 0), want_probs=True)
+            assert (group.offset(0), group.offset(1)) == (16, 16 * full)
+            runs.append((p1.cpu(), p0.cpu()))
+        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1]), max_frames
