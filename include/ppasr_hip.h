@@ -13,6 +13,10 @@
  *     passed as void*); nothing synchronises, nothing allocates after create();
  *   - the caller owns every buffer including the scratch workspace
  *     (size from ppasr_workspace_bytes); the handle owns only packed weights;
+ *   - what workspace, scratch and output buffers hold on entry is irrelevant:
+ *     results are a function of the inputs, the handle and the carried state
+ *     (stream / group caches, beam-search state buffers) only, and every output
+ *     is written in full unless its entry point says which part is undefined;
  *   - a handle is not re-entrant; distinct handles are independent;
  *   - no exceptions cross the ABI: int status + ppasr_last_error() (thread-local).
  */
@@ -249,8 +253,8 @@ PPASR_API long long ppasr_edit_distance(const int32_t* a, int na, const int32_t*
  *     call again with init_state = 0 and the SAME state buffer for every further chunk.
  * CTC prefix beam search; the external scorer variant is ppasr_ctc_beam_search_lm below.
  *   probs [B,T,V] f32, frame_lens [B] i32 or NULL; per utterance the `nbest` best prefixes:
- *   tokens [B,nbest,max_tokens] i32 (-1 padded), lens [B,nbest] (-1 = no such hypothesis),
- *   scores [B,nbest] f64 = -log P(prefix) (the upstream return convention).
+ *   tokens [B,nbest,max_tokens] i32 (-1 padded), lens [B,nbest] (-1 = no such hypothesis: its tokens are all -1 and
+ *   its score is 0), scores [B,nbest] f64 = -log P(prefix) (the upstream return convention).
  *   state: device scratch of ppasr_ctc_beam_state_bytes(B, max total frames, beam_size) bytes that
  *   holds the beam, the prefix arena (both kept between chunk calls) and the per-frame records of the
  *   pruning pre-pass (get_pruned_log_probs of every frame of the call: T <= max total frames). */

@@ -833,6 +833,28 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
   //  computes every row: its skip rules are written for the 3x3 / 2 pair of Conv2dSubsampling4)
   const bool skip = h->skip_padding && lens && !h->taps && h->desc.input_layer != 1;
   const bool skip_front = skip && h->desc.input_layer == 0;
+  // Ragged batches on the fused attention route (ppasr_set_ffn_split(0), or more than 128 row blocks): its key sub-blocks
+  // read the VALUES of whole 64-row pieces of the batch's row space times p = 0, and the QKV stage writes those values
+  // for every row of a 32-row block that holds one needed frame.  The rows behind the needed frames in such a block are
+  // computed from what their producers left: conv2 skips by its own tiles (the embed then reads rows of y2 nobody
+  // wrote), the fused attention by 32-query blocks counted from the utterance's first frame (xc / g), and behind the
+  // Efficient-Conformer's stride layer the half-rate rows lie where nobody wrote at the full rate (xa).  They must be
+  // finite, so the activation buffers (y2 .. g, one range of the workspace) start from zeros on this route (and on no
+  // other: rowblock.h PadSkip).  The vt clear above only covers rows of blocks the QKV stage skips.
+  // (tests/test_buffer_contents_gpu.py test_batched_encode[conformer-9x1000-ff], [conformer-3x131-masked-ff] and
+  // [efficient-3x400-ff], routes ffn_split=0+skip: NaN in every valid row when the workspace held NaN.)
+  // The row-count half of fusable() below, shared with it: a layer of `rows` rows may take the fused attention.  True of
+  // a layer's Mi <= M only if true of M (a forced split never fuses, the default rule fuses past fuse_min_blocks), so
+  // asking it of M covers every layer, the Efficient-Conformer's half-rate ones included.
+  // (an under-filled grid is latency-bound either way, and the two-kernel route then has 4x the workgroups in its
+  //  attention half, one per head: 2 - 6 % faster end to end up to 128 row blocks, measured in round 3), 10 %
+  //  slower at the bench shape)
+  constexpr int fuse_min_blocks = 128;
+  auto fuse_rows = [&](int rows) {
+    return ffn_split_for(h, rows) == 1 &&
+           (h->ffn_split == 0 || (rows + kRows - 1) / kRows > fuse_min_blocks);  // (ppasr_set_ffn_split(0): always fused)
+  };
+  if (skip && fuse_rows(M)) HIP_TRY(hipMemsetAsync(y2, 0, (wl.rmax - wl.y2) * sizeof(float), st));
   const int rc = h->desc.causal ? 0 : (h->desc.cnn_module_kernel - 1) / 2;
   const int slack_half = rc + 4, slack_full = eff ? 2 * slack_half + rc + 8 : rc + 4;
   auto pskip = [&](int Tcur, int mul_cur) {
@@ -901,15 +923,11 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
     const int grp = h->layer_group[i];
     // plain 4 x 64 heads: attention and the out-projection / GLU stage run as one launch (context rows stay in LDS);
     // the debug taps need the context tensor, so they take the two-kernel route
-    // (an under-filled grid is latency-bound either way, and the two-kernel route then has 4x the workgroups in its
-    //  attention half, one per head: 2 - 6 % faster end to end up to 128 row blocks, measured in round 3), 10 %
-    //  slower at the bench shape)
-    constexpr int fuse_min_blocks = 128;
+    // (from fuse_min_blocks row blocks on, or always with ppasr_set_ffn_split(0): fuse_rows above)
     auto fusable = [&](int layer) {
       // (the fused kernel reads the values in fragment order, which only the fused QKV stage -- ffn_qkv_body -- writes: a
       //  FORCED split of a large batch (ppasr_set_ffn_split(2 / 4 / 8), k_ln_qkv) therefore takes the two-kernel route)
-      return h->layer_group[layer] == 1 && h->desc.attention_heads == 4 && !h->taps && ffn_split_for(h, Mi) == 1 &&
-             (h->ffn_split == 0 || (Mi + kRows - 1) / kRows > fuse_min_blocks);  // (ppasr_set_ffn_split(0): always fused)
+      return h->layer_group[layer] == 1 && h->desc.attention_heads == 4 && !h->taps && fuse_rows(Mi);
     };
     const PadSkip ps = pskip(Ti, mul);
     // under-filled launch, 33 .. 128 row blocks: the 16-row-block kernels (conformer_kernels_t.hip) -- twice the

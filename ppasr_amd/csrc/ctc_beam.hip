@@ -1792,10 +1792,16 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
       out_scores[(size_t)u * cfg.nbest + rank] = -approx_ctc;
     }
   }
-  // ranks >= nb (beam smaller than nbest): mark empty
+  // ranks >= nb (beam smaller than nbest): mark empty -- lens -1, score 0 and, like every row of `tokens`, -1 padding
+  // (the rows used to keep what the caller's buffer held: tests/test_buffer_contents_decoders_gpu.py
+  // test_beam_search[10-10-one-shot-stale], the 0-frame utterance's ranks 1 .. 9)
   for (int r = nb + tid; r < cfg.nbest; r += BT) {
     out_lens[(size_t)u * cfg.nbest + r] = -1;
     out_scores[(size_t)u * cfg.nbest + r] = 0.0;
+  }
+  for (int r = nb; r < cfg.nbest; ++r) {
+    int32_t* dst = out_tokens + ((size_t)u * cfg.nbest + r) * cfg.max_tokens;
+    for (int j = tid; j < cfg.max_tokens; j += BT) dst[j] = -1;
   }
 }
 

@@ -82,7 +82,10 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // of `unit` rows each, time step t is valid iff mul*t < lens[b], and only the first need(b) = min(Tp, valid + slack)
 // time steps are computed -- `slack` covers what valid outputs read from the rows behind them (right context of a
 // non-causal conv module, the stride / time-reduction layers, the 3-frame groups of grouped attention).  A workgroup
-// whose rows all lie behind need(b) returns at once; its outputs keep the zeros the workspace was cleared to.
+// whose rows all lie behind need(b) returns at once and its output rows are UNDEFINED: nothing clears the workspace, and
+// every consumer either skips the same rows or bounds its reads (the stand-alone attention's value loads, the clamped key
+// rows).  The one exception is the fused attention route of encode_impl (capi.hip), which multiplies the values of whole
+// key sub-blocks by p = 0: there the activation range of the workspace is cleared before the front end.
 struct PadSkip {
   const int64_t* lens = nullptr;  // nullptr: every row is computed (the reference's behaviour)
   int Tp = 0, mul = 4, slack = 0, unit = 1;
