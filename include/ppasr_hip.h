@@ -202,18 +202,25 @@ PPASR_API ppasr_status ppasr_set_row_block(ppasr_handle h, int rows);
  * by 2.7e-7 where fp32 arithmetic deviates by 5.5e-7 (tools/experiments/r05/ffn_h3.hip), but NOT bit-identical to the
  * default mode.  The first call re-packs the weights concerned on the device (second copy, ~ 10 MB per layer).
  * Range.  Weights are scaled by 2^8, activations by 2^4 before they are cut into fp16 pieces: a weight of magnitude >= 255.9
- * makes this call fail with PPASR_EUNSUPPORTED (the handle stays in its previous mode); an activation beyond 4 094 at a
- * GEMM input (ReLU outputs in front of conv2 / the input projection, swish values in front of W2, LayerNorm outputs
- * elsewhere) is handled by the range guard below -- never Inf / NaN.
+ * makes this call fail with PPASR_EUNSUPPORTED (the handle stays in its previous mode; a Squeezeformer handle re-packs
+ * diag(ada_scale) w_1, so the product counts there); an activation beyond 4 094 at a GEMM input is handled by the range
+ * guard below -- never Inf / NaN.  The guarded inputs: ReLU outputs in front of conv2 / the input projection, LayerNorm
+ * outputs in front of W1, Q/K/V, pointwise_conv1 and the CTC head, swish values in front of W2 and pointwise_conv2, the
+ * attention context in front of linear_out, and in the fused attention K (projection + bias), q + pos_bias_u and
+ * q + pos_bias_v (tests/guard_sites.py lists every one with its source line; each is tripped alone by
+ * tests/test_gemm_guard_sites_gpu.py).
  * Built for the fused 256-wide routes: Conformer / Efficient-Conformer -- feed-forward modules, Q/K/V, pointwise_conv2
  * (8-wave 32-row layer kernels incl. the Efficient-Conformer's stride layer; depthwise kernel sizes 15 and 7), linear_out +
  * pointwise_conv1 and the score contraction
  * [q+u | q+v] [k | p]^T of the fused attention kernel (K as fp16 hi / lo planes from the QKV stage, the layer's positional
  * table re-packed by this call: + 1 KiB per table row; an entry beyond 4 094 refuses the mode like a weight does);
  * Squeezeformer -- both feed-forward modules of the 32-row layer kernels (depthwise kernel sizes 31 and 15); all three -- the
- * second convolution of the 4x front end (then its own launch behind conv1), the input projection, the CTC head;
+ * second convolution of the 4x front end (then its own launch behind conv1), the input projection (full launches; an
+ * under-filled launch splits its K over several workgroups in fp32), the CTC head;
  * Conformer / Efficient-Conformer also on the split route of under-filled launches and therefore on their stream handles and
- * session groups (ppasr_encode_chunk*: a saturated chunk is counted in the guard statistics, NOT re-run).  The other block
+ * session groups (ppasr_encode_chunk*: a saturated chunk is counted in the guard statistics, NOT re-run; a chunk's front
+ * end and CTC head keep fp32 arithmetic, as do linear_out + pointwise_conv1 of a grouped-attention layer on full launches,
+ * which has no fused attention kernel).  The other block
  * forms (16 rows, 16 waves), the non-feed-forward units of Squeezeformer's split route and streams, the attention's P V product and depthwise convolutions keep fp32 arithmetic.  ppasr_gemm_coverage
  * tells which of the three parts switched (a Conformer with cnn_module_kernel 31 gets the front end and the head only).
  * PPASR_EUNSUPPORTED on DeepSpeech2 handles and on the general layer route.  Measured (NOTES.md 9.8): logits within 1e-6 .. 3e-6

@@ -67,6 +67,7 @@ class ConformerOracle:
         self.dk = self.d // self.h
         self.max_len = max_len
         self.trace = None  # set to a dict to record per-layer intermediates (kernel-level parity tests)
+        self.taps = None  # set to a dict to record max |x| at every GEMM input (tests/guard_sites.py: fp16 x3 range guard)
         # PositionalEncoding.__init__  conformer/embedding.py:38-53 (table built in fp32)
         pe = torch.zeros(max_len, self.d, dtype=torch.float32)
         position = torch.arange(0, max_len, dtype=torch.float32).unsqueeze(1)
@@ -76,6 +77,13 @@ class ConformerOracle:
         self.pe = pe.to(dtype).unsqueeze(0)  # [1, max_len, d]
 
     # ---- shared primitives ------------------------------------------------
+    def _tap(self, name, x):
+        """max |x| over every row of a GEMM input, padded rows included (the kernels split those as well); a site reached
+        several times (chunks) keeps its largest value"""
+        if self.taps is not None and x.numel():
+            self.taps[name] = max(self.taps.get(name, 0.0), float(x.detach().abs().max()))
+        return x
+
     def _linear(self, x, prefix, bias=True):
         # paddle Linear: x @ W[in,out] + b   (utils/base.py:58)
         y = x @ self.p[prefix + ".weight"]
@@ -133,8 +141,11 @@ class ConformerOracle:
         else:
             x = x.unsqueeze(1)
             x = F.relu(F.conv2d(x, self.p["encoder.embed.conv.0.weight"], self.p["encoder.embed.conv.0.bias"], stride=2))
+            self._tap("encoder.embed.conv2_in", x)
             x = F.relu(F.conv2d(x, self.p["encoder.embed.conv.2.weight"], self.p["encoder.embed.conv.2.bias"],
                                 stride=3 if k == 6 else 2))
+            if k != 8:
+                self._tap("encoder.embed.proj_in", x)
             if k == 8:
                 x = F.relu(F.conv2d(x, self.p["encoder.embed.conv.4.weight"], self.p["encoder.embed.conv.4.bias"], stride=2))
             b, c, t, f = x.shape
@@ -159,14 +170,16 @@ class ConformerOracle:
     # ---- one encoder layer ----------------------------------------------------
     def _ffn(self, x, prefix):
         # PositionwiseFeedForward.forward  conformer/positionwise.py:32-39
-        return self._linear(self._swish(self._linear(x, prefix + ".w_1")), prefix + ".w_2")
+        self._tap(prefix + ".w1_in", x)
+        return self._linear(self._tap(prefix + ".w2_in", self._swish(self._linear(x, prefix + ".w_1"))), prefix + ".w_2")
 
     def _attention(self, x, mask, pos_emb, cache, prefix):
         # RelPositionMultiHeadedAttention.forward  conformer/attention.py:198-262
         B, T, _ = x.shape
         h, dk = self.h, self.dk
+        self._tap(prefix + ".qkv_in", x)
         q = self._linear(x, prefix + ".linear_q").reshape(B, T, h, dk).permute(0, 2, 1, 3)
-        k = self._linear(x, prefix + ".linear_k").reshape(B, T, h, dk).permute(0, 2, 1, 3)
+        k = self._tap(prefix + ".k", self._linear(x, prefix + ".linear_k")).reshape(B, T, h, dk).permute(0, 2, 1, 3)
         v = self._linear(x, prefix + ".linear_v").reshape(B, T, h, dk).permute(0, 2, 1, 3)
         if cache is not None and cache.shape[0] > 0:  # :225-229
             key_cache, value_cache = torch.split(cache, dk, dim=-1)
@@ -176,8 +189,9 @@ class ConformerOracle:
         if self.pos_type == "rel_pos":
             p = self._linear(pos_emb, prefix + ".linear_pos", bias=False)
             p = p.reshape(pos_emb.shape[0], -1, h, dk).permute(0, 2, 1, 3)  # :234-236
-            q_u = q + self.p[prefix + ".pos_bias_u"].unsqueeze(1)  # :241
-            q_v = q + self.p[prefix + ".pos_bias_v"].unsqueeze(1)  # :243
+            q_u = self._tap(prefix + ".q_u", q + self.p[prefix + ".pos_bias_u"].unsqueeze(1))  # :241
+            q_v = self._tap(prefix + ".q_v", q + self.p[prefix + ".pos_bias_v"].unsqueeze(1))  # :243
+            self._tap(prefix + ".pos", p)
             matrix_ac = q_u @ k.transpose(-1, -2)  # :250
             matrix_bd = q_v @ p.transpose(-1, -2)  # :255  (rel_shift disabled :256-258)
             scores = (matrix_ac + matrix_bd) / math.sqrt(dk)  # :260
@@ -197,7 +211,7 @@ class ConformerOracle:
             self.trace[prefix + ".k"] = k.permute(0, 2, 1, 3).reshape(B, -1, h * dk)
             self.trace[prefix + ".v"] = v.permute(0, 2, 1, 3).reshape(B, -1, h * dk)
             self.trace[prefix + ".ctx"] = ctx
-        return self._linear(ctx, prefix + ".linear_out"), new_cache
+        return self._linear(self._tap(prefix + ".out_in", ctx), prefix + ".linear_out"), new_cache
 
     def _conv_module(self, x, mask_pad, cache, prefix):
         # ConvolutionModule.forward  conformer/convolution.py:82-143
@@ -213,6 +227,7 @@ class ConformerOracle:
             new_cache = x[:, :, -self.lorder:]
         else:
             new_cache = torch.zeros(0, 0, 0, dtype=x.dtype)
+        self._tap(prefix + ".pw1_in", x)
         x = F.conv1d(x, self.p[prefix + ".pointwise_conv1.weight"], self.p[prefix + ".pointwise_conv1.bias"])
         x = F.glu(x, dim=1)
         if self.trace is not None:
@@ -221,7 +236,7 @@ class ConformerOracle:
         x = F.conv1d(x, self.p[prefix + ".depthwise_conv.weight"], self.p[prefix + ".depthwise_conv.bias"],
                      padding=pad, groups=x.shape[1])
         x = x.transpose(1, 2)
-        x = self._swish(self._cm_norm(x, prefix + ".norm"))  # LayerNorm or BatchNorm1D(eval) (convolution.py:65-71)
+        x = self._tap(prefix + ".pw2_in", self._swish(self._cm_norm(x, prefix + ".norm")))  # LayerNorm or BatchNorm1D(eval) (convolution.py:65-71)
         x = x.transpose(1, 2)
         x = F.conv1d(x, self.p[prefix + ".pointwise_conv2.weight"], self.p[prefix + ".pointwise_conv2.bias"])
         if mask_pad is not None and mask_pad.shape[2] > 0:
@@ -298,6 +313,7 @@ class ConformerOracle:
         return xs, masks
 
     def ctc_logits(self, enc):
+        self._tap("ctc.in", enc)
         return enc @ self.p["ctc.ctc_lo.weight"] + self.p["ctc.ctc_lo.bias"]
 
     def get_encoder_out(self, speech, speech_lengths, return_logits=False):

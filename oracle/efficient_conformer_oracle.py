@@ -32,8 +32,9 @@ class EfficientConformerOracle(ConformerOracle):
         # GroupedRelPositionMultiHeadedAttention.forward  efficient_conformer/attention.py:128-193
         B, T, _ = x.shape
         h, dk, g = self.h, self.dk, self.group_size
+        self._tap(prefix + ".qkv_in", x)
         q = self._linear(x, prefix + ".linear_q").reshape(B, T, h, dk).permute(0, 2, 1, 3)
-        k = self._linear(x, prefix + ".linear_k").reshape(B, T, h, dk).permute(0, 2, 1, 3)
+        k = self._tap(prefix + ".k", self._linear(x, prefix + ".linear_k")).reshape(B, T, h, dk).permute(0, 2, 1, 3)
         v = self._linear(x, prefix + ".linear_v").reshape(B, T, h, dk).permute(0, 2, 1, 3)
         p = self._linear(pos_emb, prefix + ".linear_pos")  # with bias (:31)
         if cache is not None and cache.shape[0] > 0 and cache.shape[2] > 0:  # :155-158
@@ -59,8 +60,9 @@ class EfficientConformerOracle(ConformerOracle):
         pad_p = (g - p.shape[1] % g) % g
         p = F.pad(p, (0, 0, 0, pad_p)).reshape(p.shape[0], -1, h, dk * g).permute(0, 2, 1, 3)
         q = q.permute(0, 2, 1, 3)
-        q_u = (q + self.p[prefix + ".pos_bias_u"]).permute(0, 2, 1, 3)
-        q_v = (q + self.p[prefix + ".pos_bias_v"]).permute(0, 2, 1, 3)
+        q_u = self._tap(prefix + ".q_u", q + self.p[prefix + ".pos_bias_u"]).permute(0, 2, 1, 3)
+        q_v = self._tap(prefix + ".q_v", q + self.p[prefix + ".pos_bias_v"]).permute(0, 2, 1, 3)
+        self._tap(prefix + ".pos", p)
         scores = (q_u @ k.transpose(-1, -2) + q_v @ p.transpose(-1, -2)) / math.sqrt(dk * g)
         if mask is not None and mask.shape[2] > 0:
             m = (mask.unsqueeze(1) == 0)[:, :, :, :scores.shape[-1]]
@@ -72,7 +74,7 @@ class EfficientConformerOracle(ConformerOracle):
         ctx = ctx[:, :ctx.shape[1] - pad_t]
         if self.trace is not None:
             self.trace[prefix + ".ctx"] = ctx
-        return self._linear(ctx, prefix + ".linear_out"), new_cache
+        return self._linear(self._tap(prefix + ".out_in", ctx), prefix + ".linear_out"), new_cache
 
     def _conv_eff(self, x, mask_pad, prefix, ksize, stride, cache=None):
         # efficient_conformer/convolution.py:80-138 ; mask_pad True = valid
@@ -87,12 +89,13 @@ class EfficientConformerOracle(ConformerOracle):
             new_cache = x[:, :, -lorder:]
         else:
             new_cache = x[:, :, :0]
+        self._tap(prefix + ".pw1_in", x)
         x = F.conv1d(x, self.p[prefix + ".pointwise_conv1.weight"], self.p[prefix + ".pointwise_conv1.bias"])
         x = F.glu(x, dim=1)
         x = F.conv1d(x, self.p[prefix + ".depthwise_conv.weight"], self.p[prefix + ".depthwise_conv.bias"],
                      stride=stride, padding=padding, groups=x.shape[1])
         x = x.transpose(1, 2)
-        x = self._swish(self._cm_norm(x, prefix + ".norm"))
+        x = self._tap(prefix + ".pw2_in", self._swish(self._cm_norm(x, prefix + ".norm")))
         x = x.transpose(1, 2)
         x = F.conv1d(x, self.p[prefix + ".pointwise_conv2.weight"], self.p[prefix + ".pointwise_conv2.bias"])
         if mask_pad.shape[2] != x.shape[2]:

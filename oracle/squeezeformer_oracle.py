@@ -37,6 +37,7 @@ class SqueezeformerOracle(ConformerOracle):
         return self.p[prefix + ".ada_scale"].reshape(1, 1, -1) * x + self.p[prefix + ".ada_bias"].reshape(1, 1, -1)
 
     def ctc_logits(self, enc):
+        self._tap("ctc.in", enc)
         # final_proj (encoder.py:165-167, 234-235, 381-382): Linear(encoder_dim, output_size) in front of ctc_lo
         if "encoder.final_proj.weight" in self.p:
             enc = enc @ self.p["encoder.final_proj.weight"] + self.p["encoder.final_proj.bias"]
@@ -46,10 +47,12 @@ class SqueezeformerOracle(ConformerOracle):
         # DepthwiseConv2DSubsampling4.forward  squeezeformer/subsampling.py:53-68 (dw_stride False -> groups=1)
         x = x.unsqueeze(1)
         x = F.relu(F.conv2d(x, self.p["encoder.embed.pw_conv.weight"], self.p["encoder.embed.pw_conv.bias"], stride=2))
+        self._tap("encoder.embed.conv2_in", x)
         x = F.relu(F.conv2d(x, self.p["encoder.embed.dw_conv.weight"], self.p["encoder.embed.dw_conv.bias"], stride=2,
                             groups=self.dw_groups))
         b, c, t, f = x.shape
         x = x.permute(0, 2, 1, 3).reshape(b, t, c * f)
+        self._tap("encoder.embed.proj_in", x)
         x = x * math.sqrt(self.d)  # RelPositionalEncoding on the c*f-wide tensor (pos_emb not added)
         pos_emb = self.pe[:, 0:t]
         x = self._linear(x, "encoder.embed.input_proj.0")
@@ -89,8 +92,9 @@ class SqueezeformerOracle(ConformerOracle):
 
     def _ffn_sq(self, x, prefix):
         # squeezeformer/positionwise.py:55-65
+        self._tap(prefix + ".w1_in", x)  # (the kernels fold the adaptive scale into w_1: their GEMM input is x itself)
         x = self._ada(x, prefix)
-        return self._linear(self._swish(self._linear(x, prefix + ".w_1")), prefix + ".w_2")
+        return self._linear(self._tap(prefix + ".w2_in", self._swish(self._linear(x, prefix + ".w_1"))), prefix + ".w_2")
 
     def _conv_sq(self, x, mask_pad, prefix, cache=None):
         # squeezeformer/convolution.py:102-163 ; mask_pad True = valid here (fill where ~mask_pad)

@@ -8,7 +8,15 @@ Squeezeformer and the Efficient-Conformer also the reduced / strided rows -- tur
 inputs, puts key lengths on the attention tile widths (64 / 128 / 192 / 256 +- 1) next to utterances of 1 and 3 encoder
 frames, sharpens the attention so that position and mask errors are not averaged away, and streams chunks (single
 sessions and Conformer session groups) against the float64 forward_chunk.  Each case prints its worst error; the
-budgets were set from those prints."""
+budgets were set from those prints.
+
+The opt-in fp16 x3 GEMM mode (ppasr_set_gemm_mode, csrc/h3.h) runs the row thresholds, the attention edges, the sharpened
+attention and the stream chunks a second time (`_f16x3_leg`): wherever the handle accepts the mode, the same per-utterance
+checks against the same float64 results at the same F32_BUDGET (its header puts it in fp32's class), with zero guard
+events; a handle that refuses it must do so with PPASR_EUNSUPPORTED and the case says what it skipped.  That the mode's
+kernels ran is checked too (kernel_profile: an _h3 / <.., true> kernel was launched, and where the coverage includes the
+layers one of the LAYER kernels unless the launch took the fused 16-row layer kernels, which keep fp32 by design) and the bytes
+must differ from the fp32 leg's.  The fp32 legs are unchanged."""
 import numpy as np
 import pytest
 import torch
@@ -113,6 +121,70 @@ def _check(name, model, x, lens, ref_logits, what, skip_padding=False):
         for b in range(x.shape[0]):
             n = int(lens_out[b]) if skip_padding else r.shape[1]
             assert np.array_equal(tokens[b, :int(n_tok[b])].cpu().numpy(), nm.collapse(r[b, :n].argmax(-1))), (what, b)
+    return max(e_l, e_p), logits.cpu().numpy().tobytes()
+
+
+def _check_both(test, name, x, lens, ref, what):
+    """the fp32 leg (as before), then the same case in the fp16 x3 mode"""
+    model = _model(name)
+    e32, bytes32 = _check(name, model, x, lens, ref, what)
+    e16 = _f16x3_leg(test, name, model, lambda label: _check(name, model, x, lens, ref, label + what), bytes32)
+    _note(test, name, what, e16, e32)
+
+
+WORST_F16X3 = {}  # test name -> (worst f16x3 error, the fp32 leg's error of that case, what)
+# the mode's kernels by name (csrc: the _h3 kernels, and the <.., H3 = true> forms of the split route's units, whose last
+# template parameter is H3); other kernels carry trailing bool parameters of their own, so the names are listed
+FRONT_HEAD_H3 = ("k_conv_stage_h3", "k_embed_h3", "k_ctc_head_h3")
+LAYER_H3 = ("k_ffn_qkv_h3", "k_conv_ffn_h3", "k_attn_out_glu_h3", "k_sq_mid_h3", "k_sq_tail_h3")
+LAYER_H3_TRUE = ("k_ffn_part<", "k_ln_qkv<", "k_out_glu<", "k_pw1_glu_cols<", "k_conv_pre<", "k_conv_ffn_stride<")
+ROWS16_FUSED = ("k_ffn_qkv_t<", "k_conv_ffn_t<", "k_sq_mid_t<", "k_sq_tail_t<")  # the layer kernels of 33 .. 128 row blocks
+
+
+def _mode_kernels(names):
+    """-> (the mode's kernels among `names`, its LAYER kernels among them, the fused 16-row layer kernels launched)"""
+    layer = sorted(k for k in names
+                   if k.startswith(LAYER_H3) or (k.startswith(LAYER_H3_TRUE) and k.rstrip().endswith("true>")))
+    return sorted(k for k in names if k.startswith(FRONT_HEAD_H3)) + layer, layer, sorted(k for k in names if k.startswith(ROWS16_FUSED))
+
+
+def _f16x3_leg(test, name, model, run, bytes32):
+    """`run(label)` -> (worst error, output bytes) once more with the handle in the fp16 x3 mode -> its worst error (the checks
+    are run's own); no guard event and no fallback may be counted, kernels of the mode must have run and the bytes must differ
+    from `bytes32`, the fp32 leg's.  A refusal must be PPASR_EUNSUPPORTED."""
+    from ppasr_amd import _lib
+    try:
+        model.set_gemm_mode("f16x3")
+    except _lib.PPASRHipError as e:
+        assert e.status == _lib.PPASR_EUNSUPPORTED, e
+        print(f"[fp64] {name}: f16x3 refused (PPASR_EUNSUPPORTED): fp16 x3 leg skipped on every route of this case")
+        return None
+    try:
+        cov = "+".join(sorted(model.gemm_coverage()))
+        assert cov, name
+        before = model.gemm_guard_stats()
+        with _lib.kernel_profile() as kp:
+            err, got = run(f"f16x3[{cov}] ")
+            torch.cuda.synchronize()
+        assert model.gemm_guard_stats() == before, (name, before, model.gemm_guard_stats())
+        mode, layer, t_forms = _mode_kernels(kp.kernels)
+        print(f"[fp64] {name} f16x3[{cov}]: mode kernels {len(mode)} (layer kernels {len(layer)}), 16-row layer kernels {len(t_forms)}: "
+              + " ".join(k.split("(")[0] for k in layer + t_forms))
+        assert mode, (name, sorted(kp.kernels))  # a route that quietly stayed in fp32 would pass every check above
+        if "layers" in cov:
+            assert layer or t_forms, (name, sorted(kp.kernels))
+        assert got != bytes32, name
+    finally:
+        model.set_gemm_mode("f32")
+    return err
+
+
+def _note(test, name, what, e16, e32):
+    if e16 is not None and e16 >= WORST_F16X3.get(test, (-1.0,))[0]:
+        WORST_F16X3[test] = (e16, e32, f"{name} {what}")
+    w = WORST_F16X3.get(test)
+    if w:
+        print(f"[fp64] {test}: worst f16x3 so far {w[0]:.2e} (fp32 leg of that case {w[1]:.2e}) at {w[2]}")
 
 
 def _ragged(B, Tp, seed):
@@ -141,7 +213,7 @@ ROWS_K31 = [(1, 16), (1, 17), (4, 128), (3, 171), (4, 256), (5, 205)]
 def test_rows_on_route_thresholds(name, B, Tp):
     lens_tp = _ragged(B, Tp, B * 7919 + Tp)
     x, lens, ref = _ref(name, Tp, lens_tp, Tp + B)
-    _check(name, _model(name), x, lens, ref, f"B={B} T'={Tp} M={B * Tp}")
+    _check_both("rows_on_route_thresholds", name, x, lens, ref, f"B={B} T'={Tp} M={B * Tp}")
 
 
 # ---- route knobs at fixed inputs --------------------------------------------------------------------------------------
@@ -184,7 +256,7 @@ def test_attention_key_lengths_and_tiny_utterances(name, Tp):
     utterance of 1 or 3 encoder frames and one a tile width long"""
     lens_tp = [Tp, 1 if Tp % 2 else 3, 64]
     x, lens, ref = _ref(name, Tp, lens_tp, 3 * Tp)
-    _check(name, _model(name), x, lens, ref, f"T'={Tp} lens'={lens_tp}")
+    _check_both("attention_key_lengths", name, x, lens, ref, f"T'={Tp} lens'={lens_tp}")
 
 
 @pytest.mark.parametrize("name", ["conformer_sharp", "squeezeformer_sharp", "efficient_sharp"])
@@ -192,7 +264,7 @@ def test_attention_key_lengths_and_tiny_utterances(name, Tp):
 def test_sharpened_attention(name, B, Tp):
     lens_tp = [Tp, 11, 3][:B] if B > 1 else [Tp]
     x, lens, ref = _ref(name, Tp, lens_tp, 5 + Tp)
-    _check(name, _model(name), x, lens, ref, f"B={B} T'={Tp}")
+    _check_both("sharpened_attention", name, x, lens, ref, f"B={B} T'={Tp}")
 
 
 # ---- streaming --------------------------------------------------------------------------------------------------------
@@ -211,23 +283,34 @@ def _ref_chunk(oracle, chunk, offset, required, att, cnn):
 def test_stream_chunks(name, required):
     model, oracle = _model(name), _oracle(name)
     x, _ = synth_features(1, 64 * 4 + 3, seed=51)
-    stream = model.new_stream()
+    refs = []  # the float64 chunks, once for both legs
     att = cnn = None
     offset = 0
-    worst = 0.0
     for (a, b) in _windows(x.shape[1]):
-        chunk = x[:, a:b]
-        ref, att, cnn = _ref_chunk(oracle, chunk, offset, required, att, cnn)
-        got = stream.encode_chunk(chunk, required)
-        g_att, g_cnn = stream.export_caches()
-        torch.cuda.synchronize()
-        assert tuple(got.shape) == tuple(ref.shape) and tuple(g_att.shape) == tuple(att.shape), (a, b)
-        errs = [nm.utt_rel(got, torch.softmax(ref, -1)),
-                nm.logprob_err(got, ref), nm.utt_rel(g_att, att), nm.utt_rel(g_cnn, cnn) if cnn.numel() else 0.0]
-        worst = max(worst, *errs)
-        assert max(errs) < nm.F32_BUDGET, (a, b, errs)
+        ref, att, cnn = _ref_chunk(oracle, x[:, a:b], offset, required, att, cnn)
+        refs.append((a, b, ref, att, cnn))
         offset += ref.shape[1]
-    print(f"[fp64] {name} chunks required={required}: worst {worst:.2e}")
+
+    def run(label):
+        stream = model.new_stream()
+        worst = 0.0
+        outs = []
+        for (a, b, ref, att, cnn) in refs:
+            got = stream.encode_chunk(x[:, a:b], required)
+            g_att, g_cnn = stream.export_caches()
+            torch.cuda.synchronize()
+            outs.append(got.cpu().numpy().tobytes())
+            assert tuple(got.shape) == tuple(ref.shape) and tuple(g_att.shape) == tuple(att.shape), (a, b)
+            errs = [nm.utt_rel(got, torch.softmax(ref, -1)),
+                    nm.logprob_err(got, ref), nm.utt_rel(g_att, att), nm.utt_rel(g_cnn, cnn) if cnn.numel() else 0.0]
+            worst = max(worst, *errs)
+            assert max(errs) < nm.F32_BUDGET, (label, a, b, errs)
+        print(f"[fp64] {name} {label}chunks required={required}: worst {worst:.2e}")
+        return worst, b"".join(outs)
+
+    e32, bytes32 = run("")
+    e16 = _f16x3_leg("stream_chunks", name, model, run, bytes32)
+    _note("stream_chunks", name, f"required={required}", e16, e32)
 
 
 def test_conformer_session_group():
