@@ -353,6 +353,14 @@ ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob*
         launch_posproj(pe_dev, wpos_dev, bpos_dev, static_cast<float*>(pt), max_len, nullptr, d);
         HIP_TRY(hipGetLastError());
         L.ptab = static_cast<const float*>(pt);
+        if (!grouped && d == kD && desc->attention_heads == 4) {  // plain 4 x 64 heads: the layers k_attn_out_glu can run
+          void* dt = nullptr;
+          HIP_TRY(hipMalloc(&dt, (size_t)4 * max_len * sizeof(float)));
+          m->allocs.push_back(dt);
+          launch_pos_dtab(L.ptab, L.pos_u, L.pos_v, static_cast<float*>(dt), max_len, nullptr);
+          HIP_TRY(hipGetLastError());
+          L.dtab = static_cast<const float*>(dt);
+        }
       } else {  // the attention kernel's positional half contracts with zeros (capi_generic.hip)
         L.pos_u = L.pos_v = L.ptab = m->zero_vec;
       }
@@ -950,9 +958,16 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
     // attention reads the layer's positional planes.  Producer and consumer follow the same rule: layer j's K is planes iff
     // layer j runs k_attn_out_glu_h3 (the producer of j's QKV is j's own S1 launch or the NEXT tail of j - 1, which shares
     // j's row count and block form; the stride layer has no NEXT tail)
-    auto vt_for = [&](bool fused, bool mode) {
+    // ... and on the fp32 route the fused attention contracts 64 wide against k + p (AttnArgs::dtab): layer j's K holds the
+    // positional rows iff layer j runs the fp32 k_attn_out_glu -- same pairing, `layer` = the layer whose QKV is produced
+    auto vt_for = [&](bool fused, bool mode, int layer) {
       VtOut v = fused ? vt_out : VtOut{};
       v.k_h3 = (fused && mode) ? 1 : 0;
+      if (fused && !mode && h->layers[layer].dtab) {
+        v.kpos = h->layers[layer].ptab;  // (the fp32 table, not the h3 view's planes)
+        v.kpos_stride = pstride * kD;
+        v.Ti = Ti;
+      }
       return v;
     };
     float* partial = y1;
@@ -967,9 +982,9 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
       } else if (r16) {
         timed(3, [&] { launch_ffn_qkv_16(xa, xb, qkv, L, Mi, n_chunks, st, psb); });
       } else if (w16) {
-        timed(3, [&] { launch_ffn_qkv_w16(xa, xb, qkv, L, Mi, n_chunks, st, psb, fuse_attn ? vt_out : VtOut{}); });
+        timed(3, [&] { launch_ffn_qkv_w16(xa, xb, qkv, L, Mi, n_chunks, st, psb, vt_for(fuse_attn, false, i)); });
       } else {
-        timed(3, [&] { launch_ffn_qkv(xa, xb, qkv, Lk, Mi, n_chunks, st, psb, vt_for(fuse_attn, h3), h3); });
+        timed(3, [&] { launch_ffn_qkv(xa, xb, qkv, Lk, Mi, n_chunks, st, psb, vt_for(fuse_attn, h3, i), h3); });
       }
     }
     s1_done = false;
@@ -981,6 +996,10 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
     a.pad_skip = skip ? ps.slack + 1 : 0;
     a.vt = vt_out.vt;
     a.vt_stride = vt_out.stride;
+    if (fuse_attn && !h3) {
+      a.dtab = L.dtab;
+      a.dtab_len = h->desc.max_len;
+    }
     if (fuse_attn) {
       timed(9, [&] { launch_attn_out_glu(a, B, xb, xc, g, Lk, st, h3); });
     } else {
@@ -1027,11 +1046,11 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
                              h->desc.causal != 0, psb);
         else if (w16)
           launch_conv_ffn_w16(g, xc, next ? nullptr : xa, L, lens, Mi, Ti, n_chunks, h->layer_ks[i], mul, next, xb, qkv, st,
-                              h->desc.causal != 0, psb, (next && fusable(i + 1)) ? vt_out : VtOut{});
+                              h->desc.causal != 0, psb, vt_for(next && fusable(i + 1), false, i + 1));
         else
           launch_conv_ffn(g, nullptr, xc, (next && !h->taps) ? nullptr : xa, Lk, lens, Mi, Ti, n_chunks, h->layer_ks[i], mul,
                           next, xb, qkv, st, h->desc.causal != 0, psb,
-                          vt_for(next && fusable(i + 1), h3), h3);
+                          vt_for(next && fusable(i + 1), h3, next ? i + 1 : i), h3);
       });
       s1_done = next != nullptr;
     }

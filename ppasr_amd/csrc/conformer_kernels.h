@@ -20,6 +20,9 @@ struct LayerW {
   const float *glu_pad;  // [256] GLU(pointwise_conv1(0)) = value of a zero-padded frame after GLU
   const float *pos_u, *pos_v;  // [256] = [h][dk]
   const float *ptab;     // [max_len][256] linear_pos(pe)  (weight-only, folded at create time)
+  // [4 heads][max_len] d[h][t] = (pos_v - pos_u)[h] . ptab[t][64 h ..]: the positional term of the fused attention's scores
+  // that does not depend on the query (see AttnArgs::dtab); nullptr: no relative positions, or not plain 4 x 64 heads
+  const float *dtab = nullptr;
 };
 
 struct FrontW {
@@ -85,6 +88,11 @@ struct AttnArgs {
   // model width (row stride of ptab / ctx, h * 64 <= dm); 256 everywhere except the general layer route (capi_generic.hip),
   // which runs k_attention<64> with 8 heads on 512-wide activations
   int dm = 256;
+  // fp32 k_attn_out_glu only: (q + u) . k + (q + v) . p = (q + u) . (k + p) + (v - u) . p.  The QKV stage leaves k + p in the K
+  // third of qkv (VtOut::kpos), the kernel contracts 64 wide and starts key j's score from dtab[h][pos0 + j * pos_stride]
+  // (LayerW::dtab, row length dtab_len = the table's max_len).  nullptr: the layer has no positional term (K is plain k)
+  const float* dtab = nullptr;
+  int dtab_len = 0;
 };
 // Where the QKV stage puts the values when the layer's attention runs fused: in the order the attention's P V MFMAs
 // consume them, [8 slabs of 32 columns][stride / 8 row octets][64 lanes = column + 32 * (row quad)][4 rows] -- 1 KiB
@@ -96,6 +104,12 @@ struct VtOut {
   // fp16 x3 mode, fused attention: the K third of every qkv row as [hi: 256 fp16 | lo: 256 fp16] of 2^4 K (h3.h) instead of
   // 256 floats (QkStoreTailH3 writes it, attn_out_glu_body<true> reads it)
   int k_h3 = 0;
+  // fp32 fused attention (AttnArgs::dtab): the K third of row m holds k + kpos[(m mod Ti) * kpos_stride + column] -- the
+  // positional row of the frame, kpos = the layer's fp32 ptab, kpos_stride = 256 * its positional stride, Ti = frames per
+  // utterance.  nullptr: plain k.  Producer and consumer pair up like k_h3: set iff the layer runs the fp32 k_attn_out_glu
+  const float* kpos = nullptr;
+  int kpos_stride = 0;
+  int Ti = 1;
 };
 
 // dynamic-LDS request of a ragged (PadSkip) launch: more than half of a CU's LDS, so that workgroups do not share a CU
@@ -154,6 +168,8 @@ hipError_t configure_conformer_t_kernels();
 // ---- launchers (all asynchronous on `st`) ----
 void launch_posproj(const float* pe, const float* wpos /*[d][d] in,out*/, const float* bpos_or_null, float* ptab,
                     int max_len, hipStream_t st, int d = 256);
+// dtab[h][t] = sum_c (pos_v - pos_u)[64 h + c] * ptab[t][64 h + c], 4 heads of 64 (LayerW::dtab); double accumulation
+void launch_pos_dtab(const float* ptab, const float* pos_u, const float* pos_v, float* dtab, int max_len, hipStream_t st);
 // every row-block launcher takes an optional PadSkip (rowblock.h): default = compute all rows
 void launch_conv1(const float* feats, const FrontW& fw, float* y1, int B, int T, int F, int T1, int F1, hipStream_t st,
                   const PadSkip& ps = PadSkip{}, int channels = 256);

@@ -116,15 +116,14 @@ __device__ __forceinline__ void ffn_qkv_body(float* bufX, float* bufA, float* bu
   // Q, K, V units: the global stores of unit c's tile (16 per lane) are sliced into the MFMA stream of unit c + 1
   // (QkvStoreSide, one store every second k-group) instead of running between the units with the matrix pipe idle
   // (0.4 - 1.5 us per unit, per-phase stamps); only V's tile is stored after its GEMM.
-  f32x16 tile[3][1][1];
-  bool qk_bad = false;  // (fp16 x3, K planes: range-guard events of the K split)
+  f32x16 tile[3][1][1]; bool qk_bad = false;  // (qk_bad -- fp16 x3, K planes: range-guard events of the K split)
   const int cq = wave * 32 + 4 * (lane >> 5);
   float* qrow = (lane & 31) < valid ? qkv + (size_t)(r0 + (lane & 31)) * 768 + cq : nullptr;
-  f32x4 qb[2][4];  // biases of this lane's Q / K column quads
+  f32x4 qb[2][4], kp[4];  // biases of this lane's Q / K column quads; kp: K's positional quads (VtOut::kpos: added behind the Q unit)
 #pragma unroll
-  for (int c = 0; c < 2; ++c)
+  for (int c = 0; c < 3; ++c)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) qb[c][q] = *reinterpret_cast<const f32x4*>(w.bqkv + c * 256 + cq + 8 * q);
+    for (int q = 0; q < 4; ++q) (c < 2 ? qb[c][q] : kp[q]) = qkv_bias_quad<H3>(w.bqkv, vt, c, r0 + (lane & 31), cq + 8 * q);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     acc_zero(tile[c]);
@@ -146,6 +145,7 @@ __device__ __forceinline__ void ffn_qkv_body(float* bufX, float* bufA, float* bu
       rb_gemm<1, 1, kG256, kPF, QkvStoreSide, false>(bufA, kLda, seg, 0, nseg, 0, ring, tile[c],
                                                      QkvStoreSide{tile[1][0][0], qrow ? qrow + 256 : nullptr, qb[1]});
     }
+    if (c == 0) qkv_kpos_add<H3>(qb[1], kp, vt);  // (K's bias is first read by the V unit's side stores)
     PPASR_TS(12 + c);
   }
   if constexpr (H3) h3_note(qk_bad);
@@ -447,7 +447,7 @@ constexpr int kPLd = 68;                       // private score-tile row stride:
 constexpr int kPTile = 32 * kPLd;              // floats per wave
 constexpr int kFusedAttnFloats = kWaves * kPTile + kWaves * 64 + kRows * kLda;
 static_assert(2 * kRows * kLda <= kWaves * kPTile + kWaves * 64, "bufX/bufA alias the attention scratch");
-static_assert(kRows * kLda + 128 + 4 * kPTile <= kWaves * kPTile, "Q'_v (fp16 x3: its planes, 512 B longer) and the four merge tiles fit in front of Stat");
+static_assert(kRows * kLda + 128 + 4 * kPTile <= kWaves * kPTile, "the d rows (fp16 x3: the Q'_v planes, 512 B longer) and the four merge tiles fit in front of Stat");
 static_assert(kH3TileBytes <= kRows * kLda * 4 + 512, "fp16 x3: the Q'_u planes at bufC run 512 B past it (the launch asks for them)");
 static_assert(kRows * kLda * 4 + kH3TileBytes <= kWaves * kPTile * 4, "fp16 x3: operand planes at bufA stay in front of Stat");
 static_assert(kFusedAttnFloats * 4 <= 160 * 1024, "LDS budget");
@@ -456,7 +456,7 @@ template <bool H3>
 __device__ __forceinline__ void attn_out_glu_body(const AttnArgs& a, int B, const float* __restrict__ x1, float* __restrict__ x2,
                                                   float* __restrict__ g, const LayerW& w) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* Ps = smem;                          // [32][260] Q'_v = q + pos_bias_v, then 4 merge tiles [head][32][68]
+  float* Ps = smem;                          // fp32: [4][kDRow] d rows, fp16 x3: [32][260] Q'_v = q + pos_bias_v; then 4 merge tiles [head][32][68]
   float* Stat = Ps + kWaves * kPTile;        // [8 waves][2][32]: running max, running sum of each wave's key half
   float* bufC = Stat + kWaves * 64;          // [32][260] Q'_u = q + pos_bias_u during the key loop, then the context rows
   float* bufX = smem;                        // out phase (aliases the tiles)
@@ -495,7 +495,7 @@ __device__ __forceinline__ void attn_out_glu_body(const AttnArgs& a, int B, cons
   const f32x4* seg_val = w.pw1 + (size_t)wave * kTs256;
   const f32x4* seg_gate = w.pw1 + (size_t)(8 + wave) * kTs256;
   const int hh = lane >> 5, l31 = lane & 31;
-  constexpr int NG = 16, PF = 4;
+  constexpr int NG = H3 ? 16 : 8;  // fp32: 64 wide -- the positional half is folded into the keys (AttnArgs::dtab, phases.h)
   PPASR_TS(32);
   PPASR_WG_TS(512 + 0);
 
@@ -523,24 +523,21 @@ __device__ __forceinline__ void attn_out_glu_body(const AttnArgs& a, int B, cons
                                rs_v = wstream_rsrc(a.vt + ((size_t)(2 * h) * (a.vt_stride >> 3) + ((mrow0 - shift) >> 3)) * 256);
   const int voff_v = lane * 16;
   const int kstride_b = a.k_stride * 4, pstride_b = pstride * kD * 4;
-  // byte offsets of this lane's two keys (tile 0 / 1) of the sub-block at u0, in K and in the positional table
+  // byte offsets of this lane's two keys (tile 0 / 1) of the sub-block at u0, in K and (fp16 x3) in the positional table
   int vk[2], vp[2];
   auto key_offsets = [&](int u0) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int key = min(max(u0 - shift + 32 * t + l31, 0), kv_end - 1);  // out-of-range keys are masked afterwards
       vk[t] = key * kstride_b + 16 * hh;
-      vp[t] = key * pstride_b + 16 * hh;
+      if constexpr (H3) vp[t] = key * pstride_b + 16 * hh;
     }
-  };
-  // K' fragment of k-group gk (features 8gk + 4hh .. +3 of [k | p]) of this lane's key of tile t
-  auto kfrag = [&](int t, int gk) -> f32x4 {
-    return gk < 8 ? wstream_load(rs_k, vk[t], gk * 32) : wstream_load(rs_p, vp[t], (gk - 8) * 32);
   };
   // K' operands in bursts of 4 k-groups (= one whole 128-byte line of each key row: a lane's 16-byte pieces of 4
   // consecutive k-groups are requested back to back, so the line is fetched from L2 once; one k-group at a time the
   // 8 waves push 64 KiB through the 32 KiB L1 between two uses of a line and every line is fetched 4 times), double
-  // buffered: super-group sg + 1 is in flight while sg feeds the MFMAs
+  // buffered: super-group sg + 1 is in flight while sg feeds the MFMAs.  fp32: k-group gk = features 8gk + 4hh .. +3 of k + p,
+  // two super-groups per sub-block (requesting both in prime_k took 28 more VGPRs and was no faster: NOTES §19)
   // (fp16 x3: FOUR buffers -- a super-group's MFMAs are 0.2 us and no longer cover the next one's L2 round trip, so all four
   //  planes of a sub-block are in flight at once; the values' ring below is not live yet while they are)
   constexpr int NKB = H3 ? 4 : 2;
@@ -555,8 +552,8 @@ __device__ __forceinline__ void attn_out_glu_body(const AttnArgs& a, int B, cons
         kq[buf][i][0] = sg < 2 ? wstream_load(rs_k, vk[0], soff) : wstream_load(rs_p, vp[0], soff);
         kq[buf][i][1] = sg < 2 ? wstream_load(rs_k, vk[1], soff) : wstream_load(rs_p, vp[1], soff);
       } else {
-        kq[buf][i][0] = kfrag(0, 4 * sg + i);
-        kq[buf][i][1] = kfrag(1, 4 * sg + i);
+        kq[buf][i][0] = wstream_load(rs_k, vk[0], (4 * sg + i) * 32);
+        kq[buf][i][1] = wstream_load(rs_k, vk[1], (4 * sg + i) * 32);
       }
     }
   };
@@ -566,9 +563,12 @@ __device__ __forceinline__ void attn_out_glu_body(const AttnArgs& a, int B, cons
     if constexpr (H3) load_sg(1, 1);
   };
 
-  // ---- Q' = [q + pos_bias_u | q + pos_bias_v] of the block's 32 query rows -> LDS (bufC / QV); the key loop reads
-  // its B-operand fragment Q'[row l31][8 gk + 4 hh .. +3] from there, one ds_read_b128 per k-group ----
+  // ---- Q' = q + pos_bias_u (fp16 x3: [q + pos_bias_u | q + pos_bias_v]) of the block's 32 query rows -> LDS (bufC / QV); the
+  // key loop reads its B-operand fragment Q'[row l31][8 gk + 4 hh .. +3] from there, one ds_read_b128 per k-group ----
+  const float* __restrict__ dtab = a.dtab ? a.dtab + (size_t)h * a.dtab_len + a.pos0 : nullptr;  // (fp32: d of the head's key 0)
   {
+    // fp32: d of the head's shifted keys -> Ps (up to kDRow of them; waves 2h, 2h + 1 stage head h's row)
+    if constexpr (!H3) attn_stage_d(Ps + h * kDRow, dtab, khalf * 64 + lane, shift, U <= kDRow ? U : 0, pstride);
     const f32x4 pu = *reinterpret_cast<const f32x4*>(a.pos_u + 4 * lane), pv = *reinterpret_cast<const f32x4*>(a.pos_v + 4 * lane);
     bool bad = false;
     for (int row = wave; row < kRows; row += kWaves) {
@@ -586,17 +586,13 @@ __device__ __forceinline__ void attn_out_glu_body(const AttnArgs& a, int B, cons
         *reinterpret_cast<f16x4*>(pv_pl + kPlaneH) = lo;
       } else {
         *reinterpret_cast<f32x4*>(bufC + row * kLda + 4 * lane) = v + pu;
-        *reinterpret_cast<f32x4*>(QV + row * kLda + 4 * lane) = v + pv;
       }
     }
     if constexpr (H3) h3_note(bad);
     __syncthreads();
   }
   const float* qfrag_u = bufC + l31 * kLda + h * 64 + 4 * hh;
-  const float* qfrag_v = QV + l31 * kLda + h * 64 + 4 * hh;
-  auto qfrag = [&](int gk) -> f32x4 {
-    return *reinterpret_cast<const f32x4*>(gk < 8 ? qfrag_u + 8 * gk : qfrag_v + 8 * (gk - 8));
-  };
+  auto qfrag = [&](int gk) -> f32x4 { return *reinterpret_cast<const f32x4*>(qfrag_u + 8 * gk); };  // (fp32 route)
   PPASR_TS(33);
   // (requesting these before the Q' staging, or the V operands before the score MFMAs, measured no better: NOTES §4)
   if (khalf * 128 < U) prime_k(khalf * 128);
@@ -633,10 +629,14 @@ __device__ __forceinline__ void attn_out_glu_body(const AttnArgs& a, int B, cons
       };
       // ---- S^T = K' Q'^T for 64 keys (two 32-key tiles, two independent accumulator chains) ----
       f32x16 acc_s[2];
+      if constexpr (H3) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc_s[t][r] = 0.f;
+          for (int r = 0; r < 16; ++r) acc_s[t][r] = 0.f;
+      } else {  // S = Q' K'^T + d: start from d of each register's key (phases.h)
+        attn_score_init(acc_s, U <= kDRow ? Ps + h * kDRow + u0 + 4 * hh : nullptr, dtab, u0 - shift + 4 * hh, kv_end, pstride);
+      }
       if constexpr (H3) {
         // three fp16 products per 16-wide k step (h3.h): with a HIGH plane of K' in registers K'hi Q'lo + K'hi Q'hi, with
         // the LOW plane K'lo Q'hi -- 48 v_mfma_f32_32x32x16_f16 per 64 keys where the fp32 route issues 128 32x32x2
@@ -664,13 +664,13 @@ __device__ __forceinline__ void attn_out_glu_body(const AttnArgs& a, int B, cons
       } else {
         f32x4 q_cur = qfrag(0), q_nxt = q_cur;
 #pragma unroll
-        for (int sg = 0; sg < 4; ++sg) {
-          if (sg + 1 < 4) load_sg((sg + 1) & 1, sg + 1);
+        for (int sg = 0; sg < 2; ++sg) {
+          if (sg == 0) load_sg(1, 1);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int gk = 4 * sg + i;
             if (gk + 1 < NG) q_nxt = qfrag(gk + 1);
-            const f32x4 k0 = kq[sg & 1][i][0], k1 = kq[sg & 1][i][1];
+            const f32x4 k0 = kq[sg][i][0], k1 = kq[sg][i][1];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               acc_s[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(k0[j], q_cur[j], acc_s[0], 0, 0, 0);

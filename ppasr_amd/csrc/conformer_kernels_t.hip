@@ -43,7 +43,7 @@ __device__ __forceinline__ void ffn_qkv_body_t(float* bufX, float* bufA, float* 
   rbt_layernorm<R>(bufX, bufA, w.ln_mha_g, w.ln_mha_b, 1e-5f);
   __syncthreads();
   PPASR_TS(11);
-  qkv_phase_t<R>(bufA, qkv, w.wqkv, w.bqkv, r0, valid, ring, vt.vt, vt.stride);
+  qkv_phase_t<R>(bufA, qkv, w.wqkv, w.bqkv, r0, valid, ring, vt.vt, vt.stride, vt.kpos, vt.kpos_stride, vt.Ti);
   PPASR_TS(14);
 }
 

@@ -566,4 +566,19 @@ hipError_t configure_front_kernels() {
   return hipSuccess;
 }
 
+// create-time: the query-independent positional term of the fused attention's scores (conformer_kernels.h LayerW::dtab), from
+// the fp32 table the QKV stage adds to the keys; thread = (head, position), summed in double and rounded once
+__global__ __launch_bounds__(256) void k_pos_dtab(const float* __restrict__ ptab, const float* __restrict__ pos_u,
+                                                  const float* __restrict__ pos_v, float* __restrict__ dtab, int max_len) {
+  const int t = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
+  if (t >= max_len) return;
+  double acc = 0.0;
+  for (int c = 0; c < 64; ++c)
+    acc += ((double)pos_v[64 * h + c] - (double)pos_u[64 * h + c]) * (double)ptab[(size_t)t * 256 + 64 * h + c];
+  dtab[(size_t)h * max_len + t] = (float)acc;
+}
+void launch_pos_dtab(const float* ptab, const float* pos_u, const float* pos_v, float* dtab, int max_len, hipStream_t st) {
+  PPASR_LAUNCH(k_pos_dtab, dim3((max_len + 255) / 256, 4), dim3(256), 0, st, ptab, pos_u, pos_v, dtab, max_len);
+}
+
 }  // namespace ppasr

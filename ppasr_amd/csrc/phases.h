@@ -2,6 +2,7 @@
 // Efficient-Conformer): FFN with LDS-resident hidden chunks, residual epilogue, causal depthwise
 // conv, pad-row predicate.  See rowblock.h for the execution model.
 #pragma once
+#include "conformer_kernels.h"
 #include "rowblock.h"
 
 namespace ppasr {
@@ -248,6 +249,63 @@ __device__ __forceinline__ void dwconv_ln_phase(const float* __restrict__ g, flo
   ln_rows_inreg<true, RW>(out, gam, bet, ln_eps);
 #pragma unroll
   for (int i = 0; i < RW; ++i) *reinterpret_cast<f32x4*>(bufA + (q0 + i) * kLda + 4 * lane) = out[i];
+}
+
+// =====================================================================================
+// The positional fold of the fp32 fused attention (conformer_kernels.h AttnArgs::dtab / VtOut::kpos):
+// (q + u) . k + (q + v) . p = (q + u) . (k + p) + d,  d = (v - u) . p
+// =====================================================================================
+// QKV stage of the 8-wave kernels, columns col .. col + 3 for row m of the batch: c = 0 / 1 the bias quad of Q / K, c = 2 the
+// quad of the frame's positional row (frame = m mod Ti) that the fold adds to K -- requested with the biases, added to K's
+// bias quads one GEMM unit later (qkv_kpos_add), so that the store path is the same and nothing waits for the rows' L2 trip.
+// Fold off: zeros that are never added -- the stage writes what it wrote before, bit for bit
+template <bool H3>
+__device__ __forceinline__ f32x4 qkv_bias_quad(const float* __restrict__ bqkv, const VtOut& vt, int c, int m, int col) {
+  if (c < 2) return *reinterpret_cast<const f32x4*>(bqkv + c * 256 + col);
+  if constexpr (!H3) {
+    if (vt.kpos) return *reinterpret_cast<const f32x4*>(vt.kpos + (size_t)(m - m / vt.Ti * vt.Ti) * vt.kpos_stride + col);
+  }
+  return f32x4{0.f, 0.f, 0.f, 0.f};
+}
+template <bool H3>
+__device__ __forceinline__ void qkv_kpos_add(f32x4 (&bk)[4], const f32x4 (&kp)[4], const VtOut& vt) {
+  if constexpr (!H3) {
+    if (vt.kpos) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bk[q] += kp[q];
+    }
+  }
+}
+// shifted keys per head whose d values k_attn_out_glu stages in LDS, in the space Q'_v had (longer utterances read d from L2)
+constexpr int kDRow = 2048;
+static_assert(4 * kDRow <= kRows * kLda, "the four heads' d rows fit in front of the merge tiles");
+// row[u] = d of shifted key u = key + shift for u in [0, U rounded up to 64), 0 for the masked ones at both ends; the head's
+// 128 threads (t128) stage its row.  dtab: the head's table row at key 0 (nullptr: no positional term), U = 0: nothing
+__device__ __forceinline__ void attn_stage_d(float* row, const float* __restrict__ dtab, int t128, int shift, int U, int pstride) {
+  for (int u = t128; u < ((U + 63) & ~63); u += 128)
+    row[u] = (dtab && u >= shift && u < U) ? dtab[(size_t)(u - shift) * pstride] : 0.f;
+}
+// the score accumulators of a 64-key sub-block start from d of each register's key (S^T tile: quad i of tile t = keys
+// 32t + 8i + 4hh .. +3 of the sub-block, the same for every query lane): broadcast ds_read_b128 from the staged row
+// (dl = row + u0 + 4hh), no VALU work; dl == nullptr: from the table, keys clamped to [0, kv_end) like the key rows
+// (key0 = u0 - shift + 4hh).  Masked keys get finite values here and -inf afterwards.
+__device__ __forceinline__ void attn_score_init(f32x16 (&acc_s)[2], const float* dl, const float* __restrict__ dtab, int key0,
+                                                int kv_end, int pstride) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f32x4 dq;
+      if (dl) {
+        dq = *reinterpret_cast<const f32x4*>(dl + 32 * t + 8 * i);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          dq[j] = dtab ? dtab[(size_t)min(max(key0 + 32 * t + 8 * i + j, 0), kv_end - 1) * pstride] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc_s[t][4 * i + j] = dq[j];
+    }
 }
 
 }  // namespace ppasr

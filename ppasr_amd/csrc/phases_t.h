@@ -195,10 +195,12 @@ struct QuadStoreSide {
 // vt != nullptr (16-wave form only): the values go to vt in the fragment order of the fused attention kernel instead
 // (conformer_kernels.h VtOut: [32-column slab][row octet][lane = column + 32 (row quad)][4 rows]) -- the V unit then runs
 // in the plain orientation, where a lane's register quad IS four consecutive rows of one column = one 16-byte piece.
+// kpos != nullptr: the K third holds k + the positional row of the frame (VtOut::kpos), added through K's bias quads.
 template <int R>
 __device__ __forceinline__ void qkv_phase_t(const float* bufX, float* __restrict__ qkv, const f32x4* __restrict__ wqkv,
                                             const float* __restrict__ bqkv, int r0, int valid, typename RBT<R>::Ring& ring,
-                                            float* __restrict__ vt = nullptr, int vt_stride = 0) {
+                                            float* __restrict__ vt = nullptr, int vt_stride = 0,
+                                            const float* __restrict__ kpos = nullptr, int kpos_stride = 0, int Ti = 1) {
   using T = RBT<R>;
   const LaneT<R> L;
   float* q0 = qkv + (size_t)(r0 + L.row(0)) * 768 + L.col(0);
@@ -208,6 +210,13 @@ __device__ __forceinline__ void qkv_phase_t(const float* bufX, float* __restrict
   for (int c = 0; c < 3; ++c)
 #pragma unroll
     for (int q = 0; q < T::NQ; ++q) qb[c][q] = *reinterpret_cast<const f32x4*>(bqkv + c * 256 + L.col(q));
+  if (kpos) {  // fused fp32 attention: K + the frame's positional row (VtOut::kpos; row m of the batch = frame m mod Ti)
+#pragma unroll
+    for (int q = 0; q < T::NQ; ++q) {
+      const int m = r0 + L.row(q);
+      qb[1][q] += *reinterpret_cast<const f32x4*>(kpos + (size_t)(m - m / Ti * Ti) * kpos_stride + L.col(q));
+    }
+  }
   typename T::Acc tile[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
