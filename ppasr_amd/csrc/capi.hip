@@ -947,7 +947,8 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
     const int S = r16 ? 1 : ffn_split_for(h, Mi);
     // full grid: the same 32-row blocks on 16 waves (k_*_t<kW16>: drop-in for k_ffn_qkv / k_out_glu / k_conv_ffn)
     const bool w16 = rows == kW16 && S == 1;
-    const PadSkip psb = S == 1 ? with_table(ps, Ti, r16 ? 16 : 32) : ps;  // (for the kernels of this layer's block size)
+    const int form = r16 ? 16 : w16 ? kW16 : 32;  // the layer's block form (rbt.h), as the stage launchers take it
+    const PadSkip psb = S == 1 ? with_table(ps, Ti, form_rows(form)) : ps;  // (for the kernels of this layer's block size)
     // feed-forward GEMMs on the fp16 x3 route (ppasr_set_gemm_mode): the 8-wave 32-row kernels only
     const bool h3 = h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty() && !r16 && !w16 && S == 1;
     // ... the split route of under-filled launches likewise (its kernels' units; h3 view for the weights only -- the
@@ -979,12 +980,8 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
                            xb, Mi, n_chunks, S, st, ps, false, h3s);
           launch_ln_qkv(xb, qkv, Lk, Mi, st, ps, nullptr, nullptr, h3s);
         });
-      } else if (r16) {
-        timed(3, [&] { launch_ffn_qkv_16(xa, xb, qkv, L, Mi, n_chunks, st, psb); });
-      } else if (w16) {
-        timed(3, [&] { launch_ffn_qkv_w16(xa, xb, qkv, L, Mi, n_chunks, st, psb, vt_for(fuse_attn, false, i)); });
       } else {
-        timed(3, [&] { launch_ffn_qkv(xa, xb, qkv, Lk, Mi, n_chunks, st, psb, vt_for(fuse_attn, h3, i), h3); });
+        timed(3, [&] { launch_ffn_qkv(xa, xb, qkv, Lk, Mi, n_chunks, st, psb, vt_for(fuse_attn, h3, i), h3, form); });
       }
     }
     s1_done = false;
@@ -1007,9 +1004,9 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
       tap(ctx, (size_t)Mi * kD);
       // (under-filled launch: pointwise_conv1 + GLU as its own two-column-half launch; the LayerNorm'd rows pass through
       //  xa, which is free between this layer's S1 and its output)
-      if (r16) timed(5, [&] { launch_out_glu_16(ctx, xb, xc, g, L, lens, Mi, Ti, mul, st, psb); });
-      else if (w16) timed(5, [&] { launch_out_glu_w16(ctx, xb, xc, g, L, lens, Mi, Ti, mul, st, psb); });
-      else timed(5, [&] { launch_out_glu(ctx, xb, xc, g, nullptr, h3s ? Lk : L, lens, Mi, Ti, mul, st, psb, S > 1 ? xa : nullptr, h3s); });
+      timed(5, [&] {
+        launch_out_glu(ctx, xb, xc, g, nullptr, h3s ? Lk : L, lens, Mi, Ti, mul, st, psb, S > 1 ? xa : nullptr, h3s, nullptr, form);
+      });
     }
     tap(xc, (size_t)Mi * kD);
     tap(g, (size_t)Mi * kD);
@@ -1041,16 +1038,8 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
       const LayerW* next = (i + 1 < h->desc.num_blocks) ? (h3 ? &h->layers_h3[i + 1] : &h->layers[i + 1]) : nullptr;
       timed(next ? 8 : 6, [&] {
         // with the next layer's S1 fused in, the layer output itself is only read by the debug taps: skip its store
-        if (r16)
-          launch_conv_ffn_16(g, xc, next ? nullptr : xa, L, lens, Mi, Ti, n_chunks, h->layer_ks[i], mul, next, xb, qkv, st,
-                             h->desc.causal != 0, psb);
-        else if (w16)
-          launch_conv_ffn_w16(g, xc, next ? nullptr : xa, L, lens, Mi, Ti, n_chunks, h->layer_ks[i], mul, next, xb, qkv, st,
-                              h->desc.causal != 0, psb, vt_for(next && fusable(i + 1), false, i + 1));
-        else
-          launch_conv_ffn(g, nullptr, xc, (next && !h->taps) ? nullptr : xa, Lk, lens, Mi, Ti, n_chunks, h->layer_ks[i], mul,
-                          next, xb, qkv, st, h->desc.causal != 0, psb,
-                          vt_for(next && fusable(i + 1), h3, next ? i + 1 : i), h3);
+        launch_conv_ffn(g, nullptr, xc, (next && !h->taps) ? nullptr : xa, Lk, lens, Mi, Ti, n_chunks, h->layer_ks[i], mul, next,
+                        xb, qkv, st, h->desc.causal != 0, psb, vt_for(next && fusable(i + 1), h3, next ? i + 1 : i), h3, form);
       });
       s1_done = next != nullptr;
     }

@@ -368,7 +368,7 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
   const int rowsH = h->taps ? 32 : row_block_for(h, B, Tr, 8, psH.slack, skip);
   PadSkip psF_rb = psF, psH_rb = psH;
   if (skip && tile_tab && block_tables_enabled()) {
-    const int RF = rowsF == 16 ? 16 : 32, RH = rowsH == 16 ? 16 : 32;
+    const int RF = form_rows(rowsF), RH = form_rows(rowsH);
     const size_t nF = 1 + ((size_t)M + RF - 1) / RF, nH = 1 + ((size_t)B * Tr + RH - 1) / RH;
     const size_t o1 = ((size_t)B + 2 + 15) / 16 * 16, o2 = o1 + (nF + 15) / 16 * 16;
     if (o2 + nH <= 2 * (((size_t)M + 63) / 64 * 64)) {

@@ -135,11 +135,8 @@ void launch_conv2_quad(const float* y1, const FrontW& fw, float* y2, int B, int 
                        const PadSkip& ps_frames, int* tile_scratch);
 hipError_t configure_front_fused_kernels();
 
-// conformer_kernels_t.hip: the layer kernels on 16-row blocks (under-filled launches; values row-major in qkv)
-void launch_ffn_qkv_16(const float* x_in, float* x1, float* qkv, const LayerW& w, int M, int n_chunks, hipStream_t st,
-                       const PadSkip& ps);
-void launch_out_glu_16(const float* ctx, const float* x1, float* x2, float* g, const LayerW& w, const int64_t* lens, int M,
-                       int Tp, int mask_mul, hipStream_t st, const PadSkip& ps);
+// conformer_kernels_t.hip: launches of the 16-row forms that are no form of one of the three layer stages (split route of a
+// streaming chunk, Squeezeformer's weight views)
 void launch_out_glu_split_16(const float* ctx, const float* x1, float* x2, float* g, float* xhat, const LayerW& w,
                              const int64_t* lens, int M, int Tp, int mask_mul, hipStream_t st, const PadSkip& ps,
                              float* hist = nullptr, int lo = 0);  // split route, <= 16 rows; hist: see HistMove
@@ -151,19 +148,24 @@ void launch_oproj_ln_16(const float* ctx, const float* x1, float* x2_sink, float
 void launch_pw1_glu_cols_16(const float* x, float* g, const LayerW& w, int M, hipStream_t st, float* hist = nullptr, int lo = 0,
                             const float* hist_scale = nullptr, const float* hist_bias = nullptr, const PadSkip& ps = PadSkip{},
                             const int64_t* lens = nullptr, int Tp = 1, int mask_mul = 1);
-bool conv_ffn_16_supported(int ksize, int Tp);
-void launch_conv_ffn_16(const float* g, const float* x2, float* x_out, const LayerW& w, const int64_t* lens, int M, int Tp,
-                        int n_chunks, int ksize, int mask_mul, const LayerW* next, float* x1_next, float* qkv_next,
-                        hipStream_t st, bool causal, const PadSkip& ps);
-// ... and on 32 rows x 16 waves (full launches): drop-in for launch_ffn_qkv / launch_out_glu / launch_conv_ffn
-void launch_ffn_qkv_w16(const float* x_in, float* x1, float* qkv, const LayerW& w, int M, int n_chunks, hipStream_t st,
-                        const PadSkip& ps, VtOut vt);
-void launch_out_glu_w16(const float* ctx, const float* x1, float* x2, float* g, const LayerW& w, const int64_t* lens, int M,
-                        int Tp, int mask_mul, hipStream_t st, const PadSkip& ps);
-void launch_conv_ffn_w16(const float* g, const float* x2, float* x_out, const LayerW& w, const int64_t* lens, int M, int Tp,
-                         int n_chunks, int ksize, int mask_mul, const LayerW* next, float* x1_next, float* qkv_next,
-                         hipStream_t st, bool causal, const PadSkip& ps, VtOut vt_next);
+bool conv_ffn_16_supported(int ksize, int Tp);  // the conv stage takes rows = 16 or kW16 (launch_conv_ffn)
 hipError_t configure_conformer_t_kernels();
+
+// ---- NOT FOR CALLERS: the layer stages on the forms R = 16 and kW16, whose kernels live in conformer_kernels_t.hip (no
+// -fgpu-rdc: a kernel is launched from its own translation unit).  launch_ffn_qkv / launch_out_glu / launch_conv_ffn
+// below pick the form and hold its rules; call those ----
+template <int R>
+struct LayerStagesT {
+  static hipError_t configure();
+  static void ffn_qkv(const float* x_in, float* x1, float* qkv, const LayerW& w, int M, int n_chunks, hipStream_t st,
+                      const PadSkip& ps, VtOut vt);
+  static void out_glu(const float* ctx, const float* x1, float* x2, float* g, const LayerW& w, const int64_t* lens, int M,
+                      int Tp, int mask_mul, hipStream_t st, const PadSkip& ps, float* xhat_out = nullptr,
+                      int stop_after_ln = 0);
+  static void conv_ffn(const float* g, const float* x2, float* x_out, const LayerW& w, const int64_t* lens, int M, int Tp,
+                       int n_chunks, int ksize, int mask_mul, const LayerW* next, float* x1_next, float* qkv_next,
+                       hipStream_t st, bool causal, const PadSkip& ps, VtOut vt_next);
+};
 
 // ---- launchers (all asynchronous on `st`) ----
 void launch_posproj(const float* pe, const float* wpos /*[d][d] in,out*/, const float* bpos_or_null, float* ptab,
@@ -197,9 +199,12 @@ void launch_embed(const float* y2, const FrontW& fw, float* x0, int M, int K, fl
                   const f32x4* w_h3 = nullptr);  // w_h3: fw.embed_w re-packed for the fp16 x3 route (full launches take it)
 void launch_dense(const float* a, int lda, const f32x4* w, const float* bias, float* out, int M, int K, int n_cols_padded,
                   int ldc, int n_valid, hipStream_t st, float scale = 1.0f, float* part = nullptr, size_t part_floats = 0);  // out = (a W + bias) * scale
+// The three layer stages (S1, S3, conv module + FFN) take the block form as `rows`: 32, 16 or kW16, as row_block_for and
+// launch_sq_mid / _tail spell it.  16-row blocks write the values row-major: vt / vt_next are dropped there.  h3, g_hist,
+// xhat_out, split_xhat and hm belong to the 8-wave 32-row form: another form with one of them aborts.
 // h3: the feed-forward modules on the fp16 x3 route (csrc/h3.h); w (and *next) must then be the layers' h3 views
 void launch_ffn_qkv(const float* x_in, float* x1, float* qkv, const LayerW& w, int M, int n_chunks, hipStream_t st,
-                    const PadSkip& ps = PadSkip{}, VtOut vt = VtOut{}, bool h3 = false);
+                    const PadSkip& ps = PadSkip{}, VtOut vt = VtOut{}, bool h3 = false, int rows = 32);
 // fp32 fragment-packed weight (pack_b: n_tiles x G k-groups x 1 KiB) -> the fp16 x3 packing of csrc/h3.h, same size
 void launch_repack_h3(const f32x4* src, f32x4* dst, int n_tiles, int G, unsigned int* ovf, hipStream_t st);  // ovf: device word counting weights beyond the range
 inline bool conv_ffn_h3_supported(int ksize) { return ksize == 15 || ksize == 7; }
@@ -225,12 +230,12 @@ void launch_out_glu(const float* ctx, const float* x1, float* x2, float* g, floa
                     const int64_t* lens, int M, int Tp, int mask_mul, hipStream_t st, const PadSkip& ps = PadSkip{},
                     float* split_xhat = nullptr,  // != nullptr: two launches (under-filled grids), M*256 floats of scratch
                     bool h3 = false,              // the units on the fp16 x3 route (w: the layer's h3 view)
-                    HistMove* hm = nullptr);
+                    HistMove* hm = nullptr, int rows = 32);
 // next != nullptr: also run the following layer's S1 (writes x1_next, qkv_next) in the same launch
 void launch_conv_ffn(const float* g, const float* g_hist, const float* x2, float* x_out, const LayerW& w,
                      const int64_t* lens, int M, int Tp, int n_chunks, int ksize, int mask_mul, const LayerW* next,
                      float* x1_next, float* qkv_next, hipStream_t st, bool causal = true, const PadSkip& ps = PadSkip{},
-                     VtOut vt_next = VtOut{}, bool h3 = false);
+                     VtOut vt_next = VtOut{}, bool h3 = false, int rows = 32);
 // ---- split route for under-filled grids (see split_route_kernels.hip): the layer tail cut at its FFNs, each FFN's hidden
 // dimension split over S (1, 2, 4 or 8; a divisor of n_chunks) workgroups per row block ----
 void launch_conv_pre(const float* g, const float* g_hist, const float* x2, float* x3, const LayerW& w, const int64_t* lens,

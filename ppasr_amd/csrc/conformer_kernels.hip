@@ -257,9 +257,21 @@ __global__ __launch_bounds__(kThreads) void k_ffn_qkv_h3(const float* __restrict
   rb_load_rows(bufX, kLda, x_in + (size_t)r0 * kD, kRows, valid);
   ffn_qkv_body<true>(bufX, bufA, bufH, x1, qkv, w, r0, valid, n_chunks, ring, vt);
 }
+// The block form of a stage launch (launch_ffn_qkv / launch_out_glu / launch_conv_ffn): 32, 16 or kW16.  only32: the call
+// carries an argument that only the 8-wave 32-row kernels take.  A caller that breaks the rule is wrong everywhere: abort,
+// as launch_attention does.
+static void check_form(const char* stage, int rows, bool only32) {
+  if (rows == 32 || ((rows == 16 || rows == kW16) && !only32)) return;
+  fprintf(stderr, "ppasr_hip: %s refused: row-block form %d%s\n", stage, rows,
+          only32 ? " with h3, g_hist, xhat_out, split_xhat or hm (8-wave 32-row form only)" : " (32, 16 or kW16)");
+  abort();
+}
 constexpr size_t kLdsFfnQkv = 4 * kRows * kLda * sizeof(float);
 void launch_ffn_qkv(const float* x_in, float* x1, float* qkv, const LayerW& w, int M, int n_chunks, hipStream_t st,
-                    const PadSkip& ps, VtOut vt, bool h3) {
+                    const PadSkip& ps, VtOut vt, bool h3, int rows) {
+  check_form("launch_ffn_qkv", rows, h3);
+  if (rows == 16) return LayerStagesT<16>::ffn_qkv(x_in, x1, qkv, w, M, n_chunks, st, ps, VtOut{});  // (values row-major in qkv)
+  if (rows == kW16) return LayerStagesT<kW16>::ffn_qkv(x_in, x1, qkv, w, M, n_chunks, st, ps, vt);
   if (h3) {
     PPASR_LAUNCH(k_ffn_qkv_h3, dim3((M + kRows - 1) / kRows), dim3(kThreads), kLdsFfnQkv + kH3ExtraLds, st, x_in, x1, qkv, w,
                  M, n_chunks, ps, vt);
@@ -401,7 +413,10 @@ constexpr size_t kLdsOutGlu = 2 * kRows * kLda * sizeof(float);
 constexpr size_t kLdsPw1Cols = (kRows * kLda + kRows * 132) * sizeof(float);
 void launch_out_glu(const float* ctx, const float* x1, float* x2, float* g, float* xhat_out, const LayerW& w,
                     const int64_t* lens, int M, int Tp, int mask_mul, hipStream_t st, const PadSkip& ps, float* split_xhat,
-                    bool h3, HistMove* hm) {
+                    bool h3, HistMove* hm, int rows) {
+  check_form("launch_out_glu", rows, h3 || xhat_out || split_xhat || hm);
+  if (rows == 16) return LayerStagesT<16>::out_glu(ctx, x1, x2, g, w, lens, M, Tp, mask_mul, st, ps);
+  if (rows == kW16) return LayerStagesT<kW16>::out_glu(ctx, x1, x2, g, w, lens, M, Tp, mask_mul, st, ps);
   // split_xhat != nullptr (under-filled launches): out-projection + LayerNorm in one launch (the LayerNorm'd rows go to
   // split_xhat), pointwise_conv1 + GLU in a second one with the columns over two workgroups per row block
   float* xh = xhat_out ? xhat_out : split_xhat;
@@ -1049,7 +1064,15 @@ __global__ __launch_bounds__(kThreads) void k_conv_ffn_h3(const float* __restric
 constexpr size_t kLdsConvFfn = 4 * kRows * kLda * sizeof(float);
 void launch_conv_ffn(const float* g, const float* g_hist, const float* x2, float* x_out, const LayerW& w,
                      const int64_t* lens, int M, int Tp, int n_chunks, int ksize, int mask_mul, const LayerW* next,
-                     float* x1_next, float* qkv_next, hipStream_t st, bool causal, const PadSkip& ps, VtOut vt_next, bool h3) {
+                     float* x1_next, float* qkv_next, hipStream_t st, bool causal, const PadSkip& ps, VtOut vt_next, bool h3,
+                     int rows) {
+  check_form("launch_conv_ffn", rows, h3 || g_hist);
+  if (rows == 16)  // (the next layer's values row-major in qkv_next)
+    return LayerStagesT<16>::conv_ffn(g, x2, x_out, w, lens, M, Tp, n_chunks, ksize, mask_mul, next, x1_next, qkv_next, st,
+                                      causal, ps, VtOut{});
+  if (rows == kW16)
+    return LayerStagesT<kW16>::conv_ffn(g, x2, x_out, w, lens, M, Tp, n_chunks, ksize, mask_mul, next, x1_next, qkv_next, st,
+                                        causal, ps, vt_next);
   dim3 grid((M + kRows - 1) / kRows);
   const int left_ctx = causal ? ksize - 1 : (ksize - 1) / 2;
   const LayerW& wn = next ? *next : w;

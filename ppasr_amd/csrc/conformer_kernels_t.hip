@@ -290,131 +290,96 @@ __global__ __launch_bounds__(RBT<R>::THREADS) void k_conv_ffn_t(const float* __r
   PPASR_TS(15);
 }
 
-constexpr size_t kLds16x4 = 4 * 16 * kLda * sizeof(float), kLds16x2 = 2 * 16 * kLda * sizeof(float);
-// one workgroup per CU (see lds16 in squeezeformer_kernels.hip)
-static size_t excl(size_t own) { return own < kLdsExclusive ? kLdsExclusive : own; }
+// ---- host side: everything once, the block form R (16 or kW16) as the template argument (LayerStagesT<R>,
+// conformer_kernels.h: called by launch_ffn_qkv / launch_out_glu / launch_conv_ffn, which pick the form) ----
+// excl: one workgroup per CU (see lds16 in squeezeformer_kernels.hip)
+constexpr size_t excl(size_t own) { return own < kLdsExclusive ? kLdsExclusive : own; }
+// dynamic LDS: S1 and the conv stage (which ends in S1) keep four row buffers, S3 two; launch and opt-in read the same constant
+template <int R>
+constexpr size_t kLdsStageT = excl(4 * RBT<R>::ROWS * kLda * sizeof(float));
+template <int R>
+constexpr size_t kLdsOutGluT = excl(2 * RBT<R>::ROWS * kLda * sizeof(float));
+constexpr size_t kLdsPw1Cols16 = excl((16 * kLda + 16 * 132) * sizeof(float));
+template <int R>
+static dim3 grid_t(int M) { return dim3((M + RBT<R>::ROWS - 1) / RBT<R>::ROWS); }
 
-void launch_ffn_qkv_16(const float* x_in, float* x1, float* qkv, const LayerW& w, int M, int n_chunks, hipStream_t st,
-                       const PadSkip& ps) {
-  PPASR_LAUNCH(k_ffn_qkv_t<16>, dim3((M + 15) / 16), dim3(kThreads), excl(kLds16x4), st, x_in, x1, qkv, w, M, n_chunks, ps,
-               VtOut{});
+// opt-in to the dynamic LDS of every kernel of the form
+template <int R>
+hipError_t LayerStagesT<R>::configure() {
+  hipError_t e;
+#define SET_LDS(fn, n)                                                                                              \
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(n)); \
+  if (e != hipSuccess) return e;
+  SET_LDS(k_ffn_qkv_t<R>, kLdsStageT<R>);
+  SET_LDS(k_out_glu_t<R>, kLdsOutGluT<R>);
+  if constexpr (R == 16) { SET_LDS(k_pw1_glu_cols_t<16>, kLdsPw1Cols16) }
+  SET_LDS((k_conv_ffn_t<R, 15, true>), kLdsStageT<R>);
+  SET_LDS((k_conv_ffn_t<R, 15, false>), kLdsStageT<R>);
+  SET_LDS((k_conv_ffn_t<R, 31, true>), kLdsStageT<R>);
+  SET_LDS((k_conv_ffn_t<R, 31, false>), kLdsStageT<R>);
+  SET_LDS((k_conv_ffn_t<R, 7, true>), kLdsStageT<R>);
+  SET_LDS((k_conv_ffn_t<R, 7, false>), kLdsStageT<R>);
+#undef SET_LDS
+  return hipSuccess;
 }
-void launch_out_glu_16(const float* ctx, const float* x1, float* x2, float* g, const LayerW& w, const int64_t* lens, int M,
-                       int Tp, int mask_mul, hipStream_t st, const PadSkip& ps) {
-  PPASR_LAUNCH(k_out_glu_t<16>, dim3((M + 15) / 16), dim3(kThreads), excl(kLds16x2), st, ctx, x1, x2, g, w, lens, M, Tp,
-               mask_mul, ps, (float*)nullptr, 0);
+template <int R>
+void LayerStagesT<R>::ffn_qkv(const float* x_in, float* x1, float* qkv, const LayerW& w, int M, int n_chunks, hipStream_t st,
+                              const PadSkip& ps, VtOut vt) {
+  PPASR_LAUNCH(k_ffn_qkv_t<R>, grid_t<R>(M), dim3(RBT<R>::THREADS), kLdsStageT<R>, st, x_in, x1, qkv, w, M, n_chunks, ps, vt);
 }
+template <int R>
+void LayerStagesT<R>::out_glu(const float* ctx, const float* x1, float* x2, float* g, const LayerW& w, const int64_t* lens,
+                              int M, int Tp, int mask_mul, hipStream_t st, const PadSkip& ps, float* xhat_out,
+                              int stop_after_ln) {
+  PPASR_LAUNCH(k_out_glu_t<R>, grid_t<R>(M), dim3(RBT<R>::THREADS), kLdsOutGluT<R>, st, ctx, x1, x2, g, w, lens, M, Tp,
+               mask_mul, ps, xhat_out, stop_after_ln);
+}
+template <int R>
+void LayerStagesT<R>::conv_ffn(const float* g, const float* x2, float* x_out, const LayerW& w, const int64_t* lens, int M,
+                               int Tp, int n_chunks, int ksize, int mask_mul, const LayerW* next, float* x1_next,
+                               float* qkv_next, hipStream_t st, bool causal, const PadSkip& ps, VtOut vt_next) {
+  const int left_ctx = causal ? ksize - 1 : (ksize - 1) / 2;
+  const LayerW& wn = next ? *next : w;
+#define LAUNCH_CFT(KS, NX)                                                                                               \
+  PPASR_LAUNCH((k_conv_ffn_t<R, KS, NX>), grid_t<R>(M), dim3(RBT<R>::THREADS), kLdsStageT<R>, st, g, x2, x_out, w, lens, M, \
+               Tp, n_chunks, mask_mul, wn, x1_next, qkv_next, left_ctx, ps, vt_next)
+  if (ksize == 15 && next) LAUNCH_CFT(15, true);
+  else if (ksize == 15) LAUNCH_CFT(15, false);
+  else if (ksize == 31 && next) LAUNCH_CFT(31, true);
+  else if (ksize == 31) LAUNCH_CFT(31, false);
+  else if (ksize == 7 && next) LAUNCH_CFT(7, true);
+  else if (ksize == 7) LAUNCH_CFT(7, false);
+#undef LAUNCH_CFT
+}
+// (configure() is the first member: the kernels enter the code object in the order of its list, the 16-row forms first)
+template struct LayerStagesT<16>;
+template struct LayerStagesT<kW16>;
+hipError_t configure_conformer_t_kernels() {
+  const hipError_t e = LayerStagesT<16>::configure();
+  return e != hipSuccess ? e : LayerStagesT<kW16>::configure();
+}
+
 // split route on 16-row blocks (a streaming chunk): out-projection + LayerNorm (rows -> xhat), then pointwise_conv1 + GLU
 // with the columns over two workgroups
 void launch_out_glu_split_16(const float* ctx, const float* x1, float* x2, float* g, float* xhat, const LayerW& w,
                              const int64_t* lens, int M, int Tp, int mask_mul, hipStream_t st, const PadSkip& ps, float* hist,
                              int lo) {
-  PPASR_LAUNCH(k_out_glu_t<16>, dim3((M + 15) / 16), dim3(kThreads), excl(kLds16x2), st, ctx, x1, x2, g, w, lens, M, Tp,
-               mask_mul, ps, xhat, 1);
-  PPASR_LAUNCH(k_pw1_glu_cols_t<16>, dim3((M + 15) / 16, 2), dim3(kThreads), excl((16 * kLda + 16 * 132) * sizeof(float)), st,
-               xhat, g, w, M, ps, hist, lo, (const float*)nullptr, (const float*)nullptr, (const int64_t*)nullptr, 1, 1);
+  LayerStagesT<16>::out_glu(ctx, x1, x2, g, w, lens, M, Tp, mask_mul, st, ps, xhat, 1);
+  launch_pw1_glu_cols_16(xhat, g, w, M, st, hist, lo, nullptr, nullptr, ps, nullptr, 1, 1);
 }
 // the two launches on their own, for layers that are not the Conformer's (Squeezeformer's chunk: weight views):
 // xhat_out = LN(x1 + ctx Wo + bo) with w.wo / bo / ln_conv_g / ln_conv_b (the plain sum goes to x2_sink)
 void launch_oproj_ln_16(const float* ctx, const float* x1, float* x2_sink, float* xhat_out, const LayerW& w, int M,
                         hipStream_t st, const PadSkip& ps) {
-  PPASR_LAUNCH(k_out_glu_t<16>, dim3((M + 15) / 16), dim3(kThreads), excl(kLds16x2), st, ctx, x1, x2_sink, (float*)nullptr, w,
-               (const int64_t*)nullptr, M, M, 1, ps, xhat_out, 1);
+  LayerStagesT<16>::out_glu(ctx, x1, x2_sink, nullptr, w, nullptr, M, M, 1, st, ps, xhat_out, 1);
 }
 // g = GLU(pointwise_conv1(x)) with w.pw1 / pw1_b; hist (M <= 16, one session): moves on by scale * x + bias
 void launch_pw1_glu_cols_16(const float* x, float* g, const LayerW& w, int M, hipStream_t st, float* hist, int lo,
                             const float* hist_scale, const float* hist_bias, const PadSkip& ps, const int64_t* lens, int Tp,
                             int mask_mul) {
-  PPASR_LAUNCH(k_pw1_glu_cols_t<16>, dim3((M + 15) / 16, 2), dim3(kThreads), excl((16 * kLda + 16 * 132) * sizeof(float)), st, x,
-               g, w, M, ps, hist, lo, hist_scale, hist_bias, lens, Tp, mask_mul);
+  PPASR_LAUNCH(k_pw1_glu_cols_t<16>, dim3((M + 15) / 16, 2), dim3(kThreads), kLdsPw1Cols16, st, x, g, w, M, ps, hist, lo,
+               hist_scale, hist_bias, lens, Tp, mask_mul);
 }
 bool conv_ffn_16_supported(int ksize, int Tp) { return (ksize == 7 || ksize == 15 || ksize == 31) && Tp >= 2; }
-void launch_conv_ffn_16(const float* g, const float* x2, float* x_out, const LayerW& w, const int64_t* lens, int M, int Tp,
-                        int n_chunks, int ksize, int mask_mul, const LayerW* next, float* x1_next, float* qkv_next,
-                        hipStream_t st, bool causal, const PadSkip& ps) {
-  const dim3 grid((M + 15) / 16);
-  const int left_ctx = causal ? ksize - 1 : (ksize - 1) / 2;
-  const LayerW& wn = next ? *next : w;
-#define LAUNCH_CF16(KS)                                                                                               \
-  if (next)                                                                                                           \
-    PPASR_LAUNCH((k_conv_ffn_t<16, KS, true>), grid, dim3(kThreads), excl(kLds16x4), st, g, x2, x_out, w, lens, M, Tp, \
-                 n_chunks, mask_mul, wn, x1_next, qkv_next, left_ctx, ps, VtOut{});                                   \
-  else                                                                                                                \
-    PPASR_LAUNCH((k_conv_ffn_t<16, KS, false>), grid, dim3(kThreads), excl(kLds16x4), st, g, x2, x_out, w, lens, M, Tp, \
-                 n_chunks, mask_mul, wn, x1_next, qkv_next, left_ctx, ps, VtOut{});
-  if (ksize == 15) {
-    LAUNCH_CF16(15)
-  } else if (ksize == 31) {
-    LAUNCH_CF16(31)
-  } else if (ksize == 7) {
-    LAUNCH_CF16(7)
-  }
-#undef LAUNCH_CF16
-}
-
-// ---- 32 rows on 16 waves: drop-in replacements of launch_ffn_qkv / launch_out_glu / launch_conv_ffn for full grids ----
-constexpr size_t kLdsW16x4 = 4 * 32 * kLda * sizeof(float), kLdsW16x2 = 2 * 32 * kLda * sizeof(float);
-void launch_ffn_qkv_w16(const float* x_in, float* x1, float* qkv, const LayerW& w, int M, int n_chunks, hipStream_t st,
-                        const PadSkip& ps, VtOut vt) {
-  PPASR_LAUNCH(k_ffn_qkv_t<kW16>, dim3((M + 31) / 32), dim3(1024), kLdsW16x4, st, x_in, x1, qkv, w, M, n_chunks, ps, vt);
-}
-void launch_out_glu_w16(const float* ctx, const float* x1, float* x2, float* g, const LayerW& w, const int64_t* lens, int M,
-                        int Tp, int mask_mul, hipStream_t st, const PadSkip& ps) {
-  PPASR_LAUNCH(k_out_glu_t<kW16>, dim3((M + 31) / 32), dim3(1024), excl(kLdsW16x2), st, ctx, x1, x2, g, w, lens, M, Tp,
-               mask_mul, ps, (float*)nullptr, 0);
-}
-bool conv_ffn_w16_supported(int ksize, int Tp) { return (ksize == 7 || ksize == 15 || ksize == 31) && Tp >= 2; }
-void launch_conv_ffn_w16(const float* g, const float* x2, float* x_out, const LayerW& w, const int64_t* lens, int M, int Tp,
-                         int n_chunks, int ksize, int mask_mul, const LayerW* next, float* x1_next, float* qkv_next,
-                         hipStream_t st, bool causal, const PadSkip& ps, VtOut vt_next) {
-  const dim3 grid((M + 31) / 32);
-  const int left_ctx = causal ? ksize - 1 : (ksize - 1) / 2;
-  const LayerW& wn = next ? *next : w;
-#define LAUNCH_CFW(KS)                                                                                                 \
-  if (next)                                                                                                            \
-    PPASR_LAUNCH((k_conv_ffn_t<kW16, KS, true>), grid, dim3(1024), kLdsW16x4, st, g, x2, x_out, w, lens, M, Tp, n_chunks, \
-                 mask_mul, wn, x1_next, qkv_next, left_ctx, ps, vt_next);                                              \
-  else                                                                                                                 \
-    PPASR_LAUNCH((k_conv_ffn_t<kW16, KS, false>), grid, dim3(1024), kLdsW16x4, st, g, x2, x_out, w, lens, M, Tp, n_chunks, \
-                 mask_mul, wn, x1_next, qkv_next, left_ctx, ps, vt_next);
-  if (ksize == 15) {
-    LAUNCH_CFW(15)
-  } else if (ksize == 31) {
-    LAUNCH_CFW(31)
-  } else if (ksize == 7) {
-    LAUNCH_CFW(7)
-  }
-#undef LAUNCH_CFW
-}
-
-hipError_t configure_conformer_t_kernels() {
-  hipError_t e;
-#define SET_LDS(fn)                                                                                                        \
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsExclusive); \
-  if (e != hipSuccess) return e;
-  SET_LDS(k_ffn_qkv_t<16>);
-  SET_LDS(k_out_glu_t<16>);
-  SET_LDS(k_pw1_glu_cols_t<16>);
-  SET_LDS((k_conv_ffn_t<16, 15, true>));
-  SET_LDS((k_conv_ffn_t<16, 15, false>));
-  SET_LDS((k_conv_ffn_t<16, 31, true>));
-  SET_LDS((k_conv_ffn_t<16, 31, false>));
-  SET_LDS((k_conv_ffn_t<16, 7, true>));
-  SET_LDS((k_conv_ffn_t<16, 7, false>));
-#undef SET_LDS
-#define SET_LDS_W(fn, n)                                                                                           \
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(n)); \
-  if (e != hipSuccess) return e;
-  SET_LDS_W(k_ffn_qkv_t<kW16>, kLdsW16x4);
-  SET_LDS_W(k_out_glu_t<kW16>, excl(kLdsW16x2));
-  SET_LDS_W((k_conv_ffn_t<kW16, 15, true>), kLdsW16x4);
-  SET_LDS_W((k_conv_ffn_t<kW16, 15, false>), kLdsW16x4);
-  SET_LDS_W((k_conv_ffn_t<kW16, 31, true>), kLdsW16x4);
-  SET_LDS_W((k_conv_ffn_t<kW16, 31, false>), kLdsW16x4);
-  SET_LDS_W((k_conv_ffn_t<kW16, 7, true>), kLdsW16x4);
-  SET_LDS_W((k_conv_ffn_t<kW16, 7, false>), kLdsW16x4);
-#undef SET_LDS_W
-  return hipSuccess;
-}
 
 }  // namespace ppasr

@@ -57,12 +57,8 @@ __device__ __forceinline__ void ffn_phase(const float* bufA, float* bufH, const 
     for (int q = 0; q < 4; ++q) bias[q] = *reinterpret_cast<const f32x4*>(b1 + c * 256 + wave * 32 + 8 * q + 4 * (lane >> 5));
     if (c + 1 < n_chunks) {
       acc_zero(nx);
-#ifdef PPASR_ABLATE_SWISH
-      rb_gemm<1, 1, kG256, kPF, NoSide, true>(bufA, kLda, w1seg(c + 1), 0, w2seg(c), 0, ring, nx);
-#else
       rb_gemm<1, 1, kG256, kPF, SwishSide, true>(bufA, kLda, w1seg(c + 1), 0, w2seg(c), 0, ring, nx,
                                                  SwishSide{cur[0][0], hb + hoff, bias, f32x2{0.f, 0.f}});
-#endif
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -73,9 +69,7 @@ __device__ __forceinline__ void ffn_phase(const float* bufA, float* bufH, const 
     }
     if (c < 8) PPASR_TS(16 + 2 * c);
     if (c < 8) PPASR_WAVE_TS(2 * c);
-#ifndef PPASR_ABLATE_FFN_BARRIER
     __syncthreads();
-#endif
     if (c < 8) PPASR_TS(17 + 2 * c);
     if (c < 8) PPASR_WAVE_TS(2 * c + 1);
     const f32x4* nseg = (c + 2 < n_chunks) ? w1seg(c + 2) : (c + 1 < n_chunks ? w2seg(c + 1) : after);

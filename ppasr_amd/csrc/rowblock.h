@@ -42,6 +42,7 @@ constexpr int kRows = 32;      // rows per MFMA row tile
 constexpr int kWaves = 8;      // waves per row-block workgroup
 constexpr int kThreads = 64 * kWaves;
 constexpr int kW16 = 1032;     // form id of "32 rows on 16 waves" (rbt.h; the 8-wave forms are named by their row count)
+constexpr int form_rows(int form) { return form == kW16 ? 32 : form; }  // rows per block of a form (32, 16 or kW16)
 constexpr int kG256 = kD / 8;  // k-groups of a K=256 contraction
 constexpr int kTs256 = kG256 * 64;  // packed tile stride (f32x4 units) of a K=256 weight
 
@@ -302,20 +303,12 @@ __device__ __forceinline__ void ln_rows_inreg(f32x4 (&x)[RN], const f32x4& g, co
   float mean[RN], var[RN];
 #pragma unroll
   for (int i = 0; i < RN; ++i) {
-#ifdef PPASR_ABLATE_LN
-    mean[i] = 0.f;
-#else
     mean[i] = wave_sum(x[i][0] + x[i][1] + x[i][2] + x[i][3]) * (1.0f / kD);
-#endif
   }
 #pragma unroll
   for (int i = 0; i < RN; ++i) {
     x[i] = x[i] - mean[i];
-#ifdef PPASR_ABLATE_LN
-    var[i] = 1.f;
-#else
     var[i] = wave_sum(x[i][0] * x[i][0] + x[i][1] * x[i][1] + x[i][2] * x[i][2] + x[i][3] * x[i][3]) * (1.0f / kD);
-#endif
   }
 #pragma unroll
   for (int i = 0; i < RN; ++i) {

@@ -538,8 +538,12 @@ void launch_sq_qkv(const float* x, float* qkv, const f32x4* wqkv, const float* b
 }
 // 16-row blocks always ask for more than half of a CU's LDS: one workgroup per CU, so that the (<= 256) active blocks of an
 // under-filled or ragged launch spread over all CUs instead of pairing up on some
-static size_t lds16(size_t own) { return own < kLdsExclusive ? kLdsExclusive : own; }
-constexpr size_t kLdsSqMid16 = 3 * 16 * kLda * sizeof(float), kLdsSqTail16 = 4 * 16 * kLda * sizeof(float);
+constexpr size_t lds16(size_t own) { return own < kLdsExclusive ? kLdsExclusive : own; }
+// dynamic LDS of K_B / K_C per block form: the launch and configure_squeezeformer_kernels read the same constant
+template <int R>
+constexpr size_t kLdsSqMidT = R == 16 ? lds16(3 * 16 * kLda * sizeof(float)) : kLdsSqMid;
+template <int R>
+constexpr size_t kLdsSqTailT = R == 16 ? lds16(4 * 16 * kLda * sizeof(float)) : kLdsSqTail;
 
 // fp16 x3 forms (h3.h): the residual tile + three operand tiles
 constexpr size_t kLdsSqMidH3 = kRows * kLda * sizeof(float) + 3 * kH3TileBytes;
@@ -549,15 +553,13 @@ void launch_sq_mid(const float* ctx, const float* x, float* x2, float* g, float*
   if (h3 && rows == 32)  // (w: the layer's fp16 x3 view; the caller decides h3 with sq_h3_route)
     PPASR_LAUNCH(k_sq_mid_h3, rb_grid(M), dim3(kThreads), kLdsSqMidH3, st, ctx, x, x2, g, xhat_out, w, lens, M, Tp, mask_mul,
                  n_chunks, ps);
-  else if (rows == 16)
-    PPASR_LAUNCH(k_sq_mid_t<16>, dim3((M + 15) / 16), dim3(kThreads), lds16(kLdsSqMid16), st, ctx, x, x2, g, xhat_out, w, lens,
-                 M, Tp, mask_mul, n_chunks, ps);
-  else if (rows == kW16)
-    PPASR_LAUNCH(k_sq_mid_t<kW16>, rb_grid(M), dim3(1024), kLdsSqMid, st, ctx, x, x2, g, xhat_out, w, lens, M, Tp, mask_mul,
-                 n_chunks, ps);
-  else
-    PPASR_LAUNCH(k_sq_mid_t<32>, rb_grid(M), dim3(kThreads), kLdsSqMid, st, ctx, x, x2, g, xhat_out, w, lens, M, Tp, mask_mul,
-                 n_chunks, ps);
+#define SQ_MID_T(R)                                                                                                   \
+  PPASR_LAUNCH(k_sq_mid_t<R>, dim3((M + RBT<R>::ROWS - 1) / RBT<R>::ROWS), dim3(RBT<R>::THREADS), kLdsSqMidT<R>, st, ctx, x, \
+               x2, g, xhat_out, w, lens, M, Tp, mask_mul, n_chunks, ps)
+  else if (rows == 16) SQ_MID_T(16);
+  else if (rows == kW16) SQ_MID_T(kW16);
+  else SQ_MID_T(32);
+#undef SQ_MID_T
 }
 void launch_sq_tail(const float* g, const float* g_hist, const float* x2, float* x_out, float* qkv_next, const SqLayerW& w,
                     const f32x4* wqkv_next, const float* bqkv_next, const int64_t* lens, int M, int Tp, int mask_mul,
@@ -575,15 +577,15 @@ void launch_sq_tail(const float* g, const float* g_hist, const float* x2, float*
   // the register depthwise conv needs a wave's rows to span at most two utterances (Tp >= rows per wave); streaming
   // chunks (g_hist) keep the LDS-staged form
   if (!g_hist && Tp >= 4 && (ksize == 31 || ksize == 15)) {
-#define SQ_TAIL_T(R, KS, LDS)                                                                                         \
-  PPASR_LAUNCH((k_sq_tail_t<R, KS>), dim3((M + RBT<R>::ROWS - 1) / RBT<R>::ROWS), dim3(RBT<R>::THREADS), LDS, st, g, x2, \
-               x_out, qkv_next, w, wqkv_next, bqkv_next, lens, M, Tp, mask_mul, n_chunks, ps, left_ctx)
+#define SQ_TAIL_T(R, KS)                                                                                             \
+  PPASR_LAUNCH((k_sq_tail_t<R, KS>), dim3((M + RBT<R>::ROWS - 1) / RBT<R>::ROWS), dim3(RBT<R>::THREADS), kLdsSqTailT<R>, st, \
+               g, x2, x_out, qkv_next, w, wqkv_next, bqkv_next, lens, M, Tp, mask_mul, n_chunks, ps, left_ctx)
     if (rows == 16) {
-      if (ksize == 31) SQ_TAIL_T(16, 31, lds16(kLdsSqTail16)); else SQ_TAIL_T(16, 15, lds16(kLdsSqTail16));
+      if (ksize == 31) SQ_TAIL_T(16, 31); else SQ_TAIL_T(16, 15);
     } else if (rows == kW16) {
-      if (ksize == 31) SQ_TAIL_T(kW16, 31, kLdsSqTail); else SQ_TAIL_T(kW16, 15, kLdsSqTail);
+      if (ksize == 31) SQ_TAIL_T(kW16, 31); else SQ_TAIL_T(kW16, 15);
     } else {
-      if (ksize == 31) SQ_TAIL_T(32, 31, kLdsSqTail); else SQ_TAIL_T(32, 15, kLdsSqTail);
+      if (ksize == 31) SQ_TAIL_T(32, 31); else SQ_TAIL_T(32, 15);
     }
 #undef SQ_TAIL_T
     return;
@@ -626,18 +628,18 @@ hipError_t configure_squeezeformer_kernels() {
 #define SET_LDS(fn, bytes)                                                                                     \
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
   if (e != hipSuccess) return e;
-  SET_LDS(k_sq_mid_t<32>, kLdsSqMid);
+  SET_LDS(k_sq_mid_t<32>, kLdsSqMidT<32>);
   SET_LDS(k_sq_mid_h3, kLdsSqMidH3);
   SET_LDS(k_sq_tail_h3<31>, kLdsSqTail + kH3ExtraLds);
   SET_LDS(k_sq_tail_h3<15>, kLdsSqTail + kH3ExtraLds);
-  SET_LDS(k_sq_mid_t<16>, kLdsExclusive);
-  SET_LDS(k_sq_mid_t<kW16>, kLdsSqMid);
-  SET_LDS((k_sq_tail_t<kW16, 31>), kLdsSqTail);
-  SET_LDS((k_sq_tail_t<kW16, 15>), kLdsSqTail);
-  SET_LDS((k_sq_tail_t<32, 31>), kLdsSqTail);
-  SET_LDS((k_sq_tail_t<32, 15>), kLdsSqTail);
-  SET_LDS((k_sq_tail_t<16, 31>), kLdsExclusive);
-  SET_LDS((k_sq_tail_t<16, 15>), kLdsExclusive);
+  SET_LDS(k_sq_mid_t<16>, kLdsSqMidT<16>);
+  SET_LDS(k_sq_mid_t<kW16>, kLdsSqMidT<kW16>);
+  SET_LDS((k_sq_tail_t<kW16, 31>), kLdsSqTailT<kW16>);
+  SET_LDS((k_sq_tail_t<kW16, 15>), kLdsSqTailT<kW16>);
+  SET_LDS((k_sq_tail_t<32, 31>), kLdsSqTailT<32>);
+  SET_LDS((k_sq_tail_t<32, 15>), kLdsSqTailT<32>);
+  SET_LDS((k_sq_tail_t<16, 31>), kLdsSqTailT<16>);
+  SET_LDS((k_sq_tail_t<16, 15>), kLdsSqTailT<16>);
   SET_LDS((k_sq_tail<31, false>), kLdsSqTail);
   SET_LDS((k_sq_tail<15, false>), kLdsSqTail);
   SET_LDS((k_sq_tail<31, true>), kLdsSqTail);

@@ -158,29 +158,29 @@ SITES = [
          [(CK, 105, "ffn_phase_h3("), (SR, 96, "ffn_phase_h3(")], "{l}feed_forward_macaron.w2_in", ALL,
          {FUSED: S1, SPLIT: ("k_ffn_part<",)}, _w2_in("feed_forward_macaron")),
     Site("w1_fin", "W1 input of the final FFN",
-         [(CK, 1015, "ffn_phase_h3("), (CK, 1175, "ffn_phase_h3("), (SR, 96, "ffn_phase_h3(")], "{l}feed_forward.w1_in", ALL,
+         [(CK, 1030, "ffn_phase_h3("), (CK, 1198, "ffn_phase_h3("), (SR, 96, "ffn_phase_h3(")], "{l}feed_forward.w1_in", ALL,
          FFN_FIN, _w1_in("norm_ff", "feed_forward")),
     Site("w2_fin", "swish hidden values in front of W2, final FFN",
-         [(CK, 1015, "ffn_phase_h3("), (CK, 1175, "ffn_phase_h3("), (SR, 96, "ffn_phase_h3(")], "{l}feed_forward.w2_in", ALL,
+         [(CK, 1030, "ffn_phase_h3("), (CK, 1198, "ffn_phase_h3("), (SR, 96, "ffn_phase_h3(")], "{l}feed_forward.w2_in", ALL,
          FFN_FIN, _w2_in("feed_forward")),
     Site("qkv_in", "Q / K / V input", [(CK, 114, "h3_planes_from_tile("), (SR, 215, "unit_std_h3(")], "{l}self_attn.qkv_in",
          ALL, {FUSED: S1, SPLIT: ("k_ln_qkv<",)}, _qkv_in),
     # (the three attention sites exist with the fused attention only: elsewhere K, q + u and q + v stay fp32)
     Site("k_planes", "K planes written by QkStoreTailH3 for the fused attention", [(CK, 67, "h3_split4(")],
          "{l}self_attn.k", (FUSED,), {FUSED: S1}, _k_planes),
-    Site("q_u", "q + pos_bias_u in the score contraction", [(CK, 579, "h3_split4(")], "{l}self_attn.q_u", (FUSED,),
+    Site("q_u", "q + pos_bias_u in the score contraction", [(CK, 594, "h3_split4(")], "{l}self_attn.q_u", (FUSED,),
          {FUSED: ("k_attn_out_glu_h3",)}, _q_u),
-    Site("q_v", "q + pos_bias_v in the score contraction", [(CK, 583, "h3_split4(")], "{l}self_attn.q_v", (FUSED,),
+    Site("q_v", "q + pos_bias_v in the score contraction", [(CK, 598, "h3_split4(")], "{l}self_attn.q_v", (FUSED,),
          {FUSED: ("k_attn_out_glu_h3",)}, _q_v),
-    Site("out_in", "linear_out input (attention context)", [(CK, 825, "h3_planes_from_tile("), (CK, 318, "unit_std_h3(")],
+    Site("out_in", "linear_out input (attention context)", [(CK, 840, "h3_planes_from_tile("), (CK, 330, "unit_std_h3(")],
          "{l}self_attn.out_in", ALL, {FUSED: ("k_attn_out_glu_h3",), SPLIT: ("k_out_glu<",)}, _out_in),
-    # (conformer_kernels.hip:340 is k_out_glu<true> with pointwise_conv1 inside: every launch of the <true> form passes
+    # (conformer_kernels.hip:352 is k_out_glu<true> with pointwise_conv1 inside: every launch of the <true> form passes
     #  stop_after_ln today -- launch_out_glu -- so that line is claimed here but reached by no route)
     Site("pw1_in", "pointwise_conv1 input",
-         [(CK, 861, "h3_planes_from_tile("), (CK, 384, "unit_std_h3("), (CK, 340, "h3_planes_from_tile(")],
+         [(CK, 876, "h3_planes_from_tile("), (CK, 396, "unit_std_h3("), (CK, 352, "h3_planes_from_tile(")],
          "{l}conv_module.pw1_in", ALL, {FUSED: ("k_attn_out_glu_h3",), SPLIT: ("k_pw1_glu_cols<",)}, _pw1_in),
     Site("pw2_in", "pointwise_conv2 input",
-         [(CK, 992, "h3_planes_from_tile("), (CK, 1147, "unit_std_h3("), (SR, 61, "unit_std_h3(")], "{l}conv_module.pw2_in", ALL,
+         [(CK, 1007, "h3_planes_from_tile("), (CK, 1170, "unit_std_h3("), (SR, 61, "unit_std_h3(")], "{l}conv_module.pw2_in", ALL,
          {FUSED: ("k_conv_ffn_h3", "k_conv_ffn_stride<"), SPLIT: ("k_conv_pre<", "k_conv_ffn_stride<")}, _pw2_in),
     Site("ctc_in", "CTC head input", [(HD, 49, "h3_planes_from_tile(")], "ctc.in", BATCHED,
          {FUSED: ("k_ctc_head_h3",), SPLIT: ("k_ctc_head_h3",)}, _ctc_in),
