@@ -283,6 +283,21 @@ PPASR_API ppasr_status ppasr_ctc_beam_state_grow(const void* old_state, size_t o
  * more cumulative frames were decoded than the buffer was sized for; returns PPASR_ENOSPACE then.  Synchronises. */
 PPASR_API ppasr_status ppasr_ctc_beam_status(const void* state, size_t state_bytes, int B, int beam_size, int32_t* status_host,
                                    void* stream);
+/* Streaming without an ever-growing state: compacts the prefix arenas of the B blocks of a state buffer (layout of
+ * ppasr_ctc_beam_search_ws) in place.  Every node that is neither in the beam nor an ancestor of a beam entry is dropped
+ * -- what PathTrie::remove does upstream after every frame -- and the rest is renumbered in creation order; the search
+ * continues from the compacted buffer with the same results bit for bit (node ids take part in no comparison).
+ * rebuild_table: 1 for searches with a word-based scorer (their node table is rebuilt from the compacted arena).  For
+ * those, compaction moves the search TO the upstream behaviour: without it a prefix keeps its node and the dictionary state
+ * saved there even after it left the beam with no live descendant; upstream, the C oracle and a compacted search delete
+ * such a node and create it fresh.  The two differ only for a prefix that died childless, had its dictionary state reset
+ * while alive, and is created again.
+ * live_nodes_host [B] or NULL: with it the blocks' node counts afterwards are copied back (-1: a block whose arena was
+ * exhausted, left untouched) and `stream` is synchronised; without it the call is asynchronous.  A caller that kept
+ * count of the frames decoded may continue with ceil((L - 1) / beam_size) for the largest L.  PPASR_EINVAL (null state,
+ * B <= 0, a state too small for one frame) before any device work. */
+PPASR_API ppasr_status ppasr_ctc_beam_state_compact(void* state, size_t state_bytes, int B, int beam_size, int rebuild_table,
+                                          int32_t* live_nodes_host, void* stream);
 PPASR_API ppasr_status ppasr_ctc_beam_search(const float* probs, const int32_t* frame_lens, int B, int T, int V, int beam_size,
                                    double cutoff_prob, int cutoff_top_n, int blank, int nbest, int max_tokens,
                                    int32_t* tokens, int32_t* lens, double* scores, void* state, size_t state_bytes,
@@ -525,6 +540,26 @@ PPASR_API size_t       ppasr_beam_pool_workspace_bytes(ppasr_beam_pool pool, int
 PPASR_API ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool pool, const int* sessions_host, int n, const float* probs, int T,
                                               const int32_t* frame_lens_host, int max_tokens, int32_t* tokens, int32_t* lens,
                                               double* scores, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- compaction of a pool's prefix arenas: long streams in bounded memory --------------------------------------
+ * A session's arena otherwise keeps every prefix node it ever created (36 bytes per node, beam_size nodes per frame) and
+ * its block doubles whenever its stream does.  ppasr_beam_arena_compact rewrites the listed sessions' blocks in place with
+ * ONE launch (ppasr_ctc_beam_state_compact's rule; the node table of word-based scorers is rebuilt, with the semantic note
+ * given there), reads the live node counts back (live_nodes_host [n] by list position, or NULL; -1: exhausted, left
+ * untouched), synchronises `stream` once and lowers each session's arena use to ceil((L - 1) / beam_size) frame-equivalents;
+ * ppasr_beam_pool_frames stays cumulative.  n < 0 or a NULL list: every session.  Results of later decodes do not change.
+ * ppasr_beam_arena_set_auto(pool, 1): ppasr_beam_pool_decode compacts every listed session whose chunk does not fit its
+ * block (one launch for all of them) before it plans growth; such a session keeps its block if at least half of it is
+ * free behind the chunk and otherwise grows by doubling until that holds.  Default 0: the pool behaves as without these
+ * calls.  Capacity never shrinks.  Every argument is checked before any device work; a refused call (PPASR_EINVAL: null
+ * pool, index out of range or repeated) changes nothing. */
+PPASR_API ppasr_status ppasr_beam_arena_compact(ppasr_beam_pool pool, const int* sessions_host, int n, long long* live_nodes_host,
+                                                void* stream);
+PPASR_API ppasr_status ppasr_beam_arena_set_auto(ppasr_beam_pool pool, int enable);
+/* Node count read back at the session's last compaction (0: none since its reset; -1: bad argument). */
+PPASR_API long long    ppasr_beam_arena_live_nodes(ppasr_beam_pool pool, int session);
+/* Device bytes of all state blocks now. */
+PPASR_API size_t       ppasr_beam_arena_bytes(ppasr_beam_pool pool);
 
 /* ---- Kaldi-compatible fbank front-end --------------------------------------------
  * Replaces AudioFeaturizer.featurize (ppasr/data_utils/featurizer/audio_featurizer.py:37-67,120-138):

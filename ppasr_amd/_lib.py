@@ -154,6 +154,12 @@ SYMBOLS = [
     ("ppasr_beam_pool_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int]),
     ("ppasr_beam_pool_decode", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _vp, ctypes.c_int, _vp,
                                               ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("ppasr_ctc_beam_state_compact", ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    ("ppasr_beam_arena_compact", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_longlong), _vp]),
+    ("ppasr_beam_arena_set_auto", ctypes.c_int, [_vp, ctypes.c_int]),
+    ("ppasr_beam_arena_live_nodes", ctypes.c_longlong, [_vp, ctypes.c_int]),
+    ("ppasr_beam_arena_bytes", ctypes.c_size_t, [_vp]),
     ("ppasr_fbank_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                           ctypes.POINTER(_vp)]),
     ("ppasr_fbank_destroy", ctypes.c_int, [_vp]),

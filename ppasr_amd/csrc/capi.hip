@@ -1296,6 +1296,29 @@ ppasr_status ppasr_ctc_beam_status(const void* state, size_t state_bytes, int B,
   return PPASR_OK;
 }
 
+// Compaction of a streaming state buffer (ctc_beam.h: launch_beam_compact).  The live counts are the blocks' own st[1]
+// afterwards (-1 where the status word is set), so the read-back needs no device array of its own.
+ppasr_status ppasr_ctc_beam_state_compact(void* state, size_t state_bytes, int B, int beam_size, int rebuild_table,
+                                          int32_t* live_nodes_host, void* stream) {
+  if (!state || B <= 0 || beam_size < 1 || beam_size > kMaxBeam) return fail(PPASR_EINVAL, "beam search: null state, B <= 0 or bad beam_size");
+  const size_t F = beam_frame_capacity(state_bytes / (size_t)B, beam_size);
+  if (F == 0) return fail(PPASR_EINVAL, "beam search: state buffer too small for one frame");
+  const int max_nodes = (int)beam_max_nodes(F, beam_size);
+  const size_t block_words = beam_state_words(beam_size, max_nodes);
+  int32_t* st_words = static_cast<int32_t*>(state);
+  const int32_t* status = st_words + (size_t)B * block_words;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  HIP_TRY(launch_beam_compact(st_words, status, B, beam_size, max_nodes, rebuild_table != 0, nullptr, hs));
+  if (!live_nodes_host) return PPASR_OK;
+  std::vector<int32_t> stat(B);
+  HIP_TRY(hipMemcpy2DAsync(live_nodes_host, 4, st_words + 1, block_words * 4, 4, (size_t)B, hipMemcpyDeviceToHost, hs));
+  HIP_TRY(hipMemcpyAsync(stat.data(), status, (size_t)B * 4, hipMemcpyDeviceToHost, hs));
+  HIP_TRY(hipStreamSynchronize(hs));
+  for (int b = 0; b < B; ++b)
+    if (stat[b] != 0) live_nodes_host[b] = -1;
+  return PPASR_OK;
+}
+
 // ---- beam-search session pools (include/ppasr_hip.h: ppasr_beam_pool_*) ----
 // Every session owns its state block (ctc_beam.h layout, sized for its own frame capacity) and a status word; a decode
 // call builds a slot table of the listed sessions' blocks (by list position) and runs the pruning pre-pass and the search
@@ -1306,8 +1329,14 @@ struct ppasr_beam_pool_s {
   std::vector<int32_t*> block;   // device state block of each session
   std::vector<size_t> cap;       // frames each block is sized for
   std::vector<long long> frames; // cumulative frames decoded since the session's last reset
+  // frame-equivalents of the arena in use -- what the capacity check compares: n_nodes <= 1 + used * beam.  A decode of f
+  // frames adds f, a reset sets 0, a compaction that found L live nodes sets ceil((L - 1) / beam); == frames without one
+  std::vector<long long> used;
+  std::vector<long long> live;   // node count read back at the session's last compaction (0: none since its reset)
+  bool auto_compact = false;     // ppasr_beam_arena_set_auto
   int32_t* status;               // device [n_sessions]
-  StagingRing ring;  // per-call slot tables + frame counts: [n_sessions] BeamSlot, then [n_sessions] int32 per entry
+  // per-call slot tables + frame counts (a compaction: live counts): [n_sessions] BeamSlot, then [n_sessions] int32 per entry
+  StagingRing ring;
 };
 
 namespace {
@@ -1317,6 +1346,37 @@ size_t pool_rec_bytes(const BeamConfig& c, int n, int T) {  // narrow pruning re
 }
 // largest capacity whose arena node count still fits the kernel's int arithmetic
 bool pool_cap_ok(size_t F, int beam) { return F <= (size_t)(0x3fffffff / beam) - 2; }
+
+// One compaction launch for the n listed sessions (checked by the caller): slot table up, live counts back, ONE
+// synchronisation of `hs`, then the accounting -- used = ceil((L - 1) / beam), so that n_nodes <= 1 + used * beam still
+// holds.  An exhausted session (count -1) was left as it is and keeps its accounting.  live_out [n] or null.
+ppasr_status pool_compact(ppasr_beam_pool_s* p, const int* sessions, int n, long long* live_out, hipStream_t hs) {
+  StagingRing::Entry en;
+  HIP_TRY(p->ring.acquire(&en));
+  BeamSlot* tab = reinterpret_cast<BeamSlot*>(en.host);
+  const int beam = p->cfg.beam;
+  for (int b = 0; b < n; ++b) {
+    const int s = sessions[b];
+    tab[b] = BeamSlot{p->block[s], p->status + s, (int)beam_max_nodes(p->cap[s], beam), 0};
+  }
+  const size_t live_off = (size_t)n * sizeof(BeamSlot);
+  HIP_TRY(hipMemcpyAsync(en.dev, en.host, live_off, hipMemcpyHostToDevice, hs));
+  HIP_TRY(launch_beam_compact(nullptr, nullptr, n, beam, 0, p->cfg.node_table, reinterpret_cast<int32_t*>(en.dev + live_off), hs,
+                              reinterpret_cast<const BeamSlot*>(en.dev)));
+  HIP_TRY(hipMemcpyAsync(en.host + live_off, en.dev + live_off, (size_t)n * 4, hipMemcpyDeviceToHost, hs));
+  HIP_TRY(hipStreamSynchronize(hs));
+  HIP_TRY(p->ring.release(en, hs));
+  const int32_t* live = reinterpret_cast<const int32_t*>(en.host + live_off);
+  for (int b = 0; b < n; ++b) {
+    const int s = sessions[b];
+    if (live[b] >= 1) {
+      p->live[s] = live[b];
+      p->used[s] = ((long long)live[b] - 1 + beam - 1) / beam;
+    }
+    if (live_out) live_out[b] = live[b];
+  }
+  return PPASR_OK;
+}
 }  // namespace
 
 ppasr_status ppasr_beam_pool_create(int n_sessions, int V, int beam_size, double cutoff_prob, int cutoff_top_n, int blank,
@@ -1340,6 +1400,8 @@ ppasr_status ppasr_beam_pool_create(int n_sessions, int V, int beam_size, double
   p->block.assign(n_sessions, nullptr);
   p->cap.assign(n_sessions, (size_t)init_frames);
   p->frames.assign(n_sessions, 0);
+  p->used.assign(n_sessions, 0);
+  p->live.assign(n_sessions, 0);
   auto bail = [p](const char* what, hipError_t e) {
     (void)ppasr_beam_pool_destroy(p);
     return fail(PPASR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
@@ -1379,6 +1441,8 @@ ppasr_status ppasr_beam_pool_reset(ppasr_beam_pool p, int session, void* stream)
     HIP_TRY(launch_beam_reset(p->block[i], p->status + i, p->cfg.beam, (int)beam_max_nodes(p->cap[i], p->cfg.beam),
                               p->cfg.lm.bos, p->cfg.node_table != 0, hs));
     p->frames[i] = 0;
+    p->used[i] = 0;
+    p->live[i] = 0;
   }
   return PPASR_OK;
 }
@@ -1425,17 +1489,34 @@ ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host,
   if (workspace_bytes < need || (need > 0 && !workspace))
     return fail(PPASR_ENOSPACE, "beam pool: workspace smaller than ppasr_beam_pool_workspace_bytes(pool, n, T)");
   const int beam = p->cfg.beam;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  // ---- automatic compaction (ppasr_beam_arena_set_auto): every listed session whose chunk does not fit is compacted, all
+  // of them with one launch, before growth is planned; it then keeps its block if at least half of it stays free behind
+  // this chunk, and otherwise grows from the compacted state until that holds -- so compactions of a session are at least
+  // cap / 2 frames apart.  (Compaction changes no result, so a call refused below still changes no session's search.)
+  std::vector<char> compacted(n, 0);
+  if (p->auto_compact) {
+    std::vector<int> list;
+    for (int b = 0; b < n; ++b)
+      if ((size_t)p->used[sessions_host[b]] + (size_t)fl[b] > p->cap[sessions_host[b]]) {
+        compacted[b] = 1;
+        list.push_back(sessions_host[b]);
+      }
+    if (!list.empty()) {
+      ppasr_status rc = pool_compact(p, list.data(), (int)list.size(), nullptr, hs);
+      if (rc != PPASR_OK) return rc;
+    }
+  }
   std::vector<size_t> new_cap(n, 0);  // 0: no growth
   for (int b = 0; b < n; ++b) {
     const int s = sessions_host[b];
-    const size_t want = (size_t)p->frames[s] + (size_t)fl[b];
+    const size_t want = ((size_t)p->used[s] + (size_t)fl[b]) * (compacted[b] ? 2 : 1);
     if (want <= p->cap[s]) continue;
     size_t c = p->cap[s];
     while (c < want) c *= 2;
     if (!pool_cap_ok(c, beam)) return fail(PPASR_ENOSPACE, "beam pool: a session's stream is too long for one prefix arena");
     new_cap[b] = c;
   }
-  hipStream_t hs = static_cast<hipStream_t>(stream);
   // ---- growth: the session's block moves into one sized for twice the frames (doubling until the chunk fits).  Header,
   // beam arrays and arena keep their offsets (ppasr_ctc_beam_state_grow); the node table, where the search uses one, is
   // rebuilt for its new size.  The replaced blocks are freed after ONE stream synchronisation that covers every copy of
@@ -1493,8 +1574,45 @@ ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host,
   HIP_TRY(launch_ctc_beam(probs, reinterpret_cast<const int32_t*>(en.dev + (size_t)n * sizeof(BeamSlot)), n, T, c, recs,
                           nullptr, 0, 1, tokens, lens, scores, nullptr, scratch, hs, reinterpret_cast<const BeamSlot*>(en.dev)));
   HIP_TRY(p->ring.release(en, hs));
-  for (int b = 0; b < n; ++b) p->frames[sessions_host[b]] += fl[b];
+  for (int b = 0; b < n; ++b) {
+    p->frames[sessions_host[b]] += fl[b];
+    p->used[sessions_host[b]] += fl[b];
+  }
   return PPASR_OK;
+}
+
+// ---- compaction of the pool's prefix arenas (include/ppasr_hip.h: ppasr_beam_arena_*) ----
+ppasr_status ppasr_beam_arena_compact(ppasr_beam_pool p, const int* sessions_host, int n, long long* live_nodes_host, void* stream) {
+  if (!p) return fail(PPASR_EINVAL, "null pool");
+  std::vector<int> all;
+  if (!sessions_host || n < 0) {
+    all.resize(p->n_sessions);
+    for (int i = 0; i < p->n_sessions; ++i) all[i] = i;
+    sessions_host = all.data();
+    n = p->n_sessions;
+  }
+  if (n < 1 || n > p->n_sessions) return fail(PPASR_EINVAL, "beam pool: bad n");
+  if (!session_list_ok(sessions_host, n, p->n_sessions))
+    return fail(PPASR_EINVAL, "beam pool: session index out of range or repeated");
+  return pool_compact(p, sessions_host, n, live_nodes_host, static_cast<hipStream_t>(stream));
+}
+
+ppasr_status ppasr_beam_arena_set_auto(ppasr_beam_pool p, int enable) {
+  if (!p) return fail(PPASR_EINVAL, "null pool");
+  p->auto_compact = enable != 0;
+  return PPASR_OK;
+}
+
+long long ppasr_beam_arena_live_nodes(ppasr_beam_pool p, int session) {
+  if (!p || session < 0 || session >= p->n_sessions) return -1;
+  return p->live[session];
+}
+
+size_t ppasr_beam_arena_bytes(ppasr_beam_pool p) {
+  if (!p) return 0;
+  size_t total = 0;
+  for (size_t c : p->cap) total += pool_block_bytes(c, p->cfg.beam);
+  return total;
 }
 
 // ---- kernel-name profiler: every PPASR_LAUNCH of the calling thread between begin and end carries its own dispatch-attached

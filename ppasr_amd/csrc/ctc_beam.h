@@ -91,4 +91,23 @@ hipError_t launch_beam_reset(int32_t* state, int32_t* status, int beam, int max_
 // rebuilds the node tables of B state blocks (cleared by the caller) from their arenas: after a streaming state buffer grew
 hipError_t launch_beam_rehash(int32_t* state, int B, int beam, int max_nodes, hipStream_t st);
 
+// Compacts the prefix arenas of B state blocks in place, one workgroup per block, addressed as launch_ctc_beam addresses
+// them (B contiguous blocks of max_nodes with status[B], or a slot table).  Each block becomes its canonical compacted
+// form: the live nodes -- the root, the nodes of the st[0] beam entries and their ancestors through arena word 0 -- keep
+// their order and are renumbered by rank (parents stay below children, the root stays 0; the selection's tie order is
+// (score, character, list position), never a node id, so no comparison of the search changes); arena row j becomes
+// (new id of the old parent, character, dictionary state); beam arrays 0 (node) and 2 (parent) are renumbered, values
+// that are no node id (the root hypothesis's -1) are kept; st[1] = L, the live count.  st[0], the other beam arrays, the
+// status word and other blocks are not written; arena words from row L on are unspecified.  live_nodes[u] (device, may be
+// null) receives L; a block whose status word is non-zero (arena exhausted: st[1] may exceed max_nodes) is left as it is
+// and reports -1.  The block's node-table region serves as scratch (nothing it held is relied on); rebuild_table
+// (BeamConfig::node_table searches) clears the table afterwards and re-enters the compacted arena.
+// For node-table searches this DROPS what the paragraph above on revivals keeps: a prefix that left the beam with no live
+// descendant loses its node and the dictionary state saved there, and is created fresh if it comes back -- which is what
+// upstream does (PathTrie::remove deletes every node that is neither in the beam nor an ancestor of a beam entry).  The
+// two differ only for a prefix that died childless, had its dictionary state reset while alive (k_ctc_beam, k_reset) and
+// is created again; the reference for compacted node-table searches is the C oracle with a dictionary.
+hipError_t launch_beam_compact(int32_t* state, const int32_t* status, int B, int beam, int max_nodes, int rebuild_table,
+                               int32_t* live_nodes, hipStream_t st, const BeamSlot* slots = nullptr);
+
 }  // namespace ppasr

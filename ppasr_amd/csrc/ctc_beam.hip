@@ -1805,13 +1805,12 @@ __global__ __launch_bounds__(BT, 1) void k_ctc_beam(const float* __restrict__ pr
   }
 }
 
-__global__ __launch_bounds__(256) void k_beam_rehash(int32_t* __restrict__ state, int beam, int max_nodes) {
-  int32_t* st = state + (size_t)blockIdx.x * beam_state_words(beam, max_nodes);
+// enters the nodes [1, n_nodes) of one block's arena into its (cleared) node table: one workgroup
+__device__ __forceinline__ void rehash_block(int32_t* st, int beam, int max_nodes, int n_nodes) {
   const int32_t* arena = st + beam_fixed_words(beam);
   const size_t tslots = beam_table_slots(max_nodes);
   unsigned long long* tkeys = reinterpret_cast<unsigned long long*>(st + beam_fixed_words(beam) + beam_arena_words(max_nodes));
   int32_t* tids = reinterpret_cast<int32_t*>(tkeys + tslots);
-  const int n_nodes = st[1];
   for (int id = 1 + threadIdx.x; id < n_nodes; id += blockDim.x) {
     const unsigned long long key = beam_node_key(arena[kArenaWords * (size_t)id], arena[kArenaWords * (size_t)id + 1]);
     size_t slot = beam_node_slot(key, tslots);
@@ -1819,8 +1818,135 @@ __global__ __launch_bounds__(256) void k_beam_rehash(int32_t* __restrict__ state
     tids[slot] = id;
   }
 }
+
+__global__ __launch_bounds__(256) void k_beam_rehash(int32_t* __restrict__ state, int beam, int max_nodes) {
+  int32_t* st = state + (size_t)blockIdx.x * beam_state_words(beam, max_nodes);
+  rehash_block(st, beam, max_nodes, st[1]);
+}
 hipError_t launch_beam_rehash(int32_t* state, int B, int beam, int max_nodes, hipStream_t st) {
   PPASR_LAUNCH(k_beam_rehash, dim3(B), dim3(256), 0, st, state, beam, max_nodes);
+  return hipGetLastError();
+}
+
+// ---- compaction of the prefix arena (ctc_beam.h: launch_beam_compact) ----
+// One workgroup rewrites one state block in place.  `map` -- one word per node, in the block's node-table region -- is
+// first the live flag of a node, then its new id (-1: dead).  Five passes over [0, n_nodes), each in tiles of one node
+// per thread:
+//   clear  map[0, n) = 0 (nothing in the region or in the arena rows of slots that were no children is relied on: a flag
+//          is written before it is read, and an arena row is read only once its flag is set);
+//   mark   the root and the beam entries' nodes, then a DESCENDING sweep: a live node marks its parent.  Parents lie below
+//          their children, so tiles below see every mark of the tiles above; a parent inside the same tile is resolved in
+//          LDS, round by round, until a round marks nothing new (one barrier per round; as many rounds as the longest
+//          chain inside the tile: about two at beam 300, where a tile spans under two frames; up to 512 / beam at small beams);
+//   rank   ascending block scans: map[id] = rank of id among the live nodes;
+//   move   ascending tiles: the live rows of a tile are read into registers, (barrier), and written to their new rows --
+//          which lie at or below the old ones, so a tile only overwrites rows that it or an earlier tile has read;
+//   beam   arrays 0 (node) and 2 (parent) of the n_beam hypotheses through map; st[1] = L.
+// With rebuild_table the node table (which held map) is then cleared and re-entered from the compacted arena.
+constexpr int kCompactThreads = 512;
+template <bool SLOTS>
+__global__ __launch_bounds__(kCompactThreads) void k_beam_compact(int32_t* __restrict__ state, const int32_t* __restrict__ status,
+                                                                  const BeamSlot* __restrict__ slots, int beam, int max_nodes_all,
+                                                                  int rebuild_table, int32_t* __restrict__ live_nodes) {
+  constexpr int BT = kCompactThreads, NW = BT / 64;
+  __shared__ int s_flag[BT];
+  __shared__ int s_wtot[NW];
+  __shared__ int s_any[3];
+  const int tid = threadIdx.x, u = blockIdx.x;
+  const int max_nodes = SLOTS ? slots[u].max_nodes : max_nodes_all;
+  int32_t* st = SLOTS ? slots[u].state : state + (size_t)u * beam_state_words(beam, max_nodes);
+  const int32_t stat = SLOTS ? *slots[u].status : status[u];
+  const int nb = st[0], n = st[1];
+  // an exhausted block (its node count may exceed the arena) is left as it is; so is one whose header cannot be a search's
+  if (stat != 0 || nb < 0 || nb > beam || n < 1 || n > max_nodes) {
+    if (tid == 0 && live_nodes) live_nodes[u] = -1;
+    return;
+  }
+  int32_t* g_arr = st + 2;
+  int32_t* arena = st + beam_fixed_words(beam);
+  int32_t* map = arena + beam_arena_words(max_nodes);  // 3 * beam_table_slots(max_nodes) = 6 * max_nodes words
+  const int n_tiles = (n + BT - 1) / BT;
+
+  for (int id = tid; id < n; id += BT) map[id] = 0;
+  __syncthreads();
+  if (tid == 0) map[0] = 1;
+  for (int i = tid; i < nb; i += BT) {
+    const int v = g_arr[i];
+    if (v >= 0 && v < n) map[v] = 1;
+  }
+  __syncthreads();
+  for (int t = n_tiles - 1; t >= 0; --t) {
+    const int base = t * BT, id = base + tid;
+    s_flag[tid] = id < n ? map[id] : 0;  // 0 dead (so far), 1 live, 2 live and its parent marked
+    if (tid == 0) s_any[0] = 0;
+    __syncthreads();
+    // Every thread reaches every barrier of this loop: what a thread still has to do is read from LDS in each round, and the
+    // loop ends on one LDS word that all threads read.  (A per-thread "done" register let the compiler split the loop in
+    // two by that flag, each half with barriers of its own, and the workgroup hung.)  s_any[] rotates over three words: the
+    // word of round r + 1 is cleared in round r, while nobody reads or sets it.
+    for (int r = 0;; r = r == 2 ? 0 : r + 1) {
+      if (tid == 0) s_any[r == 2 ? 0 : r + 1] = 0;
+      if (s_flag[tid] == 1) {
+        s_flag[tid] = 2;
+        const int p = id > 0 ? arena[kArenaWords * (size_t)id] : -1;
+        if (p >= 0 && p < id) {
+          if (p < base) map[p] = 1;
+          else if (s_flag[p - base] == 0) { s_flag[p - base] = 1; s_any[r] = 1; }
+        }
+      }
+      __syncthreads();
+      if (!s_any[r]) break;
+    }
+    if (id < n) map[id] = s_flag[tid] != 0;
+    __syncthreads();  // the tile below reads these flags (and s_flag is written again)
+  }
+  int n_live = 0;
+  for (int t = 0; t < n_tiles; ++t) {
+    const int id = t * BT + tid;
+    const int f = id < n ? map[id] : 0;
+    int tot;
+    const int excl = block_excl_scan<NW>(f, s_wtot, tot);
+    if (id < n) map[id] = f ? n_live + excl : -1;
+    n_live += tot;
+    __syncthreads();  // (s_wtot is written again; the moves below read map[] of other threads)
+  }
+  for (int t = 0; t < n_tiles; ++t) {
+    const int id = t * BT + tid;
+    const int nid = id < n ? map[id] : -1;
+    int p = -1, c = -1, d = 0;
+    if (nid >= 0) {
+      p = arena[kArenaWords * (size_t)id]; c = arena[kArenaWords * (size_t)id + 1]; d = arena[kArenaWords * (size_t)id + 2];
+      if (id > 0 && p >= 0 && p < id) p = map[p];
+    }
+    __syncthreads();  // every old row of this tile is in registers
+    if (nid >= 0) {
+      arena[kArenaWords * (size_t)nid] = p; arena[kArenaWords * (size_t)nid + 1] = c; arena[kArenaWords * (size_t)nid + 2] = d;
+    }
+  }
+  for (int i = tid; i < nb; i += BT) {
+    const int v = g_arr[i], q = g_arr[2 * beam + i];
+    if (v >= 0 && v < n && map[v] >= 0) g_arr[i] = map[v];
+    if (q >= 0 && q < n && map[q] >= 0) g_arr[2 * beam + i] = map[q];  // (the root hypothesis's -1 stays)
+  }
+  if (tid == 0) {
+    st[1] = n_live;
+    if (live_nodes) live_nodes[u] = n_live;
+  }
+  if (rebuild_table) {
+    __syncthreads();  // map[] has been read for the last time, the compacted rows are written
+    unsigned long long* tab = reinterpret_cast<unsigned long long*>(map);
+    const size_t words64 = 3 * beam_table_slots(max_nodes) / 2;  // uint64 keys, then int32 ids
+    for (size_t i = tid; i < words64; i += BT) tab[i] = 0ull;
+    __syncthreads();
+    rehash_block(st, beam, max_nodes, n_live);
+  }
+}
+hipError_t launch_beam_compact(int32_t* state, const int32_t* status, int B, int beam, int max_nodes, int rebuild_table,
+                               int32_t* live_nodes, hipStream_t st, const BeamSlot* slots) {
+  if (slots) PPASR_LAUNCH(k_beam_compact<true>, dim3(B), dim3(kCompactThreads), 0, st, state, status, slots, beam, max_nodes,
+                          rebuild_table, live_nodes);
+  else PPASR_LAUNCH(k_beam_compact<false>, dim3(B), dim3(kCompactThreads), 0, st, state, status, slots, beam, max_nodes,
+                    rebuild_table, live_nodes);
   return hipGetLastError();
 }
 

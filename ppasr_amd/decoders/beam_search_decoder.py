@@ -88,9 +88,17 @@ class _BeamState:
         self.bytes = int(lib.ppasr_ctc_beam_state_bytes(B, max_frames, beam_size))
         self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device)
         self.B, self.max_frames, self.beam_size = B, max_frames, beam_size
-        self.frames = 0
+        self.frames = 0   # frame-equivalents of the arenas in use; a caller that starts the buffer over sets it to 0
+        self.dropped = 0  # frame-equivalents that compactions took off ``frames`` since the search began
         self.fresh = True
         self.growable = False  # streaming decoder objects: double the buffer instead of failing (the reference has no limit)
+        self.compact = False   # ... and compact the prefix arenas first (BeamSearchDecoder(compact=True))
+        self.rebuild_table = False  # searches with a word-based scorer keep a node table, rebuilt by a compaction
+
+    @property
+    def total(self):
+        """Cumulative frames of the search (bounds the token count of a hypothesis); == frames without compaction."""
+        return self.frames + self.dropped
 
     def grow(self, need_frames):
         """Move the search into a buffer sized for at least ``need_frames`` cumulative frames (doubling)."""
@@ -105,6 +113,22 @@ class _BeamState:
             _lib.check(lib.ppasr_ctc_beam_state_grow(self.buf.data_ptr(), self.bytes, new.data_ptr(), nbytes, self.B,
                                                      self.beam_size, torch.cuda.current_stream(dev).cuda_stream))
         self.buf, self.bytes, self.max_frames = new, nbytes, cap
+
+    def compact_arenas(self):
+        """Compact every block's prefix arena in place (``ppasr_ctc_beam_state_compact``; synchronises) and lower
+        ``frames`` to what the largest block still uses: ceil((L - 1) / beam) for its L live nodes.  -> [L] per block."""
+        lib = _lib.load()
+        live = np.zeros(self.B, np.int32)
+        dev = self.buf.device
+        with torch.cuda.device(dev):
+            _lib.check(lib.ppasr_ctc_beam_state_compact(self.buf.data_ptr(), self.bytes, self.B, self.beam_size,
+                                                        1 if self.rebuild_table else 0, live.ctypes.data_as(ctypes.c_void_p),
+                                                        torch.cuda.current_stream(dev).cuda_stream))
+        if (live >= 1).all():  # (an exhausted block was left as it is: keep the count)
+            used = (int(live.max()) - 1 + self.beam_size - 1) // self.beam_size
+            self.dropped += self.frames - used
+            self.frames = used
+        return [int(v) for v in live]
 
 
 _scratch = {}  # (device, stream) -> uint8 tensor: HBM scratch of searches whose candidate / element lists outgrow LDS
@@ -137,11 +161,19 @@ def beam_search_ids(probs, beam_size, cutoff_prob=1.0, cutoff_top_n=40, blank_id
     B, T, V = p.shape
     if state is None:
         state = _BeamState(B, max_frames if max_frames is not None else T, beam_size, dev)
+    if state.fresh:
+        state.dropped = 0  # (init_state = 1 begins a new search: nothing of an earlier one counts)
     if state.frames + T > state.max_frames:
         if not (state.growable and not state.fresh):
             raise _lib.PPASRHipError("beam-search state buffer exhausted: create the decoder with a larger max_frames")
-        state.grow(state.frames + T)
-    L = max(state.frames + T, 1)
+        if state.compact:
+            # compact first; keep the buffer if at least half of it stays free behind this chunk, else grow until it does
+            state.compact_arenas()
+            if 2 * (state.frames + T) > state.max_frames:
+                state.grow(2 * (state.frames + T))
+        else:
+            state.grow(state.frames + T)
+    L = max(state.total + T, 1)
     tokens = torch.empty(B, nbest, L, dtype=torch.int32, device=dev)
     lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
     scores = torch.empty(B, nbest, dtype=torch.float64, device=dev)
@@ -202,7 +234,13 @@ class BeamSearchDecoder:
     """beam_search_decoder.py:8-96 (same constructor arguments / methods)."""
 
     def __init__(self, alpha, beta, beam_size, cutoff_prob, cutoff_top_n, vocab_list, num_processes=10, blank_id=0,
-                 language_model_path=None, max_stream_frames=5000):
+                 language_model_path=None, max_stream_frames=5000, compact=False):
+        """compact: a streaming decode (``decode_chunk``) whose state buffer is full compacts its prefix arenas -- drops
+        every prefix that is neither in the beam nor an ancestor of a beam entry, as upstream's trie does after every
+        frame -- before it would double the buffer, and grows only if less than half of it came free."""
+        if not isinstance(compact, (bool, np.bool_)):
+            raise ValueError("BeamSearchDecoder: compact must be True or False")
+        self.compact = bool(compact)
         self.alpha, self.beta = alpha, beta
         self.beam_size = int(beam_size)
         self.cutoff_prob, self.cutoff_top_n = cutoff_prob, cutoff_top_n
@@ -248,6 +286,8 @@ class BeamSearchDecoder:
             dev = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
             self._state = _BeamState(p.shape[0], max(self._max_stream_frames, p.shape[1]), self.beam_size, dev)
             self._state.growable = True
+            self._state.compact = self.compact
+            self._state.rebuild_table = self._ext_scorer is not None and not self._ext_scorer.is_character_based()
         lens = np.asarray(logits_lens).astype(np.int32)
         tokens, ln, scores, _ = beam_search_ids(p, self.beam_size, self.cutoff_prob, self.cutoff_top_n, self.blank_id,
                                                 frame_lens=lens, nbest=1, state=self._state, ext_scorer=self._ext_scorer)
@@ -265,10 +305,16 @@ class BeamSearchSessions:
     ``language_model_path`` again; its alpha / beta at construction hold).  ``decode_chunks(sessions, probs)`` advances
     the listed sessions by one chunk each with one pruning and one search launch; each session's (score, text) equals
     what its own ``BeamSearchDecoder.decode_chunk`` sequence returns.  Sessions start with room for ``init_frames``
-    frames and double on demand."""
+    frames and double on demand.  ``compact=True``: a session whose chunk does not fit its block is compacted first (every
+    prefix node that is neither in the beam nor an ancestor of a beam entry is dropped, as upstream's trie does) and
+    grows only if less than half of its block came free, so a long stream stays in bounded memory; ``compact()`` does it
+    on request.  Results do not change (word-based scorers: see ``ppasr_ctc_beam_state_compact`` in the header)."""
 
     def __init__(self, n_sessions, alpha, beta, beam_size, cutoff_prob, cutoff_top_n, vocab_list, num_processes=10,
-                 blank_id=0, language_model_path=None, scorer=None, init_frames=256, device=None):
+                 blank_id=0, language_model_path=None, scorer=None, init_frames=256, device=None, compact=False):
+        if not isinstance(compact, (bool, np.bool_)):
+            raise ValueError("BeamSearchSessions: compact must be True or False")
+        self.auto_compact = bool(compact)
         self.n_sessions, self.beam_size, self.init_frames = int(n_sessions), int(beam_size), int(init_frames)
         self.vocab_list = list(vocab_list)
         self.alpha, self.beta = alpha, beta
@@ -299,6 +345,8 @@ class BeamSearchSessions:
                                                         0.0 if sc is None else sc.beta, self.init_frames, ctypes.byref(h)))
         self._h = h
         self._ws = {}
+        if self.auto_compact:
+            _lib.check(self._lib.ppasr_beam_arena_set_auto(self._h, 1))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -327,6 +375,28 @@ class BeamSearchSessions:
         if not 0 <= int(session) < self.n_sessions:
             raise ValueError(f"BeamSearchSessions.capacity: session {session} out of range")
         return int(self._lib.ppasr_beam_pool_capacity(self._h, int(session)))
+
+    def compact(self, sessions=None):
+        """Compact the prefix arenas of the listed sessions (None: all) with one launch.  -> live node count of each, by
+        list position (-1: a session whose arena was exhausted, left untouched).  Synchronises."""
+        ids = list(range(self.n_sessions)) if sessions is None else [int(s) for s in sessions]
+        n = len(ids)
+        if n < 1 or len(set(ids)) != n or any(not 0 <= s < self.n_sessions for s in ids):
+            raise ValueError("BeamSearchSessions.compact: sessions must be distinct indices in [0, n_sessions)")
+        live = (ctypes.c_longlong * n)()
+        with torch.cuda.device(self._device):
+            _lib.check(self._lib.ppasr_beam_arena_compact(self._h, (ctypes.c_int * n)(*ids), n, live, self._stream()))
+        return [int(v) for v in live]
+
+    def live_nodes(self, session):
+        """Node count read back at the session's last compaction (0: none since its reset)."""
+        if not 0 <= int(session) < self.n_sessions:
+            raise ValueError(f"BeamSearchSessions.live_nodes: session {session} out of range")
+        return int(self._lib.ppasr_beam_arena_live_nodes(self._h, int(session)))
+
+    def arena_bytes(self):
+        """Device bytes of all sessions' state blocks now."""
+        return int(self._lib.ppasr_beam_arena_bytes(self._h))
 
     def status(self):
         """Status words of every session (non-zero: a prefix arena ran out).  Synchronises."""

@@ -35,14 +35,20 @@ class _Session:
 
 class StreamPool:
     def __init__(self, model, vocab_list, n_sessions, preprocess_conf=None, max_seconds=200.0, blank_index=0, group=None,
-                 decoder="ctc_greedy", decoder_conf=None):
+                 decoder="ctc_greedy", decoder_conf=None, beam_compact=False):
         """group: a ready session group for `model` with `n_sessions` slots (e.g. ``SqueezeformerStreamGroup``,
         ``GeneralConformerStreamGroup``); None =
         ``make_stream_group``'s choice.  decoder: "ctc_greedy" or "ctc_beam_search"; decoder_conf: keys of
         ``ctc_beam_search_decoder_conf`` (alpha, beta, beam_size, num_processes, cutoff_prob, cutoff_top_n,
-        language_model_path), over the shipped values without a language model."""
+        language_model_path), over the shipped values without a language model.  beam_compact: the beam-search pool
+        compacts a session's prefix arena before it would grow its block (``BeamSearchSessions(compact=True)``), so that
+        long streams stay in bounded memory; not a decoder_conf key, which mirror the YAML."""
         if decoder not in _DECODERS:
             raise ValueError(f"StreamPool: unknown decoder {decoder!r} (one of {', '.join(_DECODERS)})")
+        if not isinstance(beam_compact, (bool, np.bool_)):
+            raise ValueError("StreamPool: beam_compact must be True or False")
+        if beam_compact and decoder != "ctc_beam_search":
+            raise ValueError("StreamPool: beam_compact applies to decoder='ctc_beam_search' only")
         conf = dict(decoder_conf or {})
         unknown = sorted(set(conf) - set(_BEAM_DEFAULTS))
         if unknown:
@@ -70,7 +76,7 @@ class StreamPool:
         if decoder == "ctc_beam_search":
             from ppasr_amd.decoders.beam_search_decoder import BeamSearchSessions
             self.beam = BeamSearchSessions(n_sessions, vocab_list=self.vocab, blank_id=blank_index,
-                                           **{**_BEAM_DEFAULTS, **conf})
+                                           compact=bool(beam_compact), **{**_BEAM_DEFAULTS, **conf})
 
     def feed(self, session, audio_data, channels=1, samp_width=2):
         """Append PCM bytes or float samples to a session's buffer (what predict_stream does with each packet)."""

@@ -24,7 +24,14 @@ streams from one host thread.  Prints the aggregate audio-seconds/s and the sing
                              against N BeamSearchDecoder objects: the decode stage of one 16-frame round at n = 8 / 64 /
                              256 / 300, beam 10 and the shipped beam 300 (cutoff 0.99 / 40), without and with a synthetic
                              character ARPA scorer; then pool rounds end to end (Conformer group + beam pool)
-  --beam-rounds R --sessions N  R pool decode rounds of N sessions at beam 300 (no scorer), for a rocprofv3 kernel trace"""
+  --decoder beam --stream-frames F [--compact] [--sessions N] [--beam B] [--scorer]
+                             one long stream of F frames per session in 16-frame rounds through the pool (init_frames 16):
+                             the decode stage per round (median, 10th / 90th percentile), block moves, arena_bytes() at the
+                             end and the time of an explicit compact() of the F-frame arenas.  --compact: a second pool with
+                             compact=True takes the same rounds, alternately in this process; adds its rounds with a
+                             compaction (count, time) and the time of a compact() at the arena sizes the policy leaves
+  --beam-rounds R --sessions N [--compact]  R pool decode rounds of N sessions at beam 300 (no scorer), for a rocprofv3
+                             kernel trace (--compact: the pool has compact=True; 16 frames of room, so it compacts)"""
 import json, os, sys, time
 import numpy as np
 import torch
@@ -234,11 +241,69 @@ def beam_end_to_end(sizes=(8, 64, 256), n_chunks=8, reps=2):
         del g, pool
 
 
+def beam_long_streams(n, beam, lm, frames, compact, T=16):
+    """One stream of `frames` frames per session, 16 frames per round; the pool without compaction and (compact) one with
+    it take every round one after the other, so both see the same machine state."""
+    from ppasr_amd.decoders.beam_search_decoder import BeamSearchSessions
+    V = DEFAULT_VOCAB_SIZE
+    vocab, arpa, Scorer = _beam_scorer(V)
+    scorer = Scorer(2.2, 4.3, arpa, vocab) if lm else None
+    sides = {"off": BeamSearchSessions(n, 2.2, 4.3, beam, 0.99, 40, vocab, scorer=scorer, init_frames=T)}
+    if compact:
+        sides["on"] = BeamSearchSessions(n, 2.2, 4.3, beam, 0.99, 40, vocab, scorer=scorer, init_frames=T, compact=True)
+    tables = [_beam_probs(n, T, V, seed=100 + k) for k in range(8)]  # (a cycle of 8 rounds: new characters every round)
+    ids = list(range(n))
+    ms = {k: [] for k in sides}
+    event = {k: [] for k in sides}  # per round: 0 plain, 1 a compaction ran, 2 ... and / or a block moved
+    for k, pool in sides.items():  # warm-up on sessions that are reset afterwards
+        pool.decode_chunks(ids, tables[0])
+        pool.reset()
+    torch.cuda.synchronize()
+    for r in range(frames // T):
+        for k, pool in sides.items():
+            caps = [pool.capacity(s) for s in ids]
+            live = [pool.live_nodes(s) for s in ids]
+            used_before = pool.arena_bytes()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            pool.decode_chunks(ids, tables[r % len(tables)])
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t) * 1e3)
+            moved = pool.arena_bytes() != used_before or [pool.capacity(s) for s in ids] != caps
+            event[k].append(2 if moved else 1 if [pool.live_nodes(s) for s in ids] != live else 0)
+    for k, pool in sides.items():
+        t_all, ev = np.asarray(ms[k]), np.asarray(event[k])
+        plain = t_all[ev == 0]
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        live = pool.compact()
+        explicit_ms = (time.perf_counter() - t) * 1e3
+        out = {"section": "beam_long_streams", "side": k, "sessions": n, "beam": beam, "scorer": "arpa3" if lm else None,
+               "stream_frames": frames, "rounds": len(t_all),
+               "round_ms_median": round(float(np.median(t_all)), 3),
+               "round_ms_p10_p90": [round(float(np.percentile(t_all, q)), 3) for q in (10, 90)],
+               "plain_round_ms_median": round(float(np.median(plain)), 3) if plain.size else None,
+               "rounds_with_block_moves": int((ev == 2).sum()),
+               "rounds_with_compaction_only": int((ev == 1).sum()),
+               "compaction_round_ms_median": round(float(np.median(t_all[ev == 1])), 3) if (ev == 1).any() else None,
+               "move_round_ms_median": round(float(np.median(t_all[ev == 2])), 3) if (ev == 2).any() else None,
+               "capacity_frames_max": max(pool.capacity(s) for s in ids), "arena_bytes": pool.arena_bytes(),
+               "explicit_compact_ms": round(explicit_ms, 3), "explicit_compact_live_nodes_max": max(live)}
+        print(json.dumps(out), flush=True)
+
+
+if "--stream-frames" in sys.argv and _arg("--decoder", "greedy") == "beam":
+    beam_long_streams(_arg("--sessions", 64), _arg("--beam", 300), "--scorer" in sys.argv, _arg("--stream-frames", 4000),
+                      "--compact" in sys.argv)
+    sys.exit(0)
+
 if "--beam-rounds" in sys.argv:
     from ppasr_amd.decoders.beam_search_decoder import BeamSearchSessions
     _n, _R = _arg("--sessions", 64), _arg("--beam-rounds", 4)
     _vocab = [chr(0x4E00 + i) for i in range(DEFAULT_VOCAB_SIZE)]
-    _pool = BeamSearchSessions(_n, 2.2, 4.3, 300, 0.99, 40, _vocab, init_frames=16 * (_R + 1))
+    _compact = "--compact" in sys.argv
+    _pool = BeamSearchSessions(_n, 2.2, 4.3, 300, 0.99, 40, _vocab, init_frames=16 if _compact else 16 * (_R + 1),
+                               compact=_compact)
     _p = _beam_probs(_n, 16, DEFAULT_VOCAB_SIZE, seed=3)
     for _ in range(_R):
         _pool.decode_chunks(list(range(_n)), _p)
