@@ -578,6 +578,31 @@ PPASR_API size_t       ppasr_fbank_workspace_bytes(ppasr_fbank_handle f, int n_s
 PPASR_API ppasr_status ppasr_fbank_compute(ppasr_fbank_handle f, const float* samples, int n_samples, int use_db_norm,
                                  float target_db, float* feats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- batch form: n independent waveforms ("segments") packed back to back in one device buffer, featurized by one set of
+ * launches (three with dB normalisation, one without, whatever n is).  Every segment's features, chunk sums and gain
+ * equal those of a call of its own, byte for byte.  One table entry per segment: */
+typedef struct {
+  long long first_sample; /* index of the segment's first sample in `samples` */
+  long long out_row;      /* row of `feats` that takes the segment's first frame; frame j goes to out_row + j */
+  int n_samples;          /* 0 and counts below one window are legal: no frame */
+  int first_chunk;        /* the segment's first 8192-sample chunk in the workspace's chunk sums */
+  int first_frame;        /* the segment's first frame in the compact numbering 0 .. total_frames - 1 */
+  int reserved;
+} ppasr_fbank_segment;
+/* Host only, no device and no handle: fills table[0 .. n) for segments of n_samples[b] samples in the order given.
+ * t_max == 0: compact rows (out_row = first_frame, feats is [total_frames][n_mels]); t_max > 0: out_row = b * t_max
+ * (feats is [n][t_max][n_mels]; the rows past a segment's frames are not written).  PPASR_EINVAL: a negative count, a
+ * t_max below the longest segment's frame count, more than 2^31 - 1 chunks or frames. */
+PPASR_API ppasr_status ppasr_fbank_plan_batch(int sample_rate, float frame_length_ms, float frame_shift_ms, const int* n_samples,
+                                    int n, int t_max, ppasr_fbank_segment* table, int* total_chunks, int* total_frames);
+/* (workspace: total_chunks floats, the chunk sums, then {gain, gain in dB} per segment for the caller to read) */
+PPASR_API size_t       ppasr_fbank_batch_workspace_bytes(int n, int total_chunks);
+/* Asynchronous on `stream`.  samples, table_dev (a device copy of the planned table), feats, workspace: device memory.
+ * PPASR_ENOSPACE: workspace too small; PPASR_EINVAL: a null argument. */
+PPASR_API ppasr_status ppasr_fbank_compute_batch(ppasr_fbank_handle f, const float* samples, const ppasr_fbank_segment* table_dev,
+                                       int n, int total_chunks, int total_frames, int use_db_norm, float target_db,
+                                       float* feats, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,12 @@ class WeightBlob(ctypes.Structure):
                 ("shape", ctypes.c_int64 * 4)]
 
 
+class FbankSegment(ctypes.Structure):
+    """ppasr_fbank_segment: one waveform of a batch-form fbank call"""
+    _fields_ = [("first_sample", ctypes.c_longlong), ("out_row", ctypes.c_longlong), ("n_samples", ctypes.c_int),
+                ("first_chunk", ctypes.c_int), ("first_frame", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
 class ModelDesc(ctypes.Structure):
     _fields_ = [("model_type", ctypes.c_int), ("input_dim", ctypes.c_int), ("vocab_size", ctypes.c_int),
                 ("output_size", ctypes.c_int), ("attention_heads", ctypes.c_int), ("linear_units", ctypes.c_int),
@@ -167,6 +173,11 @@ SYMBOLS = [
     ("ppasr_fbank_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int]),
     ("ppasr_fbank_compute", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp,
                                            ctypes.c_size_t, _vp]),
+    ("ppasr_fbank_plan_batch", ctypes.c_int, [ctypes.c_int, ctypes.c_float, ctypes.c_float, _vp, ctypes.c_int, ctypes.c_int,
+                                              _vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    ("ppasr_fbank_batch_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    ("ppasr_fbank_compute_batch", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
 ]
 
 _lib = None

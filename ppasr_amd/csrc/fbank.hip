@@ -11,6 +11,7 @@
 // overlap) + 320 B per frame out.  HBM- / latency-bound: 4 B * 160 new samples + 320 B out per frame.
 #include "launch.h"
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 
 #include <algorithm>
@@ -66,7 +67,9 @@ __host__ __device__ __forceinline__ bool pw_node(int h, int n, int& off, int& le
   return true;
 }
 
-__global__ __launch_bounds__(1024) void k_sumsq(const float* __restrict__ x, int n, float* __restrict__ chunk_sum) {
+// The tree of one chunk: `a` = its first sample, `cn` = its length (1 .. 8192); all 1024 threads of the workgroup call it,
+// thread 0 gets the chunk's sum.
+__device__ __forceinline__ float sumsq_chunk(const float* __restrict__ a, int cn) {
   // numpy rounds every square before it is added (x ** 2 is an array of its own): no fused multiply-add here.  hipcc
   // contracts a * b + c -- also when written __fadd_rn(c, __fmul_rn(a, b)): the header's operations carry the contract
   // flag -- into v_fma_f32 under its default -ffp-contract=fast (found in round 6: one ulp of the sum for ~1 length in
@@ -74,8 +77,6 @@ __global__ __launch_bounds__(1024) void k_sumsq(const float* __restrict__ x, int
 #pragma clang fp contract(off)
   __shared__ float val[kPwSlots];
   __shared__ unsigned char inner[kPwSlots];  // 1: node with two children
-  const int c0 = blockIdx.x * kPwChunk, cn = min(kPwChunk, n - c0);
-  const float* a = x + c0;
   const int j = threadIdx.x & 7;  // 8 lanes per heap slot; 128 slots per pass, two passes
   for (int h = threadIdx.x >> 3; h < kPwSlots; h += 128) {
     int off = 0, len = 0;
@@ -117,34 +118,83 @@ __global__ __launch_bounds__(1024) void k_sumsq(const float* __restrict__ x, int
     if ((int)threadIdx.x < (1 << d) && inner[h]) val[h] = val[2 * h] + val[2 * h + 1];
     __syncthreads();
   }
-  if (threadIdx.x == 0) chunk_sum[blockIdx.x] = val[1];
+  return val[1];
 }
 
-// gain of AudioSegment.normalize (audio.py:287-304, gain_db :256-264), once per call: ws[n_chunks] <- the linear gain
-__global__ void k_gain(float* __restrict__ ws, int n_chunks, int n, float target_db) {
+__global__ __launch_bounds__(1024) void k_sumsq(const float* __restrict__ x, int n, float* __restrict__ chunk_sum) {
+  const int c0 = blockIdx.x * kPwChunk, cn = min(kPwChunk, n - c0);
+  const float r = sumsq_chunk(x + c0, cn);
+  if (threadIdx.x == 0) chunk_sum[blockIdx.x] = r;
+}
+
+// ---- segment-table (batch) forms: one launch covers n independent waveforms packed back to back in `x` ----
+// The last segment whose first chunk / first frame is <= key: the segment that owns chunk / frame `key` (segments
+// without chunks / frames share their successor's prefix value and are passed over).  key < the total, so it exists.
+template <int ppasr_fbank_segment::*kFirst>
+__device__ __forceinline__ int segment_of(const ppasr_fbank_segment* __restrict__ seg, int n_seg, int key) {
+  int lo = 0, hi = n_seg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (seg[mid].*kFirst <= key) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// grid = the total number of chunks; chunk numbering restarts in every segment (numpy's order is per waveform)
+__global__ __launch_bounds__(1024) void k_sumsq_batch(const float* __restrict__ x, const ppasr_fbank_segment* __restrict__ seg,
+                                                      int n_seg, float* __restrict__ chunk_sum) {
+  __shared__ long long s_first;
+  __shared__ int s_cn;
+  if (threadIdx.x == 0) {
+    const ppasr_fbank_segment g = seg[segment_of<&ppasr_fbank_segment::first_chunk>(seg, n_seg, (int)blockIdx.x)];
+    const int c0 = ((int)blockIdx.x - g.first_chunk) * kPwChunk;
+    s_first = g.first_sample + c0;
+    s_cn = min(kPwChunk, g.n_samples - c0);
+  }
+  __syncthreads();
+  const float r = sumsq_chunk(x + s_first, s_cn);
+  if (threadIdx.x == 0) chunk_sum[blockIdx.x] = r;
+}
+
+// gain of AudioSegment.normalize (audio.py:287-304, gain_db :256-264): the chunk sums of one waveform of n samples, added in
+// chunk order -> out[0] the linear gain, out[1] the gain in dB
+__device__ __forceinline__ void gain_of(const float* __restrict__ sums, int n_chunks, int n, float target_db,
+                                        float* __restrict__ out) {
   float s = 0.f;
-  for (int c = 0; c < n_chunks; ++c) s = __fadd_rn(s, ws[c]);
+  for (int c = 0; c < n_chunks; ++c) s = __fadd_rn(s, sums[c]);
   // the scalar types numpy 1.x gives the reference here (oracle/fbank_oracle.py; pinned by tests/golden/ref_wav.npz): the
   // mean square and its log10 are float32, 10 * log10, target_db - rms_db and the power are float64, the gain is rounded
-  // to float32 when it scales the float32 samples
-  const float ms = (float)((double)s / (double)n);
+  // to float32 when it scales the float32 samples.  (n == 0, a segment of the batch form only: rms_db 0 like silence)
+  const float ms = n > 0 ? (float)((double)s / (double)n) : 0.f;
   const double rms_db = ms != 0.f ? 10.0 * (double)(float)log10((double)ms) : 0.0;
-  ws[n_chunks] = (float)pow(10.0, ((double)target_db - rms_db) / 20.0);
-  ws[n_chunks + 1] = (float)((double)target_db - rms_db);  // the host raises beyond max_gain_db = 300 like audio.py:301
+  out[0] = (float)pow(10.0, ((double)target_db - rms_db) / 20.0);
+  out[1] = (float)((double)target_db - rms_db);  // the host raises beyond max_gain_db = 300 like audio.py:301
 }
 
-__global__ __launch_bounds__(kFT) void k_fbank(const float* __restrict__ x, int n, const float* __restrict__ gain_p,
-                                               int use_db, float target_db, FbankTables tb, int win, int shift,
-                                               int nfft, int log2n, int n_mels, float* __restrict__ feats) {
+// once per call: ws[n_chunks], ws[n_chunks + 1] <- the gain, the gain in dB
+__global__ void k_gain(float* __restrict__ ws, int n_chunks, int n, float target_db) {
+  gain_of(ws, n_chunks, n, target_db, ws + n_chunks);
+}
+
+// one thread per segment: gains[2 s], gains[2 s + 1] <- the gain of segment s, its gain in dB
+__global__ __launch_bounds__(64) void k_gain_batch(const float* __restrict__ chunk_sum,
+                                                   const ppasr_fbank_segment* __restrict__ seg, int n_seg, float target_db,
+                                                   float* __restrict__ gains) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= n_seg) return;
+  const ppasr_fbank_segment g = seg[s];
+  gain_of(chunk_sum + g.first_chunk, (g.n_samples + kPwChunk - 1) / kPwChunk, g.n_samples, target_db, gains + 2 * (size_t)s);
+}
+
+// One frame, by the 256 threads of a workgroup: `src` = its first sample, `gain` = its waveform's gain (1 without dB
+// normalisation), `out` = its n_mels log-mel values.
+__device__ __forceinline__ void fbank_frame(const float* __restrict__ src, float gain, const FbankTables& tb, int win,
+                                            int nfft, int log2n, int n_mels, float* __restrict__ out) {
   __shared__ float re[kNfftMax], im[kNfftMax];
   __shared__ double dred[4];
-  __shared__ float s_gain, s_mean;
-  const int tid = threadIdx.x, frame = blockIdx.x;
-  if (tid == 0) s_gain = use_db ? *gain_p : 1.0f;
-  __syncthreads();
-  const float gain = s_gain;
+  __shared__ float s_mean;
+  const int tid = threadIdx.x;
   // ---- load: float -> gain -> int16 (clip, truncate) ----
-  const float* src = x + (size_t)frame * shift;
   for (int i = tid; i < nfft; i += kFT) {
     float v = 0.f;
     if (i < win) {
@@ -218,8 +268,38 @@ __global__ __launch_bounds__(kFT) void k_fbank(const float* __restrict__ x, int 
     const float* w = tb.bank + (size_t)tid * (nfft / 2);
     float e = 0.f;
     for (int k = tb.bank_lo[tid]; k < tb.bank_hi[tid]; ++k) e = fmaf(re[k], w[k], e);
-    feats[(size_t)frame * n_mels + tid] = logf(fmaxf(e, 1.1920928955078125e-07f));
+    out[tid] = logf(fmaxf(e, 1.1920928955078125e-07f));
   }
+}
+
+__global__ __launch_bounds__(kFT) void k_fbank(const float* __restrict__ x, int n, const float* __restrict__ gain_p,
+                                               int use_db, float target_db, FbankTables tb, int win, int shift,
+                                               int nfft, int log2n, int n_mels, float* __restrict__ feats) {
+  __shared__ float s_gain;
+  const int frame = blockIdx.x;
+  if (threadIdx.x == 0) s_gain = use_db ? *gain_p : 1.0f;
+  __syncthreads();
+  fbank_frame(x + (size_t)frame * shift, s_gain, tb, win, nfft, log2n, n_mels, feats + (size_t)frame * n_mels);
+}
+
+// grid = the total number of frames (the compact numbering); a frame's output row = its segment's out_row + its number
+// inside the segment, so the same kernel writes a compact [sum frames][n_mels] or a padded [B][Tmax][n_mels] array
+__global__ __launch_bounds__(kFT) void k_fbank_batch(const float* __restrict__ x, const ppasr_fbank_segment* __restrict__ seg,
+                                                     int n_seg, const float* __restrict__ gains, int use_db, FbankTables tb,
+                                                     int win, int shift, int nfft, int log2n, int n_mels,
+                                                     float* __restrict__ feats) {
+  __shared__ long long s_src, s_row;
+  __shared__ float s_gain;
+  if (threadIdx.x == 0) {
+    const int s = segment_of<&ppasr_fbank_segment::first_frame>(seg, n_seg, (int)blockIdx.x);
+    const ppasr_fbank_segment g = seg[s];
+    const int local = (int)blockIdx.x - g.first_frame;
+    s_src = g.first_sample + (long long)local * shift;
+    s_row = g.out_row + local;
+    s_gain = use_db ? gains[2 * (size_t)s] : 1.0f;
+  }
+  __syncthreads();
+  fbank_frame(x + s_src, s_gain, tb, win, nfft, log2n, n_mels, feats + (size_t)s_row * n_mels);
 }
 
 }  // namespace
@@ -340,6 +420,64 @@ ppasr_status ppasr_fbank_compute(ppasr_fbank_handle f, const float* samples, int
   }
   PPASR_LAUNCH(k_fbank, dim3(frames), dim3(kFT), 0, st, samples, n_samples, ws + chunks, use_db_norm, target_db, f->tb,
                      f->win, f->shift, f->nfft, f->log2n, f->n_mels, feats);
+  HIP_TRY(hipGetLastError());
+  return PPASR_OK;
+}
+
+// ---- batch form: n waveforms ("segments") packed back to back, one set of launches ----
+ppasr_status ppasr_fbank_plan_batch(int sample_rate, float frame_length_ms, float frame_shift_ms, const int* n_samples,
+                                    int n, int t_max, ppasr_fbank_segment* table, int* total_chunks, int* total_frames) {
+  if (n < 0 || (n > 0 && (!n_samples || !table)) || !total_chunks || !total_frames || sample_rate <= 0 || t_max < 0)
+    return fail(PPASR_EINVAL, "fbank plan: bad arguments");
+  const int win = (int)(sample_rate * 0.001 * frame_length_ms), shift = (int)(sample_rate * 0.001 * frame_shift_ms);
+  if (win < 2 || shift < 1) return fail(PPASR_EINVAL, "fbank plan: frame length / shift too small");
+  long long sample = 0, chunk = 0, frame = 0;
+  for (int b = 0; b < n; ++b) {
+    const int ns = n_samples[b];
+    if (ns < 0) return fail(PPASR_EINVAL, "fbank plan: negative sample count");
+    const int frames = ns < win ? 0 : 1 + (ns - win) / shift;  // snip_edges
+    if (t_max > 0 && frames > t_max) return fail(PPASR_EINVAL, "fbank plan: a segment has more frames than the row stride");
+    if (chunk > INT_MAX || frame > INT_MAX) return fail(PPASR_EINVAL, "fbank plan: more than 2^31 - 1 chunks or frames");
+    table[b].first_sample = sample;
+    table[b].out_row = t_max > 0 ? (long long)b * t_max : frame;
+    table[b].n_samples = ns;
+    table[b].first_chunk = (int)chunk;
+    table[b].first_frame = (int)frame;
+    table[b].reserved = 0;
+    sample += ns;
+    chunk += (ns + kPwChunk - 1) / kPwChunk;
+    frame += frames;
+  }
+  if (chunk > INT_MAX || frame > INT_MAX) return fail(PPASR_EINVAL, "fbank plan: more than 2^31 - 1 chunks or frames");
+  *total_chunks = (int)chunk;
+  *total_frames = (int)frame;
+  return PPASR_OK;
+}
+
+static size_t fbank_batch_ws_bytes(int n, int total_chunks) {
+  // one float per chunk, then {gain, gain in dB} per segment; never nothing, so that the pointer is a real one
+  return std::max<size_t>(256, ((size_t)std::max(total_chunks, 0) + 2 * (size_t)std::max(n, 0)) * sizeof(float));
+}
+
+size_t ppasr_fbank_batch_workspace_bytes(int n, int total_chunks) { return fbank_batch_ws_bytes(n, total_chunks); }
+
+ppasr_status ppasr_fbank_compute_batch(ppasr_fbank_handle f, const float* samples, const ppasr_fbank_segment* table_dev,
+                                       int n, int total_chunks, int total_frames, int use_db_norm, float target_db,
+                                       float* feats, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!f || !samples || !table_dev || !feats || !workspace) return fail(PPASR_EINVAL, "fbank batch: null argument");
+  if (n < 0 || total_chunks < 0 || total_frames < 0) return fail(PPASR_EINVAL, "fbank batch: negative count");
+  if (workspace_bytes < fbank_batch_ws_bytes(n, total_chunks)) return fail(PPASR_ENOSPACE, "fbank batch: workspace too small");
+  if (n == 0) return PPASR_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* ws = static_cast<float*>(workspace);
+  float* gains = ws + total_chunks;
+  if (use_db_norm) {
+    if (total_chunks > 0) PPASR_LAUNCH(k_sumsq_batch, dim3(total_chunks), dim3(1024), 0, st, samples, table_dev, n, ws);
+    PPASR_LAUNCH(k_gain_batch, dim3((n + 63) / 64), dim3(64), 0, st, ws, table_dev, n, target_db, gains);
+  }
+  if (total_frames > 0)
+    PPASR_LAUNCH(k_fbank_batch, dim3(total_frames), dim3(kFT), 0, st, samples, table_dev, n, gains, use_db_norm, f->tb,
+                 f->win, f->shift, f->nfft, f->log2n, f->n_mels, feats);
   HIP_TRY(hipGetLastError());
   return PPASR_OK;
 }

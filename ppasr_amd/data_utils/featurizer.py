@@ -94,6 +94,8 @@ class AudioFeaturizer:
         self._device = torch.device(device or "cuda:0")
         self._h = None
         self._ws = None
+        self._scratch = {}  # featurize_many's staging buffers (pinned host, device, workspace)
+        self._uploaded = self._queued = None  # events: its last upload has left the pinned buffer / its last call has run
 
     def _handle(self):
         if self._h is None:
@@ -155,6 +157,79 @@ class AudioFeaturizer:
     def featurize(self, samples, sample_rate=None):
         """float32 mono samples -> fbank [T, n_mels] float32 (numpy), the reference's return type."""
         return self.featurize_device(samples, sample_rate).cpu().numpy()
+
+    def _stage(self, key, nbytes, pinned=False):
+        """Staging buffers of ``featurize_many``: owned by the featurizer, grow only."""
+        t = self._scratch.get(key)
+        if t is None or t.numel() < nbytes:
+            t = (torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) if pinned
+                 else torch.empty(nbytes, dtype=torch.uint8, device=self._device))
+            self._scratch[key] = t
+        return t
+
+    def featurize_many(self, waveforms, padded=False):
+        """A list of float32 mono waveforms at the featurizer's rate (numpy or tensor) -> their fbank features on the
+        device, by ONE packed upload and ONE set of launches (``ppasr_fbank_compute_batch``: three with dB normalisation,
+        one without, whatever the number of waveforms).  Every waveform's rows equal ``featurize_device`` on it alone,
+        byte for byte.
+          padded=False: (feats [sum of frames, n_mels], frame_counts [B] int64 numpy) -- waveform b's rows follow b - 1's;
+          padded=True:  (feats [B, Tmax, n_mels], lens [B] int64 tensor) -- what ``get_encoder_out`` takes; the rows
+                        past a waveform's frames are zero.
+        A waveform shorter than one window has no frame.  ``self.last_gains`` holds the gains ([B] float32) afterwards
+        when dB normalisation is on."""
+        from ppasr_amd import _lib
+        h = self._handle()
+        lib, dev = self._lib, self._device
+        wavs = [np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w, np.float32).reshape(-1) for w in waveforms]
+        n = len(wavs)
+        counts = (ctypes.c_int * max(n, 1))(*[int(w.size) for w in wavs])
+        win, shift = int(self._sr * 0.001 * 25.0), int(self._sr * 0.001 * 10.0)
+        frames = np.array([0 if w.size < win else 1 + (w.size - win) // shift for w in wavs], np.int64)
+        t_max = max(int(frames.max()) if n else 0, 1) if padded else 0
+        total = int(sum(w.size for w in wavs))
+        seg_bytes = ctypes.sizeof(_lib.FbankSegment) * n
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            # the pinned buffer: not before the upload that may still read it has finished
+            if self._uploaded is not None:
+                self._uploaded.synchronize()
+            host = self._stage("host", seg_bytes + 4 * total + 4, pinned=True)
+            chunks, n_frames = ctypes.c_int(0), ctypes.c_int(0)
+            _lib.check(lib.ppasr_fbank_plan_batch(self._sr, 25.0, 10.0, ctypes.addressof(counts), n, t_max, host.data_ptr(),
+                                                  ctypes.byref(chunks), ctypes.byref(n_frames)))
+            chunks, n_frames = chunks.value, n_frames.value
+            assert n_frames == int(frames.sum())
+            packed = host[seg_bytes:seg_bytes + 4 * total].view(torch.float32).numpy()
+            off = 0
+            for w in wavs:
+                packed[off:off + w.size] = w
+                off += w.size
+            # the device buffers: a call queued on another stream may still read them
+            if self._queued is not None:
+                cur.wait_event(self._queued)
+            stage = self._stage("stage", seg_bytes + 4 * total + 4)
+            stage[:seg_bytes + 4 * total].copy_(host[:seg_bytes + 4 * total], non_blocking=True)
+            self._uploaded = torch.cuda.Event()
+            self._uploaded.record(cur)
+            ws = self._stage("ws", int(lib.ppasr_fbank_batch_workspace_bytes(n, chunks)))
+            feats = (torch.empty(n, t_max, self._n_mels, dtype=torch.float32, device=dev) if padded
+                     else torch.empty(n_frames, self._n_mels, dtype=torch.float32, device=dev))
+            if padded:
+                feats.zero_()  # the padding rows; the kernel writes the others
+            if n:
+                _lib.check(lib.ppasr_fbank_compute_batch(h, stage.data_ptr() + seg_bytes, stage.data_ptr(), n, chunks,
+                                                         n_frames, int(bool(self._use_db)), float(self._target_db),
+                                                         feats.data_ptr() if feats.numel() else ws.data_ptr(),
+                                                         ws.data_ptr(), ws.numel(), cur.cuda_stream))
+            self._queued = torch.cuda.Event()
+            self._queued.record(cur)
+            if self._use_db:  # the workspace's tail: {gain, gain in dB} per waveform
+                gains = ws[4 * chunks:4 * chunks + 8 * n].view(torch.float32).cpu().numpy().reshape(n, 2)
+                for b in range(n):
+                    if frames[b] > 0:  # (as featurize: a waveform without a frame is not normalised)
+                        check_gain_db(float(gains[b, 1]), self._target_db)
+                self.last_gains = gains[:, 0].copy()
+        return (feats, torch.from_numpy(frames)) if padded else (feats, frames)
 
 
 class TextFeaturizer:

@@ -91,9 +91,49 @@ class StreamPool:
             s.remained_wav = s.remained_wav * db_gain(s.remained_wav, self.featurizer.target_db)
         if feat.shape[0] > 0:
             feat = feat[np.newaxis]
-            s.cached_feat = feat if s.cached_feat is None else np.concatenate([s.cached_feat, feat], axis=1)
+            s.cached_feat = self._joined(s.cached_feat, feat)
             hop = int(round(getattr(self.featurizer, "sample_rate", 16000) * 0.010))  # 10 ms at the featurizer's rate
             s.remained_wav = s.remained_wav[hop * feat.shape[1]:]
+
+    def _joined(self, cached, feat):
+        """cached_feat [1, T, F] + new frames [1, t, F]: numpy while a session is fed by ``feed`` alone, a device tensor
+        from its first ``feed_many`` on (the same float32 values either way)."""
+        if cached is None:
+            return feat
+        if isinstance(cached, np.ndarray) and isinstance(feat, np.ndarray):
+            return np.concatenate([cached, feat], axis=1)
+        dev = self.featurizer._device
+        return torch.cat([torch.as_tensor(cached).to(dev), torch.as_tensor(feat).to(dev)], dim=1)
+
+    def feed_many(self, packets, channels=1, samp_width=2):
+        """``feed`` for many sessions at once: packets = {session: PCM bytes or float samples}.  The listed sessions'
+        buffers go to the device in one upload and are featurized by one set of launches
+        (``AudioFeaturizer.featurize_many``); their features stay on the device (``cached_feat`` becomes a device tensor,
+        ``step`` / ``finish`` cut the windows there).  Every session ends up exactly where ``feed`` would leave it.  An
+        unknown or repeated session index and a refused gain raise ValueError before any session is modified."""
+        ids = [int(i) for i in (packets.keys() if hasattr(packets, "keys") else [p[0] for p in packets])]
+        audio = list(packets.values()) if hasattr(packets, "values") else [p[1] for p in packets]
+        if len(set(ids)) != len(ids) or any(i < 0 or i >= len(self.sessions) for i in ids):
+            raise ValueError(f"StreamPool.feed_many: session indices must be distinct and in 0..{len(self.sessions) - 1}")
+        wavs = []
+        for i, a in zip(ids, audio):
+            s = self.sessions[i]
+            samples = (pcm_bytes_to_float(a, channels, samp_width) if isinstance(a, (bytes, bytearray))
+                       else np.asarray(a, np.float32).reshape(-1))
+            wavs.append(samples if s.remained_wav is None else np.concatenate([s.remained_wav, samples]))
+        feats, counts = self.featurizer.featurize_many(wavs)
+        # (the remainder's gain: on the host, as in feed)
+        if self.featurizer.use_db_normalization:
+            wavs = [w * db_gain(w, self.featurizer.target_db) if w.size else w for w in wavs]
+        hop = int(round(getattr(self.featurizer, "sample_rate", 16000) * 0.010))
+        row = 0
+        for i, w, t in zip(ids, wavs, counts.tolist()):
+            s = self.sessions[i]
+            if t > 0:
+                s.cached_feat = self._joined(s.cached_feat, feats[row:row + t].unsqueeze(0))
+                w = w[hop * t:]
+                row += t
+            s.remained_wav = w
 
     def step(self):
         """Advance, as often as possible, every session that holds a full 67-frame window; -> {session: result dict}
@@ -104,7 +144,12 @@ class StreamPool:
                      if s.cached_feat is not None and s.cached_feat.shape[1] >= _WINDOW]
             if not ready:
                 break
-            chunks = np.concatenate([self.sessions[i].cached_feat[:, :_WINDOW] for i in ready], axis=0)
+            windows = [self.sessions[i].cached_feat[:, :_WINDOW] for i in ready]
+            if all(isinstance(w, np.ndarray) for w in windows):
+                chunks = np.concatenate(windows, axis=0)
+            else:  # sessions fed by feed_many: the windows are cut and stacked on the device
+                dev = self.featurizer._device
+                chunks = torch.cat([torch.as_tensor(w).to(dev) for w in windows], dim=0)
             results = self._advance(ready, chunks)
             for k, i in enumerate(ready):
                 s = self.sessions[i]

@@ -31,7 +31,12 @@ streams from one host thread.  Prints the aggregate audio-seconds/s and the sing
                              compact=True takes the same rounds, alternately in this process; adds its rounds with a
                              compaction (count, time) and the time of a compact() at the arena sizes the policy leaves
   --beam-rounds R --sessions N [--compact]  R pool decode rounds of N sessions at beam 300 (no scorer), for a rocprofv3
-                             kernel trace (--compact: the pool has compact=True; 16 frames of room, so it compacts)"""
+                             kernel trace (--compact: the pool has compact=True; 16 frames of room, so it compacts)
+  --front [--rounds R]       the audio front stage of a serving round on the Conformer group with greedy decoding, n = 8 / 64 /
+                             256 sessions and one 0.64 s packet per session per round: N x StreamPool.feed against one
+                             StreamPool.feed_many, the front stage alone and the whole round (front + step), the two
+                             variants alternating round by round in this process after warm-up; one JSON line per n with the
+                             median and the 10th / 90th percentile over R rounds (default 12)"""
 import json, os, sys, time
 import numpy as np
 import torch
@@ -291,6 +296,65 @@ def beam_long_streams(n, beam, lm, frames, compact, T=16):
                "explicit_compact_ms": round(explicit_ms, 3), "explicit_compact_live_nodes_max": max(live)}
         print(json.dumps(out), flush=True)
 
+
+def front_section(sizes=(8, 64, 256), rounds=12, warmup=3, packet=10240):
+    """ms of the front stage (packets -> cached features) and of the whole round (front + step) per variant; a host clock
+    around work that ends in a device synchronise.  Both pools take the same packets, one round each in turn."""
+    from ppasr_amd.serving import StreamPool
+    from ppasr_amd.utils.synth import synth_vocabulary
+    V = DEFAULT_VOCAB_SIZE
+    model = ConformerModel(80, V, streaming=True, device="cuda:0",
+                           encoder_conf=dict(output_size=256, attention_heads=4, linear_units=2048, num_blocks=12,
+                                             cnn_module_kernel=15),
+                           state_dict=conformer_state_dict(vocab_size=V, num_blocks=12, seed=1234))
+    vocab = synth_vocabulary(V)
+    total = warmup + rounds
+    for n in sizes:
+        rng = np.random.Generator(np.random.PCG64(n))
+        t = np.arange(4 * packet) / 16000.0
+        audio = (0.1 * np.sin(2 * np.pi * (150 + 3 * np.arange(n))[:, None] * t) + 0.03 * rng.standard_normal((n, t.size)))
+        audio = audio.astype(np.float32)
+        pools = {k: StreamPool(model, vocab, n_sessions=n, max_seconds=0.64 * total + 2.0) for k in ("feed", "feed_many")}
+        front = {k: [] for k in pools}
+        whole = {k: [] for k in pools}
+        windows = {k: 0 for k in pools}
+        for r in range(total):
+            lo = (r % 4) * packet
+            packets = {i: audio[i, lo:lo + packet] for i in range(n)}
+            for k, pool in pools.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if k == "feed":
+                    for i, p in packets.items():
+                        pool.feed(i, p)
+                else:
+                    pool.feed_many(packets)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                updated = pool.step()
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                if r >= warmup:
+                    front[k].append((t1 - t0) * 1e3)
+                    whole[k].append((t2 - t0) * 1e3)
+                    windows[k] += len(updated)
+        same = all(a.frame_ids == b.frame_ids for a, b in zip(pools["feed"].sessions, pools["feed_many"].sessions))
+        out = {"section": "front_batch", "sessions": n, "packet_s": packet / 16000.0, "rounds": rounds,
+               "sessions_advanced_per_round": round(windows["feed"] / rounds, 1), "same_frame_ids": bool(same)}
+        for k in pools:
+            out[k] = {"front_ms_median": round(float(np.median(front[k])), 3),
+                      "front_ms_p10_p90": [round(float(np.percentile(front[k], q)), 3) for q in (10, 90)],
+                      "round_ms_median": round(float(np.median(whole[k])), 3),
+                      "round_ms_p10_p90": [round(float(np.percentile(whole[k], q)), 3) for q in (10, 90)]}
+        out["front_ratio"] = round(out["feed"]["front_ms_median"] / out["feed_many"]["front_ms_median"], 2)
+        out["round_ratio"] = round(out["feed"]["round_ms_median"] / out["feed_many"]["round_ms_median"], 2)
+        print(json.dumps(out), flush=True)
+        del pools
+
+
+if "--front" in sys.argv:
+    front_section(rounds=_arg("--rounds", 12))
+    sys.exit(0)
 
 if "--stream-frames" in sys.argv and _arg("--decoder", "greedy") == "beam":
     beam_long_streams(_arg("--sessions", 64), _arg("--beam", 300), "--scorer" in sys.argv, _arg("--stream-frames", 4000),
