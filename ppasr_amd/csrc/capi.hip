@@ -1,5 +1,6 @@
 // capi.hip -- the C-ABI of libppasr_hip.so (declared in include/ppasr_hip.h).
-// Host side: weight re-packing into MFMA fragment order, workspace carving, launch sequence.
+// Host side: descriptor checks and the dispatch of ppasr_create (the weights: weights.h and the families' *_create),
+// workspace carving, launch sequence.
 #include <cxxabi.h>
 #include <cstdlib>
 
@@ -12,53 +13,16 @@ thread_local LaunchProf g_launch_prof;  // launch.h
 static thread_local std::string g_err;
 std::string& ppasr_err_slot() { return g_err; }
 
-
-ppasr_status upload_pe_table(ppasr_model_s* m, BlobMap& sd, const float** pe_dev) {
-  const int d = m->desc.output_size > 0 ? m->desc.output_size : kD;
-  const int max_len = m->desc.max_len > 0 ? m->desc.max_len : 5000;
-  m->desc.max_len = max_len;
-  std::vector<float> pe((size_t)max_len * d);
-  auto it = sd.find("__pe_table__");
-  if (it != sd.end() && it->second.numel() == pe.size()) {
-    std::memcpy(pe.data(), it->second.p, pe.size() * sizeof(float));
-  } else {  // PositionalEncoding.__init__ (embedding.py:38-53)
-    for (int i = 0; i < d / 2; ++i) {
-      float div = expf((float)(2 * i) * (float)(-(std::log(10000.0) / d)));
-      for (int pos = 0; pos < max_len; ++pos) {
-        float a = (float)pos * div;
-        pe[(size_t)pos * d + 2 * i] = sinf(a);
-        pe[(size_t)pos * d + 2 * i + 1] = cosf(a);
-      }
-    }
-  }
-  return m->upload(pe, pe_dev);
-}
-
-extern "C" {
-
-const char* ppasr_last_error(void) { return g_err.c_str(); }
-const char* ppasr_version(void) { return "ppasr_hip 0.1 (gfx950, fp32 MFMA)"; }
-
-ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob* blobs, int n_blobs, ppasr_handle* out) {
-  if (!desc || !blobs || !out) return fail(PPASR_EINVAL, "null argument");
+// The checks of ppasr_create that need no weights, in their order of precedence; fills what they derive: m->desc (the
+// Efficient-Conformer's stride layers in one representation), the route (m->generic, m->gen) and the front-end geometry.
+static ppasr_status validate_desc(const ppasr_model_desc* desc, ppasr_model_s* m) {
+  m->desc = *desc;
+  const int F = desc->input_dim;
   if (desc->model_type == PPASR_MODEL_DEEPSPEECH2) {
-    if (desc->input_dim > 128 || desc->input_dim < 7) return fail(PPASR_EUNSUPPORTED, "input_dim out of range");
-    HIP_TRY(configure_kernels());
-    BlobMap sd2;
-    for (int i = 0; i < n_blobs; ++i) {
-      Blob b{blobs[i].data_host, blobs[i].ndim, {0, 0, 0, 0}};
-      for (int j = 0; j < blobs[i].ndim && j < 4; ++j) b.shape[j] = blobs[i].shape[j];
-      sd2[blobs[i].name] = b;
-    }
-    std::unique_ptr<ppasr_model_s> g2(new ppasr_model_s());
-    g2->desc = *desc;
-    g2->F1 = (desc->input_dim - 1) / 2;
-    g2->F2 = (g2->F1 - 1) / 2;
-    if (g2->F1 > 40) return fail(PPASR_EUNSUPPORTED, "deepspeech2: input_dim <= 82 ((input_dim - 1) / 2 <= 40)");
-    ppasr_status s2 = ds2_create(g2.get(), sd2);
-    if (s2 != PPASR_OK) return s2;
-    HIP_TRY(hipDeviceSynchronize());
-    *out = g2.release();
+    if (F > 128 || F < 7) return fail(PPASR_EUNSUPPORTED, "input_dim out of range");
+    m->F1 = (F - 1) / 2;
+    m->F2 = (m->F1 - 1) / 2;
+    if (m->F1 > 40) return fail(PPASR_EUNSUPPORTED, "deepspeech2: input_dim <= 82 ((input_dim - 1) / 2 <= 40)");
     return PPASR_OK;
   }
   if (desc->model_type != PPASR_MODEL_CONFORMER && desc->model_type != PPASR_MODEL_SQUEEZEFORMER &&
@@ -115,37 +79,10 @@ ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob*
     return fail(PPASR_EUNSUPPORTED, "squeezeformer: cnn_module_kernel must be 15 or 31");
   if (desc->input_dim > 128 || (desc->input_dim < 7 && desc->input_layer != 1) || desc->input_dim < 1)
     return fail(PPASR_EUNSUPPORTED, "input_dim out of range");
-  HIP_TRY(configure_kernels());
-  HIP_TRY(configure_generic_kernels());
-  HIP_TRY(configure_squeezeformer_kernels());
-
-  BlobMap sd;
-  for (int i = 0; i < n_blobs; ++i) {
-    Blob b{blobs[i].data_host, blobs[i].ndim, {0, 0, 0, 0}};
-    for (int j = 0; j < blobs[i].ndim && j < 4; ++j) b.shape[j] = blobs[i].shape[j];
-    sd[blobs[i].name] = b;
-  }
-  std::string missing;
-  auto get = [&](const std::string& name, size_t numel) -> const float* {
-    auto it = sd.find(name);
-    if (it == sd.end() || it->second.numel() != numel) {
-      missing = name;
-      return nullptr;
-    }
-    return it->second.p;
-  };
-#define GET(var, name, numel)                         \
-  const float* var = get(name, (size_t)(numel));      \
-  if (!var) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + missing)
-
-  auto* m = new ppasr_model_s();
-  std::unique_ptr<ppasr_model_s> guard(m);
-  m->desc = *desc;
   if (eff) {  // one representation inside: the mask, and stride_layer_idx = its first (for the shipped shape: only) layer
     m->desc.stride_layer_mask = (int)smask;
     m->desc.stride_layer_idx = smask ? __builtin_ctz(smask) : -1;
   }
-  const int F = desc->input_dim, d = desc->output_size, H = desc->linear_units, V = desc->vocab_size, KS = desc->cnn_module_kernel;
   const int il = desc->input_layer;
   if (il != 0 && il != 1 && il != 6 && il != 8)
     return fail(PPASR_EINVAL, "input_layer: 0 (conv2d), 1 (linear), 6 (conv2d6) or 8 (conv2d8)");
@@ -157,7 +94,6 @@ ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob*
   m->gen.use_cnn = !(desc->options & PPASR_OPT_NO_CNN);
   m->gen.act = (desc->options >> PPASR_OPT_ACT_SHIFT) & PPASR_OPT_ACT_MASK;
   m->gen.sq_pre_norm = (desc->options & PPASR_OPT_SQ_PRE_NORM) != 0;
-  const auto& go = m->gen;
   if (il != 0 && desc->model_type == PPASR_MODEL_SQUEEZEFORMER)
     return fail(PPASR_EUNSUPPORTED, "squeezeformer: only the conv2d front end is built");
   m->F1 = (F - 1) / 2;
@@ -167,260 +103,33 @@ ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob*
   m->F2 = il == 6 ? (m->F1 - 5) / 3 + 1 : (m->F1 - 1) / 2;
   m->F3 = il == 8 ? (m->F2 - 1) / 2 : 0;
   if (il != 1 && m->F_last() < 1) return fail(PPASR_EINVAL, "input_dim too small for this input_layer");
-  const int F2 = m->F_last();  // feature bins entering the linear layer
-  ppasr_status st;
-#define UP(vec, dst) \
-  if ((st = m->upload(vec, &(dst))) != PPASR_OK) return st
-#define UP4(vec, dst) \
-  if ((st = m->upload4(vec, &(dst))) != PPASR_OK) return st
-  auto vec_of = [](const float* p, size_t n) { return std::vector<float>(p, p + n); };
+  return PPASR_OK;
+}
 
-  if (desc->model_type == PPASR_MODEL_SQUEEZEFORMER) {
-    const float* pe_sq = nullptr;
-    if ((st = upload_pe_table(m, sd, &pe_sq)) != PPASR_OK) return st;
-    if ((st = squeezeformer_create(m, sd, pe_sq)) != PPASR_OK) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    *out = guard.release();
-    return PPASR_OK;
-  }
-  if (il == 1) {  // ---- LinearNoSubsampling (subsampling.py:24-65): out.0 = Linear(idim, odim), out.1 = LayerNorm(eps 1e-12), ReLU ----
-    GET(mean, "encoder.global_cmvn.mean", F);
-    GET(istd, "encoder.global_cmvn.istd", F);
-    GET(ew, "encoder.embed.out.0.weight", (size_t)F * d);
-    GET(eb, "encoder.embed.out.0.bias", d);
-    GET(lg, "encoder.embed.out.1.weight", d);
-    GET(lb, "encoder.embed.out.1.bias", d);
-    UP(vec_of(mean, F), m->front.cmvn_mean);
-    UP(vec_of(istd, F), m->front.cmvn_istd);
-    m->lin_kpad = (F + 255) / 256 * 256;  // the feature rows are zero-padded to whole K chunks (k_g_cmvn_pad)
-    UP4(pack_b(m->lin_kpad, d, [&](int k, int n) { return k < F ? ew[(size_t)k * d + n] : 0.f; }), m->front.embed_w);
-    UP(vec_of(eb, d), m->front.embed_b);
-    UP(vec_of(lg, d), m->lin_ln_g);
-    UP(vec_of(lb, d), m->lin_ln_b);
-    m->front.conv1_w = m->front.conv1_b = m->front.conv2_b = nullptr;
-    m->front.conv2_w = nullptr;
-  } else {  // ---- conv front ends ----
-    GET(mean, "encoder.global_cmvn.mean", F);
-    GET(istd, "encoder.global_cmvn.istd", F);
-    GET(c1w, "encoder.embed.conv.0.weight", d * 9);
-    GET(c1b, "encoder.embed.conv.0.bias", d);
-    const int k2 = il == 6 ? 5 : 3;  // Conv2dSubsampling6: Conv2D(odim, odim, 5, 3) (subsampling.py:139-141)
-    GET(c2w, "encoder.embed.conv.2.weight", (size_t)d * d * k2 * k2);
-    GET(c2b, "encoder.embed.conv.2.bias", d);
-    // Conv2dSubsampling4 names its projection `out` (a Sequential), the 6x / 8x classes `linear` (subsampling.py:142,189)
-    const std::string lin = il ? "encoder.embed.linear" : "encoder.embed.out.0";
-    GET(ew, lin + ".weight", (size_t)d * F2 * d);
-    GET(eb, lin + ".bias", d);
-    UP(vec_of(mean, F), m->front.cmvn_mean);
-    UP(vec_of(istd, F), m->front.cmvn_istd);
-    std::vector<float> c1(9 * d);
-    for (int c = 0; c < d; ++c)
-      for (int j = 0; j < 9; ++j) c1[j * d + c] = c1w[c * 9 + j];
-    UP(c1, m->front.conv1_w);
-    UP(vec_of(c1b, d), m->front.conv1_b);
-    // conv2: K index = (kh*k+kw)*256 + cin ; weight layout [cout][cin][kh][kw]
-    const int taps2 = k2 * k2;
-    auto c2 = [&](int k, int n) { return c2w[((size_t)n * d + (k % d)) * taps2 + (k / d)]; };
-    UP4(pack_b(taps2 * d, d, c2), m->front.conv2_w);
-    m->front.conv2_wp = nullptr;
-    if (il == 0 && d == kD) UP4(pack_conv2_quad(d, c2), m->front.conv2_wp);  // (batched calls: front_fused.hip)
-    UP(vec_of(c2b, d), m->front.conv2_b);
-    m->front.conv2_k = k2;
-    m->front.conv2_s = il == 6 ? 3 : 2;
-    m->front.conv3_w = nullptr;
-    m->front.conv3_b = nullptr;
-    if (il == 8) {  // third Conv2D(odim, odim, 3, 2) (subsampling.py:183-187)
-      GET(c3w, "encoder.embed.conv.4.weight", (size_t)d * d * 9);
-      GET(c3b, "encoder.embed.conv.4.bias", d);
-      UP4(pack_b(9 * d, d, [&](int k, int n) { return c3w[((size_t)n * d + (k % d)) * 9 + (k / d)]; }), m->front.conv3_w);
-      UP(vec_of(c3b, d), m->front.conv3_b);
-    }
-    // embed: our K index = f*256 + c ; Paddle's = c*F2 + f (subsampling.py:113 transpose+reshape)
-    UP4(pack_b(F2 * d, d, [&](int k, int n) { return ew[((size_t)(k % d) * F2 + (k / d)) * d + n]; }), m->front.embed_w);
-    UP(vec_of(eb, d), m->front.embed_b);
-  }
+extern "C" {
 
-  const float* pe_dev = nullptr;
-  if ((st = upload_pe_table(m, sd, &pe_dev)) != PPASR_OK) return st;
-  m->pe_dev = pe_dev;
-  UP(std::vector<float>(d, 0.f), m->zero_vec);
-  if (generic) m->gen_x.resize(desc->num_blocks);
-  const int max_len = m->desc.max_len;
-  m->layers.resize(desc->num_blocks);
-  m->layer_ks.assign(desc->num_blocks, KS);
-  m->layer_group.assign(desc->num_blocks, 1);
-  for (int i = 0; i < desc->num_blocks; ++i) {
-    LayerW& L = m->layers[i];
-    // Efficient-Conformer: kernel halves after the stride layer (encoder.py:123-128), grouped attention layers
-    const int KSi = eff ? (KS >> eff_strides_before(*desc, i)) : KS;  // (cnn_module_kernels: // 2 per stride layer passed)
-    const bool grouped = eff && ((desc->group_layer_mask >> i) & 1);
-    m->layer_ks[i] = KSi;
-    m->layer_group[i] = grouped ? desc->group_size : 1;
-    const int pbn = grouped ? desc->group_size * d : d;  // pos_bias_u/v are [h][dk*group_size] on grouped layers
-    const std::string p = "encoder.encoders." + std::to_string(i) + ".";
-    auto ln = [&](const std::string& n, const float** g, const float** b) -> ppasr_status {
-      const float* gw = get(p + n + ".weight", d);
-      const float* gb = get(p + n + ".bias", d);
-      if (!gw || !gb) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + missing);
-      ppasr_status s1 = m->upload(vec_of(gw, d), g);
-      if (s1 != PPASR_OK) return s1;
-      return m->upload(vec_of(gb, d), b);
-    };
-    L = LayerW{};
-    // (encoder.py:327-336: norm_ff_macaron exists with the macaron half only, norm_conv / norm_final with the conv module only)
-    if (go.macaron && (st = ln("norm_ff_macaron", &L.ln_mac_g, &L.ln_mac_b)) != PPASR_OK) return st;
-    if ((st = ln("norm_mha", &L.ln_mha_g, &L.ln_mha_b)) != PPASR_OK) return st;
-    if (go.use_cnn && (st = ln("norm_conv", &L.ln_conv_g, &L.ln_conv_b)) != PPASR_OK) return st;
-    if ((st = ln("norm_ff", &L.ln_ff_g, &L.ln_ff_b)) != PPASR_OK) return st;
-    if (go.use_cnn && (st = ln("norm_final", &L.ln_fin_g, &L.ln_fin_b)) != PPASR_OK) return st;
-    // ConvolutionModule.norm (convolution.py:65-71): nn.LayerNorm, or nn.BatchNorm1D (cnn_module_norm: batch_norm), which
-    // at inference is the per-channel affine y = (x - _mean) / sqrt(_variance + 1e-5) * weight + bias: folded here into
-    // scale / shift vectors in the LayerNorm slots, marked by cm_eps < 0 (ln_rows_inreg then skips the row statistics)
-    L.cm_eps = 1e-5f;
-    if (!go.use_cnn) {
-    } else if (sd.find(p + "conv_module.norm._mean") != sd.end()) {
-      const float* mean = get(p + "conv_module.norm._mean", d);
-      const float* var = get(p + "conv_module.norm._variance", d);
-      const float* gw = get(p + "conv_module.norm.weight", d);
-      const float* gb = get(p + "conv_module.norm.bias", d);
-      if (!mean || !var || !gw || !gb) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + missing);
-      std::vector<float> sc(d), sh(d);
-      for (int c = 0; c < d; ++c) {
-        sc[c] = gw[c] / std::sqrt(var[c] + 1e-5f);
-        sh[c] = gb[c] - mean[c] * sc[c];
-      }
-      if ((st = m->upload(sc, &L.ln_cm_g)) != PPASR_OK || (st = m->upload(sh, &L.ln_cm_b)) != PPASR_OK) return st;
-      L.cm_eps = -1.f;
-    } else if ((st = ln("conv_module.norm", &L.ln_cm_g, &L.ln_cm_b)) != PPASR_OK) {
-      return st;
-    }
-    auto ffn = [&](const std::string& n, const f32x4** w1, const float** b1, const f32x4** w2,
-                   const float** b2) -> ppasr_status {
-      const float* a1 = get(p + n + ".w_1.weight", (size_t)d * H);
-      const float* c1 = get(p + n + ".w_1.bias", H);
-      const float* a2 = get(p + n + ".w_2.weight", (size_t)H * d);
-      const float* c2 = get(p + n + ".w_2.bias", d);
-      if (!a1 || !c1 || !a2 || !c2) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + missing);
-      ppasr_status s;
-      if ((s = m->upload4(pack_b(d, H, [&](int k, int nn) { return a1[(size_t)k * H + nn]; }), w1)) != PPASR_OK) return s;
-      if ((s = m->upload(vec_of(c1, H), b1)) != PPASR_OK) return s;
-      if ((s = m->upload4(pack_b(H, d, [&](int k, int nn) { return a2[(size_t)k * d + nn]; }), w2)) != PPASR_OK) return s;
-      return m->upload(vec_of(c2, d), b2);
-    };
-    if (go.macaron && (st = ffn("feed_forward_macaron", &L.ffm_w1, &L.ffm_b1, &L.ffm_w2, &L.ffm_b2)) != PPASR_OK) return st;
-    if ((st = ffn("feed_forward", &L.ff_w1, &L.ff_b1, &L.ff_w2, &L.ff_b2)) != PPASR_OK) return st;
-    {
-      GET(wq, p + "self_attn.linear_q.weight", d * d);
-      GET(wk, p + "self_attn.linear_k.weight", d * d);
-      GET(wv, p + "self_attn.linear_v.weight", d * d);
-      GET(bq, p + "self_attn.linear_q.bias", d);
-      GET(bk, p + "self_attn.linear_k.bias", d);
-      GET(bv, p + "self_attn.linear_v.bias", d);
-      GET(wo, p + "self_attn.linear_out.weight", d * d);
-      GET(bo, p + "self_attn.linear_out.bias", d);
-      const bool rel = go.pos == PPASR_OPT_POS_REL;  // MultiHeadedAttention (abs_pos / no_pos) has no positional parameters
-      const float *wp = nullptr, *pu = nullptr, *pv = nullptr;
-      if (rel) {
-        wp = get(p + "self_attn.linear_pos.weight", (size_t)d * d);
-        pu = get(p + "self_attn.pos_bias_u", pbn);
-        pv = get(p + "self_attn.pos_bias_v", pbn);
-        if (!wp || !pu || !pv) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + missing);
-      }
-      const float* bp = nullptr;  // linear_pos has a bias only in GroupedRelPositionMultiHeadedAttention
-      if (grouped) {
-        bp = get(p + "self_attn.linear_pos.bias", d);
-        if (!bp) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + missing);
-      }
-      const float* ws[3] = {wq, wk, wv};
-      UP4(pack_b(d, 3 * d, [&](int k, int n) { return ws[n / d][(size_t)k * d + (n % d)]; }), L.wqkv);
-      std::vector<float> bqkv(3 * d);
-      std::memcpy(&bqkv[0], bq, d * sizeof(float));
-      std::memcpy(&bqkv[d], bk, d * sizeof(float));
-      std::memcpy(&bqkv[2 * d], bv, d * sizeof(float));
-      UP(bqkv, L.bqkv);
-      UP4(pack_b(d, d, [&](int k, int n) { return wo[(size_t)k * d + n]; }), L.wo);
-      UP(vec_of(bo, d), L.bo);
-      if (rel) {
-        UP(vec_of(pu, pbn), L.pos_u);
-        UP(vec_of(pv, pbn), L.pos_v);
-        const float* bpos_dev = nullptr;
-        if (bp) UP(vec_of(bp, d), bpos_dev);
-        const float* wpos_dev = nullptr;
-        UP(vec_of(wp, (size_t)d * d), wpos_dev);
-        void* pt = nullptr;
-        HIP_TRY(hipMalloc(&pt, (size_t)max_len * d * sizeof(float)));
-        m->allocs.push_back(pt);
-        launch_posproj(pe_dev, wpos_dev, bpos_dev, static_cast<float*>(pt), max_len, nullptr, d);
-        HIP_TRY(hipGetLastError());
-        L.ptab = static_cast<const float*>(pt);
-        if (!grouped && d == kD && desc->attention_heads == 4) {  // plain 4 x 64 heads: the layers k_attn_out_glu can run
-          void* dt = nullptr;
-          HIP_TRY(hipMalloc(&dt, (size_t)4 * max_len * sizeof(float)));
-          m->allocs.push_back(dt);
-          launch_pos_dtab(L.ptab, L.pos_u, L.pos_v, static_cast<float*>(dt), max_len, nullptr);
-          HIP_TRY(hipGetLastError());
-          L.dtab = static_cast<const float*>(dt);
-        }
-      } else {  // the attention kernel's positional half contracts with zeros (capi_generic.hip)
-        L.pos_u = L.pos_v = L.ptab = m->zero_vec;
-      }
-      if (go.concat_after) {  // concat_linear = Linear(2 size, size) (encoder.py:341-342)
-        GET(wc, p + "concat_linear.weight", (size_t)2 * d * d);
-        GET(bc, p + "concat_linear.bias", d);
-        UP4(pack_b(2 * d, d, [&](int k, int n) { return wc[(size_t)k * d + n]; }), m->gen_x[i].wcat);
-        UP(vec_of(bc, d), m->gen_x[i].bcat);
-      }
-    }
-    if (go.use_cnn) {
-      GET(p1w, p + "conv_module.pointwise_conv1.weight", 2 * d * d);
-      GET(p1b, p + "conv_module.pointwise_conv1.bias", 2 * d);
-      GET(dww, p + "conv_module.depthwise_conv.weight", d * KSi);
-      GET(dwb, p + "conv_module.depthwise_conv.bias", d);
-      GET(p2w, p + "conv_module.pointwise_conv2.weight", d * d);
-      GET(p2b, p + "conv_module.pointwise_conv2.bias", d);
-      // Conv1D weight [out][in][1]: W[k][n] = w[n][k]; GLU value = channels [0,256), gate = [256,512)
-      UP4(pack_b(d, 2 * d, [&](int k, int n) { return p1w[(size_t)n * d + k]; }), L.pw1);
-      std::vector<float> b1p(p1b, p1b + 2 * d), gp(d);
-      for (int c = 0; c < d; ++c) gp[c] = p1b[c] * (1.0f / (1.0f + expf(-p1b[c + d])));
-      UP(b1p, L.pw1_b);
-      UP(gp, L.glu_pad);
-      std::vector<float> dwt((size_t)KSi * d);
-      for (int c = 0; c < d; ++c)
-        for (int j = 0; j < KSi; ++j) dwt[(size_t)j * d + c] = dww[(size_t)c * KSi + j];
-      UP(dwt, L.dw_w);
-      UP(vec_of(dwb, d), L.dw_b);
-      UP4(pack_b(d, d, [&](int k, int n) { return p2w[(size_t)n * d + k]; }), L.pw2);
-      UP(vec_of(p2b, d), L.pw2_b);
-    }
+const char* ppasr_last_error(void) { return g_err.c_str(); }
+const char* ppasr_version(void) { return "ppasr_hip 0.1 (gfx950, fp32 MFMA)"; }
+
+ppasr_status ppasr_create(const ppasr_model_desc* desc, const ppasr_weight_blob* blobs, int n_blobs, ppasr_handle* out) {
+  if (!desc || !blobs || !out) return fail(PPASR_EINVAL, "null argument");
+  std::unique_ptr<ppasr_model_s> m(new ppasr_model_s());
+  LOAD_TRY(validate_desc(desc, m.get()));
+  HIP_TRY(configure_kernels());
+  if (desc->model_type != PPASR_MODEL_DEEPSPEECH2) {
+    HIP_TRY(configure_generic_kernels());
+    HIP_TRY(configure_squeezeformer_kernels());
   }
-  {
-    GET(ag, "encoder.after_norm.weight", d);
-    GET(ab, "encoder.after_norm.bias", d);
-    GET(cw, "ctc.ctc_lo.weight", (size_t)d * V);
-    GET(cb, "ctc.ctc_lo.bias", V);
-    UP(vec_of(ag, d), m->head.ln_g);
-    UP(vec_of(ab, d), m->head.ln_b);
-    m->head.V = V;
-    m->head.n_tiles = (V + 31) / 32;
-    UP4(pack_b(d, V, [&](int k, int n) { return cw[(size_t)k * V + n]; }), m->head.w);
-    std::vector<float> cbp((size_t)m->head.n_tiles * 32, 0.f);
-    std::memcpy(cbp.data(), cb, V * sizeof(float));
-    UP(cbp, m->head.b);
-    if (generic) {  // general route: the head as a plain dense layer, vocabulary padded to whole 256-column blocks
-      m->gen_vpad = (V + 255) / 256 * 256;
-      const int Vp = m->gen_vpad;
-      UP4(pack_b(d, Vp, [&](int k, int n) { return n < V ? cw[(size_t)k * V + n] : 0.f; }), m->gen_head_w);
-      std::vector<float> hb(Vp, 0.f);
-      std::memcpy(hb.data(), cb, V * sizeof(float));
-      UP(hb, m->gen_head_b);
-    }
+  const BlobMap sd = blob_map(blobs, n_blobs);
+  Loader ld{m.get(), sd, ""};
+  switch (desc->model_type) {
+    case PPASR_MODEL_DEEPSPEECH2: LOAD_TRY(ds2_create(m.get(), ld)); break;
+    case PPASR_MODEL_SQUEEZEFORMER: LOAD_TRY(squeezeformer_create(m.get(), ld)); break;
+    default: LOAD_TRY(conformer_create(m.get(), ld));
   }
   HIP_TRY(hipDeviceSynchronize());
-  *out = guard.release();
+  *out = m.release();
   return PPASR_OK;
-#undef GET
-#undef UP
-#undef UP4
 }
 
 ppasr_status ppasr_destroy(ppasr_handle h) {
@@ -629,8 +338,7 @@ static ppasr_status guard_alloc(ppasr_handle h) {
   for (int i = 0; i < N; ++i)
     if (!h->guard_ctr[i]) return fail(PPASR_EHIP, "fp16 x3 range guard: counter symbols not found");
   void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, 2 * N * sizeof(unsigned int)));
-  h->allocs.push_back(d);
+  LOAD_TRY(h->alloc(2 * N * sizeof(unsigned int), &d));
   h->guard_dev = static_cast<unsigned int*>(d);
   void* p = nullptr;
   HIP_TRY(hipHostMalloc(&p, 2 * N * sizeof(unsigned int), hipHostMallocDefault));
@@ -671,6 +379,14 @@ ppasr_status ppasr_set_gemm_mode(ppasr_handle h, int mode) {
     struct OvfFree { unsigned int* p; ~OvfFree() { (void)hipFree(p); } } w_ovf_free{w_ovf};
     HIP_TRY(hipMemset(w_ovf, 0, sizeof(unsigned int)));
     const size_t alloc_mark = h->allocs.size();  // re-packed copies made by THIS call start here (freed if the mode is refused)
+    // a weight [32 n_tiles columns][8 G deep] as scaled fp16 pieces in a block of its own; *w then points at the copy
+    auto repack = [&](const f32x4** w, int n_tiles, int G) -> ppasr_status {
+      void* dst = nullptr;
+      LOAD_TRY(h->alloc((size_t)n_tiles * G * 256 * sizeof(float), &dst));
+      launch_repack_h3(*w, static_cast<f32x4*>(dst), n_tiles, G, w_ovf, nullptr);
+      *w = static_cast<const f32x4*>(dst);
+      return PPASR_OK;
+    };
     HIP_TRY(hipDeviceSynchronize());
     if (layers_ok && h->layers_h3.empty()) {
       std::vector<LayerW> view = h->layers;
@@ -680,18 +396,11 @@ ppasr_status ppasr_set_gemm_mode(ppasr_handle h, int mode) {
         struct { const f32x4** w; int n_tiles, G; } items[8] = {
             {&L.ffm_w1, H / 32, d / 8}, {&L.ffm_w2, d / 32, H / 8}, {&L.ff_w1, H / 32, d / 8}, {&L.ff_w2, d / 32, H / 8},
             {&L.wqkv, 3 * d / 32, d / 8}, {&L.wo, d / 32, d / 8},   {&L.pw1, 2 * d / 32, d / 8}, {&L.pw2, d / 32, d / 8}};
-        for (auto& it : items) {
-          void* dst = nullptr;
-          HIP_TRY(hipMalloc(&dst, (size_t)it.n_tiles * it.G * 256 * sizeof(float)));
-          h->allocs.push_back(dst);
-          launch_repack_h3(*it.w, static_cast<f32x4*>(dst), it.n_tiles, it.G, w_ovf, nullptr);
-          *it.w = static_cast<const f32x4*>(dst);
-        }
+        for (auto& it : items) LOAD_TRY(repack(it.w, it.n_tiles, it.G));
         // the layer's projected positional table as operand planes (the fused attention's score MFMAs in the mode)
         if (L.ptab != h->zero_vec) {
           void* dst = nullptr;
-          HIP_TRY(hipMalloc(&dst, (size_t)h->desc.max_len * d * sizeof(float)));
-          h->allocs.push_back(dst);
+          LOAD_TRY(h->alloc((size_t)h->desc.max_len * d * sizeof(float), &dst));
           launch_split_rows_h3(L.ptab, static_cast<float*>(dst), h->desc.max_len, w_ovf, nullptr);
           L.ptab = static_cast<const float*>(dst);
         }
@@ -704,44 +413,28 @@ ppasr_status ppasr_set_gemm_mode(ppasr_handle h, int mode) {
       std::vector<SqLayerW> view = h->sq_layers;
       for (SqLayerW& L : view) {
         const f32x4** w[4] = {&L.ff1_w1, &L.ff1_w2, &L.ff2_w1, &L.ff2_w2};
-        for (int j = 0; j < 4; ++j) {
-          void* dst = nullptr;
-          HIP_TRY(hipMalloc(&dst, (size_t)d * H * sizeof(float)));
-          h->allocs.push_back(dst);
-          launch_repack_h3(*w[j], static_cast<f32x4*>(dst), (j & 1) ? d / 32 : H / 32, (j & 1) ? H / 8 : d / 8, w_ovf, nullptr);
-          *w[j] = static_cast<const f32x4*>(dst);
-        }
+        for (int j = 0; j < 4; ++j) LOAD_TRY(repack(w[j], (j & 1) ? d / 32 : H / 32, (j & 1) ? H / 8 : d / 8));
       }
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipDeviceSynchronize());
       h->sq_layers_h3 = std::move(view);
     }
     if ((layers_ok || sq_ok || front_ok) && !h->head_w_h3 && h->head.w) {  // the CTC head of the fused routes
-      void* dst = nullptr;
-      HIP_TRY(hipMalloc(&dst, (size_t)h->head.n_tiles * (d / 8) * 256 * sizeof(float)));
-      h->allocs.push_back(dst);
-      launch_repack_h3(h->head.w, static_cast<f32x4*>(dst), h->head.n_tiles, d / 8, w_ovf, nullptr);
+      const f32x4* w = h->head.w;
+      LOAD_TRY(repack(&w, h->head.n_tiles, d / 8));
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipDeviceSynchronize());
-      h->head_w_h3 = static_cast<const f32x4*>(dst);
+      h->head_w_h3 = w;
     }
     if (front_ok && !h->conv2_w_h3) {  // K = 9 * 256
-      void* dst = nullptr;
-      HIP_TRY(hipMalloc(&dst, (size_t)9 * d * d * sizeof(float)));
-      h->allocs.push_back(dst);
-      launch_repack_h3(h->front.conv2_w, static_cast<f32x4*>(dst), d / 32, 9 * d / 8, w_ovf, nullptr);
+      // ... and the input projection behind it: K = F2 * 256 (a whole number of 256-deep chunks), 256 columns
+      const f32x4 *wc = h->front.conv2_w, *we = h->front.embed_w;
+      LOAD_TRY(repack(&wc, d / 32, 9 * d / 8));
+      LOAD_TRY(repack(&we, d / 32, h->F2 * d / 8));
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipDeviceSynchronize());
-      h->conv2_w_h3 = static_cast<const f32x4*>(dst);
-      // the input projection behind it: K = F2 * 256 (a whole number of 256-deep chunks), 256 columns
-      const int Ke = h->F2 * d;
-      void* dste = nullptr;
-      HIP_TRY(hipMalloc(&dste, (size_t)Ke * d * sizeof(float)));
-      h->allocs.push_back(dste);
-      launch_repack_h3(h->front.embed_w, static_cast<f32x4*>(dste), d / 32, Ke / 8, w_ovf, nullptr);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-      h->embed_w_h3 = static_cast<const f32x4*>(dste);
+      h->conv2_w_h3 = wc;
+      h->embed_w_h3 = we;
     }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(&w_after, w_ovf, sizeof(unsigned int), hipMemcpyDeviceToHost));

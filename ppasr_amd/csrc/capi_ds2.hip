@@ -6,65 +6,34 @@
 #include "capi_internal.h"
 
 namespace {
-struct Getter {
-  BlobMap& sd;
-  std::string missing;
-  const float* operator()(const std::string& name, size_t numel) {
-    auto it = sd.find(name);
-    if (it == sd.end() || it->second.numel() != numel) {
-      if (missing.empty()) missing = name;
-      return nullptr;
-    }
-    return it->second.p;
-  }
-};
-std::vector<float> vec_of(const float* p, size_t n) { return std::vector<float>(p, p + n); }
 size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
 }  // namespace
 
-#define GETW(var, name, numel)                   \
-  const float* var = get(name, (size_t)(numel)); \
-  if (!var) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing)
-#define UP(vec, dst) \
-  if ((st = m->upload(vec, &(dst))) != PPASR_OK) return st
-#define UP4(vec, dst) \
-  if ((st = m->upload4(vec, &(dst))) != PPASR_OK) return st
-
 // desc fields for DeepSpeech2: output_size = rnn_size, num_blocks = num_rnn_layers, causal = streaming
 // (rnn_direction 'forward', deepspeech2/model.py:40) else 'bidirect'.
-ppasr_status ds2_create(ppasr_model_s* m, BlobMap& sd) {
+ppasr_status ds2_create(ppasr_model_s* m, Loader& ld) {
   const ppasr_model_desc& dsc = m->desc;
   const int F = dsc.input_dim, H = dsc.output_size, L = dsc.num_blocks, V = dsc.vocab_size;
   const int dirs = dsc.causal ? 1 : 2;
   if (H % 1024 != 0 || H > 2048) return fail(PPASR_EUNSUPPORTED, "deepspeech2: rnn_size must be 1024 or 2048");
   if (L < 1 || L > 16) return fail(PPASR_EUNSUPPORTED, "deepspeech2: bad num_rnn_layers");
   const int F2 = m->F2, C = 32;
-  Getter get{sd, ""};
-  ppasr_status st;
   Ds2W& W = m->ds2;
   const int G = dsc.use_gru ? 3 : 4;  // gate rows per hidden unit: nn.GRU (r, z, c) / nn.LSTM (i, f, g, o)
   W.H = H; W.dirs = dirs; W.n_layers = L; W.V = V; W.gates = G;
   W.Vpad = (V + 255) / 256 * 256;
   W.ldx = (C * F2 + 255) / 256 * 256;  // conv feature width padded to the GEMM's K granularity
   {
-    GETW(mean, "encoder.global_cmvn.mean", F);
-    GETW(istd, "encoder.global_cmvn.istd", F);
-    GETW(c1w, "encoder.conv.conv.0.weight", C * 9);
-    GETW(c1b, "encoder.conv.conv.0.bias", C);
+    LOAD_TRY(ld.cmvn(F, &W.cmvn_mean, &W.cmvn_istd));
+    LOAD_TRY(ld.taps("encoder.conv.conv.0.weight", C, 9, &W.c1_w));
+    LOAD_TRY(ld.vec("encoder.conv.conv.0.bias", C, &W.c1_b));
     GETW(c2w, "encoder.conv.conv.2.weight", C * C * 9);
-    GETW(c2b, "encoder.conv.conv.2.bias", C);
-    UP(vec_of(mean, F), W.cmvn_mean);
-    UP(vec_of(istd, F), W.cmvn_istd);
-    std::vector<float> w1(9 * C), w2((size_t)9 * C * C);
-    for (int c = 0; c < C; ++c)
-      for (int j = 0; j < 9; ++j) w1[j * C + c] = c1w[c * 9 + j];
+    std::vector<float> w2((size_t)9 * C * C);  // [co][ci][9] -> [9][ci][co]
     for (int co = 0; co < C; ++co)
       for (int ci = 0; ci < C; ++ci)
         for (int j = 0; j < 9; ++j) w2[((size_t)j * C + ci) * C + co] = c2w[((size_t)co * C + ci) * 9 + j];
-    UP(w1, W.c1_w);
-    UP(vec_of(c1b, C), W.c1_b);
-    UP(w2, W.c2_w);
-    UP(vec_of(c2b, C), W.c2_b);
+    LOAD_TRY(ld.up(w2, &W.c2_w));
+    LOAD_TRY(ld.vec("encoder.conv.conv.2.bias", C, &W.c2_b));
   }
   m->ds2_layers.resize(L);
   std::vector<Ds2WaveLayer> wave(L);           // unidirectional models: table of the wavefront path (k_lstm_wave)
@@ -81,31 +50,31 @@ ppasr_status ds2_create(ppasr_model_s* m, BlobMap& sd) {
     const float* bhh[2] = {nullptr, nullptr};
     for (int d = 0; d < dirs; ++d) {
       const std::string sfx = d == 0 ? "_l0" : "_l0_reverse";
-      wih[d] = get(p + "weight_ih" + sfx, (size_t)G * H * in_dim);
-      whh[d] = get(p + "weight_hh" + sfx, (size_t)G * H * H);
-      bih[d] = get(p + "bias_ih" + sfx, G * H);
-      bhh[d] = get(p + "bias_hh" + sfx, G * H);
-      if (!wih[d] || !whh[d] || !bih[d] || !bhh[d]) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing);
+      wih[d] = ld.get(p + "weight_ih" + sfx, (size_t)G * H * in_dim);
+      whh[d] = ld.get(p + "weight_hh" + sfx, (size_t)G * H * H);
+      bih[d] = ld.get(p + "bias_ih" + sfx, G * H);
+      bhh[d] = ld.get(p + "bias_hh" + sfx, G * H);
+      if (!wih[d] || !whh[d] || !bih[d] || !bhh[d]) return ld.emissing();
     }
     // one GEMM per layer: columns [d*4H, (d+1)*4H) = direction d's gate pre-activations; W[k][n] = weight_ih[n][k]
     const int N = dirs * G * H;
-    UP4(pack_b(in_pad, N, [&](int k, int n) {
-          if (k >= in_dim) return 0.f;
-          const int d = n / (G * H), r = n % (G * H);
-          return wih[d][(size_t)r * in_dim + k];
-        }), Lw.w_ih);
+    LOAD_TRY(ld.packed(in_pad, N, [&](int k, int n) {
+      if (k >= in_dim) return 0.f;
+      const int d = n / (G * H), r = n % (G * H);
+      return wih[d][(size_t)r * in_dim + k];
+    }, &Lw.w_ih));
     std::vector<float> bsum(N), hh((size_t)dirs * G * H * H);
     for (int d = 0; d < dirs; ++d) {
       // LSTM: both biases enter the gate pre-activation; GRU: b_hh stays with the recurrent product (k_gru_step)
       for (int r = 0; r < G * H; ++r) bsum[d * G * H + r] = bih[d][r] + (G == 4 ? bhh[d][r] : 0.f);
       std::memcpy(&hh[(size_t)d * G * H * H], whh[d], (size_t)G * H * H * sizeof(float));
     }
-    UP(bsum, Lw.b_sum);
-    UP(hh, Lw.w_hh);
+    LOAD_TRY(ld.up(bsum, &Lw.b_sum));
+    LOAD_TRY(ld.up(hh, &Lw.w_hh));
     if (G == 3) {
       std::vector<float> bh((size_t)dirs * G * H);
       for (int d = 0; d < dirs; ++d) std::memcpy(&bh[(size_t)d * G * H], bhh[d], (size_t)G * H * sizeof(float));
-      UP(bh, Lw.b_hh);
+      LOAD_TRY(ld.up(bh, &Lw.b_hh));
     }
     // fragment-ordered copy for the batched step kernel: per direction, packed column 32 t + 8 gate + u = row
     // gate * H + 8 t + u of weight_hh (every gate of units 8t .. 8t+7 in one 32-column tile)
@@ -121,7 +90,7 @@ ppasr_status ds2_create(ppasr_model_s* m, BlobMap& sd) {
         });
         pk.insert(pk.end(), one.begin(), one.end());
       }
-      UP4(pk, Lw.w_hh_pk);
+      LOAD_TRY(ld.up4(pk, &Lw.w_hh_pk));
     }
     if (dirs == 1) {
       wave[l] = Ds2WaveLayer{Lw.w_hh_pk, nullptr, nullptr, nullptr};
@@ -132,7 +101,7 @@ ppasr_status ds2_create(ppasr_model_s* m, BlobMap& sd) {
         std::vector<float> bn(4 * H, 0.f);
         for (int n = 0; n < 4 * H; ++n)
           if (rowof(n) >= 0) bn[n] = bhh[0][rowof(n)];
-        UP(bn, wave[l].bhh_n);
+        LOAD_TRY(ld.up(bn, &wave[l].bhh_n));
       }
       if (l > 0) {
         // W' = W_ih diag(gamma_{l-1}) in the gate-interleaved fragment order; s_n = its column sums;
@@ -150,34 +119,25 @@ ppasr_status ds2_create(ppasr_model_s* m, BlobMap& sd) {
           sn[n] = (float)a;
           cn[n] = (float)(c0 + (double)bih[0][rowof(n)] + (G == 4 ? (double)bhh[0][rowof(n)] : 0.0));
         }
-        UP4(pack_b(H, 4 * H, [&](int k, int n) { return rowof(n) >= 0 ? prev_g[k] * wd[(size_t)rowof(n) * H + k] : 0.f; }),
-            wave[l].wih_pk);
-        UP(sn, wave[l].s_n);
-        UP(cn, wave[l].c_n);
+        LOAD_TRY(ld.packed(H, 4 * H, [&](int k, int n) { return rowof(n) >= 0 ? prev_g[k] * wd[(size_t)rowof(n) * H + k] : 0.f; },
+                           &wave[l].wih_pk));
+        LOAD_TRY(ld.up(sn, &wave[l].s_n));
+        LOAD_TRY(ld.up(cn, &wave[l].c_n));
       }
     }
     GETW(lg, "encoder.layernorm_list." + std::to_string(l) + ".weight", dirs * H);
     GETW(lb, "encoder.layernorm_list." + std::to_string(l) + ".bias", dirs * H);
-    UP(vec_of(lg, dirs * H), Lw.ln_g);
-    UP(vec_of(lb, dirs * H), Lw.ln_b);
+    LOAD_TRY(ld.norm("encoder.layernorm_list." + std::to_string(l), dirs * H, &Lw.ln_g, &Lw.ln_b));
     prev_g = vec_of(lg, dirs * H);
     prev_b = vec_of(lb, dirs * H);
   }
   if (dirs == 1 && H % 64 == 0) {
-    void* d = nullptr;
-    if (hipMalloc(&d, L * sizeof(Ds2WaveLayer)) != hipSuccess) return fail(PPASR_EHIP, "hipMalloc failed");
-    m->allocs.push_back(d);
-    if (hipMemcpy(d, wave.data(), L * sizeof(Ds2WaveLayer), hipMemcpyHostToDevice) != hipSuccess)
-      return fail(PPASR_EHIP, "hipMemcpy failed");
-    W.wave_tab = static_cast<const Ds2WaveLayer*>(d);
+    LOAD_TRY(m->upload_bytes(wave.data(), L * sizeof(Ds2WaveLayer), reinterpret_cast<const void**>(&W.wave_tab)));
   }
   {
     GETW(cw, "decoder.ctc_lo.weight", (size_t)dirs * H * V);
     GETW(cb, "decoder.ctc_lo.bias", V);
-    UP4(pack_b(dirs * H, W.Vpad, [&](int k, int n) { return n < V ? cw[(size_t)k * V + n] : 0.f; }), W.ctc_w);
-    std::vector<float> cbp(W.Vpad, 0.f);
-    std::memcpy(cbp.data(), cb, V * sizeof(float));
-    UP(cbp, W.ctc_b);
+    LOAD_TRY(ld.head(cw, cb, dirs * H, V, 256, &W.ctc_w, &W.ctc_b));
   }
   return PPASR_OK;
 }

@@ -138,6 +138,27 @@ inline std::vector<float> pack_conv2_quad(int d, Acc w) {
 
 typedef std::unordered_map<std::string, Blob> BlobMap;
 
+// Device memory a handle owns (model, language model, fbank tables): every block is freed with the handle
+struct DeviceAllocs {
+  std::vector<void*> allocs;
+  ppasr_status alloc(size_t bytes, void** out) {
+    HIP_TRY(hipMalloc(out, bytes));
+    allocs.push_back(*out);
+    return PPASR_OK;
+  }
+  ppasr_status upload_bytes(const void* src, size_t bytes, const void** out) {
+    void* d = nullptr;
+    ppasr_status s = alloc(bytes, &d);
+    if (s != PPASR_OK) return s;
+    HIP_TRY(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    *out = d;
+    return PPASR_OK;
+  }
+  ~DeviceAllocs() {
+    for (void* p : allocs) (void)hipFree(p);
+  }
+};
+
 // Efficient-Conformer: bit i = layer i is a stride-2 layer (ppasr_model_desc::stride_layer_mask, or the single
 // stride_layer_idx of the shipped configuration)
 inline unsigned eff_stride_mask(const ppasr_model_desc& d) {
@@ -149,7 +170,7 @@ inline int eff_strides_before(const ppasr_model_desc& d, int layer) {  // stride
   return __builtin_popcount(eff_stride_mask(d) & ((1u << layer) - 1u));
 }
 
-struct ppasr_model_s {
+struct ppasr_model_s : DeviceAllocs {
   ppasr_model_desc desc;
   int F1, F2;
   // general layer route (capi_generic.hip): CTC head as a dense layer over the padded vocabulary
@@ -196,7 +217,6 @@ struct ppasr_model_s {
   const float* zero_vec = nullptr;  // [d] zeros: pos_bias_u / _v and the one-row "positional table" of MultiHeadedAttention
   const float *lin_ln_g = nullptr, *lin_ln_b = nullptr;  // LinearNoSubsampling's LayerNorm (eps 1e-12)
   int lin_kpad = 0;                                      //   and its input width padded to whole 256-wide K chunks
-  std::vector<void*> allocs;
   FrontW front;
   std::vector<LayerW> layers;
   std::vector<int> layer_ks;     // depthwise kernel size per layer (Efficient-Conformer halves it after the stride layer)
@@ -245,18 +265,10 @@ struct ppasr_model_s {
   std::vector<Span> spans;
 
   ppasr_status upload(const std::vector<float>& v, const float** out) {
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, v.size() * sizeof(float)));
-    allocs.push_back(d);
-    HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    *out = static_cast<const float*>(d);
-    return PPASR_OK;
+    return upload_bytes(v.data(), v.size() * sizeof(float), reinterpret_cast<const void**>(out));
   }
   ppasr_status upload4(const std::vector<float>& v, const f32x4** out) {
-    const float* p = nullptr;
-    ppasr_status s = upload(v, &p);
-    *out = reinterpret_cast<const f32x4*>(p);
-    return s;
+    return upload_bytes(v.data(), v.size() * sizeof(float), reinterpret_cast<const void**>(out));
   }
   hipEvent_t next_event() {
     if (ev_used == ev_pool.size()) {
@@ -267,7 +279,6 @@ struct ppasr_model_s {
     return ev_pool[ev_used++];
   }
   ~ppasr_model_s() {
-    for (void* p : allocs) (void)hipFree(p);
     for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
     if (guard_host) (void)hipHostFree(guard_host);
   }
@@ -317,8 +328,6 @@ bool block_tables_enabled();  // active-block lists for ragged layer kernels (PP
 bool conv12_enabled(const ppasr_model_s* m);
 ppasr::LayerW sq_conv_view(const ppasr::SqLayerW& W);  // capi_squeezeformer.hip
 
-ppasr_status upload_pe_table(ppasr_model_s* m, BlobMap& sd, const float** pe_dev);
-
 // general Conformer layer route (widths 512 / 768 / 1024, non-default constructor options): capi_generic.hip
 size_t generic_ws_floats(const ppasr_model_s* m, int B, int T);
 ppasr_status generic_encode(ppasr_model_s* h, const float* feats, const int64_t* lens, int B, int T, float* probs,
@@ -343,14 +352,18 @@ hipError_t configure_generic_kernels();
 ppasr_status generic_sq_encode(ppasr_model_s* h, const float* feats, const int64_t* lens, int B, int T, float* probs,
                                float* logits, int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st);
 
-// model-family back ends
-ppasr_status ds2_create(ppasr_model_s* m, BlobMap& sd);
+// model-family back ends: each turns the checkpoint behind `ld` (weights.h) into the device memory of `m`
+struct Loader;
+ppasr_status conformer_create(ppasr_model_s* m, Loader& ld);  // capi_conformer.hip
+ppasr_status ds2_create(ppasr_model_s* m, Loader& ld);
 // DeepSpeech2 session groups (capi_ds2.hip): workspace of a round of n windows of T frames, and the round itself
 size_t ds2_group_ws_floats(const ppasr_model_s* m, int n, int T);
 ppasr_status ds2_group_round(ppasr_model_s* h, const int* slots, int n, const float* feats, int T, float* state_h,
                              float* state_c, float* probs, int32_t* frame_argmax, float* frame_maxprob, float* ws,
                              hipStream_t st);
-ppasr_status squeezeformer_create(ppasr_model_s* m, BlobMap& sd, const float* pe_dev);
+ppasr_status squeezeformer_create(ppasr_model_s* m, Loader& ld);
 ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const int64_t* lens, int B, int T, float* probs,
                                   float* logits, int32_t* frame_argmax, float* frame_maxprob, float* ws,
                                   const WsLayout& wl, hipStream_t st);
+
+#include "weights.h"

@@ -1,272 +1,116 @@
 // capi_squeezeformer.hip -- weight packing and launch sequence of the Squeezeformer encoder
 // (ppasr/model_utils/squeezeformer/{encoder,attention,convolution,positionwise,subsampling,
-// time_reduction}.py) behind ppasr_create / ppasr_encode.
+// time_reduction}.py) behind ppasr_create / ppasr_encode.  The packing goes through the loader every family shares
+// (weights.h); what is written here is the Squeezeformer's own: the adaptive-scale vectors, final_proj.
 #include "capi_internal.h"
 
-namespace {
-
-struct Getter {
-  BlobMap& sd;
-  std::string missing;
-  const float* operator()(const std::string& name, size_t numel) {
-    auto it = sd.find(name);
-    if (it == sd.end() || it->second.numel() != numel) {
-      if (missing.empty()) missing = name;
-      return nullptr;
-    }
-    return it->second.p;
-  }
-};
-
-std::vector<float> vec_of(const float* p, size_t n) { return std::vector<float>(p, p + n); }
-
-}  // namespace
-
-#define GETW(var, name, numel)                 \
-  const float* var = get(name, (size_t)(numel)); \
-  if (!var) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing)
-#define UP(vec, dst) \
-  if ((st = m->upload(vec, &(dst))) != PPASR_OK) return st
-#define UP4(vec, dst) \
-  if ((st = m->upload4(vec, &(dst))) != PPASR_OK) return st
-
-ppasr_status squeezeformer_create(ppasr_model_s* m, BlobMap& sd, const float* pe_dev) {
+ppasr_status squeezeformer_create(ppasr_model_s* m, Loader& ld) {
   const ppasr_model_desc& dsc = m->desc;
   const int F = dsc.input_dim, d = dsc.output_size, H = dsc.linear_units, V = dsc.vocab_size, KS = dsc.cnn_module_kernel;
-  const int F2 = m->F2, L = dsc.num_blocks, max_len = dsc.max_len;
+  const int F2 = m->F2, L = dsc.num_blocks;
+  const float* pe_dev = nullptr;
+  LOAD_TRY(ld.pe_table(&pe_dev));
   if (dsc.reduce_idx >= 0 && (dsc.recover_idx <= dsc.reduce_idx || dsc.recover_idx >= L || dsc.reduce_idx == 0))
     return fail(PPASR_EUNSUPPORTED, "squeezeformer: need 0 < reduce_idx < recover_idx < num_blocks (or reduce_idx = -1)");
-  Getter get{sd, ""};
-  ppasr_status st;
   // adaptive_scale = False (encoder.py:44): the ada_scale / ada_bias parameters exist in the checkpoint (every module creates
   // them, attention.py:34-37) but are not applied -- fold ones / zeros instead
   const bool no_ada = (dsc.options & PPASR_OPT_SQ_NO_ADAPTIVE_SCALE) != 0;
   const std::vector<float> ones_d(d, 1.f), zeros_d(d, 0.f);
-  auto adapt = [&](const float*& as, const float*& ab) {
-    if (no_ada) {
-      as = ones_d.data();
-      ab = zeros_d.data();
-    }
+  // a module's adaptive scale / bias [d], which the loader's recipes fold into the module's first dense layer
+  const float *as = nullptr, *ab = nullptr;
+  auto ada = [&](const std::string& module) -> ppasr_status {
+    GETW(s, module + ".ada_scale", d);
+    GETW(b, module + ".ada_bias", d);
+    as = no_ada ? ones_d.data() : s;
+    ab = no_ada ? zeros_d.data() : b;
+    return PPASR_OK;
   };
+  FrontW& fr = m->front;
   {  // DepthwiseConv2DSubsampling4 (subsampling.py:36-47): two 3x3 / 2 convs; dw_stride = True makes the second one depthwise
-    GETW(mean, "encoder.global_cmvn.mean", F);
-    GETW(istd, "encoder.global_cmvn.istd", F);
-    GETW(c1w, "encoder.embed.pw_conv.weight", d * 9);
-    GETW(c1b, "encoder.embed.pw_conv.bias", d);
+    LOAD_TRY(ld.cmvn(F, &fr.cmvn_mean, &fr.cmvn_istd));
+    LOAD_TRY(ld.taps("encoder.embed.pw_conv.weight", d, 9, &fr.conv1_w));
+    LOAD_TRY(ld.vec("encoder.embed.pw_conv.bias", d, &fr.conv1_b));
     // dw_stride = True (groups = odim): weight [d][1][3][3].  Run as the ordinary conv with a block-diagonal weight -- the
     // off-diagonal products are exact zeros, so the sums are the depthwise conv's; no shipped config sets the option
-    const float* c2w = get("encoder.embed.dw_conv.weight", (size_t)d * d * 9);
-    const bool dw_stride = !c2w;
-    if (!c2w) {
-      get.missing.clear();
-      c2w = get("encoder.embed.dw_conv.weight", (size_t)d * 9);
-    }
-    if (!c2w) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing);
-    GETW(c2b, "encoder.embed.dw_conv.bias", d);
-    GETW(ew, "encoder.embed.input_proj.0.weight", (size_t)d * F2 * d);
-    GETW(eb, "encoder.embed.input_proj.0.bias", d);
-    GETW(pg, "encoder.preln.weight", d);
-    GETW(pb, "encoder.preln.bias", d);
-    UP(vec_of(mean, F), m->front.cmvn_mean);
-    UP(vec_of(istd, F), m->front.cmvn_istd);
-    std::vector<float> c1(9 * d);
-    for (int c = 0; c < d; ++c)
-      for (int j = 0; j < 9; ++j) c1[j * d + c] = c1w[c * 9 + j];
-    UP(c1, m->front.conv1_w);
-    UP(vec_of(c1b, d), m->front.conv1_b);
-    auto c2 = [&](int k, int n) {
-      if (dw_stride) return (k % d) == n ? c2w[(size_t)n * 9 + (k / d)] : 0.f;
-      return c2w[((size_t)n * d + (k % d)) * 9 + (k / d)];
-    };
-    UP4(pack_b(9 * d, d, c2), m->front.conv2_w);
-    if (d == kD) UP4(pack_conv2_quad(d, c2), m->front.conv2_wp);  // (batched calls: front_fused.hip)
-    UP(vec_of(c2b, d), m->front.conv2_b);
-    UP4(pack_b(F2 * d, d, [&](int k, int n) { return ew[((size_t)(k % d) * F2 + (k / d)) * d + n]; }), m->front.embed_w);
-    UP(vec_of(eb, d), m->front.embed_b);
-    UP(vec_of(pg, d), m->preln_g);
-    UP(vec_of(pb, d), m->preln_b);
+    bool dw_stride = false;
+    const float* c2w = ld.get_either("encoder.embed.dw_conv.weight", (size_t)d * d * 9, (size_t)d * 9, &dw_stride);
+    if (!c2w) return ld.emissing();
+    const bool quad = d == kD;  // (batched calls: front_fused.hip)
+    if (dw_stride)
+      LOAD_TRY(ld.conv2(d, 9, [=](int k, int n) { return (k % d) == n ? c2w[(size_t)n * 9 + (k / d)] : 0.f; }, quad,
+                        &fr.conv2_w, &fr.conv2_wp));
+    else
+      LOAD_TRY(ld.conv2(d, 9, Loader::dense_conv(c2w, d, 9), quad, &fr.conv2_w, &fr.conv2_wp));
+    LOAD_TRY(ld.vec("encoder.embed.dw_conv.bias", d, &fr.conv2_b));
+    LOAD_TRY(ld.embed("encoder.embed.input_proj.0", F2, d, &fr.embed_w, &fr.embed_b));
+    LOAD_TRY(ld.norm("encoder.preln", d, &m->preln_g, &m->preln_b));
   }
   m->sq_layers.resize(L);
   for (int i = 0; i < L; ++i) {
     SqLayerW& W = m->sq_layers[i];
     const std::string p = "encoder.encoders." + std::to_string(i) + ".";
-    auto ln = [&](const std::string& n, const float** g, const float** b) -> ppasr_status {
-      const float* gw = get(p + n + ".weight", d);
-      const float* gb = get(p + n + ".bias", d);
-      if (!gw || !gb) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing);
-      ppasr_status s1 = m->upload(vec_of(gw, d), g);
-      return s1 != PPASR_OK ? s1 : m->upload(vec_of(gb, d), b);
-    };
-    if ((st = ln("layer_norm1", &W.ln1_g, &W.ln1_b)) != PPASR_OK) return st;
-    if ((st = ln("layer_norm2", &W.ln2_g, &W.ln2_b)) != PPASR_OK) return st;
-    if ((st = ln("layer_norm3", &W.ln3_g, &W.ln3_b)) != PPASR_OK) return st;
-    if ((st = ln("layer_norm4", &W.ln4_g, &W.ln4_b)) != PPASR_OK) return st;
-    // conv-module norm: LayerNorm, or (cnn_norm_type: batch_norm) BatchNorm1D at inference folded into scale / shift,
-    // cm_eps < 0 -- same convention as the Conformer loader (capi.hip)
-    W.cm_eps = 1e-5f;
-    if (sd.find(p + "conv_module.norm._mean") != sd.end()) {
-      const float* mean = get(p + "conv_module.norm._mean", d);
-      const float* var = get(p + "conv_module.norm._variance", d);
-      const float* gw = get(p + "conv_module.norm.weight", d);
-      const float* gb = get(p + "conv_module.norm.bias", d);
-      if (!mean || !var || !gw || !gb) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing);
-      std::vector<float> sc(d), sh(d);
-      for (int c = 0; c < d; ++c) {
-        sc[c] = gw[c] / std::sqrt(var[c] + 1e-5f);
-        sh[c] = gb[c] - mean[c] * sc[c];
-      }
-      if ((st = m->upload(sc, &W.ln_cm_g)) != PPASR_OK || (st = m->upload(sh, &W.ln_cm_b)) != PPASR_OK) return st;
-      W.cm_eps = -1.f;
-    } else if ((st = ln("conv_module.norm", &W.ln_cm_g, &W.ln_cm_b)) != PPASR_OK) {
-      return st;
-    }
-    // FFN with the adaptive scale folded into w_1:  (s.x + a) W1 + b1 = x (diag(s) W1) + (a W1 + b1)
-    auto ffn = [&](const std::string& n, const f32x4** w1, const float** b1, const f32x4** w2,
-                   const float** b2) -> ppasr_status {
-      const float* a1 = get(p + n + ".w_1.weight", (size_t)d * H);
-      const float* c1 = get(p + n + ".w_1.bias", H);
-      const float* a2 = get(p + n + ".w_2.weight", (size_t)H * d);
-      const float* c2 = get(p + n + ".w_2.bias", d);
-      const float* as = get(p + n + ".ada_scale", d);
-      const float* ab = get(p + n + ".ada_bias", d);
-      if (!a1 || !c1 || !a2 || !c2 || !as || !ab) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing);
-      adapt(as, ab);
-      std::vector<float> b1f(c1, c1 + H);
-      for (int nn = 0; nn < H; ++nn) {
-        double acc = 0.0;
-        for (int k = 0; k < d; ++k) acc += (double)ab[k] * (double)a1[(size_t)k * H + nn];
-        b1f[nn] = (float)((double)c1[nn] + acc);
-      }
-      ppasr_status s;
-      if ((s = m->upload4(pack_b(d, H, [&](int k, int nn) { return as[k] * a1[(size_t)k * H + nn]; }), w1)) != PPASR_OK) return s;
-      if ((s = m->upload(b1f, b1)) != PPASR_OK) return s;
-      if ((s = m->upload4(pack_b(H, d, [&](int k, int nn) { return a2[(size_t)k * d + nn]; }), w2)) != PPASR_OK) return s;
-      return m->upload(vec_of(c2, d), b2);
-    };
-    if ((st = ffn("ffn1", &W.ff1_w1, &W.ff1_b1, &W.ff1_w2, &W.ff1_b2)) != PPASR_OK) return st;
-    if ((st = ffn("ffn2", &W.ff2_w1, &W.ff2_b1, &W.ff2_w2, &W.ff2_b2)) != PPASR_OK) return st;
-    {
-      GETW(wq, p + "self_attn.linear_q.weight", d * d);
-      GETW(wk, p + "self_attn.linear_k.weight", d * d);
-      GETW(wv, p + "self_attn.linear_v.weight", d * d);
-      GETW(bq, p + "self_attn.linear_q.bias", d);
-      GETW(bk, p + "self_attn.linear_k.bias", d);
-      GETW(bv, p + "self_attn.linear_v.bias", d);
-      GETW(wo, p + "self_attn.linear_out.weight", d * d);
-      GETW(bo, p + "self_attn.linear_out.bias", d);
-      // pos_enc_layer_type != rel_pos (squeezeformer/encoder.py:101-105): conformer's plain MultiHeadedAttention -- no
-      // linear_pos, no pos_bias_u / _v, no adaptive scale.  The attention kernels then contract the positional half with a
-      // row of zeros (pos_bias = 0, table stride 0), like the Conformer's abs_pos / no_pos layers
-      const bool plain_mha = (dsc.options & PPASR_OPT_POS_MASK) != PPASR_OPT_POS_REL;
-      const float *wp = nullptr, *bp = nullptr, *pu = zeros_d.data(), *pv = zeros_d.data(), *as = ones_d.data(), *ab = zeros_d.data();
-      if (!plain_mha) {
-        wp = get(p + "self_attn.linear_pos.weight", (size_t)d * d);
-        bp = get(p + "self_attn.linear_pos.bias", d);  // linear_pos HAS a bias here (squeezeformer/attention.py:28)
-        pu = get(p + "self_attn.pos_bias_u", d);
-        pv = get(p + "self_attn.pos_bias_v", d);
-        as = get(p + "self_attn.ada_scale", d);
-        ab = get(p + "self_attn.ada_bias", d);
-        if (!wp || !bp || !pu || !pv || !as || !ab) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing);
-        adapt(as, ab);
-      }
-      const float* ws[3] = {wq, wk, wv};
-      const float* bs[3] = {bq, bk, bv};
-      UP4(pack_b(d, 3 * d, [&](int k, int n) { return as[k] * ws[n / d][(size_t)k * d + (n % d)]; }), W.wqkv);
-      std::vector<float> bqkv(3 * d);
-      for (int n = 0; n < 3 * d; ++n) {
-        double acc = 0.0;
-        for (int k = 0; k < d; ++k) acc += (double)ab[k] * (double)ws[n / d][(size_t)k * d + (n % d)];
-        bqkv[n] = (float)((double)bs[n / d][n % d] + acc);
-      }
-      UP(bqkv, W.bqkv);
-      UP4(pack_b(d, d, [&](int k, int n) { return wo[(size_t)k * d + n]; }), W.wo);
-      UP(vec_of(bo, d), W.bo);
-      UP(vec_of(pu, d), W.pos_u);
-      UP(vec_of(pv, d), W.pos_v);
-      if (plain_mha) {
-        W.ptab = W.pos_u;  // (a row of zeros; read with stride 0)
-      } else {
-        const float* wpos_dev = nullptr;
-        UP(vec_of(wp, (size_t)d * d), wpos_dev);
-        const float* bpos_dev = nullptr;
-        UP(vec_of(bp, d), bpos_dev);
-        void* pt = nullptr;
-        HIP_TRY(hipMalloc(&pt, (size_t)max_len * d * sizeof(float)));
-        m->allocs.push_back(pt);
-        launch_posproj(pe_dev, wpos_dev, bpos_dev, static_cast<float*>(pt), max_len, nullptr, d);
-        HIP_TRY(hipGetLastError());
-        W.ptab = static_cast<const float*>(pt);
-      }
+    LOAD_TRY(ld.norm(p + "layer_norm1", d, &W.ln1_g, &W.ln1_b));
+    LOAD_TRY(ld.norm(p + "layer_norm2", d, &W.ln2_g, &W.ln2_b));
+    LOAD_TRY(ld.norm(p + "layer_norm3", d, &W.ln3_g, &W.ln3_b));
+    LOAD_TRY(ld.norm(p + "layer_norm4", d, &W.ln4_g, &W.ln4_b));
+    LOAD_TRY(ld.conv_module_norm(p + "conv_module.norm", d, &W.ln_cm_g, &W.ln_cm_b, &W.cm_eps));
+    LOAD_TRY(ada(p + "ffn1"));
+    LOAD_TRY(ld.ffn(p + "ffn1", d, H, as, ab, &W.ff1_w1, &W.ff1_b1, &W.ff1_w2, &W.ff1_b2));
+    LOAD_TRY(ada(p + "ffn2"));
+    LOAD_TRY(ld.ffn(p + "ffn2", d, H, as, ab, &W.ff2_w1, &W.ff2_b1, &W.ff2_w2, &W.ff2_b2));
+    // pos_enc_layer_type != rel_pos (squeezeformer/encoder.py:101-105): conformer's plain MultiHeadedAttention -- no
+    // linear_pos, no pos_bias_u / _v, no adaptive scale.  The attention kernels then contract the positional half with a
+    // row of zeros (pos_bias = 0, table stride 0), like the Conformer's abs_pos / no_pos layers
+    if ((dsc.options & PPASR_OPT_POS_MASK) != PPASR_OPT_POS_REL) {
+      LOAD_TRY(ld.qkv_out(p + "self_attn.", d, ones_d.data(), zeros_d.data(), &W.wqkv, &W.bqkv, &W.wo, &W.bo));
+      LOAD_TRY(ld.up(zeros_d, &W.pos_u));
+      LOAD_TRY(ld.up(zeros_d, &W.pos_v));
+      W.ptab = W.pos_u;  // (a row of zeros; read with stride 0)
+    } else {
+      LOAD_TRY(ada(p + "self_attn"));
+      LOAD_TRY(ld.qkv_out(p + "self_attn.", d, as, ab, &W.wqkv, &W.bqkv, &W.wo, &W.bo));
+      LOAD_TRY(ld.vec(p + "self_attn.pos_bias_u", d, &W.pos_u));
+      LOAD_TRY(ld.vec(p + "self_attn.pos_bias_v", d, &W.pos_v));
+      // (linear_pos HAS a bias here, squeezeformer/attention.py:28)
+      LOAD_TRY(ld.pos_table(p + "self_attn.", d, true, pe_dev, &W.ptab));
     }
     {
-      GETW(p1w, p + "conv_module.pointwise_conv1.weight", 2 * d * d);
-      GETW(p1b, p + "conv_module.pointwise_conv1.bias", 2 * d);
-      GETW(dww, p + "conv_module.depthwise_conv.weight", d * KS);
-      GETW(dwb, p + "conv_module.depthwise_conv.bias", d);
-      GETW(p2w, p + "conv_module.pointwise_conv2.weight", d * d);
-      GETW(p2b, p + "conv_module.pointwise_conv2.bias", d);
-      GETW(as, p + "conv_module.ada_scale", d);
-      GETW(ab, p + "conv_module.ada_bias", d);
-      adapt(as, ab);
-      UP4(pack_b(d, 2 * d, [&](int k, int n) { return as[k] * p1w[(size_t)n * d + k]; }), W.pw1);
-      std::vector<float> b1f(2 * d), gp(d);
-      for (int n = 0; n < 2 * d; ++n) {
-        double acc = 0.0;
-        for (int k = 0; k < d; ++k) acc += (double)ab[k] * (double)p1w[(size_t)n * d + k];
-        b1f[n] = (float)((double)p1b[n] + acc);
-      }
-      // zero-padded / PAD frames see pointwise_conv1(0) = the ORIGINAL bias (mask is applied after the scale)
-      for (int c = 0; c < d; ++c) gp[c] = p1b[c] * (1.0f / (1.0f + expf(-p1b[c + d])));
-      UP(b1f, W.pw1_b);
-      UP(gp, W.glu_pad);
-      UP(vec_of(as, d), W.cm_scale);
-      UP(vec_of(ab, d), W.cm_bias);
-      UP4(pack_b(d, 2 * d, [&](int k, int n) { return p1w[(size_t)n * d + k]; }), W.pw1_raw);
-      UP(vec_of(p1b, 2 * d), W.pw1_b_raw);
-      std::vector<float> dwt((size_t)KS * d);
-      for (int c = 0; c < d; ++c)
-        for (int j = 0; j < KS; ++j) dwt[(size_t)j * d + c] = dww[(size_t)c * KS + j];
-      UP(dwt, W.dw_w);
-      UP(vec_of(dwb, d), W.dw_b);
-      UP4(pack_b(d, d, [&](int k, int n) { return p2w[(size_t)n * d + k]; }), W.pw2);
-      UP(vec_of(p2b, d), W.pw2_b);
+      const std::string cm = p + "conv_module.";
+      LOAD_TRY(ada(p + "conv_module"));
+      LOAD_TRY(ld.conv_pointwise(cm, d, as, ab, &W.pw1, &W.pw1_b, &W.glu_pad, &W.pw2, &W.pw2_b));
+      // the scale / bias and the unfolded pointwise_conv1 as well: a chunk applies the scale in front of its cached inputs
+      LOAD_TRY(ld.up(vec_of(as, d), &W.cm_scale));
+      LOAD_TRY(ld.up(vec_of(ab, d), &W.cm_bias));
+      GETW(p1w, cm + "pointwise_conv1.weight", (size_t)2 * d * d);
+      LOAD_TRY(ld.packed(d, 2 * d, [&](int k, int n) { return p1w[(size_t)n * d + k]; }, &W.pw1_raw));
+      LOAD_TRY(ld.vec(cm + "pointwise_conv1.bias", 2 * d, &W.pw1_b_raw));
+      LOAD_TRY(ld.taps(cm + "depthwise_conv.weight", d, KS, &W.dw_w));
+      LOAD_TRY(ld.vec(cm + "depthwise_conv.bias", d, &W.dw_b));
     }
   }
   if (dsc.reduce_idx >= 0) {
     // TimeReductionLayerStream: depthwise kernel 1; TimeReductionLayer1D (non-streaming model): kernel 5
-    int tr_k = 1;
-    const float* rdw = get("encoder.time_reduction_layer.dw_conv.weight", d);
-    if (!rdw) {
-      get.missing.clear();
-      rdw = get("encoder.time_reduction_layer.dw_conv.weight", (size_t)d * 5);
-      tr_k = 5;
-    }
-    if (!rdw) return fail(PPASR_EMISSING, "missing or mis-shaped weight: " + get.missing);
-    GETW(rdb, "encoder.time_reduction_layer.dw_conv.bias", d);
-    GETW(rpw, "encoder.time_reduction_layer.pw_conv.weight", d * d);
-    GETW(rpb, "encoder.time_reduction_layer.pw_conv.bias", d);
+    const std::string tr = "encoder.time_reduction_layer.";
+    bool k5 = false;
+    const float* rdw = ld.get_either(tr + "dw_conv.weight", d, (size_t)d * 5, &k5);
+    if (!rdw) return ld.emissing();
+    m->sq_reduce.ks = k5 ? 5 : 1;
+    LOAD_TRY(ld.taps(rdw, d, m->sq_reduce.ks, &m->sq_reduce.dw_w));
+    LOAD_TRY(ld.vec(tr + "dw_conv.bias", d, &m->sq_reduce.dw_b));
+    GETW(rpw, tr + "pw_conv.weight", d * d);
+    LOAD_TRY(ld.packed(d, d, [&](int k, int n) { return rpw[(size_t)n * d + k]; }, &m->sq_reduce.pw));
+    LOAD_TRY(ld.vec(tr + "pw_conv.bias", d, &m->sq_reduce.pw_b));
     GETW(rw, "encoder.time_recover_layer.weight", d * d);
-    GETW(rb, "encoder.time_recover_layer.bias", d);
-    {
-      std::vector<float> taps((size_t)tr_k * d);  // [C][1][k] -> tap-major [k][C]
-      for (int c = 0; c < d; ++c)
-        for (int k = 0; k < tr_k; ++k) taps[(size_t)k * d + c] = rdw[(size_t)c * tr_k + k];
-      UP(taps, m->sq_reduce.dw_w);
-      m->sq_reduce.ks = tr_k;
-    }
-    UP(vec_of(rdb, d), m->sq_reduce.dw_b);
-    UP4(pack_b(d, d, [&](int k, int n) { return rpw[(size_t)n * d + k]; }), m->sq_reduce.pw);
-    UP(vec_of(rpb, d), m->sq_reduce.pw_b);
-    UP4(pack_b(d, d, [&](int k, int n) { return rw[(size_t)k * d + n]; }), m->sq_wrec);
-    UP(vec_of(rb, d), m->sq_brec);
+    LOAD_TRY(ld.packed(d, d, [&](int k, int n) { return rw[(size_t)k * d + n]; }, &m->sq_wrec));
+    LOAD_TRY(ld.vec("encoder.time_recover_layer.bias", d, &m->sq_brec));
   }
   {
     // final_proj (output_size != encoder_dim, encoder.py:165-167,234-235): a Linear between the last layer and ctc_lo with
     // nothing in between -- folded into the head at create time, logits = x (W_fp W_ctc) + (b_fp W_ctc + b_ctc), in double
     std::vector<float> cw_f, cb_f;
     const float *cw = nullptr, *cb = nullptr;
-    auto fp = sd.find("encoder.final_proj.weight");
-    if (fp != sd.end()) {
+    auto fp = ld.sd.find("encoder.final_proj.weight");
+    if (fp != ld.sd.end()) {
       const Blob& fb = fp->second;
       if (fb.ndim != 2 || fb.shape[0] != d) return fail(PPASR_EMISSING, "mis-shaped weight: encoder.final_proj.weight");
       const int O = (int)fb.shape[1];
@@ -302,17 +146,10 @@ ppasr_status squeezeformer_create(ppasr_model_s* m, BlobMap& sd, const float* pe
     m->head.ln_b = nullptr;
     m->head.V = V;
     m->head.n_tiles = (V + 31) / 32;
-    UP4(pack_b(d, V, [&](int k, int n) { return cw[(size_t)k * V + n]; }), m->head.w);
-    std::vector<float> cbp((size_t)m->head.n_tiles * 32, 0.f);
-    std::memcpy(cbp.data(), cb, V * sizeof(float));
-    UP(cbp, m->head.b);
+    LOAD_TRY(ld.head(cw, cb, d, V, 32, &m->head.w, &m->head.b));
     if (m->generic) {  // general route (encoder_dim 512 ..): the head as a plain dense layer over the padded vocabulary
       m->gen_vpad = (V + 255) / 256 * 256;
-      const int Vp = m->gen_vpad;
-      UP4(pack_b(d, Vp, [&](int k, int n) { return n < V ? cw[(size_t)k * V + n] : 0.f; }), m->gen_head_w);
-      std::vector<float> hb(Vp, 0.f);
-      std::memcpy(hb.data(), cb, V * sizeof(float));
-      UP(hb, m->gen_head_b);
+      LOAD_TRY(ld.head(cw, cb, d, V, 256, &m->gen_head_w, &m->gen_head_b));
     }
   }
   return PPASR_OK;

@@ -304,13 +304,9 @@ __global__ __launch_bounds__(kFT) void k_fbank_batch(const float* __restrict__ x
 
 }  // namespace
 
-struct ppasr_fbank_s {
+struct ppasr_fbank_s : DeviceAllocs {
   int sample_rate, n_mels, win, shift, nfft, log2n;
   FbankTables tb;
-  std::vector<void*> allocs;
-  ~ppasr_fbank_s() {
-    for (void* p : allocs) (void)hipFree(p);
-  }
 };
 
 extern "C" {
@@ -360,14 +356,7 @@ ppasr_status ppasr_fbank_create(int sample_rate, int n_mels, float frame_length_
     lo[m] = first < 0 ? 0 : first;
     hi[m] = first < 0 ? 0 : last + 1;
   }
-  auto up = [&](const void* src, size_t bytes, const void** dst) -> ppasr_status {
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, bytes));
-    f->allocs.push_back(d);
-    HIP_TRY(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-    *dst = d;
-    return PPASR_OK;
-  };
+  auto up = [&](const void* src, size_t bytes, const void** dst) { return f->upload_bytes(src, bytes, dst); };
   const void* p = nullptr;
   ppasr_status s;
   if ((s = up(window.data(), window.size() * 4, &p)) != PPASR_OK) return s;

@@ -226,14 +226,7 @@ std::string lm_build_table(ppasr_lm_s& lm, const std::vector<LmEntry>& entries) 
 }
 
 ppasr_status lm_upload(ppasr_lm_s& lm) {
-  auto up = [&](const void* src, size_t bytes, const void** dst) -> ppasr_status {
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, bytes));
-    lm.allocs.push_back(d);
-    HIP_TRY(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-    *dst = d;
-    return PPASR_OK;
-  };
+  auto up = [&](const void* src, size_t bytes, const void** dst) { return lm.upload_bytes(src, bytes, dst); };
   const void* p = nullptr;
   ppasr_status s;
   if ((s = up(lm.slots.data(), lm.slots.size() * sizeof(LmSlot), &p)) != PPASR_OK) return s;

@@ -10,7 +10,7 @@
 #include "capi_internal.h"
 #include "lm.h"
 
-struct ppasr_lm_s {
+struct ppasr_lm_s : DeviceAllocs {
   ppasr::LmDev dev{};
   int order = 0;
   int n_words = 0;
@@ -27,10 +27,6 @@ struct ppasr_lm_s {
   int space_id = -1;
   size_t dict_words = 0;  // Scorer::get_dict_size(): vocabulary words that could be spelt in acoustic characters
   std::vector<int32_t> dict_first, dict_arc_char, dict_arc_next, dict_word;
-  std::vector<void*> allocs;
-  ~ppasr_lm_s() {
-    for (void* p : allocs) (void)hipFree(p);
-  }
 };
 
 namespace ppasr {

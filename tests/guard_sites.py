@@ -9,7 +9,7 @@ finite and benign (the pushed value meets a zero weight) and the result does not
 
 What a site's tap sees is the oracle's value of the tensor the kernel splits (oracle `taps`).  Where the library folds a
 parameter at create time the kernel's operand is NOT the reference's: the Squeezeformer feed-forward modules get their
-adaptive scale and bias folded into w_1 / b_1 (capi_squeezeformer.hip), so the W1 input the kernels split is the
+adaptive scale and bias folded into w_1 / b_1 (capi_squeezeformer.hip, by the loader's `linear`: csrc/weights.h), so the W1 input the kernels split is the
 LayerNorm output in front of the module, and an `ada_bias` edit never reaches it -- the recipe goes through that
 LayerNorm's bias."""
 import os
