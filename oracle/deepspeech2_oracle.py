@@ -21,11 +21,29 @@ class DeepSpeech2Oracle:
         self.L, self.H = num_rnn_layers, rnn_size
         self.dirs = 1 if streaming else 2  # rnn_direction 'forward' / 'bidirect' (deepspeech2/model.py:40)
         self.dtype = dtype
+        self.taps = None  # set to a dict to record the largest |gate pre-activation| (tests/offcentre_cases.py)
+
+    # ---- patch points of the tests (tests/offcentre_cases.py: mutations, conditioning records); the arithmetic is the
+    # inline code they replaced ----
+    def _ln(self, x, prefix, eps=1e-5):
+        return F.layer_norm(x, (x.shape[-1],), self.p[prefix + ".weight"], self.p[prefix + ".bias"], eps)
+
+    def _sigmoid(self, x):
+        return torch.sigmoid(x)
+
+    def _xproj(self, x, bi, t, prefix, sfx):
+        """input part of one step's gate pre-activations, without its bias"""
+        return self.p[prefix + "weight_ih" + sfx] @ x[bi, t]
+
+    def _tap(self, g):
+        if self.taps is not None:
+            self.taps["gates"] = max(self.taps.get("gates", 0.0), float(g.detach().abs().max()))
+        return g
 
     def _lstm_dir(self, x, lens, prefix, sfx, h0, c0, reverse):
         B, T, _ = x.shape
         H = self.H
-        w_ih, w_hh = self.p[prefix + "weight_ih" + sfx], self.p[prefix + "weight_hh" + sfx]
+        w_hh = self.p[prefix + "weight_hh" + sfx]
         b = self.p[prefix + "bias_ih" + sfx] + self.p[prefix + "bias_hh" + sfx]
         out = torch.zeros(B, T, H, dtype=x.dtype)
         hT, cT = h0.clone(), c0.clone()
@@ -36,18 +54,19 @@ class DeepSpeech2Oracle:
             for t in order:
                 if self.use_gru:
                     # paddle GRUCell: r, z, c rows; c = tanh(x_c + r * (W_hc h + b_hc)); h = (h - c) * z + c
-                    xg = w_ih @ x[bi, t] + self.p[prefix + "bias_ih" + sfx]
+                    xg = self._xproj(x, bi, t, prefix, sfx) + self.p[prefix + "bias_ih" + sfx]
                     hg = w_hh @ h + self.p[prefix + "bias_hh" + sfx]
-                    r = torch.sigmoid(xg[:H] + hg[:H])
-                    z = torch.sigmoid(xg[H:2 * H] + hg[H:2 * H])
-                    cand = torch.tanh(xg[2 * H:] + r * hg[2 * H:])
+                    self._tap(xg[:2 * H] + hg[:2 * H])
+                    r = self._sigmoid(xg[:H] + hg[:H])
+                    z = self._sigmoid(xg[H:2 * H] + hg[H:2 * H])
+                    cand = torch.tanh(self._tap(xg[2 * H:] + r * hg[2 * H:]))
                     h = (h - cand) * z + cand
                     out[bi, t] = h
                     continue
-                g = w_ih @ x[bi, t] + w_hh @ h + b
+                g = self._tap(self._xproj(x, bi, t, prefix, sfx) + w_hh @ h + b)
                 i, f, gg, o = g[:H], g[H:2 * H], g[2 * H:3 * H], g[3 * H:]
-                c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-                h = torch.sigmoid(o) * torch.tanh(c)
+                c = self._sigmoid(f) * c + self._sigmoid(i) * torch.tanh(gg)
+                h = self._sigmoid(o) * torch.tanh(c)
                 out[bi, t] = h
             hT[bi], cT[bi] = h, c
         return out, hT, cT
@@ -80,8 +99,7 @@ class DeepSpeech2Oracle:
                     hs.append(hT)
                     cs.append(cT)
                 x = torch.cat(outs, dim=-1)
-                x = F.layer_norm(x, (x.shape[-1],), self.p[f"encoder.layernorm_list.{l}.weight"],
-                                 self.p[f"encoder.layernorm_list.{l}.bias"], 1e-5)
+                x = self._ln(x, f"encoder.layernorm_list.{l}")
             logits = x @ self.p["decoder.ctc_lo.weight"] + self.p["decoder.ctc_lo.bias"]
             # GRU: the c box is handed through unchanged (encoder.py:95-97)
             c_box = torch.stack(cs) if not self.use_gru else (None if init_c is None else torch.as_tensor(init_c))

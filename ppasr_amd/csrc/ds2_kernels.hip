@@ -320,9 +320,9 @@ __global__ __launch_bounds__(kThreads) void k_lstm_step_mfma(const float* __rest
 // time t, so launch s runs every layer l with 0 <= s - l < T at time t = s - l: T + L - 1 dependent launches instead
 // of T * L.  For l >= 1 the input projection is folded into the step (there is no [B*T][4H] pre-pass to wait for):
 //   W_ih LN(y) + b = rstd * (W' y - mean * colsum(W')) + (W_ih beta + b),   W' = W_ih diag(gamma)
-// so the MFMA runs on the RAW previous-layer output y_{l-1}[t] (a second accumulator tile next to h_{t-1} W_hh^T) and
-// the LayerNorm of the row enters through its mean / rstd, which the waves accumulate from the very A fragments they
-// load (sum and sum of squares per row).  Same workgroup shape as k_lstm_step_mfma.
+// so the MFMA runs on the previous-layer output y_{l-1}[t] less a per-row pivot (a second accumulator tile next to
+// h_{t-1} W_hh^T) and the LayerNorm of the row enters through its mean / rstd, which the waves accumulate from the very A
+// fragments they load (sum and sum of squares per row).  Same workgroup shape as k_lstm_step_mfma.
 // Occupancy: at 152 VGPRs (prefetch depth 8) ONE workgroup fits a CU and the 5 x 128 workgroups of a launch ran as 2.5
 // rounds (round 3: depth 4, 103 registers: two workgroups per CU, 1.25 rounds).  Round 4: one accumulator tile for both
 // products, buffer loads instead of 64-bit per-lane addresses and depth 2 keep the kernel at 80 registers = six waves per
@@ -428,6 +428,16 @@ __global__ __launch_bounds__(kThreads, PPASR_WAVE_OCC) void k_lstm_wave(const fl
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const __amdgpu_buffer_rsrc_t rs_a = wstream_rsrc(yprev + rtile_f), rs_w = wstream_rsrc(lay.wih_pk + (size_t)tile * n_groups * 64);
+    // The fold subtracts twice -- E[y^2] - mean^2 and acc - mean s_n -- and both cancel once |mean| >> std, which the rows of a
+    // trained stack are (h near one value in every unit).  So the row is shifted by a per-row PIVOT before the statistics AND
+    // the product: with y' = y - p, LN(y) = LN(y') exactly, the sums below are those of y', and the cancellation shrinks to
+    // |mean - p| against std.  p = the mean of the row's first four elements (k-group 0, the fragment every lane half of every
+    // K slice can load with one instruction: the same p in all 8 waves of a row); finished rows read zeros and p = 0.
+    float pivot;
+    {
+      const f32x4 p4 = wstream_load(rs_a, row_live ? l31 * 16 : 0x7fffffff, 0);
+      pivot = 0.25f * ((p4[0] + p4[1]) + (p4[2] + p4[3]));
+    }
     f32x4 ra[PFD], rb[PFD];
 #pragma unroll
     for (int q = 0; q < PFD; ++q) {
@@ -442,10 +452,11 @@ __global__ __launch_bounds__(kThreads, PPASR_WAVE_OCC) void k_lstm_wave(const fl
           ra[q] = wstream_load(rs_a, voff_a, (g0 + g + PFD + q) * 1024);
           rb[q] = wstream_load(rs_w, voff_w, (g0 + g + PFD + q) * 1024);
         }
-        sum += a[0] + a[1] + a[2] + a[3];
-        sq += a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + a[3] * a[3];
+        const f32x4 ap = a - pivot;
+        sum += ap[0] + ap[1] + ap[2] + ap[3];
+        sq += ap[0] * ap[0] + ap[1] * ap[1] + ap[2] * ap[2] + ap[3] * ap[3];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], bq[j], acc, 0, 0, 0);
+        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[j], bq[j], acc, 0, 0, 0);
       }
     }
     sum += __shfl_xor(sum, 32);
@@ -478,7 +489,7 @@ __global__ __launch_bounds__(kThreads, PPASR_WAVE_OCC) void k_lstm_wave(const fl
           ss += stat_s[w * NR + row];
           qq += stat_q[w * NR + row];
         }
-        const float mean = ss / (float)H;
+        const float mean = ss / (float)H;  // of the pivoted row (mean - pivot of the raw one); acc is the pivoted row's too
         const float var = fmaxf(qq / (float)H - mean * mean, 0.f);
         const float rstd = 1.0f / sqrtf(var + 1e-5f);
         vi = rstd * (acc - mean * lay.s_n[n]) + lay.c_n[n];

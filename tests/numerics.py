@@ -5,7 +5,13 @@ The budgets were set from measurement, not borrowed from an acceptance bar (NOTE
 the MI355X route matrix (tests/test_fp64_routes_gpu.py) printed against the float64 oracle, rounded up to 1 / 2 / 5 x
 10^k.  tests/test_numerics_budget_cpu.py pins them from the other side: the fp32 oracle sits below a
 tenth of each budget, every constant is <= 1e-4, and each mutation of a fixed list of realistic kernel bugs exceeds its
-family's budget by at least 5x."""
+family's budget by at least 5x.
+
+Off-centre and saturated checkpoints (tests/offcentre_cases.py) are ill-conditioned on purpose: exact fp32 arithmetic
+itself leaves the budget there.  Their tolerance is `tol(budget, e32)` below: the family budget, or four times the error
+of the fp32 oracle against the float64 oracle on that very case when that is larger.  e32 is computed when the test runs,
+never taken from the library under test; a case is admitted only while tol <= TOL_CAP and every mutation stays >= 5x
+above it (tests/test_offcentre_cases_cpu.py)."""
 import numpy as np
 import torch
 
@@ -21,6 +27,17 @@ F32_BUDGET = 2e-5
 F32_BUDGET_DS2 = 5e-5
 # every fp32 budget of this module; none may exceed 1e-4 (tests/test_numerics_budget_cpu.py)
 BUDGETS = {"F32_BUDGET": F32_BUDGET, "F32_BUDGET_DS2": F32_BUDGET_DS2}
+
+# Ill-conditioned cases: the largest ratio of a measured MI355X error to the fp32 oracle's floor recorded above is
+# 5.1e-6 / 1.5e-6 = 3.4 (DeepSpeech2), rounded up.
+FLOOR_FACTOR = 4.0
+TOL_CAP = 1e-3  # a case whose tolerance would pass this is not admitted
+
+
+def tol(budget, e32):
+    """tolerance of one off-centre / saturated case: max(family budget, FLOOR_FACTOR x the fp32 oracle's error on it)"""
+    return max(budget, FLOOR_FACTOR * e32)
+
 
 # log-probabilities below this are compared clipped: fp32 probabilities end at ~1e-38 (e^-87)
 LOG_FLOOR = -80.0
