@@ -256,7 +256,7 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
     const int mul = reduced ? 8 : 4;
     const PadSkip& ps = reduced ? psH : psF;
     // under-filled launches up to kSplitRows16Max rows (one utterance, small batches; fp32): the single-unit launches on
-    // the Conformer's 16-row kernels through weight views, as the streaming chunk does (capi_stream.hip)
+    // the Conformer's 16-row kernels through weight views, as a stream handle's chunk does (capi_stream.hip sq_stream_layers)
     const bool views16 = ffn_split_for(h, Mi) > 1 && !(rowsF == 16 && h->ffn_split < 0) && Mi <= kSplitRows16Max &&
                          !(h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty());
     auto qkv_view = [](const SqLayerW& w) {

@@ -41,11 +41,6 @@ ppasr_status shift_cache(float* buf, int from, int keep, float* tmp, hipStream_t
   return PPASR_OK;
 }
 
-// pointwise_conv1 + GLU of the cached conv inputs of EVERY layer -> s->g_hist[i] (lo_i rows each), one launch: the
-// histories are last chunk's state (hist_update of layer i runs after layer i has consumed g_hist[i])
-void history_glu_all(ppasr_stream_s* s, hipStream_t st) {
-  launch_pw1_glu_layers(s->xh_hist, s->g_hist, s->hist_tab, s->m->desc.num_blocks, s->lo, st);
-}
 
 // the reference's shape arithmetic for one chunk of c frames on a session whose caches hold cache_t (full-rate layers) /
 // cache_r (half-rate layers) frames, `offset` frames emitted so far and room for `cap` keys per layer; shared by the
@@ -111,20 +106,144 @@ ppasr_status finish_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* shift_tm
   return PPASR_OK;
 }
 
-// ---- Conformer / Efficient-Conformer ----
-// `partial`: scratch for the split route of under-filled launches (ppasr_set_ffn_split; a chunk is ONE row block, so by
-// default its feed-forward modules are split over 8 workgroups) -- the conv1 buffer, free after the front-end
-ppasr_status conformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* xa, float* xb, float* xc, float* qkv, float* ctx,
-                             float* g, float* xhat, float* partial, int* frames_out, hipStream_t st) {
-  ppasr_model_s* h = s->m;
-  const int n_chunks = h->desc.linear_units / 256;
-  const int H = h->desc.attention_heads;
-  int Ti = p.c, mul = 4, pstride = 1;
+// ---- the rows a streaming round runs on ----
+// n chunks of c frames each (c_r behind a time reduction / the stride layer), stacked: ONE chunk of a stream handle, or the
+// chunks of the sessions a group round lists.  The layer walks below are written once against this view; what differs by
+// caller -- where the caches live and who moves them on -- is behind its helpers.
+struct StreamRows {
+  int n, c, c_r;
+  float *kc, *vc;       // K / V caches [session][L][cap][256]
+  int cap;
+  long long kv_sess;    // floats from one session's caches to the next's
+  float* xh_hist;       // conv-module input histories [session][L][lo][256]
+  int lo;
+  long long hist_sess;
+  // GLU(pointwise_conv1(history)) scratch.  hist_tab (device [L]): every layer's in one launch ahead of the walk, layer i's
+  // slab [n * lo][256] at i * n * lo rows.  No table (the Conformer group): layer i gathers its sessions' histories to
+  // [n][lo][256] at g_hist and GLUs them to the [n][lo][256] behind, inside the walk
+  float* g_hist;
+  const HistLayer* hist_tab;
+  int cache_t, used_r, pos0;      // a stream handle: cached frames of the full-rate / half-rate layers, position of key 0
+  const SessDesc *full, *half;    // a session group: the round's device descriptors of the full-rate / half-rate layers
+
+  bool handle() const { return !full; }
+  float* k_of(int i) const { return kc + (size_t)i * cap * kD; }
+  float* v_of(int i) const { return vc + (size_t)i * cap * kD; }
+  float* hist_of(int i) const { return xh_hist + (size_t)i * lo * kD; }
+  const SessDesc* desc(bool half_rate) const { return half_rate ? half : full; }
+  int cached(bool half_rate) const { return half_rate ? used_r : cache_t; }
+  // Where the launch that makes layer i's qkv writes the K / V rows.  A handle: straight behind the cached frames of its
+  // cache.  A group: nowhere (they stay in qkv), kv_append scatters them to the listed sessions
+  float* k_dst(int i, bool half_rate) const { return handle() ? k_of(i) + (size_t)cached(half_rate) * kD : nullptr; }
+  float* v_dst(int i, bool half_rate) const { return handle() ? v_of(i) + (size_t)cached(half_rate) * kD : nullptr; }
+  void kv_append(const float* qkv, int i, bool half_rate, int Ti, hipStream_t st) const {
+    if (handle()) launch_kv_append(qkv, k_dst(i, half_rate), v_dst(i, half_rate), Ti, st);
+    else launch_kv_append_group(qkv, k_of(i), v_of(i), kv_sess, desc(half_rate), n, Ti, st);
+  }
+  // the cache half of a layer's attention (a: built for Ti query frames in tokens of grp frames, no cache).  A handle:
+  // cache + chunk frames re-cut into tokens from the START of the cache (pad4group on the concatenated keys,
+  // efficient_conformer/attention.py:160-175).  A group: the same per session, from its descriptor (k_attention_t)
+  void attn_cache(AttnArgs& a, bool half_rate, int Ti, int grp) const {
+    if (handle()) {
+      a.kv_frames = cached(half_rate) + Ti;
+      a.T2 = ceil_div(a.kv_frames, grp);
+      a.pos0 = pos0;
+    } else {
+      a.sess = desc(half_rate);
+      a.sess_stride = kv_sess;
+    }
+  }
+  // pointwise_conv1 + GLU of the cached conv inputs: the histories are last chunk's state (hist_step of layer i runs after
+  // layer i has consumed its slab)
+  void glu_histories(int L, hipStream_t st) const {
+    if (!hist_tab) return;
+    if (handle()) launch_pw1_glu_layers(xh_hist, g_hist, hist_tab, L, lo, st);
+    else launch_pw1_glu_layers_group(xh_hist, hist_sess, full, g_hist, hist_tab, L, n, lo, st);
+  }
+  void glu_layer_history(int i, const LayerW& W, hipStream_t st) const {
+    if (hist_tab) return;
+    launch_hist_gather(hist_of(i), hist_sess, full, g_hist, n, lo, st);
+    launch_pw1_glu(g_hist, g_hist_of(i), W, n * lo, st);
+  }
+  float* g_hist_of(int i) const { return g_hist + (size_t)(hist_tab ? i : 1) * n * lo * kD; }  // (list position b at row b * lo_i)
+  // layer i's histories move on by the chunk's Ti rows of xhat (moved: a handle's launch did it on the side -- HistMove,
+  // launch_pw1_glu_cols_16)
+  void hist_step(int i, bool half_rate, const float* xhat, int Ti, int lo_i, bool moved, hipStream_t st) const {
+    if (!handle()) launch_hist_update_group(hist_of(i), hist_sess, desc(half_rate), xhat, n, Ti, lo_i, st);
+    else if (!moved) launch_hist_update(hist_of(i), xhat, Ti, lo_i, st);
+  }
+};
+
+StreamRows handle_rows(const ppasr_stream_s* s, const ChunkPlan& p) {
+  return StreamRows{1, p.c, p.c_r, s->kc, s->vc, s->cap, 0, s->xh_hist, s->lo, 0, s->g_hist, s->hist_tab, s->cache_t, p.used_r,
+                    p.pos0, nullptr, nullptr};
+}
+
+// the buffers of a round in its workspace: the batched layout for B = n and, behind it, the conv-module input rows
+// xhat [rows][256] of this chunk; `behind` = the first float past them (64-float aligned), the caller's own scratch
+struct StreamWs {
+  float *y1, *y2, *xa, *xb, *xc, *qkv, *ctx, *g, *xs, *rmax, *rsum, *fa, *fp, *xhat, *behind;
+};
+StreamWs carve_ws(float* ws, const WsLayout& wl, int rows) {
+  float* xhat = ws + wl.total;
+  return StreamWs{ws + wl.y1, ws + wl.y2, ws + wl.xa, ws + wl.xb, ws + wl.xc, ws + wl.qkv, ws + wl.ctx, ws + wl.g, ws + wl.xs,
+                  ws + wl.rmax, ws + wl.rsum, ws + wl.fa, ws + wl.fp, xhat, xhat + (((size_t)rows * kD + 63) & ~(size_t)63)};
+}
+
+// conv front end + input projection of the n chunks of T frames -> w.xa [n * c][256].
+// The caller is a stream handle: ONE row block, so
+//   - conv2 splits its taps (K) over workgroups, scratch at conv2_part (behind the handle's shift scratch);
+//   - up to 32 rows the input projection runs a workgroup per 256-wide K chunk -- F2 of them -- instead of 8 workgroups of
+//     2 - 3 chunks;
+//   - the conv2d6 / conv2d8 front ends exist (Conformer handles only; groups are built for conv2d).
+void stream_front(const ppasr_model_s* h, const StreamRows& v, const StreamWs& w, const float* feats, int T, float* conv2_part,
+                  hipStream_t st) {
+  const auto fd = h->front_dims(T);
+  const int F1 = h->F1, F2 = h->F2, M = v.n * v.c, S = ffn_split_for(h, M);
+  launch_conv1(feats, h->front, w.y1, v.n, T, h->desc.input_dim, fd.T1, F1, st);
+  if (h->desc.input_layer == 8) {  // Conv2dSubsampling8: three 3x3 / 2 convs, the third one over conv1's output buffer
+    launch_conv_stage(w.y1, h->front.conv2_w, h->front.conv2_b, w.y2, 1, fd.T1, F1, fd.T2, F2, 3, 2, st);
+    launch_conv_stage(w.y2, h->front.conv3_w, h->front.conv3_b, w.y1, 1, fd.T2, F2, v.c, h->F3, 3, 2, st);
+    launch_embed(w.y1, h->front, w.xa, v.c, h->F3 * kD, sqrtf((float)kD), false, st, PadSkip{}, S, w.y2);
+    return;
+  }
+  // (3x3 / 2, or conv2d6's 5x5 / 3: FrontW::conv2_k / _s)
+  launch_conv2(w.y1, h->front, w.y2, v.n, fd.T1, F1, v.c, F2, st, PadSkip{}, nullptr, nullptr, conv2_part,
+               conv2_part ? conv_stage_part_floats(v.c * F2) : 0);
+  launch_embed(w.y2, h->front, w.xa, M, F2 * kD, sqrtf((float)kD), /*scale_before_bias=*/is_sq(h), st, PadSkip{},
+               (v.handle() && v.c <= 32 && S > 1) ? F2 : S, w.y1);
+}
+
+// CTC head over the n * frames encoder rows x.  The caller is a stream handle: up to 32 rows are one row block, which takes
+// as many column slices as give every wave ONE 32-column vocabulary tile -- 17 at V = 4233 -- not 8
+void stream_head(const ppasr_model_s* h, const StreamRows& v, const StreamWs& w, const float* x, int frames, float* probs,
+                 int32_t* frame_argmax, float* frame_maxprob, hipStream_t st) {
+  const int M = v.n * frames, S = ffn_split_for(h, M);
+  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(w.fa);
+  float* fp = frame_maxprob ? frame_maxprob : w.fp;
+  const int slices = (v.handle() && frames <= 32 && S > 1) ? std::min((h->head.n_tiles + 7) / 8, 32) : S;
+  launch_ctc_head(x, h->head, probs, fa, fp, w.rmax, w.rsum, M, st, PadSkip{}, slices, w.y1);
+  if (probs) launch_softmax_from_stats(probs, w.rmax, w.rsum, M, h->head.V, st);
+}
+
+// ---- Conformer / Efficient-Conformer: the layers of a streaming round over the rows of v, w.xa -> w.xa; returns the
+// frames each chunk leaves with (c_r behind a stride layer).  Few rows are an under-filled grid: the split route
+// (ppasr_set_ffn_split) runs the feed-forward modules over S workgroups per row block, partial sums in w.y1 (the conv1
+// buffer, free after the front end); S == 1 runs the fused kernels.
+// ppasr_set_gemm_mode(h, PPASR_GEMM_F16X3) puts the split route's GEMM units on the fp16 x3 route (Lk = the layer's h3 view: the
+// same LayerNorm / bias pointers, re-packed weights; its ptab are operand planes, so the attention keeps L's); the fused
+// kernels stay fp32.  Out-of-range activations are saturated and counted (ppasr_gemm_guard_stats); a chunk is not re-run.
+int conformer_stream_layers(const ppasr_model_s* h, const StreamRows& v, const StreamWs& w, hipStream_t st) {
+  const int n_chunks = h->desc.linear_units / 256, H = h->desc.attention_heads, n = v.n;
+  const bool h3_mode = h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty();
+  float *xa = w.xa, *xb = w.xb, *xc = w.xc, *qkv = w.qkv, *ctx = w.ctx, *g = w.g, *xhat = w.xhat, *partial = w.y1;
+  int Ti = v.c, mul = 4, pstride = 1;
   bool half = false;
-  history_glu_all(s, st);
-  // Consumer-side joins (conformer_kernels.h JoinIn; fp32 route, <= 16 rows): a feed-forward module leaves 2 S partial tiles
-  // and a PENDING join that the next launch computes in its prologue.  Macaron slices go to partial, final slices to
-  // the tiles behind them (the pending final join of block i is read while block i + 1's macaron slices are written).
+  v.glu_histories(h->desc.num_blocks, st);
+  // Consumer-side joins (conformer_kernels.h JoinIn; a stream handle's chunk on the fp32 route, <= 16 rows): a feed-forward
+  // module leaves 2 S partial tiles and a PENDING join that the next launch computes in its prologue.  Macaron slices go to
+  // partial, final slices to the tiles behind them (the pending final join of block i is read while block i + 1's macaron
+  // slices are written).  Single-session kernels: a group never takes them, whatever its rows.
   JoinIn pending;
   auto flush = [&](int M) {  // a launch that cannot take a pending join in: the join alone
     if (pending.partial) launch_join16(pending, M, st);
@@ -132,139 +251,131 @@ ppasr_status conformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* xa, f
   };
   for (int i = 0; i < h->desc.num_blocks; ++i) {
     const LayerW& L = h->layers[i];
-    const int grp = h->layer_group[i];
-    const int n_cache = half ? p.used_r : s->cache_t;
-    const int T2f = n_cache + Ti;
-    float* kc = s->kc + (size_t)i * s->cap * kD;
-    float* vc = s->vc + (size_t)i * s->cap * kD;
-    float* xh = s->xh_hist + (size_t)i * s->lo * kD;
-    const int lo_i = layer_lo(h, i);
-    const int S = ffn_split_for(h, Ti);
-    // ppasr_set_gemm_mode(h, PPASR_GEMM_F16X3): the split route's GEMM units on the fp16 x3 route (Lk = the layer's h3 view: the
-    // same LayerNorm / bias pointers, re-packed weights; its ptab are operand planes, so the attention below keeps L's).
-    // Out-of-range activations are saturated and counted (ppasr_gemm_guard_stats); a chunk is not re-run.
-    const bool h3 = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty();
+    const int grp = h->layer_group[i], KS = h->layer_ks[i], lo_i = layer_lo(h, i), M = n * Ti;
+    const int S = ffn_split_for(h, M);
+    const bool h3 = S > 1 && h3_mode;
     const LayerW& Lk = h3 ? h->layers_h3[i] : L;
-    const bool fused_joins = !h3 && ffn_half16_route(Ti, S, n_chunks);
+    const bool fused_joins = v.handle() && !h3 && ffn_half16_route(Ti, S, n_chunks);
     if (fused_joins) {
       launch_ffn_half16(xa, pending, L.ln_mac_g, L.ln_mac_b, L.ffm_w1, L.ffm_b1, L.ffm_w2, partial, Ti, n_chunks, st);
       const JoinIn mac{partial, 2 * S, L.ffm_b2, 0.5f, xa, nullptr, nullptr, xb};
-      launch_join_ln_qkv16(mac, qkv, L, Ti, st, kc + (size_t)n_cache * kD, vc + (size_t)n_cache * kD);
+      launch_join_ln_qkv16(mac, qkv, L, Ti, st, v.k_dst(i, half), v.v_dst(i, half));
       pending = JoinIn{};
     } else if (S > 1) {
-      flush(Ti);
+      flush(M);
       launch_ffn_split(xa, L.ln_mac_g, L.ln_mac_b, Lk.ffm_w1, L.ffm_b1, Lk.ffm_w2, L.ffm_b2, 0.5f, nullptr, nullptr, partial, xb,
-                       Ti, n_chunks, S, st, PadSkip{}, false, h3);
-      launch_ln_qkv(xb, qkv, Lk, Ti, st, PadSkip{}, kc + (size_t)n_cache * kD, vc + (size_t)n_cache * kD, h3);
+                       M, n_chunks, S, st, PadSkip{}, false, h3);
+      launch_ln_qkv(xb, qkv, Lk, M, st, PadSkip{}, v.k_dst(i, half), v.v_dst(i, half), h3);
     } else {
-      flush(Ti);
-      launch_ffn_qkv(xa, xb, qkv, L, Ti, n_chunks, st);
-      launch_kv_append(qkv, kc + (size_t)n_cache * kD, vc + (size_t)n_cache * kD, Ti, st);
+      flush(M);
+      launch_ffn_qkv(xa, xb, qkv, L, M, n_chunks, st);
     }
-    // grouped attention re-cuts cache + chunk frames into groups of 3 from the START of the cache (pad4group on the
-    // concatenated keys, efficient_conformer/attention.py:160-175), zero-padded tail group
-    AttnArgs a{qkv, 768, kc, kD, vc, kD, ceil_div(Ti, grp), ceil_div(T2f, grp), p.pos0, nullptr, ctx, L.pos_u, L.pos_v,
-               L.ptab, pstride, mul * grp, Ti, T2f, grp};
-    launch_attention(a, 1, H, st);
-    float* gh = s->g_hist + (size_t)i * s->lo * kD;
-    HistMove hm{xh, lo_i, false};
-    launch_out_glu(ctx, xb, xc, g, xhat, Lk, nullptr, Ti, Ti, mul, st, PadSkip{}, S > 1 ? xhat : nullptr, h3, &hm);
+    if (S == 1 || !v.handle()) v.kv_append(qkv, i, half, Ti, st);  // (a handle's split-route launches wrote them in place)
+    const int Tq = ceil_div(Ti, grp);
+    AttnArgs a{qkv, 768, v.k_of(i), kD, v.v_of(i), kD, Tq, Tq, 0, nullptr, ctx, L.pos_u, L.pos_v, L.ptab, pstride, mul * grp,
+               Ti, Ti, grp};
+    v.attn_cache(a, half, Ti, grp);
+    launch_attention(a, n, H, st);
+    v.glu_layer_history(i, L, st);
+    float* gh = v.g_hist_of(i);
+    HistMove hm{v.hist_of(i), lo_i, false};  // (a handle's out_glu launch may move the history on the side)
+    launch_out_glu(ctx, xb, xc, g, xhat, Lk, nullptr, M, Ti, mul, st, PadSkip{}, S > 1 ? xhat : nullptr, h3,
+                   v.handle() ? &hm : nullptr);
     if (is_eff(h) && i == h->desc.stride_layer_idx) {
-      const int Ts = ceil_div(Ti, 2);
-      const int Ss = ffn_split_for(h, Ts);
-      if (Ss > 1) {  // one row block: the conv half of the stride layer alone, its feed-forward module over the slices
-        launch_conv_ffn_stride(g, gh, xc, xa, Lk, nullptr, 1, Ti, Ts, n_chunks, h->layer_ks[i], mul * 2, st, PadSkip{}, true, h3, ctx);
-        launch_ffn_split(ctx, L.ln_ff_g, L.ln_ff_b, Lk.ff_w1, L.ff_b1, Lk.ff_w2, L.ff_b2, 0.5f, L.ln_fin_g, L.ln_fin_b, partial, xa, Ts,
-                         n_chunks, Ss, st, PadSkip{}, false, h3);
-      } else {
-        launch_conv_ffn_stride(g, gh, xc, xa, Lk, nullptr, 1, Ti, Ts, n_chunks, h->layer_ks[i], mul * 2, st, PadSkip{}, true, h3);
-      }
-      if (!hm.done) launch_hist_update(xh, xhat, Ti, lo_i, st);
-      Ti = Ts;
+      const int Ts = ceil_div(Ti, 2), Ms = n * Ts, Ss = ffn_split_for(h, Ms);
+      // the fp16 x3 view of the stride layer: a handle keeps the layer's (from S), a group decides by the strided rows (Ss)
+      const bool h3s = v.handle() ? h3 : (Ss > 1 && h3_mode);
+      const LayerW& Ls = h3s ? h->layers_h3[i] : L;
+      // Ss > 1: the conv half of the stride layer alone (x3 -> ctx), its feed-forward module over the slices
+      launch_conv_ffn_stride(g, gh, xc, xa, Ls, nullptr, n, Ti, Ts, n_chunks, KS, mul * 2, st, PadSkip{}, true, h3s,
+                             Ss > 1 ? ctx : nullptr);
+      if (Ss > 1)
+        launch_ffn_split(ctx, L.ln_ff_g, L.ln_ff_b, Ls.ff_w1, L.ff_b1, Ls.ff_w2, L.ff_b2, 0.5f, L.ln_fin_g, L.ln_fin_b, partial, xa,
+                         Ms, n_chunks, Ss, st, PadSkip{}, false, h3s);
+      v.hist_step(i, half, xhat, Ti, lo_i, hm.done, st);
+      Ti = Ts;  // masks[:, :, ::2], pos_emb[:, ::2]  (efficient_conformer/encoder.py:252-257)
       mul *= 2;
       pstride *= 2;
       half = true;
-    } else {
-      if (fused_joins) {
-        launch_conv_pre(g, gh, xc, ctx, L, nullptr, Ti, Ti, h->layer_ks[i], mul, st, true, PadSkip{}, false);
-        float* part_fin = partial + (size_t)2 * S * Ti * kD;  // (behind the macaron module's 2 S tiles of Ti rows)
-        launch_ffn_half16(ctx, JoinIn{}, L.ln_ff_g, L.ln_ff_b, L.ff_w1, L.ff_b1, L.ff_w2, part_fin, Ti, n_chunks, st);
-        pending = JoinIn{part_fin, 2 * S, L.ff_b2, 0.5f, ctx, L.ln_fin_g, L.ln_fin_b, xa};
-      } else if (S > 1) {
-        launch_conv_pre(g, gh, xc, ctx, Lk, nullptr, Ti, Ti, h->layer_ks[i], mul, st, true, PadSkip{}, h3);
-        launch_ffn_split(ctx, L.ln_ff_g, L.ln_ff_b, Lk.ff_w1, L.ff_b1, Lk.ff_w2, L.ff_b2, 0.5f, L.ln_fin_g, L.ln_fin_b, partial,
-                         xa, Ti, n_chunks, S, st, PadSkip{}, false, h3);
-      } else {
-        launch_conv_ffn(g, gh, xc, xa, L, nullptr, Ti, Ti, n_chunks, h->layer_ks[i], mul, nullptr, nullptr, nullptr, st);
-      }
-      if (!hm.done) launch_hist_update(xh, xhat, Ti, lo_i, st);
+      continue;
     }
+    if (fused_joins) {
+      launch_conv_pre(g, gh, xc, ctx, L, nullptr, Ti, Ti, KS, mul, st, true, PadSkip{}, false);
+      float* part_fin = partial + (size_t)2 * S * Ti * kD;  // (behind the macaron module's 2 S tiles of Ti rows)
+      launch_ffn_half16(ctx, JoinIn{}, L.ln_ff_g, L.ln_ff_b, L.ff_w1, L.ff_b1, L.ff_w2, part_fin, Ti, n_chunks, st);
+      pending = JoinIn{part_fin, 2 * S, L.ff_b2, 0.5f, ctx, L.ln_fin_g, L.ln_fin_b, xa};
+    } else if (S > 1) {
+      launch_conv_pre(g, gh, xc, ctx, Lk, nullptr, M, Ti, KS, mul, st, true, PadSkip{}, h3);
+      launch_ffn_split(ctx, L.ln_ff_g, L.ln_ff_b, Lk.ff_w1, L.ff_b1, Lk.ff_w2, L.ff_b2, 0.5f, L.ln_fin_g, L.ln_fin_b, partial, xa,
+                       M, n_chunks, S, st, PadSkip{}, false, h3);
+    } else {
+      launch_conv_ffn(g, gh, xc, xa, L, nullptr, M, Ti, n_chunks, KS, mul, nullptr, nullptr, nullptr, st);
+    }
+    v.hist_step(i, half, xhat, Ti, lo_i, hm.done, st);
   }
-  flush(Ti);  // (the last block's final join)
-  *frames_out = Ti;
-  return PPASR_OK;
+  flush(n * Ti);  // (the last block's final join)
+  return Ti;
 }
 
-// ---- Squeezeformer ----
-ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* xa, float* xb, float* xc, float* qkv,
-                                 float* ctx, float* g, float* xs, float* xhat, float* partial, float** x_final,
-                                 hipStream_t st) {
-  ppasr_model_s* h = s->m;
-  const int L = h->desc.num_blocks, H = h->desc.attention_heads;
+// ---- Squeezeformer: the layers of a streaming round over the rows of v (n * c full-rate rows, n * c_r half-rate rows
+// between reduce_idx and recover_idx), w.xa -> *x_final.  Split route and fp16 x3 mode as in conformer_stream_layers: the
+// mode covers the feed-forward slices of the split route, a layer whose rows leave it (ffn_split_for = 1: more than 4 096
+// stacked rows at the default setting, or ppasr_set_ffn_split(0)) runs the fused fp32 kernels in either mode.
+ppasr_status sq_stream_layers(const ppasr_model_s* h, const StreamRows& v, const StreamWs& w, float** x_final, hipStream_t st) {
+  const int L = h->desc.num_blocks, H = h->desc.attention_heads, n = v.n;
   const int n_chunks = h->desc.linear_units / 256, KS = h->desc.cnn_module_kernel;
-  launch_ln_rows(xa, h->preln_g, h->preln_b, p.c, st);
-  history_glu_all(s, st);
-  float* x = xa;
-  float* other = xb;
+  float *xc = w.xc, *qkv = w.qkv, *ctx = w.ctx, *g = w.g, *xhat = w.xhat, *partial = w.y1;
+  launch_ln_rows(w.xa, h->preln_g, h->preln_b, n * v.c, st);
+  v.glu_histories(L, st);
+  float* x = w.xa;
+  float* other = w.xb;
   bool reduced = false, have_qkv = false;
-  // Round 6: on the split route (fp32) the layer's single-unit launches run on the Conformer's 16-row kernels through weight
-  // views -- Q / K / V thirds (no LayerNorm: ln_mha_g = nullptr; K and V straight into the cache rows), out-projection +
-  // LayerNorm, pointwise_conv1 + GLU over two column halves (which also moves the SCALED conv-input history on)
+  // A stream handle on the split route (fp32) runs the layer's single-unit launches on the Conformer's 16-row kernels through
+  // weight views -- Q / K / V thirds (no LayerNorm: ln_mha_g = nullptr; K and V straight into the cache rows), out-projection
+  // + LayerNorm, pointwise_conv1 + GLU over two column halves (which also moves the SCALED conv-input history on).
+  // Single-session launches: a group runs launch_sq_qkv / _oproj / _pw1glu, whatever its rows
   bool kv_in_cache = false;  // this layer's K / V rows were written to its cache by the launch that made its qkv
-  auto qkv_view = [](const SqLayerW& w) {
-    LayerW v{};
-    v.wqkv = w.wqkv;
-    v.bqkv = w.bqkv;
-    return v;
+  auto qkv_view = [](const SqLayerW& W) {
+    LayerW view{};
+    view.wqkv = W.wqkv;
+    view.bqkv = W.bqkv;
+    return view;
   };
   for (int i = 0; i < L; ++i) {
     const SqLayerW& W = h->sq_layers[i];
     if (i == h->desc.reduce_idx) {
-      HIP_TRY(hipMemcpyAsync(xs, x, (size_t)p.c * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
-      launch_sq_reduce(x, other, qkv, h->sq_reduce, W.wqkv, W.bqkv, nullptr, 1, p.c, p.c_r, st);
+      HIP_TRY(hipMemcpyAsync(w.xs, x, (size_t)n * v.c * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
+      launch_sq_reduce(x, other, qkv, h->sq_reduce, W.wqkv, W.bqkv, nullptr, n, v.c, v.c_r, st);
       std::swap(x, other);
       reduced = true;
       have_qkv = true;
     }
     if (i == h->desc.recover_idx && reduced) {
-      launch_sq_recover(x, xs, other, qkv, h->sq_wrec, h->sq_brec, W.wqkv, W.bqkv, 1, p.c, p.c_r, st);
+      launch_sq_recover(x, w.xs, other, qkv, h->sq_wrec, h->sq_brec, W.wqkv, W.bqkv, n, v.c, v.c_r, st);
       std::swap(x, other);
       reduced = false;
       have_qkv = true;
     }
-    const int Ti = reduced ? p.c_r : p.c;
+    const int Ti = reduced ? v.c_r : v.c, M = n * Ti;
     const int mul = reduced ? 8 : 4;
-    const int n_cache = reduced ? p.used_r : s->cache_t;
-    float* kc = s->kc + (size_t)i * s->cap * kD;
-    float* vc = s->vc + (size_t)i * s->cap * kD;
-    float* xh = s->xh_hist + (size_t)i * s->lo * kD;
-    const int S = ffn_split_for(h, Ti);  // one row block: split route (see squeezeformer_encode)
+    const int S = ffn_split_for(h, M);
     const bool h3s = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty();  // (the FFN slices in the mode)
-    const bool r16 = S > 1 && !h3s && Ti <= kSplitRows16Max;
+    const bool r16 = v.handle() && S > 1 && !h3s && Ti <= kSplitRows16Max;
     if (!have_qkv) {
       if (r16) {
-        launch_ln_qkv(x, qkv, qkv_view(W), Ti, st, PadSkip{}, kc + (size_t)n_cache * kD, vc + (size_t)n_cache * kD, false);
+        launch_ln_qkv(x, qkv, qkv_view(W), Ti, st, PadSkip{}, v.k_dst(i, reduced), v.v_dst(i, reduced), false);
         kv_in_cache = true;
       } else {
-        launch_sq_qkv(x, qkv, W.wqkv, W.bqkv, Ti, st);
+        launch_sq_qkv(x, qkv, W.wqkv, W.bqkv, M, st);
       }
     }
-    if (!kv_in_cache) launch_kv_append(qkv, kc + (size_t)n_cache * kD, vc + (size_t)n_cache * kD, Ti, st);
+    if (!kv_in_cache) v.kv_append(qkv, i, reduced, Ti, st);
     kv_in_cache = false;
-    AttnArgs a{qkv, 768, kc, kD, vc, kD, Ti, n_cache + Ti, p.pos0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, reduced ? 2 : 1,
-               mul, Ti, n_cache + Ti, 1};
-    launch_attention(a, 1, H, st);
-    float* gh = s->g_hist + (size_t)i * s->lo * kD;
+    AttnArgs a{qkv, 768, v.k_of(i), kD, v.v_of(i), kD, Ti, Ti, 0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, reduced ? 2 : 1, mul,
+               Ti, Ti, 1};
+    v.attn_cache(a, reduced, Ti, 1);
+    launch_attention(a, n, H, st);
+    float* gh = v.g_hist_of(i);
     const bool fuse_next = (i + 1 < L) && (i + 1 != h->desc.reduce_idx) && !(i + 1 == h->desc.recover_idx && reduced);
     const SqLayerW* Wn = fuse_next ? &h->sq_layers[i + 1] : nullptr;
     bool hist_moved = false;
@@ -275,39 +386,55 @@ ppasr_status squeezeformer_chunk(ppasr_stream_s* s, const ChunkPlan& p, float* x
         vo.wo = W.wo; vo.bo = W.bo; vo.ln_conv_g = W.ln1_g; vo.ln_conv_b = W.ln1_b;
         launch_oproj_ln_16(ctx, x, g, other, vo, Ti, st);
       } else {
-        launch_sq_oproj(ctx, x, other, W, Ti, st);
+        launch_sq_oproj(ctx, x, other, W, M, st);
       }
-      launch_ffn_split(other, nullptr, nullptr, Ws.ff1_w1, W.ff1_b1, Ws.ff1_w2, W.ff1_b2, 1.0f, W.ln2_g, W.ln2_b, partial, xc,
-                       Ti, n_chunks, S, st, PadSkip{}, false, h3s);
+      launch_ffn_split(other, nullptr, nullptr, Ws.ff1_w1, W.ff1_b1, Ws.ff1_w2, W.ff1_b2, 1.0f, W.ln2_g, W.ln2_b, partial, xc, M,
+                       n_chunks, S, st, PadSkip{}, false, h3s);
       if (r16 && KS - 1 <= 30) {
         LayerW vp{};
         vp.pw1 = W.pw1; vp.pw1_b = W.pw1_b;
-        launch_pw1_glu_cols_16(xc, g, vp, Ti, st, xh, KS - 1, W.cm_scale, W.cm_bias);
+        launch_pw1_glu_cols_16(xc, g, vp, Ti, st, v.hist_of(i), KS - 1, W.cm_scale, W.cm_bias);
         hist_moved = true;
       } else {
-        launch_sq_pw1glu(xc, g, xhat, W, nullptr, Ti, Ti, mul, st);
+        launch_sq_pw1glu(xc, g, xhat, W, nullptr, M, Ti, mul, st);
       }
-      launch_conv_pre(g, gh, xc, ctx, sq_conv_view(W), nullptr, Ti, Ti, KS, mul, st);
-      launch_ffn_split(ctx, W.ln3_g, W.ln3_b, Ws.ff2_w1, W.ff2_b1, Ws.ff2_w2, W.ff2_b2, 1.0f, W.ln4_g, W.ln4_b, partial, other,
-                       Ti, n_chunks, S, st, PadSkip{}, /*residual_is_normed=*/true, h3s);
+      launch_conv_pre(g, gh, xc, ctx, sq_conv_view(W), nullptr, M, Ti, KS, mul, st);
+      launch_ffn_split(ctx, W.ln3_g, W.ln3_b, Ws.ff2_w1, W.ff2_b1, Ws.ff2_w2, W.ff2_b2, 1.0f, W.ln4_g, W.ln4_b, partial, other, M,
+                       n_chunks, S, st, PadSkip{}, /*residual_is_normed=*/true, h3s);
       if (Wn && r16) {  // (fuse_next: layer i + 1 runs at this layer's rate -- same rows, same cache length)
-        float* kcn = s->kc + (size_t)(i + 1) * s->cap * kD;
-        float* vcn = s->vc + (size_t)(i + 1) * s->cap * kD;
-        launch_ln_qkv(other, qkv, qkv_view(*Wn), Ti, st, PadSkip{}, kcn + (size_t)n_cache * kD, vcn + (size_t)n_cache * kD, false);
+        launch_ln_qkv(other, qkv, qkv_view(*Wn), Ti, st, PadSkip{}, v.k_dst(i + 1, reduced), v.v_dst(i + 1, reduced), false);
         kv_in_cache = true;
       } else if (Wn) {
-        launch_sq_qkv(other, qkv, Wn->wqkv, Wn->bqkv, Ti, st);
+        launch_sq_qkv(other, qkv, Wn->wqkv, Wn->bqkv, M, st);
       }
     } else {
-      launch_sq_mid(ctx, x, xc, g, xhat, W, nullptr, Ti, Ti, mul, n_chunks, st);
-      launch_sq_tail(g, gh, xc, other, qkv, W, Wn ? Wn->wqkv : nullptr, Wn ? Wn->bqkv : nullptr, nullptr, Ti, Ti, mul,
-                     n_chunks, KS, st);
+      launch_sq_mid(ctx, x, xc, g, xhat, W, nullptr, M, Ti, mul, n_chunks, st);
+      launch_sq_tail(g, gh, xc, other, qkv, W, Wn ? Wn->wqkv : nullptr, Wn ? Wn->bqkv : nullptr, nullptr, M, Ti, mul, n_chunks,
+                     KS, st);
     }
-    if (!hist_moved) launch_hist_update(xh, xhat, Ti, KS - 1, st);
+    v.hist_step(i, reduced, xhat, Ti, KS - 1, hist_moved, st);
     std::swap(x, other);
     have_qkv = fuse_next;
   }
   *x_final = x;
+  return PPASR_OK;
+}
+
+// One streaming round on the fused 256-wide route -- a stream handle's chunk or a session group's listed chunks: front
+// end, the family's layers, head.  *frames = the encoder frames each chunk leaves with
+ppasr_status stream_round(const ppasr_model_s* h, const StreamRows& v, const StreamWs& w, const float* feats, int T,
+                          float* conv2_part, float* probs, int32_t* frame_argmax, float* frame_maxprob, hipStream_t st,
+                          int* frames) {
+  stream_front(h, v, w, feats, T, conv2_part, st);
+  float* x_final = w.xa;
+  *frames = v.c;
+  if (is_sq(h)) {
+    ppasr_status r = sq_stream_layers(h, v, w, &x_final, st);
+    if (r != PPASR_OK) return r;
+  } else {
+    *frames = conformer_stream_layers(h, v, w, st);
+  }
+  stream_head(h, v, w, x_final, *frames, probs, frame_argmax, frame_maxprob, st);
   return PPASR_OK;
 }
 
@@ -416,8 +543,7 @@ ppasr_status ppasr_encode_chunk(ppasr_stream s, const float* feats, int T, int r
   ppasr_model_s* h = s->m;
   if (T < h->min_frames())
     return fail(PPASR_EINVAL, "chunk shorter than the conv front-end's receptive field (7 frames; conv2d6: 11, conv2d8: 15)");
-  const auto fd = h->front_dims(T);
-  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2;
+  const int c = h->front_dims(T).Tp;
   if (workspace_bytes < ppasr_chunk_workspace_bytes(h, T)) return fail(PPASR_ENOSPACE, "workspace too small");
   ChunkPlan p{};
   ppasr_status r = plan_chunk(s, c, required_cache_size, &p);
@@ -436,35 +562,12 @@ ppasr_status ppasr_encode_chunk(ppasr_stream s, const float* feats, int T, int r
     if (c_out_host) *c_out_host = gframes;
     return PPASR_OK;
   }
-  float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
-  float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *g = ws + wl.g;
-  float* xhat = ws + wl.total;
-  float* shift_tmp = xhat + (((size_t)c * kD + 63) & ~(size_t)63);
-  launch_conv1(feats, h->front, y1, 1, T, F, T1, F1, st);
-  if (h->desc.input_layer == 8) {  // Conv2dSubsampling8: three 3x3 / 2 convs, the third one over conv1's output buffer
-    launch_conv_stage(y1, h->front.conv2_w, h->front.conv2_b, y2, 1, T1, F1, fd.T2, F2, 3, 2, st);
-    launch_conv_stage(y2, h->front.conv3_w, h->front.conv3_b, y1, 1, fd.T2, F2, c, h->F3, 3, 2, st);
-    launch_embed(y1, h->front, xa, c, h->F3 * kD, sqrtf((float)kD), false, st, PadSkip{}, ffn_split_for(h, c), y2);
-  } else {
-    // (3x3 / 2, or conv2d6's 5x5 / 3: FrontW::conv2_k / _s)
-    launch_conv2(y1, h->front, y2, 1, T1, F1, c, F2, st, PadSkip{}, nullptr, nullptr, shift_tmp + (size_t)h->desc.max_len * kD,
-                 conv_stage_part_floats(c * F2));
-    // (one row block: a workgroup per 256-wide K chunk -- F2 of them -- instead of 8 workgroups of 2 - 3 chunks)
-    launch_embed(y2, h->front, xa, c, F2 * kD, sqrtf((float)kD), /*scale_before_bias=*/is_sq(h), st, PadSkip{},
-                 (c <= 32 && ffn_split_for(h, c) > 1) ? F2 : ffn_split_for(h, c), y1);
-  }
-  float* x_final = xa;
+  const StreamWs w = carve_ws(ws, wl, c);
+  float* shift_tmp = w.behind;
   int frames = c;
-  if (is_sq(h)) r = squeezeformer_chunk(s, p, xa, xb, xc, qkv, ctx, g, ws + wl.xs, xhat, y1, &x_final, st);
-  else r = conformer_chunk(s, p, xa, xb, xc, qkv, ctx, g, xhat, y1, &frames, st);
+  r = stream_round(h, handle_rows(s, p), w, feats, T, shift_tmp + (size_t)h->desc.max_len * kD, probs, frame_argmax,
+                   frame_maxprob, st, &frames);
   if (r != PPASR_OK) return r;
-  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
-  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
-  // (one row block: as many column slices as give every wave ONE 32-column vocabulary tile -- 17 at V = 4233 -- not 8)
-  const int head_slices = (frames <= 32 && ffn_split_for(h, frames) > 1) ? std::min((h->head.n_tiles + 7) / 8, 32)
-                                                                        : ffn_split_for(h, frames);
-  launch_ctc_head(x_final, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, frames, st, PadSkip{}, head_slices, y1);
-  if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, frames, h->head.V, st);
   r = finish_chunk(s, p, shift_tmp, st);
   if (r != PPASR_OK) return r;
   s->offset += frames;
@@ -526,10 +629,10 @@ ppasr_status ppasr_stream_import_cache(ppasr_stream s, const float* att_cache, i
 // sessions are stacked: n x c frames -> ceil(n*c/32) row blocks per kernel instead of one).  No reference counterpart:
 // PPASR streams one session per call (predict.py:232-337, forward_chunk asserts B = 1); each session here follows exactly
 // the single-session arithmetic (required_cache_size < 0: the full history is kept, what PPASRPredictor passes,
-// predict.py:306-307).  Each family has its own create call and launch body:
-//   Conformer            ppasr_stream_group_create      conformer_group_body
-//   Squeezeformer        ppasr_sq_stream_group_create   sq_group_body
-//   Efficient-Conformer  ppasr_eff_stream_group_create  eff_group_body
+// predict.py:306-307).  Each family has its own create call; the launch body of a round:
+//   Conformer            ppasr_stream_group_create      fused_group_body: the view of the listed sessions' rows
+//   Squeezeformer        ppasr_sq_stream_group_create   (group_rows), then the round a stream handle's chunk runs
+//   Efficient-Conformer  ppasr_eff_stream_group_create  (stream_round: front, conformer_ / sq_stream_layers, head)
 //   general route        ppasr_gen_stream_group_create  gen_group_body: the same caches at the model's width D;
 //                                                       gen_front + gen_layers (capi_generic.hip generic_group_chunk)
 //   DeepSpeech2          ppasr_ds2_stream_group_create  ds2_group_body: each session's LSTM / GRU state [L][H] (h, and
@@ -613,6 +716,20 @@ size_t layered_group_ws_floats(const ppasr_model_s* h, int n, int T) {
   return ws_layout(h, n, T).total + (((size_t)n * c * kD + 63) & ~(size_t)63) +
          (size_t)h->desc.num_blocks * n * (h->desc.cnn_module_kernel - 1) * kD;
 }
+// Conformer session group: the workspace of n chunks of T frames -- the batched layout for B = n, the conv-module input
+// rows [n*c][256] and, for the layer at hand, the listed sessions' gathered and GLU'd histories [n][lo][256] each
+size_t conformer_group_ws_floats(const ppasr_model_s* h, int n, int T) {
+  const size_t c = ((T - 1) / 2 - 1) / 2;  // (the conv2d front end, the one these groups are built for)
+  return ws_layout(h, n, T).total + (size_t)n * c * kD + 64 + (size_t)n * (h->desc.cnn_module_kernel - 1) * kD * 2 + 64;
+}
+
+// the rows of a round over the n listed sessions, c frames each: `desc` = the descriptors the round staged (device; the
+// half-rate layers' behind the full-rate ones), scratch = the GLU'd-history floats of the family's workspace
+StreamRows group_rows(const ppasr_stream_group_s* g, const SessDesc* desc, int n, int c, float* scratch) {
+  const long long L = g->m->desc.num_blocks;
+  return StreamRows{n, c, ceil_div(c, 2), g->kc, g->vc, g->cap, L * g->cap * kD, g->xh_hist, g->lo, L * g->lo * kD, scratch,
+                    g->hist_tab, 0, 0, 0, desc, is_layered(g->family) ? desc + n : nullptr};
+}
 
 // ---- launch bodies of a round (ppasr_encode_chunk_group): the launches over the n listed sessions' stacked chunks,
 // with the descriptors `desc` the round staged (device) and the workspace ws; *frames = the encoder frames each session
@@ -620,239 +737,16 @@ size_t layered_group_ws_floats(const ppasr_model_s* h, int n, int T) {
 typedef ppasr_status (*GroupBody)(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
                                   int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames);
 
-// Conformer: conformer_chunk's arithmetic for every listed session, rows stacked (n*c rows).  Each layer gathers the
-// listed sessions' conv histories and GLUs them (hist_gather + pw1_glu).  fp16 x3 as on a stream handle: the split
-// route's feed-forward slices on the layers' h3 views, the fused kernels (stacked rows beyond the split route) in fp32.
-ppasr_status conformer_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
-                                  int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
+// Conformer, Squeezeformer and Efficient-Conformer on the fused 256-wide route: a stream handle's chunk for every listed
+// session, rows stacked.  The Efficient-Conformer's plans (plan_chunk_for) double the offset, do not trim the half-rate
+// cache and refuse odd cache lengths; its half-rate descriptors carry {sess, cache_r, pos0}, pos0 = 2 offset - cache_t (the
+// half-rate layers read every second positional row).
+ppasr_status fused_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
+                              int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
   ppasr_model_s* h = g->m;
-  const int F = h->desc.input_dim, T1 = (T - 1) / 2, F1 = h->F1, c = (T1 - 1) / 2, F2 = h->F2;
-  const WsLayout wl = ws_layout(h, n, T);
-  float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
-  float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g;
-  float* xhat = ws + wl.total;
-  const int lo = g->lo;
-  float* xh_act = xhat + (((size_t)n * c * kD + 63) & ~(size_t)63);  // [n][lo][256] gathered histories
-  float* g_hist = xh_act + (size_t)n * lo * kD;                       // [n][lo][256] GLU(pointwise_conv1(history))
-  const int M = n * c, L = h->desc.num_blocks, H = h->desc.attention_heads;
-  const int n_chunks = h->desc.linear_units / 256;
-  const long long kv_sess = (long long)L * g->cap * kD, hist_sess = (long long)L * lo * kD;
-  launch_conv1(feats, h->front, y1, n, T, F, T1, F1, st);
-  launch_conv2(y1, h->front, y2, n, T1, F1, c, F2, st);
-  launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), false, st, PadSkip{}, ffn_split_for(h, M), y1);
-  for (int i = 0; i < L; ++i) {
-    const LayerW& W = h->layers[i];
-    float* kc = g->kc + (size_t)i * g->cap * kD;
-    float* vc = g->vc + (size_t)i * g->cap * kD;
-    float* xh = g->xh_hist + (size_t)i * lo * kD;
-    const int S = ffn_split_for(h, M);  // few sessions = an under-filled grid: split route (partial sums in y1)
-    const bool h3 = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty();  // (see conformer_chunk)
-    const LayerW& Wk = h3 ? h->layers_h3[i] : W;
-    if (S > 1) {
-      launch_ffn_split(xa, W.ln_mac_g, W.ln_mac_b, Wk.ffm_w1, W.ffm_b1, Wk.ffm_w2, W.ffm_b2, 0.5f, nullptr, nullptr, y1, xb, M,
-                       n_chunks, S, st, PadSkip{}, false, h3);
-      launch_ln_qkv(xb, qkv, Wk, M, st, PadSkip{}, nullptr, nullptr, h3);
-    } else {
-      launch_ffn_qkv(xa, xb, qkv, W, M, n_chunks, st);
-    }
-    launch_kv_append_group(qkv, kc, vc, kv_sess, desc, n, c, st);
-    AttnArgs a{qkv, 768, kc, kD, vc, kD, c, c, 0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, 1, 4, c, c, 1, desc, kv_sess};
-    launch_attention(a, n, H, st);
-    launch_hist_gather(xh, hist_sess, desc, xh_act, n, lo, st);
-    launch_pw1_glu(xh_act, g_hist, W, n * lo, st);
-    launch_out_glu(ctx, xb, xc, gg, xhat, Wk, nullptr, M, c, 4, st, PadSkip{}, S > 1 ? xhat : nullptr, h3);
-    if (S > 1) {
-      launch_conv_pre(gg, g_hist, xc, ctx, Wk, nullptr, M, c, h->desc.cnn_module_kernel, 4, st, true, PadSkip{}, h3);
-      launch_ffn_split(ctx, W.ln_ff_g, W.ln_ff_b, Wk.ff_w1, W.ff_b1, Wk.ff_w2, W.ff_b2, 0.5f, W.ln_fin_g, W.ln_fin_b, y1, xa, M,
-                       n_chunks, S, st, PadSkip{}, false, h3);
-    } else {
-      launch_conv_ffn(gg, g_hist, xc, xa, W, nullptr, M, c, n_chunks, h->desc.cnn_module_kernel, 4, nullptr, nullptr, nullptr, st);
-    }
-    launch_hist_update_group(xh, hist_sess, desc, xhat, n, c, lo, st);
-  }
-  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
-  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
-  launch_ctc_head(xa, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, M, st, PadSkip{}, ffn_split_for(h, M), y1);
-  if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, M, h->head.V, st);
-  *frames = c;
-  return PPASR_OK;
-}
-
-// Squeezeformer: squeezeformer_chunk's arithmetic for every listed session, rows stacked (n*c full-rate rows, n*c_r
-// half-rate rows).  The fp16 x3 mode covers what it covers on a stream handle: the feed-forward slices of the split
-// route.  A layer whose stacked rows leave the split route (ffn_split_for(Mi) = 1: more than 4 096 rows at the default
-// setting, ppasr_set_ffn_split(0)) runs the fused fp32 kernels in either mode, as the Conformer group does; a stream
-// handle's one-session chunk never gets there.
-ppasr_status sq_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
-                           int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
-  ppasr_model_s* h = g->m;
-  const auto fd = h->front_dims(T);
-  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2, c_r = ceil_div(c, 2);
-  const SessDesc* d_full = desc;
-  const SessDesc* d_half = desc + n;
-  const WsLayout wl = ws_layout(h, n, T);
-  float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
-  float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g, *xs = ws + wl.xs;
-  float* xhat = ws + wl.total;                                        // [n*c][256] conv-module inputs of this chunk
-  float* g_hist = xhat + (((size_t)n * c * kD + 63) & ~(size_t)63);  // [L][n][lo][256]
-  const int lo = g->lo, M = n * c, L = h->desc.num_blocks, H = h->desc.attention_heads;
-  const int n_chunks = h->desc.linear_units / 256, KS = h->desc.cnn_module_kernel;
-  const long long kv_sess = (long long)L * g->cap * kD, hist_sess = (long long)L * lo * kD;
-  launch_conv1(feats, h->front, y1, n, T, F, T1, F1, st);
-  launch_conv2(y1, h->front, y2, n, T1, F1, c, F2, st);
-  launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), /*scale_before_bias=*/true, st, PadSkip{}, ffn_split_for(h, M), y1);
-  launch_ln_rows(xa, h->preln_g, h->preln_b, M, st);
-  launch_pw1_glu_layers_group(g->xh_hist, hist_sess, d_full, g_hist, g->hist_tab, L, n, lo, st);
-  float* x = xa;
-  float* other = xb;
-  bool reduced = false, have_qkv = false;
-  for (int i = 0; i < L; ++i) {
-    const SqLayerW& W = h->sq_layers[i];
-    if (i == h->desc.reduce_idx) {
-      HIP_TRY(hipMemcpyAsync(xs, x, (size_t)M * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
-      launch_sq_reduce(x, other, qkv, h->sq_reduce, W.wqkv, W.bqkv, nullptr, n, c, c_r, st);
-      std::swap(x, other);
-      reduced = true;
-      have_qkv = true;
-    }
-    if (i == h->desc.recover_idx && reduced) {
-      launch_sq_recover(x, xs, other, qkv, h->sq_wrec, h->sq_brec, W.wqkv, W.bqkv, n, c, c_r, st);
-      std::swap(x, other);
-      reduced = false;
-      have_qkv = true;
-    }
-    const int Ti = reduced ? c_r : c, Mi = n * Ti;
-    const int mul = reduced ? 8 : 4;
-    const SessDesc* dsc = reduced ? d_half : d_full;
-    float* kc = g->kc + (size_t)i * g->cap * kD;
-    float* vc = g->vc + (size_t)i * g->cap * kD;
-    float* xh = g->xh_hist + (size_t)i * lo * kD;
-    float* gh = g_hist + (size_t)i * n * lo * kD;
-    const int S = ffn_split_for(h, Mi);  // few sessions = an under-filled grid: split route (partial sums in y1)
-    const bool h3s = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty();  // (as squeezeformer_chunk)
-    if (!have_qkv) launch_sq_qkv(x, qkv, W.wqkv, W.bqkv, Mi, st);
-    launch_kv_append_group(qkv, kc, vc, kv_sess, dsc, n, Ti, st);
-    AttnArgs a{qkv, 768, kc, kD, vc, kD, Ti, Ti, 0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, reduced ? 2 : 1, mul, Ti, Ti, 1,
-               dsc, kv_sess};
-    launch_attention(a, n, H, st);
-    const bool fuse_next = (i + 1 < L) && (i + 1 != h->desc.reduce_idx) && !(i + 1 == h->desc.recover_idx && reduced);
-    const SqLayerW* Wn = fuse_next ? &h->sq_layers[i + 1] : nullptr;
-    if (S > 1) {
-      const SqLayerW& Ws = h3s ? h->sq_layers_h3[i] : W;
-      launch_sq_oproj(ctx, x, other, W, Mi, st);
-      launch_ffn_split(other, nullptr, nullptr, Ws.ff1_w1, W.ff1_b1, Ws.ff1_w2, W.ff1_b2, 1.0f, W.ln2_g, W.ln2_b, y1, xc, Mi,
-                       n_chunks, S, st, PadSkip{}, false, h3s);
-      launch_sq_pw1glu(xc, gg, xhat, W, nullptr, Mi, Ti, mul, st);
-      launch_conv_pre(gg, gh, xc, ctx, sq_conv_view(W), nullptr, Mi, Ti, KS, mul, st);
-      launch_ffn_split(ctx, W.ln3_g, W.ln3_b, Ws.ff2_w1, W.ff2_b1, Ws.ff2_w2, W.ff2_b2, 1.0f, W.ln4_g, W.ln4_b, y1, other, Mi,
-                       n_chunks, S, st, PadSkip{}, /*residual_is_normed=*/true, h3s);
-      if (Wn) launch_sq_qkv(other, qkv, Wn->wqkv, Wn->bqkv, Mi, st);
-    } else {
-      launch_sq_mid(ctx, x, xc, gg, xhat, W, nullptr, Mi, Ti, mul, n_chunks, st);
-      launch_sq_tail(gg, gh, xc, other, qkv, W, Wn ? Wn->wqkv : nullptr, Wn ? Wn->bqkv : nullptr, nullptr, Mi, Ti, mul,
-                     n_chunks, KS, st);
-    }
-    launch_hist_update_group(xh, hist_sess, dsc, xhat, n, Ti, lo, st);
-    std::swap(x, other);
-    have_qkv = fuse_next;
-  }
-  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
-  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
-  launch_ctc_head(x, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, M, st, PadSkip{}, ffn_split_for(h, M), y1);
-  if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, M, h->head.V, st);
-  *frames = c;
-  return PPASR_OK;
-}
-
-// Efficient-Conformer: conformer_chunk's arithmetic for every listed session, rows stacked (n*c full-rate rows up to and
-// including the stride layer, n*c_r half-rate rows behind it).  The session plans (plan_chunk_for) double the offset, do
-// not trim the half-rate cache and refuse odd cache lengths.  The descriptors of the full-rate layers carry
-// {sess, cache_t, pos0}, those of the half-rate layers {sess, cache_r, pos0}, pos0 = 2 offset - cache_t (the half-rate
-// layers read every second positional row).  Grouped-attention layers re-cut each session's cache + chunk frames into
-// tokens from the start of its cache (k_attention_t's per-session branch).  The conv histories of every layer and
-// session are GLU'd in one launch; layer i's are kernel_i - 1 rows per session (7-tap convs behind the stride layer).
-// fp16 x3 follows the stream handle's rule per launch, as in the other groups: the split route's units on the layers' h3
-// views, the fused kernels (stacked rows beyond the split route) in fp32.  The consumer-side joins of a stream handle's
-// chunk (ffn_half16 / join16) are single-session and not used here.
-ppasr_status eff_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
-                            int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
-  ppasr_model_s* h = g->m;
-  const auto fd = h->front_dims(T);
-  const int F = h->desc.input_dim, T1 = fd.T1, F1 = h->F1, c = fd.Tp, F2 = h->F2, c_r = ceil_div(c, 2);
-  const WsLayout wl = ws_layout(h, n, T);
-  float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
-  float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *gg = ws + wl.g;
-  float* xhat = ws + wl.total;                                        // [n*c][256] conv-module inputs of this chunk
-  float* g_hist = xhat + (((size_t)n * c * kD + 63) & ~(size_t)63);  // [L][n * lo][256]
-  const int lo = g->lo, M = n * c, L = h->desc.num_blocks, H = h->desc.attention_heads;
-  const int n_chunks = h->desc.linear_units / 256;
-  const long long kv_sess = (long long)L * g->cap * kD, hist_sess = (long long)L * lo * kD;
-  const bool h3_mode = h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty();
-  launch_conv1(feats, h->front, y1, n, T, F, T1, F1, st);
-  launch_conv2(y1, h->front, y2, n, T1, F1, c, F2, st);
-  launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), /*scale_before_bias=*/false, st, PadSkip{}, ffn_split_for(h, M),
-               y1);
-  launch_pw1_glu_layers_group(g->xh_hist, hist_sess, desc, g_hist, g->hist_tab, L, n, lo, st);
-  int Ti = c, mul = 4, pstride = 1;
-  const SessDesc* dsc = desc;  // (the half-rate descriptors behind the stride layer)
-  for (int i = 0; i < L; ++i) {
-    const LayerW& W = h->layers[i];
-    const int grp = h->layer_group[i], KS = h->layer_ks[i], lo_i = layer_lo(h, i), Mi = n * Ti;
-    float* kc = g->kc + (size_t)i * g->cap * kD;
-    float* vc = g->vc + (size_t)i * g->cap * kD;
-    float* xh = g->xh_hist + (size_t)i * lo * kD;
-    float* gh = g_hist + (size_t)i * n * lo * kD;  // list position b at row b * lo_i (k_pw1_glu_layers)
-    const int S = ffn_split_for(h, Mi);  // few sessions = an under-filled grid: split route (partial sums in y1)
-    const bool h3 = S > 1 && h3_mode;
-    const LayerW& Wk = h3 ? h->layers_h3[i] : W;
-    if (S > 1) {
-      launch_ffn_split(xa, W.ln_mac_g, W.ln_mac_b, Wk.ffm_w1, W.ffm_b1, Wk.ffm_w2, W.ffm_b2, 0.5f, nullptr, nullptr, y1, xb, Mi,
-                       n_chunks, S, st, PadSkip{}, false, h3);
-      launch_ln_qkv(xb, qkv, Wk, Mi, st, PadSkip{}, nullptr, nullptr, h3);
-    } else {
-      launch_ffn_qkv(xa, xb, qkv, W, Mi, n_chunks, st);
-    }
-    launch_kv_append_group(qkv, kc, vc, kv_sess, dsc, n, Ti, st);
-    // (T2 / kv_frames: per session from dsc -- cache + Ti frames, ceil(/ grp) tokens)
-    const int Tq = ceil_div(Ti, grp);
-    AttnArgs a{qkv, 768, kc, kD, vc, kD, Tq, Tq, 0, nullptr, ctx, W.pos_u, W.pos_v, W.ptab, pstride, mul * grp, Ti, Ti, grp,
-               dsc, kv_sess};
-    launch_attention(a, n, H, st);
-    launch_out_glu(ctx, xb, xc, gg, xhat, Wk, nullptr, Mi, Ti, mul, st, PadSkip{}, S > 1 ? xhat : nullptr, h3);
-    if (i == h->desc.stride_layer_idx) {
-      const int Ms = n * c_r, Ss = ffn_split_for(h, Ms);
-      const bool h3s = Ss > 1 && h3_mode;
-      const LayerW& Ws = h3s ? h->layers_h3[i] : W;
-      if (Ss > 1) {  // the conv half alone (x3 -> ctx), its feed-forward module over the slices
-        launch_conv_ffn_stride(gg, gh, xc, xa, Ws, nullptr, n, Ti, c_r, n_chunks, KS, mul * 2, st, PadSkip{}, true, h3s, ctx);
-        launch_ffn_split(ctx, W.ln_ff_g, W.ln_ff_b, Ws.ff_w1, W.ff_b1, Ws.ff_w2, W.ff_b2, 0.5f, W.ln_fin_g, W.ln_fin_b, y1, xa,
-                         Ms, n_chunks, Ss, st, PadSkip{}, false, h3s);
-      } else {
-        launch_conv_ffn_stride(gg, gh, xc, xa, W, nullptr, n, Ti, c_r, n_chunks, KS, mul * 2, st);
-      }
-      launch_hist_update_group(xh, hist_sess, dsc, xhat, n, Ti, lo_i, st);
-      Ti = c_r;  // masks[:, :, ::2], pos_emb[:, ::2]  (efficient_conformer/encoder.py:252-257)
-      mul *= 2;
-      pstride *= 2;
-      dsc = desc + n;
-    } else {
-      if (S > 1) {
-        launch_conv_pre(gg, gh, xc, ctx, Wk, nullptr, Mi, Ti, KS, mul, st, true, PadSkip{}, h3);
-        launch_ffn_split(ctx, W.ln_ff_g, W.ln_ff_b, Wk.ff_w1, W.ff_b1, Wk.ff_w2, W.ff_b2, 0.5f, W.ln_fin_g, W.ln_fin_b, y1, xa, Mi,
-                         n_chunks, S, st, PadSkip{}, false, h3);
-      } else {
-        launch_conv_ffn(gg, gh, xc, xa, W, nullptr, Mi, Ti, n_chunks, KS, mul, nullptr, nullptr, nullptr, st);
-      }
-      launch_hist_update_group(xh, hist_sess, dsc, xhat, n, Ti, lo_i, st);
-    }
-  }
-  const int Mo = n * Ti;  // (Ti = c_r behind a stride layer, c without one: ppasr_out_frames)
-  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
-  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
-  launch_ctc_head(xa, h->head, probs, fa, fp, ws + wl.rmax, ws + wl.rsum, Mo, st, PadSkip{}, ffn_split_for(h, Mo), y1);
-  if (probs) launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, Mo, h->head.V, st);
-  *frames = Ti;
-  return PPASR_OK;
+  const int c = h->front_dims(T).Tp;
+  const StreamWs w = carve_ws(ws, ws_layout(h, n, T), n * c);
+  return stream_round(h, group_rows(g, desc, n, c, w.behind), w, feats, T, nullptr, probs, frame_argmax, frame_maxprob, st, frames);
 }
 
 // general route: generic_group_chunk over the listed sessions.  pos0 = offset - cache_t picks the relative positional
@@ -884,11 +778,11 @@ const struct {
 } kGroupKinds[] = {
     {PPASR_MODEL_CONFORMER,
      "session groups are built for streaming (causal) model_type=conformer (Squeezeformer: ppasr_sq_stream_group_create)",
-     conformer_group_body},
+     fused_group_body},
     {PPASR_MODEL_SQUEEZEFORMER, "Squeezeformer session groups are built for streaming (causal) model_type=squeezeformer",
-     sq_group_body},
+     fused_group_body},
     {PPASR_MODEL_EFFICIENT_CONFORMER,
-     "Efficient-Conformer session groups are built for streaming (causal) model_type=efficient_conformer", eff_group_body},
+     "Efficient-Conformer session groups are built for streaming (causal) model_type=efficient_conformer", fused_group_body},
     {PPASR_MODEL_DEEPSPEECH2,
      "DeepSpeech2 session groups are built for streaming (unidirectional) model_type=deepspeech2 "
      "(the reference streams no bidirectional model)",
@@ -991,10 +885,7 @@ size_t ppasr_group_chunk_workspace_bytes(ppasr_handle h, int n, int T) {
   if (h->desc.model_type == PPASR_MODEL_DEEPSPEECH2) return ds2_group_ws_floats(h, n, T) * sizeof(float);
   if (h->generic) return generic_group_ws_floats(h, n, T) * sizeof(float);
   if (is_sq(h) || is_eff(h)) return layered_group_ws_floats(h, n, T) * sizeof(float);
-  const size_t Tp = ((T - 1) / 2 - 1) / 2;
-  // the batched layout for B = n, plus the conv-module input rows and the GLU'd histories of the active sessions
-  return (ws_layout(h, n, T).total + (size_t)n * Tp * kD + 64 + (size_t)n * (h->desc.cnn_module_kernel - 1) * kD * 2 + 64) *
-         sizeof(float);
+  return conformer_group_ws_floats(h, n, T) * sizeof(float);
 }
 
 // One chunk [T frames] for each of the n DISTINCT sessions listed in sessions_host; feats [n][T][F] (device).

@@ -233,7 +233,8 @@ def oracle_kwargs(family):
 
 
 def _routes(family, site, layer):
-    """The routes of `site` at `layer` of the family's fixture, read off capi.hip / capi_stream.hip: a grouped-attention
+    """The routes of `site` at `layer` of the family's fixture, read off capi.hip / capi_stream.hip (encode_impl; conformer_stream_layers /
+    sq_stream_layers, one walk for stream handles and session groups): a grouped-attention
     layer has no fused attention (its out-projection and pointwise_conv1 then keep fp32 on the fused route, and the three
     attention sites do not exist); session groups are exercised on the Conformer."""
     routes = [r for r in SITE[site].routes if r != GROUP or family == "conformer"]
