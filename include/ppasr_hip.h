@@ -603,6 +603,23 @@ PPASR_API ppasr_status ppasr_fbank_compute_batch(ppasr_fbank_handle f, const flo
                                        int n, int total_chunks, int total_frames, int use_db_norm, float target_db,
                                        float* feats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- MFCC form of the same front-end (`preprocess_conf.feature_method: mfcc`, audio_featurizer.py:55-61,140-154) ----
+ * paddleaudio.compliance.kaldi.mfcc(n_mels, n_mfcc, frame_length=25, frame_shift=10, dither=0, sr) with its other
+ * arguments at their defaults (use_energy False, subtract_mean False, cepstral_lifter 22): the log-mel stage above, then
+ *   mfcc[t][k] = L[k] * sum_m logmel[t][m] * D[m][k],   D[m][0] = sqrt(1/M),  D[m][k] = sqrt(2/M) cos(pi/M (m + 1/2) k),
+ *   L[k] = 1 + (Q/2) sin(pi k / Q)  (1 when Q == 0),    M = n_mels, Q = cepstral_lifter,
+ * one extra contraction per frame inside the frame kernel: no further launch.  The handle is a ppasr_fbank_handle: every
+ * ppasr_fbank_* call above takes it, and wherever those say "[n_mels]" for a row of `feats` its rows are n_mfcc floats.
+ * Third-party and not installable offline like the fbank: parity unpinned.
+ * PPASR_EINVAL: n_mfcc < 1, n_mfcc > n_mels, cepstral_lifter < 0 (or not finite), whatever ppasr_fbank_create refuses. */
+PPASR_API ppasr_status ppasr_mfcc_create(int sample_rate, int n_mels, int n_mfcc, float frame_length_ms, float frame_shift_ms,
+                               float cepstral_lifter, ppasr_fbank_handle* out);
+/* Floats per row of `feats`: n_mels for a handle of ppasr_fbank_create, n_mfcc for one of ppasr_mfcc_create, 0 for NULL. */
+PPASR_API int          ppasr_fbank_feature_dim(ppasr_fbank_handle f);
+/* Host only, no device: the very tables ppasr_mfcc_create uploads -- dct [n_mels][n_mfcc] = D, lifter [n_mfcc] = L --
+ * computed in double and rounded to float once.  Same refusals as ppasr_mfcc_create, and PPASR_EINVAL for a null pointer. */
+PPASR_API ppasr_status ppasr_mfcc_tables(int n_mels, int n_mfcc, float cepstral_lifter, float* dct, float* lifter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,10 @@ SYMBOLS = [
     ("ppasr_fbank_batch_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     ("ppasr_fbank_compute_batch", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("ppasr_mfcc_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_float, ctypes.POINTER(_vp)]),
+    ("ppasr_fbank_feature_dim", ctypes.c_int, [_vp]),
+    ("ppasr_mfcc_tables", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp]),
 ]
 
 _lib = None

@@ -9,6 +9,9 @@
 // One 256-thread workgroup per frame: the frame lives in LDS from the raw samples to the 80 log-mel values
 // (radix-2 FFT, one butterfly per thread per stage); HBM traffic = the samples once (L2 absorbs the 2.5x frame
 // overlap) + 320 B per frame out.  HBM- / latency-bound: 4 B * 160 new samples + 320 B out per frame.
+// MFCC form (ppasr_mfcc_create; paddleaudio.compliance.kaldi.mfcc with use_energy False, subtract_mean False, lifter 22):
+// the same frame kernel, compiled a second time with one more stage -- the log-mel values go to LDS instead of HBM, and
+// n_mfcc threads contract them with the orthonormal DCT-II table and apply the lifter.  No further launch.
 #include "launch.h"
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -31,6 +34,13 @@ struct FbankTables {
   const float* bank;     // [n_mels][nfft/2]
   const int* bank_lo;    // [n_mels] first bin with a non-zero weight
   const int* bank_hi;    // [n_mels] one past the last
+};
+
+// The MFCC form's own tables, a trailing kernel argument of their own: the fbank form's argument layout stays as it is.
+struct MfccTables {
+  const float* dct;     // [n_mels][n_mfcc] D[m][k]: column k is read by thread k, so a row is one coalesced load
+  const float* lifter;  // [n_mfcc] L[k]
+  int n_mfcc;
 };
 
 // ---- mean square of AudioSegment.rms_db (audio.py:526: np.mean(self._samples ** 2) on float32 samples) ----
@@ -187,9 +197,10 @@ __global__ __launch_bounds__(64) void k_gain_batch(const float* __restrict__ chu
 }
 
 // One frame, by the 256 threads of a workgroup: `src` = its first sample, `gain` = its waveform's gain (1 without dB
-// normalisation), `out` = its n_mels log-mel values.
+// normalisation), `out` = its n_mels log-mel values (kMfcc: its mc.n_mfcc cepstral coefficients; `mc` is not read otherwise).
+template <bool kMfcc>
 __device__ __forceinline__ void fbank_frame(const float* __restrict__ src, float gain, const FbankTables& tb, int win,
-                                            int nfft, int log2n, int n_mels, float* __restrict__ out) {
+                                            int nfft, int log2n, int n_mels, float* __restrict__ out, const MfccTables& mc) {
   __shared__ float re[kNfftMax], im[kNfftMax];
   __shared__ double dred[4];
   __shared__ float s_mean;
@@ -268,26 +279,44 @@ __device__ __forceinline__ void fbank_frame(const float* __restrict__ src, float
     const float* w = tb.bank + (size_t)tid * (nfft / 2);
     float e = 0.f;
     for (int k = tb.bank_lo[tid]; k < tb.bank_hi[tid]; ++k) e = fmaf(re[k], w[k], e);
-    out[tid] = logf(fmaxf(e, 1.1920928955078125e-07f));
+    const float v = logf(fmaxf(e, 1.1920928955078125e-07f));
+    if constexpr (kMfcc) im[tid] = v;  // (im[] is free since the power spectrum went to re[]; n_mels <= kFT <= kNfftMax)
+    else out[tid] = v;
+  }
+  if constexpr (kMfcc) {
+    // ---- DCT-II over the mel axis + lifter: thread k forms coefficient k.  im[m] is one address for the whole wave (an
+    // LDS broadcast), D's row m is n_mfcc consecutive floats (<= 256 KB in all, shared by every frame: it stays in L2) ----
+    __syncthreads();
+    if (tid < mc.n_mfcc) {
+      const float* d = mc.dct + tid;
+      float a = 0.f;
+#pragma unroll 8  // eight table loads in flight per wait: the loop is bound by their L2 latency, not by the fma chain
+      for (int m = 0; m < n_mels; ++m) a = fmaf(im[m], d[(size_t)m * mc.n_mfcc], a);
+      out[tid] = a * mc.lifter[tid];
+    }
   }
 }
 
+template <bool kMfcc>
 __global__ __launch_bounds__(kFT) void k_fbank(const float* __restrict__ x, int n, const float* __restrict__ gain_p,
                                                int use_db, float target_db, FbankTables tb, int win, int shift,
-                                               int nfft, int log2n, int n_mels, float* __restrict__ feats) {
+                                               int nfft, int log2n, int n_mels, float* __restrict__ feats, MfccTables mc) {
   __shared__ float s_gain;
   const int frame = blockIdx.x;
   if (threadIdx.x == 0) s_gain = use_db ? *gain_p : 1.0f;
   __syncthreads();
-  fbank_frame(x + (size_t)frame * shift, s_gain, tb, win, nfft, log2n, n_mels, feats + (size_t)frame * n_mels);
+  const int row = kMfcc ? mc.n_mfcc : n_mels;
+  fbank_frame<kMfcc>(x + (size_t)frame * shift, s_gain, tb, win, nfft, log2n, n_mels, feats + (size_t)frame * row, mc);
 }
 
 // grid = the total number of frames (the compact numbering); a frame's output row = its segment's out_row + its number
 // inside the segment, so the same kernel writes a compact [sum frames][n_mels] or a padded [B][Tmax][n_mels] array
+// (kMfcc: rows of n_mfcc floats)
+template <bool kMfcc>
 __global__ __launch_bounds__(kFT) void k_fbank_batch(const float* __restrict__ x, const ppasr_fbank_segment* __restrict__ seg,
                                                      int n_seg, const float* __restrict__ gains, int use_db, FbankTables tb,
                                                      int win, int shift, int nfft, int log2n, int n_mels,
-                                                     float* __restrict__ feats) {
+                                                     float* __restrict__ feats, MfccTables mc) {
   __shared__ long long s_src, s_row;
   __shared__ float s_gain;
   if (threadIdx.x == 0) {
@@ -299,7 +328,8 @@ __global__ __launch_bounds__(kFT) void k_fbank_batch(const float* __restrict__ x
     s_gain = use_db ? gains[2 * (size_t)s] : 1.0f;
   }
   __syncthreads();
-  fbank_frame(x + s_src, s_gain, tb, win, nfft, log2n, n_mels, feats + (size_t)s_row * n_mels);
+  const int row = kMfcc ? mc.n_mfcc : n_mels;
+  fbank_frame<kMfcc>(x + s_src, s_gain, tb, win, nfft, log2n, n_mels, feats + (size_t)s_row * row, mc);
 }
 
 }  // namespace
@@ -307,14 +337,32 @@ __global__ __launch_bounds__(kFT) void k_fbank_batch(const float* __restrict__ x
 struct ppasr_fbank_s : DeviceAllocs {
   int sample_rate, n_mels, win, shift, nfft, log2n;
   FbankTables tb;
+  MfccTables mc = {nullptr, nullptr, 0};  // n_mfcc == 0: the fbank form
 };
 
-extern "C" {
+// What ppasr_mfcc_create and ppasr_mfcc_tables refuse beyond ppasr_fbank_create's own refusals
+static ppasr_status mfcc_check(int n_mels, int n_mfcc, float cepstral_lifter) {
+  if (n_mels < 1 || n_mels > kFT || n_mfcc < 1 || n_mfcc > n_mels || !(cepstral_lifter >= 0.f) || std::isinf(cepstral_lifter))
+    return fail(PPASR_EINVAL, "mfcc: needs 1 <= n_mfcc <= n_mels <= 256 and a finite cepstral_lifter >= 0");
+  return PPASR_OK;
+}
 
-ppasr_status ppasr_fbank_create(int sample_rate, int n_mels, float frame_length_ms, float frame_shift_ms,
-                                ppasr_fbank_handle* out) {
-  if (!out || sample_rate <= 0 || n_mels < 1 || n_mels > kFT) return fail(PPASR_EINVAL, "fbank: bad arguments");
-  auto f = std::make_unique<ppasr_fbank_s>();
+// The tables of the MFCC stage (ppasr_mfcc_create uploads them, ppasr_mfcc_tables hands them out): computed in double,
+// rounded to float once.
+static void mfcc_host_tables(int n_mels, int n_mfcc, float cepstral_lifter, float* dct, float* lifter) {
+  const double pi = 3.14159265358979323846, q = (double)cepstral_lifter;
+  for (int m = 0; m < n_mels; ++m) {  // orthonormal DCT-II: D^T D = I for n_mfcc == n_mels
+    dct[(size_t)m * n_mfcc] = (float)sqrt(1.0 / n_mels);
+    for (int k = 1; k < n_mfcc; ++k) dct[(size_t)m * n_mfcc + k] = (float)(sqrt(2.0 / n_mels) * cos(pi / n_mels * (m + 0.5) * k));
+  }
+  for (int k = 0; k < n_mfcc; ++k) lifter[k] = q > 0.0 ? (float)(1.0 + 0.5 * q * sin(pi * k / q)) : 1.0f;
+}
+
+// What ppasr_fbank_create and ppasr_mfcc_create share: the frame geometry and the tables of the log-mel stage.
+static ppasr_status fbank_build(int sample_rate, int n_mels, float frame_length_ms, float frame_shift_ms,
+                                std::unique_ptr<ppasr_fbank_s>& f) {
+  if (sample_rate <= 0 || n_mels < 1 || n_mels > kFT) return fail(PPASR_EINVAL, "fbank: bad arguments");
+  f = std::make_unique<ppasr_fbank_s>();
   f->sample_rate = sample_rate;
   f->n_mels = n_mels;
   f->win = (int)(sample_rate * 0.001 * frame_length_ms);
@@ -371,9 +419,48 @@ ppasr_status ppasr_fbank_create(int sample_rate, int n_mels, float frame_length_
   f->tb.bank_lo = static_cast<const int*>(p);
   if ((s = up(hi.data(), hi.size() * 4, &p)) != PPASR_OK) return s;
   f->tb.bank_hi = static_cast<const int*>(p);
+  return PPASR_OK;
+}
+
+extern "C" {
+
+ppasr_status ppasr_fbank_create(int sample_rate, int n_mels, float frame_length_ms, float frame_shift_ms,
+                                ppasr_fbank_handle* out) {
+  if (!out) return fail(PPASR_EINVAL, "fbank: bad arguments");
+  std::unique_ptr<ppasr_fbank_s> f;
+  ppasr_status s = fbank_build(sample_rate, n_mels, frame_length_ms, frame_shift_ms, f);
+  if (s != PPASR_OK) return s;
   *out = f.release();
   return PPASR_OK;
 }
+
+ppasr_status ppasr_mfcc_tables(int n_mels, int n_mfcc, float cepstral_lifter, float* dct, float* lifter) {
+  if (!dct || !lifter) return fail(PPASR_EINVAL, "mfcc: null argument");
+  ppasr_status s = mfcc_check(n_mels, n_mfcc, cepstral_lifter);
+  if (s == PPASR_OK) mfcc_host_tables(n_mels, n_mfcc, cepstral_lifter, dct, lifter);
+  return s;
+}
+
+ppasr_status ppasr_mfcc_create(int sample_rate, int n_mels, int n_mfcc, float frame_length_ms, float frame_shift_ms,
+                               float cepstral_lifter, ppasr_fbank_handle* out) {
+  if (!out) return fail(PPASR_EINVAL, "mfcc: null argument");
+  ppasr_status s = mfcc_check(n_mels, n_mfcc, cepstral_lifter);  // (refused before any allocation or device call)
+  if (s != PPASR_OK) return s;
+  std::vector<float> dct((size_t)n_mels * n_mfcc), lifter(n_mfcc);
+  mfcc_host_tables(n_mels, n_mfcc, cepstral_lifter, dct.data(), lifter.data());
+  std::unique_ptr<ppasr_fbank_s> f;
+  if ((s = fbank_build(sample_rate, n_mels, frame_length_ms, frame_shift_ms, f)) != PPASR_OK) return s;
+  const void* p = nullptr;
+  if ((s = f->upload_bytes(dct.data(), dct.size() * 4, &p)) != PPASR_OK) return s;
+  f->mc.dct = static_cast<const float*>(p);
+  if ((s = f->upload_bytes(lifter.data(), lifter.size() * 4, &p)) != PPASR_OK) return s;
+  f->mc.lifter = static_cast<const float*>(p);
+  f->mc.n_mfcc = n_mfcc;
+  *out = f.release();
+  return PPASR_OK;
+}
+
+int ppasr_fbank_feature_dim(ppasr_fbank_handle f) { return !f ? 0 : f->mc.n_mfcc > 0 ? f->mc.n_mfcc : f->n_mels; }
 
 ppasr_status ppasr_fbank_destroy(ppasr_fbank_handle f) {
   delete f;
@@ -407,8 +494,12 @@ ppasr_status ppasr_fbank_compute(ppasr_fbank_handle f, const float* samples, int
     PPASR_LAUNCH(k_sumsq, dim3(chunks), dim3(1024), 0, st, samples, n_samples, ws);
     PPASR_LAUNCH(k_gain, dim3(1), dim3(1), 0, st, ws, chunks, n_samples, target_db);
   }
-  PPASR_LAUNCH(k_fbank, dim3(frames), dim3(kFT), 0, st, samples, n_samples, ws + chunks, use_db_norm, target_db, f->tb,
-                     f->win, f->shift, f->nfft, f->log2n, f->n_mels, feats);
+  if (f->mc.n_mfcc > 0)
+    PPASR_LAUNCH(k_fbank<true>, dim3(frames), dim3(kFT), 0, st, samples, n_samples, ws + chunks, use_db_norm, target_db, f->tb,
+                 f->win, f->shift, f->nfft, f->log2n, f->n_mels, feats, f->mc);
+  else
+    PPASR_LAUNCH(k_fbank<false>, dim3(frames), dim3(kFT), 0, st, samples, n_samples, ws + chunks, use_db_norm, target_db, f->tb,
+                 f->win, f->shift, f->nfft, f->log2n, f->n_mels, feats, f->mc);
   HIP_TRY(hipGetLastError());
   return PPASR_OK;
 }
@@ -464,9 +555,12 @@ ppasr_status ppasr_fbank_compute_batch(ppasr_fbank_handle f, const float* sample
     if (total_chunks > 0) PPASR_LAUNCH(k_sumsq_batch, dim3(total_chunks), dim3(1024), 0, st, samples, table_dev, n, ws);
     PPASR_LAUNCH(k_gain_batch, dim3((n + 63) / 64), dim3(64), 0, st, ws, table_dev, n, target_db, gains);
   }
-  if (total_frames > 0)
-    PPASR_LAUNCH(k_fbank_batch, dim3(total_frames), dim3(kFT), 0, st, samples, table_dev, n, gains, use_db_norm, f->tb,
-                 f->win, f->shift, f->nfft, f->log2n, f->n_mels, feats);
+  if (total_frames > 0 && f->mc.n_mfcc > 0)
+    PPASR_LAUNCH(k_fbank_batch<true>, dim3(total_frames), dim3(kFT), 0, st, samples, table_dev, n, gains, use_db_norm, f->tb,
+                 f->win, f->shift, f->nfft, f->log2n, f->n_mels, feats, f->mc);
+  else if (total_frames > 0)
+    PPASR_LAUNCH(k_fbank_batch<false>, dim3(total_frames), dim3(kFT), 0, st, samples, table_dev, n, gains, use_db_norm, f->tb,
+                 f->win, f->shift, f->nfft, f->log2n, f->n_mels, feats, f->mc);
   HIP_TRY(hipGetLastError());
   return PPASR_OK;
 }

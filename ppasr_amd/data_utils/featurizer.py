@@ -6,6 +6,8 @@ The arithmetic runs in ``csrc/fbank.hip`` behind ``ppasr_fbank_*`` (one workgrou
 from the raw samples to the 80 log-mel values); this module only loads audio and moves buffers.  There is no CPU
 path: without a HIP device ``featurize`` raises.  paddleaudio is not installable offline, so the front-end is
 "parity unpinned" (checked against ``oracle/fbank_oracle.py``, a float64 restatement of Kaldi's algorithm).
+``feature_method='mfcc'`` is the same kernel with one more stage (``ppasr_mfcc_create``: DCT-II over the mel axis and the
+cepstral lifter, Kaldi's defaults); ``'linear'`` is not built.
 """
 import ctypes
 import io
@@ -65,6 +67,7 @@ def db_gain(samples, target_db=-20.0):
 
 
 MAX_GAIN_DB = 300.0  # AudioSegment.normalize's max_gain_db default (data_utils/audio.py:287)
+CEPSTRAL_LIFTER = 22.0  # paddleaudio.compliance.kaldi.mfcc's default, which audio_featurizer.py:109-115 leaves alone
 
 
 def check_gain_db(gain, target_db):
@@ -85,9 +88,17 @@ def pcm_bytes_to_float(data, channels=1, samp_width=2):
 class AudioFeaturizer:
     def __init__(self, feature_method="fbank", n_mels=80, n_mfcc=40, sample_rate=16000, use_dB_normalization=True,
                  target_dB=-20, train=False, device=None, **_ignored):
-        if feature_method != "fbank":
-            raise NotImplementedError("only feature_method='fbank' is on the hot path")
+        if feature_method == "linear":
+            # 161 wide: beyond what any front end takes (input_dim <= 128), and a 320-point transform of un-quantised samples
+            raise NotImplementedError("feature_method='linear' is not built: its 161-wide rows fit no encoder front end here "
+                                      "(input_dim <= 128); use 'fbank' or 'mfcc'")
+        if feature_method not in ("fbank", "mfcc"):
+            raise NotImplementedError(f"feature_method={feature_method!r} is not built: 'fbank' and 'mfcc' are")
+        if feature_method == "mfcc" and not 1 <= n_mfcc <= n_mels:  # paddleaudio.compliance.kaldi.mfcc asserts this
+            raise AssertionError(f"n_mfcc must be in 1 .. n_mels: {n_mfcc} vs {n_mels}")
+        self._feature_method = feature_method
         self._n_mels = n_mels
+        self._n_mfcc = n_mfcc
         self._sr = sample_rate
         self._use_db = use_dB_normalization
         self._target_db = target_dB
@@ -105,7 +116,12 @@ class AudioFeaturizer:
             self._lib = _lib.load()
             h = ctypes.c_void_p()
             with torch.cuda.device(self._device):
-                _lib.check(self._lib.ppasr_fbank_create(self._sr, self._n_mels, 25.0, 10.0, ctypes.byref(h)))
+                if self._feature_method == "mfcc":
+                    _lib.check(self._lib.ppasr_mfcc_create(self._sr, self._n_mels, self._n_mfcc, 25.0, 10.0, CEPSTRAL_LIFTER,
+                                                           ctypes.byref(h)))
+                else:
+                    _lib.check(self._lib.ppasr_fbank_create(self._sr, self._n_mels, 25.0, 10.0, ctypes.byref(h)))
+                assert self._lib.ppasr_fbank_feature_dim(h) == self.feature_dim
             self._h = h
         return self._h
 
@@ -117,7 +133,8 @@ class AudioFeaturizer:
 
     @property
     def feature_dim(self):
-        return self._n_mels
+        """audio_featurizer.py:140-154: the width of a feature row, the model's ``input_dim``"""
+        return self._n_mfcc if self._feature_method == "mfcc" else self._n_mels
 
     @property
     def use_db_normalization(self):
@@ -128,7 +145,7 @@ class AudioFeaturizer:
         return self._target_db
 
     def featurize_device(self, samples, sample_rate=None):
-        """float32 mono samples in [-1, 1] (numpy or tensor) -> fbank [T, n_mels] float32 DEVICE tensor."""
+        """float32 mono samples in [-1, 1] (numpy or tensor) -> fbank [T, n_mels] (mfcc: [T, n_mfcc]) float32 DEVICE tensor."""
         from ppasr_amd import _lib
         sr = sample_rate or self._sr
         if sr != self._sr:  # audio_featurizer.py:46-47: up / down-sample to the model's rate first (host side)
@@ -137,7 +154,7 @@ class AudioFeaturizer:
         x = torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self._device).contiguous()
         n = int(x.numel())
         frames = int(self._lib.ppasr_fbank_frames(h, n))
-        feats = torch.empty(frames, self._n_mels, dtype=torch.float32, device=self._device)
+        feats = torch.empty(frames, self.feature_dim, dtype=torch.float32, device=self._device)
         if frames == 0:
             return feats
         need = int(self._lib.ppasr_fbank_workspace_bytes(h, n))
@@ -155,7 +172,7 @@ class AudioFeaturizer:
         return feats
 
     def featurize(self, samples, sample_rate=None):
-        """float32 mono samples -> fbank [T, n_mels] float32 (numpy), the reference's return type."""
+        """float32 mono samples -> fbank [T, n_mels] (mfcc: [T, n_mfcc]) float32 (numpy), the reference's return type."""
         return self.featurize_device(samples, sample_rate).cpu().numpy()
 
     def _stage(self, key, nbytes, pinned=False):
@@ -176,7 +193,7 @@ class AudioFeaturizer:
           padded=True:  (feats [B, Tmax, n_mels], lens [B] int64 tensor) -- what ``get_encoder_out`` takes; the rows
                         past a waveform's frames are zero.
         A waveform shorter than one window has no frame.  ``self.last_gains`` holds the gains ([B] float32) afterwards
-        when dB normalisation is on."""
+        when dB normalisation is on.  (``feature_method='mfcc'``: read n_mfcc for n_mels.)"""
         from ppasr_amd import _lib
         h = self._handle()
         lib, dev = self._lib, self._device
@@ -212,8 +229,8 @@ class AudioFeaturizer:
             self._uploaded = torch.cuda.Event()
             self._uploaded.record(cur)
             ws = self._stage("ws", int(lib.ppasr_fbank_batch_workspace_bytes(n, chunks)))
-            feats = (torch.empty(n, t_max, self._n_mels, dtype=torch.float32, device=dev) if padded
-                     else torch.empty(n_frames, self._n_mels, dtype=torch.float32, device=dev))
+            feats = (torch.empty(n, t_max, self.feature_dim, dtype=torch.float32, device=dev) if padded
+                     else torch.empty(n_frames, self.feature_dim, dtype=torch.float32, device=dev))
             if padded:
                 feats.zero_()  # the padding rows; the kernel writes the others
             if n:

@@ -43,7 +43,11 @@ class InferencePredictor:
         enc = _get(configs, "encoder_conf", {})
         enc = dict(enc) if isinstance(enc, dict) else dict(vars(enc))
         pre = _get(configs, "preprocess_conf", {})
-        input_dim = int(_get(pre, "n_mels", 80))
+        # AudioFeaturizer.feature_dim (audio_featurizer.py:140-154): n_mfcc for MFCC features, n_mels for fbank
+        if _get(pre, "feature_method", "fbank") == "mfcc":
+            input_dim = int(_get(pre, "n_mfcc", 40))
+        else:
+            input_dim = int(_get(pre, "n_mels", 80))
         if vocab_size is None:
             key = "decoder.ctc_lo.bias" if use_model == "deepspeech2" else "ctc.ctc_lo.bias"
             vocab_size = int(state_dict[key].shape[0])
