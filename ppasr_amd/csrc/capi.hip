@@ -1,7 +1,8 @@
-// capi.hip -- the C-ABI of libppasr_hip.so (declared in include/ppasr_hip.h).
-// Host side: descriptor checks and the dispatch of ppasr_create (the weights: weights.h and the families' *_create),
-// workspace carving, launch sequence.
-#include <cxxabi.h>
+// capi.hip -- the model handle and the offline encode of the C-ABI of libppasr_hip.so (declared in include/ppasr_hip.h).
+// Host side: descriptor checks and the dispatch of ppasr_create (the weights: weights.h and the families' *_create), the
+// ppasr_set_* calls, the fp16 x3 mode and its range guard, workspace carving, the split / row-block rules, and the launch
+// sequence of ppasr_encode (encode_impl; the frame it shares with the other walks: encode_common.h).  The decoders' entry
+// points are in capi_decode.hip, the profilers in capi_profile.hip.
 #include <cstdlib>
 
 #include "capi_internal.h"
@@ -276,28 +277,6 @@ ppasr_status ppasr_set_debug_taps(ppasr_handle h, float* taps, size_t n_floats) 
   return PPASR_OK;
 }
 
-long long ppasr_edit_distance(const int32_t* a, int na, const int32_t* b, int nb) {
-  if (na < 0 || nb < 0 || (na > 0 && !a) || (nb > 0 && !b)) return -1;
-  if (na < nb) {
-    std::swap(a, b);
-    std::swap(na, nb);
-  }
-  if (nb == 0) return na;
-  std::vector<int> prev(nb + 1), cur(nb + 1);
-  for (int j = 0; j <= nb; ++j) prev[j] = j;
-  for (int i = 1; i <= na; ++i) {
-    cur[0] = i;
-    const int32_t ca = a[i - 1];
-    for (int j = 1; j <= nb; ++j) {
-      const int sub = prev[j - 1] + (ca != b[j - 1]);
-      const int del = prev[j] + 1, ins = cur[j - 1] + 1;
-      cur[j] = sub < del ? (sub < ins ? sub : ins) : (del < ins ? del : ins);
-    }
-    std::swap(prev, cur);
-  }
-  return prev[nb];
-}
-
 ppasr_status ppasr_set_ffn_split(ppasr_handle h, int mode) {
   if (!h) return fail(PPASR_EINVAL, "null handle");
   if (mode != -1 && mode != 0 && mode != 2 && mode != 4 && mode != 8) return fail(PPASR_EINVAL, "ffn split: -1, 0, 2, 4 or 8");
@@ -499,12 +478,7 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
   // the fused attention reads whole 64-row key sub-blocks of V^T: rows outside an utterance (padding behind the last
   // row, frames a ragged batch skips) are multiplied by p = 0 and must be finite
   HIP_TRY(hipMemsetAsync(ws + wl.vt, 0, (size_t)kD * wl.vt_stride * sizeof(float), st));
-  size_t tap_off = 0;
-  auto tap = [&](const float* src, size_t n) {
-    if (h->taps && tap_off + n <= h->taps_floats)
-      (void)hipMemcpyAsync(h->taps + tap_off, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    tap_off += n;
-  };
+  Taps tap{h->taps, h->taps_floats, st};
   if (h->prof) {
     h->ev_used = 0;
     h->spans.clear();
@@ -526,14 +500,12 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
     fn();
     g_launch_prof = LaunchProf{};
   };
-  // ragged batches (ppasr_set_skip_padding): rows behind an utterance's valid frames + slack are skipped.  Slack =
-  // what valid outputs read from the rows behind them: the right context of the non-causal conv module, and with a
-  // rate change (Efficient-Conformer) the stride layer's 2j / 2j+1 rows and the 3-frame groups of grouped attention.
+  // ragged batches (ppasr_set_skip_padding; the rule: RaggedPlan)
   const bool eff = h->desc.model_type == PPASR_MODEL_EFFICIENT_CONFORMER;
   // (6x / 8x front ends: the LAYERS and the head skip -- frame t is valid iff 6t / 8t < len --, the front end itself
   //  computes every row: its skip rules are written for the 3x3 / 2 pair of Conv2dSubsampling4)
   const bool skip = h->skip_padding && lens && !h->taps && h->desc.input_layer != 1;
-  const bool skip_front = skip && h->desc.input_layer == 0;
+  const RaggedPlan ragged{skip, lens, h->desc.causal ? 0 : (h->desc.cnn_module_kernel - 1) / 2, eff, sub};
   // Ragged batches on the fused attention route (ppasr_set_ffn_split(0), or more than 128 row blocks): its key sub-blocks
   // read the VALUES of whole 64-row pieces of the batch's row space times p = 0, and the QKV stage writes those values
   // for every row of a 32-row block that holds one needed frame.  The rows behind the needed frames in such a block are
@@ -544,120 +516,45 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
   // other: rowblock.h PadSkip).  The vt clear above only covers rows of blocks the QKV stage skips.
   // (tests/test_buffer_contents_gpu.py test_batched_encode[conformer-9x1000-ff], [conformer-3x131-masked-ff] and
   // [efficient-3x400-ff], routes ffn_split=0+skip: NaN in every valid row when the workspace held NaN.)
-  // The row-count half of fusable() below, shared with it: a layer of `rows` rows may take the fused attention.  True of
-  // a layer's Mi <= M only if true of M (a forced split never fuses, the default rule fuses past fuse_min_blocks), so
-  // asking it of M covers every layer, the Efficient-Conformer's half-rate ones included.
-  // (an under-filled grid is latency-bound either way, and the two-kernel route then has 4x the workgroups in its
-  //  attention half, one per head: 2 - 6 % faster end to end up to 128 row blocks, measured in round 3), 10 %
-  //  slower at the bench shape)
-  constexpr int fuse_min_blocks = 128;
-  auto fuse_rows = [&](int rows) {
-    return ffn_split_for(h, rows) == 1 &&
-           (h->ffn_split == 0 || (rows + kRows - 1) / kRows > fuse_min_blocks);  // (ppasr_set_ffn_split(0): always fused)
-  };
-  if (skip && fuse_rows(M)) HIP_TRY(hipMemsetAsync(y2, 0, (wl.rmax - wl.y2) * sizeof(float), st));
-  const int rc = h->desc.causal ? 0 : (h->desc.cnn_module_kernel - 1) / 2;
-  const int slack_half = rc + 4, slack_full = eff ? 2 * slack_half + rc + 8 : rc + 4;
-  auto pskip = [&](int Tcur, int mul_cur) {
-    PadSkip ps;
-    if (skip) {
-      ps.lens = lens;
-      ps.Tp = Tcur;
-      ps.mul = mul_cur;
-      ps.slack = mul_cur == sub ? slack_full : slack_half;
-    }
-    return ps;
-  };
-  // Conv2dSubsampling4: both convolutions in one launch, conv1's output never leaves the chip (front_fused.hip)
-  // (fp16 x3 mode: conv2 runs on that route as its own launch behind k_conv1)
-  const f32x4* conv2_h3 = h->gemm_mode == PPASR_GEMM_F16X3 ? h->conv2_w_h3 : nullptr;
-  const bool conv12 = h->desc.input_layer == 0 && !conv2_h3 && conv12_enabled(h) && conv12_supported(h->front, F, F2);
-  const PadSkip ps_front = skip_front ? pskip(Tp, sub) : PadSkip{};  // (the front end's own kernels)
-  if (!conv12) timed(0, [&] { launch_conv1(feats, h->front, y1, B, T, F, T1, F1, st, ps_front); });
+  // (fuse_rows of the M entry-rate rows: no layer has more)
+  if (skip && fuse_rows(h, M)) HIP_TRY(hipMemsetAsync(y2, 0, (wl.rmax - wl.y2) * sizeof(float), st));
+  BlockTables tables(skip, B, M, ws + wl.rmax, st);
   if (h->desc.input_layer == 8) {
     // Conv2dSubsampling8: conv1 -> conv2 (3x3 / 2) -> conv3 (3x3 / 2, written over conv1's output) -> linear
+    timed(0, [&] { launch_conv1(feats, h->front, y1, B, T, F, T1, F1, st, PadSkip{}); });
     timed(1, [&] {
       launch_conv_stage(y1, h->front.conv2_w, h->front.conv2_b, y2, B, T1, F1, fd.T2, F2, 3, 2, st);
       launch_conv_stage(y2, h->front.conv3_w, h->front.conv3_b, y1, B, fd.T2, F2, Tp, h->F3, 3, 2, st);
     });
     timed(2, [&] { launch_embed(y1, h->front, xa, M, h->F3 * kD, sqrtf((float)kD), false, st, PadSkip{}, ffn_split_for(h, M), y2); });
   } else {
-    timed(1, [&] {
-      // (ragged batches: the active-tile table of conv2 lives in the CTC head's statistics buffer, unused until the head)
-      int* tile_tab = (size_t)B + 2 <= ((size_t)M + 63) / 64 * 64 ? reinterpret_cast<int*>(ws + wl.rmax) : nullptr;
-      if (conv12) launch_conv12(feats, h->front, y2, B, T, F, Tp, F2, st, ps_front, tile_tab);
-      else if (h->desc.input_layer == 0 && !conv2_h3 && conv2_quad_supported(h->front))
-        launch_conv2_quad(y1, h->front, y2, B, T1, F1, Tp, F2, st, ps_front, tile_tab);
-      else launch_conv2(y1, h->front, y2, B, T1, F1, Tp, F2, st, ps_front, tile_tab, h->desc.input_layer == 0 ? conv2_h3 : nullptr);
-    });
-    timed(2, [&] {
-      launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), false, st, ps_front, wide_slices_for(h, M, F2), y1,
-                   conv2_h3 ? h->embed_w_h3 : nullptr);
-    });
+    const PadSkip ps_front = skip && h->desc.input_layer == 0 ? ragged.at(Tp, sub) : PadSkip{};  // (the front end's own kernels)
+    front4_fused(h, feats, B, T, ps_front, tables.tile_tab(), /*scale_before_bias=*/false, wide_slices_for(h, M, F2), ps_front, y1,
+                 y2, xa, st, timed);
   }
   tap(xa, (size_t)M * kD);
   const int n_chunks = h->desc.linear_units / 256;
-  // ragged batches: lists of the active row blocks per (frame rate, block size), made on first use (rowblock.h
-  // PadSkip::tab; they live behind conv2's tile table in the CTC head's statistics buffers, unused until the head)
-  struct BlkTab { int Ti, R; int* tab; } btabs[4];
-  int n_bt = 0;
-  size_t bt_off = ((size_t)B + 2 + 15) / 16 * 16;
-  const bool bt_ok = skip && block_tables_enabled() && (size_t)B + 2 <= ((size_t)M + 63) / 64 * 64;
-  auto with_table = [&](PadSkip p, int Tcur, int R) {
-    if (!bt_ok) return p;
-    for (int k = 0; k < n_bt; ++k)
-      if (btabs[k].Ti == Tcur && btabs[k].R == R) { p.tab = btabs[k].tab; return p; }
-    const size_t n = 1 + ((size_t)B * Tcur + R - 1) / R;
-    if (n_bt == 4 || bt_off + n > 2 * (((size_t)M + 63) / 64 * 64)) return p;
-    int* t = reinterpret_cast<int*>(ws + wl.rmax) + bt_off;
-    launch_block_table(p, B * Tcur, R, t, st);
-    btabs[n_bt++] = BlkTab{Tcur, R, t};
-    bt_off += (n + 15) / 16 * 16;
-    p.tab = t;
-    return p;
-  };
   int Ti = Tp, mul = sub, pstride = 1;  // frames per utterance / pad-mask multiplier / positional stride of the current layer
   bool s1_done = false;               // this layer's S1 already ran inside the previous layer's last launch
   for (int i = 0; i < h->desc.num_blocks; ++i) {
     const LayerW& L = h->layers[i];
     const int Mi = B * Ti;
     const int grp = h->layer_group[i];
-    // plain 4 x 64 heads: attention and the out-projection / GLU stage run as one launch (context rows stay in LDS);
-    // the debug taps need the context tensor, so they take the two-kernel route
-    // (from fuse_min_blocks row blocks on, or always with ppasr_set_ffn_split(0): fuse_rows above)
-    auto fusable = [&](int layer) {
-      // (the fused kernel reads the values in fragment order, which only the fused QKV stage -- ffn_qkv_body -- writes: a
-      //  FORCED split of a large batch (ppasr_set_ffn_split(2 / 4 / 8), k_ln_qkv) therefore takes the two-kernel route)
-      return h->layer_group[layer] == 1 && h->desc.attention_heads == 4 && !h->taps && fuse_rows(Mi);
-    };
-    const PadSkip ps = pskip(Ti, mul);
-    // under-filled launch, 33 .. 128 row blocks: the 16-row-block kernels (conformer_kernels_t.hip) -- twice the
-    // workgroups, each half as long -- with the stand-alone attention between them; up to 32 blocks the split route below
-    const int rows = (!h->taps && conv_ffn_16_supported(h->layer_ks[i], Ti)) ? row_block_for(h, B, Ti, mul, ps.slack, skip) : 32;
-    const bool r16 = rows == 16 && h->ffn_split < 0;
-    const bool fuse_attn = !r16 && fusable(i);
-    // under-filled grid: FFNs split over S workgroups per row block (partial sums in the conv1 buffer, free by now)
-    const int S = r16 ? 1 : ffn_split_for(h, Mi);
-    // full grid: the same 32-row blocks on 16 waves (k_*_t<kW16>: drop-in for k_ffn_qkv / k_out_glu / k_conv_ffn)
-    const bool w16 = rows == kW16 && S == 1;
-    const int form = r16 ? 16 : w16 ? kW16 : 32;  // the layer's block form (rbt.h), as the stage launchers take it
-    const PadSkip psb = S == 1 ? with_table(ps, Ti, form_rows(form)) : ps;  // (for the kernels of this layer's block size)
-    // feed-forward GEMMs on the fp16 x3 route (ppasr_set_gemm_mode): the 8-wave 32-row kernels only
-    const bool h3 = h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty() && !r16 && !w16 && S == 1;
-    // ... the split route of under-filled launches likewise (its kernels' units; h3 view for the weights only -- the
-    // stand-alone attention keeps the fp32 positional table)
-    const bool h3s = h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty() && S > 1;
+    const PadSkip ps = ragged.at(Ti, mul);
+    const LayerRoute route = layer_route(h, B, Ti, mul, ps.slack, skip, i);
+    const int S = route.S, form = route.form;
+    const bool fuse_attn = route.fuse_attn, h3 = route.h3, h3s = route.h3s;
+    const PadSkip psb = S == 1 ? tables.with_table(ps, Ti, form_rows(form)) : ps;  // (for the kernels of this layer's block size)
     const LayerW& Lk = (h3 || h3s) ? h->layers_h3[i] : L;
-    // ... and with the fused attention the score MFMAs: the QKV stage then leaves K as fp16 hi / lo planes (VtOut::k_h3) and the
-    // attention reads the layer's positional planes.  Producer and consumer follow the same rule: layer j's K is planes iff
-    // layer j runs k_attn_out_glu_h3 (the producer of j's QKV is j's own S1 launch or the NEXT tail of j - 1, which shares
-    // j's row count and block form; the stride layer has no NEXT tail)
-    // ... and on the fp32 route the fused attention contracts 64 wide against k + p (AttnArgs::dtab): layer j's K holds the
-    // positional rows iff layer j runs the fp32 k_attn_out_glu -- same pairing, `layer` = the layer whose QKV is produced
-    auto vt_for = [&](bool fused, bool mode, int layer) {
-      VtOut v = fused ? vt_out : VtOut{};
-      v.k_h3 = (fused && mode) ? 1 : 0;
-      if (fused && !mode && h->layers[layer].dtab) {
+    // What the QKV stage that feeds layer `layer` (route r; its own S1 launch, or the NEXT tail of the layer before, which
+    // runs at the same rate) leaves besides row-major qkv.  Fused attention: the values in fragment order.  In the fp16 x3
+    // mode the attention's score MFMAs read K as fp16 hi / lo planes (VtOut::k_h3) and the layer's positional planes; on
+    // the fp32 route it contracts 64 wide against k + p (AttnArgs::dtab), so K holds the positional rows.  Producer and
+    // consumer both read r: layer j's K is planes iff j runs k_attn_out_glu_h3, holds k + p iff j runs the fp32 k_attn_out_glu.
+    auto vt_for = [&](const LayerRoute& r, int layer) {
+      VtOut v = r.fuse_attn ? vt_out : VtOut{};
+      v.k_h3 = (r.fuse_attn && r.h3) ? 1 : 0;
+      if (r.fuse_attn && !r.h3 && h->layers[layer].dtab) {
         v.kpos = h->layers[layer].ptab;  // (the fp32 table, not the h3 view's planes)
         v.kpos_stride = pstride * kD;
         v.Ti = Ti;
@@ -674,7 +571,7 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
           launch_ln_qkv(xb, qkv, Lk, Mi, st, ps, nullptr, nullptr, h3s);
         });
       } else {
-        timed(3, [&] { launch_ffn_qkv(xa, xb, qkv, Lk, Mi, n_chunks, st, psb, vt_for(fuse_attn, h3, i), h3, form); });
+        timed(3, [&] { launch_ffn_qkv(xa, xb, qkv, Lk, Mi, n_chunks, st, psb, vt_for(route, i), h3, form); });
       }
     }
     s1_done = false;
@@ -683,7 +580,7 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
     const int Tt = (Ti + grp - 1) / grp;  // tokens: frames, or zero-padded groups of 3 (pad4group)
     AttnArgs a{qkv, 768, qkv + 256, 768, qkv + 512, 768, Tt, Tt, 0, lens, ctx, L.pos_u, L.pos_v, (h3 && fuse_attn) ? Lk.ptab : L.ptab, pstride,
                mul * grp, Ti, Ti, grp};
-    a.pad_skip = skip ? ps.slack + 1 : 0;
+    a.pad_skip = ragged.attn_pad_skip(ps);
     a.vt = vt_out.vt;
     a.vt_stride = vt_out.stride;
     if (fuse_attn && !h3) {
@@ -706,15 +603,15 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
     if (eff && i == h->desc.stride_layer_idx) {
       const int Ts = (Ti + 1) / 2;
       timed(6, [&] {
-        const int Ss = r16 ? 1 : ffn_split_for(h, B * Ts);
+        const int Ss = form == 16 ? 1 : ffn_split_for(h, B * Ts);
         if (Ss > 1) {  // under-filled: the conv half alone (x3 -> ctx), the feed-forward module over the slices
           launch_conv_ffn_stride(g, nullptr, xc, xa, h3s ? Lk : L, lens, B, Ti, Ts, n_chunks, h->layer_ks[i], mul * 2, st,
-                                 pskip(Ts, mul * 2), h->desc.causal != 0, h3s, ctx);
+                                 ragged.at(Ts, mul * 2), h->desc.causal != 0, h3s, ctx);
           launch_ffn_split(ctx, L.ln_ff_g, L.ln_ff_b, Lk.ff_w1, L.ff_b1, Lk.ff_w2, L.ff_b2, 0.5f, L.ln_fin_g, L.ln_fin_b, partial,
-                           xa, B * Ts, n_chunks, Ss, st, pskip(Ts, mul * 2), false, h3s);
+                           xa, B * Ts, n_chunks, Ss, st, ragged.at(Ts, mul * 2), false, h3s);
         } else {
           launch_conv_ffn_stride(g, nullptr, xc, xa, (h3 || h3s) ? Lk : L, lens, B, Ti, Ts, n_chunks, h->layer_ks[i], mul * 2, st,
-                                 pskip(Ts, mul * 2), h->desc.causal != 0, h3 || h3s);
+                                 ragged.at(Ts, mul * 2), h->desc.causal != 0, h3 || h3s);
         }
       });
       Ti = Ts;  // masks[:, :, ::2], pos_emb[:, ::2]  (efficient_conformer/encoder.py:252-257)
@@ -729,35 +626,21 @@ static ppasr_status encode_impl(ppasr_handle h, const float* feats, const int64_
     } else {
       // fuse the next layer's S1 into this launch (it writes xb / qkv, which this layer no longer reads)
       const LayerW* next = (i + 1 < h->desc.num_blocks) ? (h3 ? &h->layers_h3[i + 1] : &h->layers[i + 1]) : nullptr;
+      // (the next layer runs at this layer's rate: the stride layer has no NEXT tail)
+      const VtOut vt_next = next ? vt_for(layer_route(h, B, Ti, mul, ps.slack, skip, i + 1), i + 1) : VtOut{};
       timed(next ? 8 : 6, [&] {
         // with the next layer's S1 fused in, the layer output itself is only read by the debug taps: skip its store
         launch_conv_ffn(g, nullptr, xc, (next && !h->taps) ? nullptr : xa, Lk, lens, Mi, Ti, n_chunks, h->layer_ks[i], mul, next,
-                        xb, qkv, st, h->desc.causal != 0, psb, vt_for(next && fusable(i + 1), h3, next ? i + 1 : i), h3, form);
+                        xb, qkv, st, h->desc.causal != 0, psb, vt_next, h3, form);
       });
       s1_done = next != nullptr;
     }
     tap(xa, (size_t)B * Ti * kD);
   }
   const int Mo = B * Ti;
-  float* lg = logits ? logits : probs;  // probs are produced in place from the logits tap
-  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
-  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
-  // (under-filled launch: the vocabulary tiles are split over several workgroups per row block, scratch = conv1 buffer)
-  timed(7, [&] {
-    const bool head_h3 = h->gemm_mode == PPASR_GEMM_F16X3 && h->head_w_h3;
-    HeadW hw = h->head;
-    if (head_h3) hw.w = h->head_w_h3;
-    launch_ctc_head(xa, hw, lg, fa, fp, ws + wl.rmax, ws + wl.rsum, Mo, st, pskip(Ti, mul),
-                    wide_slices_for(h, Mo, std::min((hw.n_tiles + 7) / 8, 32)), y1, head_h3);
-  });
-  if (probs) {
-    if (logits)
-      HIP_TRY(hipMemcpyAsync(probs, logits, (size_t)Mo * h->head.V * sizeof(float), hipMemcpyDeviceToDevice, st));
-    launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, Mo, h->head.V, st, pskip(Ti, mul));
-  }
-  if (skip) launch_zero_pad_rows(probs, logits, fa, fp, lens, B, Ti, mul, h->head.V, st);
-  HIP_TRY(hipGetLastError());
-  return PPASR_OK;
+  // (under-filled launch: the vocabulary tiles are split over several workgroups per row block)
+  return fused_head_tail(h, xa, probs, logits, frame_argmax, frame_maxprob, ws, wl, B, Mo,
+                         wide_slices_for(h, Mo, std::min((h->head.n_tiles + 7) / 8, 32)), ragged.at(Ti, mul), st, timed);
 }
 
 ppasr_status ppasr_encode(ppasr_handle h, const float* feats, const int64_t* lens, int B, int T, float* probs,
@@ -809,728 +692,6 @@ ppasr_status ppasr_gemm_guard_stats(ppasr_handle h, long long* fallbacks_host, l
   }
   if (fallbacks_host) *fallbacks_host = h->guard_fallbacks;
   if (events_host) *events_host = h->guard_events;
-  return PPASR_OK;
-}
-
-
-// =====================================================================================
-// CTC prefix beam search (see ctc_beam.hip)
-// =====================================================================================
-static ppasr_status beam_config(int V, int beam_size, double cutoff_prob, int cutoff_top_n, int blank, int nbest,
-                                int max_tokens, BeamConfig* c) {
-  if (V <= 1 || V >= 16384) return fail(PPASR_EUNSUPPORTED, "beam search: vocabulary must be in (1, 16384)");
-  if (beam_size < 1 || beam_size > kMaxBeam) return fail(PPASR_EUNSUPPORTED, "beam search: beam_size must be in [1, 512]");
-  if (blank < 0 || blank >= V) return fail(PPASR_EINVAL, "beam search: blank id out of range");
-  if (nbest < 1 || nbest > beam_size || max_tokens < 1) return fail(PPASR_EINVAL, "beam search: bad nbest / max_tokens");
-  if (cutoff_top_n < 1) return fail(PPASR_EINVAL, "beam search: cutoff_top_n < 1");
-  // candidates per frame: pruned to cutoff_top_n only when cutoff_prob < 1 (upstream get_pruned_log_probs); with
-  // cutoff_prob >= 1 -- the default of the reference's wrappers, swig_wrapper.py:38,71 -- upstream keeps EVERY character
-  // (sorted when cutoff_top_n < V, in vocabulary order otherwise), and so does the kernel: wide records and the element
-  // lists they produce go through HBM scratch (ppasr_ctc_beam_scratch_bytes)
-  const int n_cand = (cutoff_prob < 1.0) ? (cutoff_top_n < V ? cutoff_top_n : V) : V;
-  c->V = V; c->beam = beam_size; c->blank = blank; c->cutoff_top_n = cutoff_top_n; c->cutoff_prob = cutoff_prob;
-  c->n_cand_max = n_cand; c->nbest = nbest; c->max_tokens = max_tokens; c->max_nodes = 0;
-  c->sorted = (cutoff_prob < 1.0 || cutoff_top_n < V) ? 1 : 0;
-  {
-    const char* m = getenv("PPASR_BEAM_MARGIN");  // (tuning knob: rows of the clipped element list, ctc_beam.hip)
-    c->margin = m ? atoi(m) : 2;
-    if (c->margin < 0) c->margin = 0;
-  }
-  c->list_cap = beam_list_cap(beam_size, V, n_cand, c->lm.order > 0);
-  if (c->list_cap <= 0) return fail(PPASR_EUNSUPPORTED, "beam search: beam_size x vocabulary does not fit LDS");
-  return PPASR_OK;
-}
-
-// state buffer = B x [header | beam arrays | arena of 1 + (F+1)*beam nodes | node table] | B status words | scratch of the
-// pruning pre-pass (B x F frame records of the largest record size), F = max_frames.  The layout is recomputed from
-// (state_bytes, B, beam_size) on every call, so it is the same for every chunk of a streaming decode.
-
-// bytes of one utterance's share of the state buffer for a capacity of F frames: state block (ctc_beam.h: header, beam
-// arrays, arena and node table for max_nodes = 1 + (F + 1) * beam nodes) + its status word + F pruning records
-static size_t beam_max_nodes(size_t F, int beam_size) { return 1 + (F + 1) * (size_t)beam_size; }
-static size_t beam_utt_bytes(size_t F, int beam_size) {
-  return 4 * beam_state_words(beam_size, (int)beam_max_nodes(F, beam_size)) + 4 + F * 4 * (size_t)prune_rec_words(kSmallCand);
-}
-// frame capacity a state buffer of `per_utt_bytes` per utterance was sized for (0: too small for one frame)
-static size_t beam_frame_capacity(size_t per_utt_bytes, int beam_size) {
-  if (per_utt_bytes < beam_utt_bytes(1, beam_size)) return 0;
-  const size_t per_frame = beam_utt_bytes(2, beam_size) - beam_utt_bytes(1, beam_size);
-  size_t F = 1 + (per_utt_bytes - beam_utt_bytes(1, beam_size)) / per_frame;
-  while (F > 1 && beam_utt_bytes(F, beam_size) > per_utt_bytes) --F;  // (the fixed part is padded to an even word)
-  return F;
-}
-
-size_t ppasr_ctc_beam_state_bytes(int B, int max_frames, int beam_size) {
-  if (B <= 0 || max_frames < 0 || beam_size < 1) return 0;
-  return (size_t)B * beam_utt_bytes((size_t)(max_frames < 1 ? 1 : max_frames), beam_size);
-}
-
-}  // extern "C"
-namespace ppasr { const LmDev* lm_device_view(ppasr_lm_handle lm); }  // lm.hip (internal: C++ linkage, not exported)
-extern "C" {
-
-ppasr_status ppasr_ctc_beam_search(const float* probs, const int32_t* frame_lens, int B, int T, int V, int beam_size,
-                                   double cutoff_prob, int cutoff_top_n, int blank, int nbest, int max_tokens,
-                                   int32_t* tokens, int32_t* lens, double* scores, void* state, size_t state_bytes,
-                                   int init_state, void* stream) {
-  return ppasr_ctc_beam_search_lm(probs, frame_lens, B, T, V, beam_size, cutoff_prob, cutoff_top_n, blank, nbest, max_tokens,
-                                  tokens, lens, scores, state, state_bytes, init_state, nullptr, 0.0, 0.0, stream);
-}
-
-ppasr_status ppasr_ctc_beam_search_lm(const float* probs, const int32_t* frame_lens, int B, int T, int V, int beam_size,
-                                      double cutoff_prob, int cutoff_top_n, int blank, int nbest, int max_tokens,
-                                      int32_t* tokens, int32_t* lens, double* scores, void* state, size_t state_bytes,
-                                      int init_state, ppasr_lm_handle lm, double alpha, double beta, void* stream) {
-  return ppasr_ctc_beam_search_ws(probs, frame_lens, B, T, V, beam_size, cutoff_prob, cutoff_top_n, blank, nbest, max_tokens,
-                                  tokens, lens, scores, state, state_bytes, init_state, lm, alpha, beta, nullptr, 0, stream);
-}
-
-size_t ppasr_ctc_beam_scratch_bytes(int B, int T, int V, int beam_size, double cutoff_prob, int cutoff_top_n) {
-  BeamConfig c{};
-  if (B <= 0 || T < 0) return 0;
-  c.lm.order = 1;  // sized for a search WITH a scorer (its context summaries take LDS from the element list): enough for both
-  if (beam_config(V, beam_size, cutoff_prob, cutoff_top_n, 0, 1, 1, &c) != PPASR_OK) return 0;
-  return beam_scratch_bytes(c, B, T);
-}
-
-ppasr_status ppasr_ctc_beam_search_ws(const float* probs, const int32_t* frame_lens, int B, int T, int V, int beam_size,
-                                      double cutoff_prob, int cutoff_top_n, int blank, int nbest, int max_tokens,
-                                      int32_t* tokens, int32_t* lens, double* scores, void* state, size_t state_bytes,
-                                      int init_state, ppasr_lm_handle lm, double alpha, double beta, void* scratch,
-                                      size_t scratch_bytes, void* stream) {
-  if (!tokens || !lens || !scores || !state || (!probs && T > 0)) return fail(PPASR_EINVAL, "null argument");
-  if (B <= 0 || T < 0) return fail(PPASR_EINVAL, "empty batch");
-  BeamConfig c{};
-  if (lm) {  // before beam_config: the LDS budget depends on it
-    c.lm = *ppasr::lm_device_view(lm);
-    c.alpha = alpha;
-    c.beta = beta;
-  }
-  ppasr_status s = beam_config(V, beam_size, cutoff_prob, cutoff_top_n, blank, nbest, max_tokens, &c);
-  if (s != PPASR_OK) return s;
-  c.node_table = lm && c.lm.word_based;
-  {
-    const char* f = getenv("PPASR_BEAM_FAST");  // (read per call: the tests run both selections in one process)
-    c.fast_path = f ? (atoi(f) != 0) : 1;
-  }
-  const size_t per_utt_bytes = state_bytes / (size_t)B;
-  const size_t F = beam_frame_capacity(per_utt_bytes, beam_size);
-  if (F == 0) return fail(PPASR_ENOSPACE, "beam search: state buffer too small");
-  if ((size_t)T > F) return fail(PPASR_ENOSPACE, "beam search: more frames in one call than the state buffer was sized for");
-  c.max_nodes = (int)beam_max_nodes(F, beam_size);
-  const size_t block_words = beam_state_words(beam_size, c.max_nodes);
-  int32_t* st_words = static_cast<int32_t*>(state);
-  int32_t* status = st_words + (size_t)B * block_words;
-  int32_t* prune_recs = status + B;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  if (init_state) {
-    HIP_TRY(hipMemsetAsync(status, 0, (size_t)B * 4, hs));
-    // empty node tables (the kernel enters every prefix it creates) -- only where the search uses them: the default route
-    // of scorer-less / character-LM searches never reads the table, and clearing 24 bytes per node per call is tens of MB
-    // of memset on the latency-bound decoder path
-    if (c.node_table) {
-    const size_t tab_off = (beam_fixed_words(beam_size) + beam_arena_words(c.max_nodes)) * 4, tab_bytes = 12 * beam_table_slots(c.max_nodes);
-    HIP_TRY(hipMemset2DAsync(reinterpret_cast<char*>(state) + tab_off, block_words * 4, 0, tab_bytes, (size_t)B, hs));
-    }
-  }
-  const size_t need_scratch = beam_scratch_bytes(c, B, T);
-  if (need_scratch > 0 && (!scratch || scratch_bytes < need_scratch))
-    return fail(PPASR_ENOSPACE, "beam search: this pruning configuration keeps more characters per frame than the LDS-resident "
-                                "search holds (cutoff_prob >= 1 keeps the whole vocabulary): call ppasr_ctc_beam_search_ws with "
-                                "ppasr_ctc_beam_scratch_bytes(...) bytes of device scratch");
-  HIP_TRY(launch_ctc_beam(probs, frame_lens, B, T, c, prune_recs, st_words, init_state, 1, tokens, lens, scores, status,
-                          need_scratch ? scratch : nullptr, hs));
-  return PPASR_OK;
-}
-
-// State layout: B blocks of (fixed + 2 * max_nodes) words (beam arrays, then the parent-pointer arena, node ids in
-// creation order), B status words, the per-call pruning records.  A larger buffer therefore holds the same search once
-// every block's words sit at the start of the new, longer block (the arena simply has room for more nodes behind them).
-ppasr_status ppasr_ctc_beam_state_grow(const void* old_state, size_t old_bytes, void* new_state, size_t new_bytes, int B,
-                                       int beam_size, void* stream) {
-  if (!old_state || !new_state || B <= 0 || beam_size < 1) return fail(PPASR_EINVAL, "null argument");
-  const size_t Fo = beam_frame_capacity(old_bytes / (size_t)B, beam_size), Fn = beam_frame_capacity(new_bytes / (size_t)B, beam_size);
-  if (Fo == 0 || Fn == 0) return fail(PPASR_ENOSPACE, "beam search: state buffer too small");
-  if (Fn < Fo) return fail(PPASR_EINVAL, "beam search: the new state buffer is smaller than the old one");
-  const int mo = (int)beam_max_nodes(Fo, beam_size), mn = (int)beam_max_nodes(Fn, beam_size);
-  const size_t ow = beam_state_words(beam_size, mo), nw = beam_state_words(beam_size, mn);
-  const size_t head_words = beam_fixed_words(beam_size) + beam_arena_words(mo);  // header, beam arrays, arena: same offsets in both
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  const int32_t* o = static_cast<const int32_t*>(old_state);
-  int32_t* n = static_cast<int32_t*>(new_state);
-  HIP_TRY(hipMemcpy2DAsync(n, nw * 4, o, ow * 4, head_words * 4, (size_t)B, hipMemcpyDeviceToDevice, hs));
-  HIP_TRY(hipMemcpyAsync(n + (size_t)B * nw, o + (size_t)B * ow, (size_t)B * 4, hipMemcpyDeviceToDevice, hs));  // status
-  // the node table is rebuilt for the new size from the arena (every node but the root is an entry)
-  const size_t tab_off = (beam_fixed_words(beam_size) + beam_arena_words(mn)) * 4, tab_bytes = 12 * beam_table_slots(mn);
-  HIP_TRY(hipMemset2DAsync(reinterpret_cast<char*>(new_state) + tab_off, nw * 4, 0, tab_bytes, (size_t)B, hs));
-  HIP_TRY(launch_beam_rehash(n, B, beam_size, mn, hs));
-  return PPASR_OK;
-}
-
-// Streaming callers of the C-ABI: the kernel flags an utterance whose prefix arena ran out (more cumulative frames than
-// the state buffer was sized for) in a status word of the state buffer; this reads the B words back (synchronises the
-// stream) and returns PPASR_ENOSPACE if any is set -- the hypotheses of that utterance are then truncated.
-ppasr_status ppasr_ctc_beam_status(const void* state, size_t state_bytes, int B, int beam_size, int32_t* status_host,
-                                   void* stream) {
-  if (!state || B <= 0 || beam_size < 1) return fail(PPASR_EINVAL, "null argument");
-  const size_t F = beam_frame_capacity(state_bytes / (size_t)B, beam_size);
-  if (F == 0) return fail(PPASR_ENOSPACE, "beam search: state buffer too small");
-  const int32_t* status = static_cast<const int32_t*>(state) + (size_t)B * beam_state_words(beam_size, (int)beam_max_nodes(F, beam_size));
-  std::vector<int32_t> host(B);
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  HIP_TRY(hipMemcpyAsync(host.data(), status, (size_t)B * 4, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(hipStreamSynchronize(hs));
-  bool any = false;
-  for (int b = 0; b < B; ++b) {
-    if (status_host) status_host[b] = host[b];
-    any |= host[b] != 0;
-  }
-  if (any) return fail(PPASR_ENOSPACE, "beam search: the prefix arena of at least one utterance is exhausted (state sized for fewer frames)");
-  return PPASR_OK;
-}
-
-// Compaction of a streaming state buffer (ctc_beam.h: launch_beam_compact).  The live counts are the blocks' own st[1]
-// afterwards (-1 where the status word is set), so the read-back needs no device array of its own.
-ppasr_status ppasr_ctc_beam_state_compact(void* state, size_t state_bytes, int B, int beam_size, int rebuild_table,
-                                          int32_t* live_nodes_host, void* stream) {
-  if (!state || B <= 0 || beam_size < 1 || beam_size > kMaxBeam) return fail(PPASR_EINVAL, "beam search: null state, B <= 0 or bad beam_size");
-  const size_t F = beam_frame_capacity(state_bytes / (size_t)B, beam_size);
-  if (F == 0) return fail(PPASR_EINVAL, "beam search: state buffer too small for one frame");
-  const int max_nodes = (int)beam_max_nodes(F, beam_size);
-  const size_t block_words = beam_state_words(beam_size, max_nodes);
-  int32_t* st_words = static_cast<int32_t*>(state);
-  const int32_t* status = st_words + (size_t)B * block_words;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  HIP_TRY(launch_beam_compact(st_words, status, B, beam_size, max_nodes, rebuild_table != 0, nullptr, hs));
-  if (!live_nodes_host) return PPASR_OK;
-  std::vector<int32_t> stat(B);
-  HIP_TRY(hipMemcpy2DAsync(live_nodes_host, 4, st_words + 1, block_words * 4, 4, (size_t)B, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(hipMemcpyAsync(stat.data(), status, (size_t)B * 4, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(hipStreamSynchronize(hs));
-  for (int b = 0; b < B; ++b)
-    if (stat[b] != 0) live_nodes_host[b] = -1;
-  return PPASR_OK;
-}
-
-// ---- beam-search session pools (include/ppasr_hip.h: ppasr_beam_pool_*) ----
-// Every session owns its state block (ctc_beam.h layout, sized for its own frame capacity) and a status word; a decode
-// call builds a slot table of the listed sessions' blocks (by list position) and runs the pruning pre-pass and the search
-// once for all of them.  Growth is planned on the host from the sessions' frame counters before anything is launched.
-struct ppasr_beam_pool_s {
-  BeamConfig cfg;  // shared configuration (max_nodes / max_tokens / fast_path set per call)
-  int n_sessions;
-  std::vector<int32_t*> block;   // device state block of each session
-  std::vector<size_t> cap;       // frames each block is sized for
-  std::vector<long long> frames; // cumulative frames decoded since the session's last reset
-  // frame-equivalents of the arena in use -- what the capacity check compares: n_nodes <= 1 + used * beam.  A decode of f
-  // frames adds f, a reset sets 0, a compaction that found L live nodes sets ceil((L - 1) / beam); == frames without one
-  std::vector<long long> used;
-  std::vector<long long> live;   // node count read back at the session's last compaction (0: none since its reset)
-  bool auto_compact = false;     // ppasr_beam_arena_set_auto
-  int32_t* status;               // device [n_sessions]
-  // per-call slot tables + frame counts (a compaction: live counts): [n_sessions] BeamSlot, then [n_sessions] int32 per entry
-  StagingRing ring;
-};
-
-namespace {
-size_t pool_block_bytes(size_t F, int beam) { return 4 * beam_state_words(beam, (int)beam_max_nodes(F, beam)); }
-size_t pool_rec_bytes(const BeamConfig& c, int n, int T) {  // narrow pruning records (wide ones live in the scratch)
-  return c.n_cand_max > kSmallCand ? 0 : (((size_t)n * T * prune_rec_words(c.n_cand_max) * 4 + 255) & ~(size_t)255);
-}
-// largest capacity whose arena node count still fits the kernel's int arithmetic
-bool pool_cap_ok(size_t F, int beam) { return F <= (size_t)(0x3fffffff / beam) - 2; }
-
-// One compaction launch for the n listed sessions (checked by the caller): slot table up, live counts back, ONE
-// synchronisation of `hs`, then the accounting -- used = ceil((L - 1) / beam), so that n_nodes <= 1 + used * beam still
-// holds.  An exhausted session (count -1) was left as it is and keeps its accounting.  live_out [n] or null.
-ppasr_status pool_compact(ppasr_beam_pool_s* p, const int* sessions, int n, long long* live_out, hipStream_t hs) {
-  StagingRing::Entry en;
-  HIP_TRY(p->ring.acquire(&en));
-  BeamSlot* tab = reinterpret_cast<BeamSlot*>(en.host);
-  const int beam = p->cfg.beam;
-  for (int b = 0; b < n; ++b) {
-    const int s = sessions[b];
-    tab[b] = BeamSlot{p->block[s], p->status + s, (int)beam_max_nodes(p->cap[s], beam), 0};
-  }
-  const size_t live_off = (size_t)n * sizeof(BeamSlot);
-  HIP_TRY(hipMemcpyAsync(en.dev, en.host, live_off, hipMemcpyHostToDevice, hs));
-  HIP_TRY(launch_beam_compact(nullptr, nullptr, n, beam, 0, p->cfg.node_table, reinterpret_cast<int32_t*>(en.dev + live_off), hs,
-                              reinterpret_cast<const BeamSlot*>(en.dev)));
-  HIP_TRY(hipMemcpyAsync(en.host + live_off, en.dev + live_off, (size_t)n * 4, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(hipStreamSynchronize(hs));
-  HIP_TRY(p->ring.release(en, hs));
-  const int32_t* live = reinterpret_cast<const int32_t*>(en.host + live_off);
-  for (int b = 0; b < n; ++b) {
-    const int s = sessions[b];
-    if (live[b] >= 1) {
-      p->live[s] = live[b];
-      p->used[s] = ((long long)live[b] - 1 + beam - 1) / beam;
-    }
-    if (live_out) live_out[b] = live[b];
-  }
-  return PPASR_OK;
-}
-}  // namespace
-
-ppasr_status ppasr_beam_pool_create(int n_sessions, int V, int beam_size, double cutoff_prob, int cutoff_top_n, int blank,
-                                    ppasr_lm_handle lm, double alpha, double beta, int init_frames, ppasr_beam_pool* out) {
-  if (!out) return fail(PPASR_EINVAL, "null argument");
-  *out = nullptr;
-  if (n_sessions < 1 || init_frames < 1) return fail(PPASR_EINVAL, "beam pool: n_sessions and init_frames must be >= 1");
-  BeamConfig c{};
-  if (lm) {  // before beam_config: the LDS budget depends on it
-    c.lm = *ppasr::lm_device_view(lm);
-    c.alpha = alpha;
-    c.beta = beta;
-  }
-  ppasr_status s = beam_config(V, beam_size, cutoff_prob, cutoff_top_n, blank, 1, 1, &c);
-  if (s != PPASR_OK) return s;
-  if (!pool_cap_ok((size_t)init_frames, beam_size)) return fail(PPASR_EINVAL, "beam pool: init_frames too large");
-  c.node_table = lm && c.lm.word_based;
-  auto* p = new ppasr_beam_pool_s();  // (value-initialised: every pointer and event null until it exists)
-  p->cfg = c;
-  p->n_sessions = n_sessions;
-  p->block.assign(n_sessions, nullptr);
-  p->cap.assign(n_sessions, (size_t)init_frames);
-  p->frames.assign(n_sessions, 0);
-  p->used.assign(n_sessions, 0);
-  p->live.assign(n_sessions, 0);
-  auto bail = [p](const char* what, hipError_t e) {
-    (void)ppasr_beam_pool_destroy(p);
-    return fail(PPASR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  };
-  const size_t bb = pool_block_bytes((size_t)init_frames, beam_size);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->status), (size_t)n_sessions * 4);
-  for (int i = 0; i < n_sessions && e == hipSuccess; ++i) e = hipMalloc(reinterpret_cast<void**>(&p->block[i]), bb);
-  if (e == hipSuccess) e = p->ring.alloc(((size_t)n_sessions * (sizeof(BeamSlot) + 4) + 255) & ~(size_t)255);
-  if (e != hipSuccess) return bail("allocation failed for the beam pool", e);
-  for (int i = 0; i < n_sessions; ++i) {
-    e = launch_beam_reset(p->block[i], p->status + i, beam_size, (int)beam_max_nodes(p->cap[i], beam_size), c.lm.bos,
-                          c.node_table != 0, nullptr);
-    if (e != hipSuccess) return bail("initialising the beam-pool sessions failed", e);
-  }
-  e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) return bail("initialising the beam-pool sessions failed", e);
-  *out = p;
-  return PPASR_OK;
-}
-
-ppasr_status ppasr_beam_pool_destroy(ppasr_beam_pool p) {
-  if (!p) return fail(PPASR_EINVAL, "null pool");
-  p->ring.destroy();
-  for (int32_t* b : p->block)
-    if (b) (void)hipFree(b);
-  if (p->status) (void)hipFree(p->status);
-  delete p;
-  return PPASR_OK;
-}
-
-ppasr_status ppasr_beam_pool_reset(ppasr_beam_pool p, int session, void* stream) {
-  if (!p) return fail(PPASR_EINVAL, "null pool");
-  if (session >= p->n_sessions) return fail(PPASR_EINVAL, "beam pool: session out of range");
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  const int lo = session < 0 ? 0 : session, hi = session < 0 ? p->n_sessions : session + 1;
-  for (int i = lo; i < hi; ++i) {
-    HIP_TRY(launch_beam_reset(p->block[i], p->status + i, p->cfg.beam, (int)beam_max_nodes(p->cap[i], p->cfg.beam),
-                              p->cfg.lm.bos, p->cfg.node_table != 0, hs));
-    p->frames[i] = 0;
-    p->used[i] = 0;
-    p->live[i] = 0;
-  }
-  return PPASR_OK;
-}
-
-long long ppasr_beam_pool_frames(ppasr_beam_pool p, int session) {
-  if (!p || session < 0 || session >= p->n_sessions) return -1;
-  return p->frames[session];
-}
-
-long long ppasr_beam_pool_capacity(ppasr_beam_pool p, int session) {
-  if (!p || session < 0 || session >= p->n_sessions) return -1;
-  return (long long)p->cap[session];
-}
-
-ppasr_status ppasr_beam_pool_status(ppasr_beam_pool p, int32_t* status_host, void* stream) {
-  if (!p || !status_host) return fail(PPASR_EINVAL, "null argument");
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  HIP_TRY(hipMemcpyAsync(status_host, p->status, (size_t)p->n_sessions * 4, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(hipStreamSynchronize(hs));
-  for (int i = 0; i < p->n_sessions; ++i)
-    if (status_host[i] != 0) return fail(PPASR_ENOSPACE, "beam pool: the prefix arena of at least one session is exhausted");
-  return PPASR_OK;
-}
-
-size_t ppasr_beam_pool_workspace_bytes(ppasr_beam_pool p, int n, int T) {
-  if (!p || n < 1 || T < 0) return 0;
-  return pool_rec_bytes(p->cfg, n, T) + beam_scratch_bytes(p->cfg, n, T);
-}
-
-ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host, int n, const float* probs, int T,
-                                    const int32_t* frame_lens_host, int max_tokens, int32_t* tokens, int32_t* lens,
-                                    double* scores, void* workspace, size_t workspace_bytes, void* stream) {
-  // ---- every check before any device work: a refused call changes no session ----
-  if (!p || !sessions_host || !tokens || !lens || !scores || (!probs && T > 0)) return fail(PPASR_EINVAL, "null argument");
-  if (n < 1 || n > p->n_sessions || T < 0 || max_tokens < 1) return fail(PPASR_EINVAL, "beam pool: bad n / T / max_tokens");
-  if (!session_list_ok(sessions_host, n, p->n_sessions))
-    return fail(PPASR_EINVAL, "beam pool: session index out of range or repeated");
-  std::vector<int> fl(n);
-  for (int b = 0; b < n; ++b) {
-    fl[b] = frame_lens_host ? frame_lens_host[b] : T;
-    if (fl[b] < 0 || fl[b] > T) return fail(PPASR_EINVAL, "beam pool: frame_lens must lie in [0, T]");
-  }
-  const size_t need = ppasr_beam_pool_workspace_bytes(p, n, T);
-  if (workspace_bytes < need || (need > 0 && !workspace))
-    return fail(PPASR_ENOSPACE, "beam pool: workspace smaller than ppasr_beam_pool_workspace_bytes(pool, n, T)");
-  const int beam = p->cfg.beam;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  // ---- automatic compaction (ppasr_beam_arena_set_auto): every listed session whose chunk does not fit is compacted, all
-  // of them with one launch, before growth is planned; it then keeps its block if at least half of it stays free behind
-  // this chunk, and otherwise grows from the compacted state until that holds -- so compactions of a session are at least
-  // cap / 2 frames apart.  (Compaction changes no result, so a call refused below still changes no session's search.)
-  std::vector<char> compacted(n, 0);
-  if (p->auto_compact) {
-    std::vector<int> list;
-    for (int b = 0; b < n; ++b)
-      if ((size_t)p->used[sessions_host[b]] + (size_t)fl[b] > p->cap[sessions_host[b]]) {
-        compacted[b] = 1;
-        list.push_back(sessions_host[b]);
-      }
-    if (!list.empty()) {
-      ppasr_status rc = pool_compact(p, list.data(), (int)list.size(), nullptr, hs);
-      if (rc != PPASR_OK) return rc;
-    }
-  }
-  std::vector<size_t> new_cap(n, 0);  // 0: no growth
-  for (int b = 0; b < n; ++b) {
-    const int s = sessions_host[b];
-    const size_t want = ((size_t)p->used[s] + (size_t)fl[b]) * (compacted[b] ? 2 : 1);
-    if (want <= p->cap[s]) continue;
-    size_t c = p->cap[s];
-    while (c < want) c *= 2;
-    if (!pool_cap_ok(c, beam)) return fail(PPASR_ENOSPACE, "beam pool: a session's stream is too long for one prefix arena");
-    new_cap[b] = c;
-  }
-  // ---- growth: the session's block moves into one sized for twice the frames (doubling until the chunk fits).  Header,
-  // beam arrays and arena keep their offsets (ppasr_ctc_beam_state_grow); the node table, where the search uses one, is
-  // rebuilt for its new size.  The replaced blocks are freed after ONE stream synchronisation that covers every copy of
-  // this call (growth is rare: a session's capacity doubles, so a stream of F frames grows log2(F / init_frames) times).
-  std::vector<int32_t*> retired;
-  for (int b = 0; b < n; ++b) {
-    if (!new_cap[b]) continue;
-    const int s = sessions_host[b];
-    const int mo = (int)beam_max_nodes(p->cap[s], beam), mn = (int)beam_max_nodes(new_cap[b], beam);
-    int32_t* nb = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&nb), pool_block_bytes(new_cap[b], beam)));
-    const size_t head_words = beam_fixed_words(beam) + beam_arena_words(mo);
-    hipError_t e = hipMemcpyAsync(nb, p->block[s], head_words * 4, hipMemcpyDeviceToDevice, hs);
-    if (e == hipSuccess && p->cfg.node_table) {
-      const size_t tab_off = (beam_fixed_words(beam) + beam_arena_words(mn)) * 4, tab_bytes = 12 * beam_table_slots(mn);
-      e = hipMemsetAsync(reinterpret_cast<char*>(nb) + tab_off, 0, tab_bytes, hs);
-      if (e == hipSuccess) e = launch_beam_rehash(nb, 1, beam, mn, hs);
-    }
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(hs);
-      (void)hipFree(nb);
-      return fail(PPASR_EHIP, std::string("beam pool: growing a session failed: ") + hipGetErrorString(e));
-    }
-    retired.push_back(p->block[s]);
-    p->block[s] = nb;
-    p->cap[s] = new_cap[b];
-  }
-  if (!retired.empty()) {
-    HIP_TRY(hipStreamSynchronize(hs));
-    for (int32_t* o : retired) (void)hipFree(o);
-  }
-  // ---- the slot table and frame counts of this call ----
-  StagingRing::Entry en;
-  HIP_TRY(p->ring.acquire(&en));
-  BeamSlot* tab = reinterpret_cast<BeamSlot*>(en.host);
-  int32_t* fl_host = reinterpret_cast<int32_t*>(en.host + (size_t)n * sizeof(BeamSlot));
-  for (int b = 0; b < n; ++b) {
-    const int s = sessions_host[b];
-    tab[b] = BeamSlot{p->block[s], p->status + s, (int)beam_max_nodes(p->cap[s], beam), 0};
-    fl_host[b] = fl[b];
-  }
-  const size_t used = (size_t)n * (sizeof(BeamSlot) + 4);
-  HIP_TRY(hipMemcpyAsync(en.dev, en.host, used, hipMemcpyHostToDevice, hs));
-  BeamConfig c = p->cfg;
-  c.max_tokens = max_tokens;
-  c.max_nodes = 0;  // (per session: the slot table)
-  {
-    const char* f = getenv("PPASR_BEAM_FAST");  // (read per call, as ppasr_ctc_beam_search_ws does)
-    c.fast_path = f ? (atoi(f) != 0) : 1;
-  }
-  char* ws = static_cast<char*>(workspace);
-  const size_t rec_bytes = pool_rec_bytes(c, n, T), scratch_bytes = beam_scratch_bytes(c, n, T);
-  int32_t* recs = rec_bytes ? reinterpret_cast<int32_t*>(ws) : nullptr;
-  void* scratch = scratch_bytes ? ws + rec_bytes : nullptr;
-  HIP_TRY(launch_ctc_beam(probs, reinterpret_cast<const int32_t*>(en.dev + (size_t)n * sizeof(BeamSlot)), n, T, c, recs,
-                          nullptr, 0, 1, tokens, lens, scores, nullptr, scratch, hs, reinterpret_cast<const BeamSlot*>(en.dev)));
-  HIP_TRY(p->ring.release(en, hs));
-  for (int b = 0; b < n; ++b) {
-    p->frames[sessions_host[b]] += fl[b];
-    p->used[sessions_host[b]] += fl[b];
-  }
-  return PPASR_OK;
-}
-
-// ---- compaction of the pool's prefix arenas (include/ppasr_hip.h: ppasr_beam_arena_*) ----
-ppasr_status ppasr_beam_arena_compact(ppasr_beam_pool p, const int* sessions_host, int n, long long* live_nodes_host, void* stream) {
-  if (!p) return fail(PPASR_EINVAL, "null pool");
-  std::vector<int> all;
-  if (!sessions_host || n < 0) {
-    all.resize(p->n_sessions);
-    for (int i = 0; i < p->n_sessions; ++i) all[i] = i;
-    sessions_host = all.data();
-    n = p->n_sessions;
-  }
-  if (n < 1 || n > p->n_sessions) return fail(PPASR_EINVAL, "beam pool: bad n");
-  if (!session_list_ok(sessions_host, n, p->n_sessions))
-    return fail(PPASR_EINVAL, "beam pool: session index out of range or repeated");
-  return pool_compact(p, sessions_host, n, live_nodes_host, static_cast<hipStream_t>(stream));
-}
-
-ppasr_status ppasr_beam_arena_set_auto(ppasr_beam_pool p, int enable) {
-  if (!p) return fail(PPASR_EINVAL, "null pool");
-  p->auto_compact = enable != 0;
-  return PPASR_OK;
-}
-
-long long ppasr_beam_arena_live_nodes(ppasr_beam_pool p, int session) {
-  if (!p || session < 0 || session >= p->n_sessions) return -1;
-  return p->live[session];
-}
-
-size_t ppasr_beam_arena_bytes(ppasr_beam_pool p) {
-  if (!p) return 0;
-  size_t total = 0;
-  for (size_t c : p->cap) total += pool_block_bytes(c, p->cfg.beam);
-  return total;
-}
-
-// ---- kernel-name profiler: every PPASR_LAUNCH of the calling thread between begin and end carries its own dispatch-attached
-// event pair (launch.h); entries are keyed by the kernel's function pointer and named from the code object, so the names
-// are the ones rocprofv3's kernel trace prints.  Covers every model family and the decoders (bench.py roofline leg). ----
-}  // extern "C"
-namespace {
-struct KProf {
-  std::vector<hipEvent_t> pool;
-  size_t used = 0;
-  struct Rec { const void* fn; hipEvent_t s, e; };
-  std::vector<Rec> recs;
-  hipEvent_t next() {
-    if (used == pool.size()) {
-      hipEvent_t e;
-      (void)hipEventCreate(&e);
-      pool.push_back(e);
-    }
-    return pool[used++];
-  }
-};
-thread_local KProf g_kprof;
-
-std::string kernel_display_name(const void* fn) {
-  const char* mangled = hipKernelNameRefByPtr(fn, nullptr);
-  if (!mangled) return "?";
-  int status = 0;
-  char* dem = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-  std::string n = (status == 0 && dem) ? dem : mangled;
-  free(dem);
-  // drop the parameter list (the last balanced parenthesis group), "void " and the namespace
-  if (!n.empty() && n.back() == ')') {
-    int depth = 0;
-    for (size_t i = n.size(); i-- > 0;) {
-      if (n[i] == ')') ++depth;
-      else if (n[i] == '(' && --depth == 0) { n.erase(i); break; }
-    }
-  }
-  if (n.rfind("void ", 0) == 0) n.erase(0, 5);
-  for (size_t p; (p = n.find("ppasr::")) != std::string::npos;) n.erase(p, 7);
-  for (size_t p; (p = n.find("(anonymous namespace)::")) != std::string::npos;) n.erase(p, 23);
-  return n;
-}
-}  // namespace
-extern "C" {
-
-ppasr_status ppasr_kprof_begin(void) {
-  g_kprof.used = 0;
-  g_kprof.recs.clear();
-  g_launch_prof.ctx = &g_kprof;
-  g_launch_prof.next = [](void* ctx, const void* fn, hipEvent_t* s, hipEvent_t* e) {
-    KProf* k = static_cast<KProf*>(ctx);
-    *s = k->next();
-    *e = k->next();
-    k->recs.push_back({fn, *s, *e});
-  };
-  return PPASR_OK;
-}
-
-ppasr_status ppasr_kprof_end(int max_entries, char* names_host, float* total_ms_host, int* launches_host, int* n_out_host) {
-  g_launch_prof = LaunchProf{};
-  if (!names_host || !total_ms_host || !launches_host || !n_out_host || max_entries <= 0)
-    return fail(PPASR_EINVAL, "null argument");
-  std::vector<const void*> order;
-  std::unordered_map<const void*, std::pair<double, int>> acc;
-  for (auto& r : g_kprof.recs) {
-    HIP_TRY(hipEventSynchronize(r.e));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, r.s, r.e));
-    auto it = acc.find(r.fn);
-    if (it == acc.end()) {
-      order.push_back(r.fn);
-      it = acc.emplace(r.fn, std::make_pair(0.0, 0)).first;
-    }
-    it->second.first += ms;
-    it->second.second += 1;
-  }
-  g_kprof.recs.clear();
-  int n = 0;
-  for (const void* fn : order) {
-    if (n == max_entries) break;
-    const std::string name = kernel_display_name(fn);
-    char* dst = names_host + (size_t)n * PPASR_KPROF_NAME_LEN;
-    std::snprintf(dst, PPASR_KPROF_NAME_LEN, "%s", name.c_str());
-    total_ms_host[n] = (float)acc[fn].first;
-    launches_host[n] = acc[fn].second;
-    ++n;
-  }
-  *n_out_host = n;
-  return PPASR_OK;
-}
-
-static const char* kKernelClassNames[PPASR_N_KERNEL_CLASSES] = {
-    "k_conv1", "k_gemm_stream<conv2>", "k_gemm_stream<embed>", "k_ffn_qkv", "k_attention", "k_out_glu", "k_conv_ffn",
-    "k_ctc_head", "k_conv_ffn+ffn_qkv", "k_attn_out_glu"};
-
-ppasr_status ppasr_profile_enable(ppasr_handle h, int enable) {
-  if (!h) return fail(PPASR_EINVAL, "null handle");
-  if (enable && (h->desc.model_type != PPASR_MODEL_CONFORMER && h->desc.model_type != PPASR_MODEL_EFFICIENT_CONFORMER))
-    return fail(PPASR_EUNSUPPORTED, "ppasr_profile_enable: kernel classes exist for the Conformer route only; use ppasr_kprof_begin / _end");
-  if (enable && h->generic)
-    return fail(PPASR_EUNSUPPORTED, "ppasr_profile_enable: the general layer route has no kernel classes; use ppasr_kprof_begin / _end");
-  h->prof = enable != 0;
-  h->spans.clear();
-  h->ev_used = 0;
-  return PPASR_OK;
-}
-
-ppasr_status ppasr_profile_read(ppasr_handle h, float* total_ms_host, int* launches_host) {
-  if (!h || !total_ms_host || !launches_host) return fail(PPASR_EINVAL, "null argument");
-  for (int i = 0; i < PPASR_N_KERNEL_CLASSES; ++i) {
-    total_ms_host[i] = 0.f;
-    launches_host[i] = 0;
-  }
-  for (auto& sp : h->spans) {
-    if (sp.ev.empty()) continue;  // (a span whose kernels do not go through PPASR_LAUNCH)
-    for (auto& pr : sp.ev) {
-      HIP_TRY(hipEventSynchronize(pr.second));
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, pr.first, pr.second));
-      total_ms_host[sp.cls] += ms;
-    }
-    launches_host[sp.cls] += 1;
-  }
-  return PPASR_OK;
-}
-
-const char* ppasr_kernel_class_name(int cls) {
-  return (cls >= 0 && cls < PPASR_N_KERNEL_CLASSES) ? kKernelClassNames[cls] : "";
-}
-
-ppasr_status ppasr_ctc_collapse(const int32_t* frame_argmax, const float* frame_maxprob, const int32_t* frame_lens, int B,
-                                int Tp, int blank, int32_t* tokens, int32_t* n_tokens, double* score, void* stream) {
-  if (!frame_argmax || !frame_maxprob || !tokens || !n_tokens || !score) return fail(PPASR_EINVAL, "null argument");
-  if (B <= 0 || Tp <= 0) return fail(PPASR_EINVAL, "empty batch");
-  launch_ctc_collapse(frame_argmax, frame_maxprob, frame_lens, B, Tp, blank, tokens, n_tokens, score,
-                      static_cast<hipStream_t>(stream));
-  HIP_TRY(hipGetLastError());
-  return PPASR_OK;
-}
-
-ppasr_status ppasr_ctc_greedy(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank,
-                              int32_t* tokens, int32_t* n_tokens, double* score, void* workspace, size_t workspace_bytes,
-                              void* stream) {
-  if (!probs || !tokens || !n_tokens || !score || !workspace) return fail(PPASR_EINVAL, "null argument");
-  if (B <= 0 || Tp <= 0 || V <= 0) return fail(PPASR_EINVAL, "empty batch");
-  const size_t n = (size_t)B * Tp;
-  if (workspace_bytes < n * (sizeof(int32_t) + sizeof(float))) return fail(PPASR_ENOSPACE, "workspace too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int32_t* fa = static_cast<int32_t*>(workspace);
-  float* fp = reinterpret_cast<float*>(fa + n);
-  launch_frame_argmax(probs, fa, fp, B * Tp, V, st);
-  launch_ctc_collapse(fa, fp, frame_lens, B, Tp, blank, tokens, n_tokens, score, st);
-  HIP_TRY(hipGetLastError());
-  return PPASR_OK;
-}
-
-// ---- hypothesis records of the data-parallel path (ppasr_amd/parallel.py): int32 rows
-// tokens[cols] (-1 padded) | n_tokens | score (f64 as two words) [| utterance index].  One launch packs a batch's
-// hypotheses into its rows of the rank's record, one launch restores the caller's utterance order after the all-gather --
-// the record never passes through torch's indexing / elementwise kernels. ----
-}  // extern "C"
-namespace {
-__global__ __launch_bounds__(256) void k_hyp_pack(const int32_t* __restrict__ tokens, long long token_stride, int L,
-                                                  const int32_t* __restrict__ n, long long n_stride,
-                                                  const double* __restrict__ score, long long score_stride,
-                                                  const int32_t* __restrict__ index, int k, int32_t* __restrict__ rec,
-                                                  int row0, int cols, int extra) {
-  const int W = cols + extra;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)k * W) return;
-  const int r = (int)(i / W), j = (int)(i - (long long)r * W);
-  int32_t v;
-  if (j < cols) {
-    v = j < L ? tokens[r * token_stride + j] : -1;
-  } else if (j == cols) {
-    v = n[r * n_stride];
-  } else if (j <= cols + 2) {
-    const long long bits = __double_as_longlong(score[r * score_stride]);
-    v = (int32_t)(j == cols + 1 ? (uint32_t)bits : (uint32_t)((unsigned long long)bits >> 32));
-  } else {
-    v = index ? index[r] : -1;
-  }
-  rec[(size_t)(row0 + r) * W + j] = v;
-}
-__global__ __launch_bounds__(256) void k_hyp_unpack(const int32_t* __restrict__ rec, const int64_t* __restrict__ order, int N,
-                                                    int cols, int extra, int32_t* __restrict__ tokens, int32_t* __restrict__ n,
-                                                    double* __restrict__ score, int32_t* __restrict__ index) {
-  const int W = cols + extra;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)N * (cols + 1)) return;
-  const int r = (int)(i / (cols + 1)), j = (int)(i - (long long)r * (cols + 1));
-  const int32_t* src = rec + (size_t)(order ? order[r] : r) * W;
-  if (j < cols) {
-    tokens[(size_t)r * cols + j] = src[j];
-  } else {
-    n[r] = src[cols];
-    const unsigned long long bits = (unsigned long long)(uint32_t)src[cols + 1] | ((unsigned long long)(uint32_t)src[cols + 2] << 32);
-    score[r] = __longlong_as_double((long long)bits);
-    if (index) index[r] = extra > 3 ? src[cols + 3] : -1;
-  }
-}
-}  // namespace
-extern "C" {
-
-ppasr_status ppasr_hyp_pack(const int32_t* tokens, long long token_stride, int L, const int32_t* n_tokens, long long n_stride,
-                            const double* score, long long score_stride, const int32_t* index, int k, int32_t* rec, int row0,
-                            int cols, int extra, void* stream) {
-  if (!tokens || !n_tokens || !score || !rec) return fail(PPASR_EINVAL, "null argument");
-  if (k <= 0 || cols <= 0 || L < 0 || row0 < 0 || (extra != 3 && extra != 4)) return fail(PPASR_EINVAL, "hyp_pack: bad shape");
-  const long long total = (long long)k * (cols + extra);
-  PPASR_LAUNCH(k_hyp_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), tokens,
-               token_stride, L, n_tokens, n_stride, score, score_stride, index, k, rec, row0, cols, extra);
-  HIP_TRY(hipGetLastError());
-  return PPASR_OK;
-}
-
-ppasr_status ppasr_hyp_unpack(const int32_t* rec, const int64_t* order, int N, int cols, int extra, int32_t* tokens,
-                              int32_t* n_tokens, double* score, int32_t* index, void* stream) {
-  if (!rec || !tokens || !n_tokens || !score) return fail(PPASR_EINVAL, "null argument");
-  if (N <= 0 || cols <= 0 || (extra != 3 && extra != 4)) return fail(PPASR_EINVAL, "hyp_unpack: bad shape");
-  const long long total = (long long)N * (cols + 1);
-  PPASR_LAUNCH(k_hyp_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), rec, order,
-               N, cols, extra, tokens, n_tokens, score, index);
-  HIP_TRY(hipGetLastError());
   return PPASR_OK;
 }
 

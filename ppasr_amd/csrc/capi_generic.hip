@@ -596,11 +596,38 @@ struct GenRun {
   int gcap = 0, glo = 0;
 };
 
+// The head of the general route over the M = B x ps.Tp rows of `enc`: ctc_lo as a dense layer over the padded vocabulary ->
+// logits (into the caller's buffer, else the probabilities', else the scratch lg_ws), softmax, frame argmax / maxprob
+// when asked for (missing one of the two: its half of the scratch y); ragged batches (ps.lens): outputs behind the valid
+// frames are zeroed.
+ppasr_status dense_head_tail(const ppasr_model_s* h, const float* enc, float* probs, float* logits, int32_t* frame_argmax,
+                             float* frame_maxprob, float* lg_ws, float* y, int B, int M, const PadSkip& ps, hipStream_t st) {
+  const int D = h->desc.output_size, V = h->desc.vocab_size;
+  float* lg = logits ? logits : (probs ? probs : lg_ws);
+  GemmEpi e;
+  e.ps = ps;
+  dense(enc, D, h->gen_head_w, h->gen_head_b, lg, M, D, h->gen_vpad, V, V, st, 1.0f, e);
+  float* pr = probs;
+  if (!pr && (frame_argmax || frame_maxprob)) pr = (lg == lg_ws) ? lg : lg_ws;
+  if (pr) {
+    if (pr != lg) HIP_TRY(hipMemcpyAsync(pr, lg, (size_t)M * V * sizeof(float), hipMemcpyDeviceToDevice, st));
+    launch_softmax_from_stats(pr, nullptr, nullptr, M, V, st);
+    if (frame_argmax || frame_maxprob) {
+      int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(y);
+      float* fp = frame_maxprob ? frame_maxprob : y + M;
+      launch_frame_argmax(pr, fa, fp, M, V, st);
+    }
+  }
+  if (ps.lens) launch_zero_pad_rows(probs, logits, frame_argmax, frame_maxprob, ps.lens, B, ps.Tp, ps.mul, V, st);
+  HIP_TRY(hipGetLastError());
+  return PPASR_OK;
+}
+
 ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* frame_argmax, float* frame_maxprob) {
   ppasr_model_s* h = r.h;
   hipStream_t st = r.st;
   const auto& o = h->gen;
-  const int D = h->desc.output_size, H = h->desc.linear_units, V = h->desc.vocab_size, heads = h->desc.attention_heads;
+  const int D = h->desc.output_size, H = h->desc.linear_units, heads = h->desc.attention_heads;
   const int B = r.B;
   // frames per utterance / rows / mask multiplier / positional stride of the CURRENT layer: the Efficient-Conformer's
   // stride layer halves the rate (masks[:, :, ::2], pos_emb[:, ::2], efficient_conformer/encoder.py:252-257)
@@ -611,24 +638,13 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
   const bool rel = o.pos == PPASR_OPT_POS_REL;
   bool half = false;  // behind the stride layer
   // ragged batches (ppasr_set_skip_padding; batched calls only): per utterance only the rows its valid output frames depend
-  // on are computed, with the slack of the fused route (capi.hip ppasr_encode): the right context of a non-causal conv
-  // module, and with a rate change the stride layer's 2j / 2j + 1 rows and the 3-frame groups of grouped attention.  Rows
+  // on are computed, with the slack of the fused route (encode_common.h RaggedPlan).  Rows
   // behind them keep whatever the buffers hold; the valid rows never read them (PAD frames enter the conv module through
   // its mask, keys and values through the attention's) and the outputs behind the valid frames are zeroed at the end.
   const bool skip = h->skip_padding && lens && !r.s;
   const int rc = (h->desc.causal || !o.use_cnn) ? 0 : (h->desc.cnn_module_kernel - 1) / 2;
-  const int slack_half = rc + 4, slack_full = eff ? 2 * slack_half + rc + 8 : rc + 4, mul0 = mul;
-  auto pskip = [&](int Tcur, int mul_cur) {
-    PadSkip p;
-    if (skip) {
-      p.lens = lens;
-      p.Tp = Tcur;
-      p.mul = mul_cur;
-      p.slack = mul_cur == mul0 ? slack_full : slack_half;
-    }
-    return p;
-  };
-  PadSkip ps = pskip(Tp, mul);
+  const RaggedPlan ragged{skip, lens, rc, eff, mul};
+  PadSkip ps = ragged.at(Tp, mul);
   auto ln = [&](const float* in, float* out, const float* gg, const float* bb, float eps, int act, bool mask, int rows) {
     PPASR_LAUNCH(k_g_ln, dim3((rows + 3) / 4), dim3(256), 0, st, in, out, gg, bb, rows, D, eps, act, mask ? lens : nullptr, Tp, mul, 1.0f,
                  rows == M ? ps : PadSkip{});
@@ -721,7 +737,7 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
         at.sess = r.sess;
         at.sess_stride = kv_sess;
       }
-      at.pad_skip = skip ? ps.slack + 1 : 0;
+      at.pad_skip = ragged.attn_pad_skip(ps);
       at.dm = D;
       launch_attention(at, B, heads, st);
       if (o.concat_after) {  // x + concat_linear([attention input | linear_out(ctx)])
@@ -768,14 +784,14 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
         // StrideConformerEncoderLayer (efficient_conformer/encoder.py:455-548): depthwise conv with stride 2, the residual
         // through AvgPool1D(2, ceil_mode); everything behind runs on ceil(T / 2) frames with masks / positions [::2]
         const int Ts = (Tp + 1) / 2, Ms = B * Ts;
-        launch_dwconv(g, y, L.dw_w, L.dw_b, L.glu_pad, B, Ts, D, KS, left, lo_s, 2, Tp, st, pskip(Ts, mul * 2));
+        launch_dwconv(g, y, L.dw_w, L.dw_b, L.glu_pad, B, Ts, D, KS, left, lo_s, 2, Tp, st, ragged.at(Ts, mul * 2));
         half = true;
         PPASR_LAUNCH(k_g_avgpool2, blocks((size_t)Ms * D), dim3(256), 0, st, x, ctx, B, Tp, Ts, D);
         Tp = Ts;
         M = Ms;
         mul *= 2;
         pstride *= 2;
-        ps = pskip(Tp, mul);
+        ps = ragged.at(Tp, mul);
         std::swap(x, ctx);  // (res_epi below reads the new x = the pooled residual)
       } else {
         launch_dwconv(g, y, L.dw_w, L.dw_b, L.glu_pad, B, Tp, D, KS, left, lo_s, 1, Tp, st, ps);
@@ -794,22 +810,7 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
     ln(x, a, h->head.ln_g, h->head.ln_b, 1e-5f, kActNone, false, M);
     enc = a;
   }
-  float* lg = logits ? logits : (probs ? probs : r.lg);
-  dense(enc, D, h->gen_head_w, h->gen_head_b, lg, M, D, h->gen_vpad, V, V, st, 1.0f, plain_epi());
-  float* pr = probs;
-  if (!pr && (frame_argmax || frame_maxprob)) pr = (lg == r.lg) ? lg : r.lg;
-  if (pr) {
-    if (pr != lg) HIP_TRY(hipMemcpyAsync(pr, lg, (size_t)M * V * sizeof(float), hipMemcpyDeviceToDevice, st));
-    launch_softmax_from_stats(pr, nullptr, nullptr, M, V, st);
-    if (frame_argmax || frame_maxprob) {
-      int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(y);
-      float* fp = frame_maxprob ? frame_maxprob : y + M;
-      launch_frame_argmax(pr, fa, fp, M, V, st);
-    }
-  }
-  if (skip) launch_zero_pad_rows(probs, logits, frame_argmax, frame_maxprob, lens, B, Tp, mul, V, st);
-  HIP_TRY(hipGetLastError());
-  return PPASR_OK;
+  return dense_head_tail(h, enc, probs, logits, frame_argmax, frame_maxprob, r.lg, y, B, M, ps, st);
 }
 
 // front end: GlobalCMVN + the subsampling class + the positional encoding's scaling (subsampling.py, embedding.py)
@@ -892,7 +893,7 @@ ppasr_status sq_run(ppasr_model_s* h, const float* feats, const int64_t* lens, i
                     const ChunkPlan* plan) {
   if (h->taps) return fail(PPASR_EUNSUPPORTED, "debug taps are built for the fused 256-wide route");
   const GenWs wl = gen_layout(h, B, T);
-  const int D = h->desc.output_size, H = h->desc.linear_units, V = h->desc.vocab_size, heads = h->desc.attention_heads;
+  const int D = h->desc.output_size, H = h->desc.linear_units, heads = h->desc.attention_heads;
   const int F = h->desc.input_dim, L = h->desc.num_blocks, KS = h->desc.cnn_module_kernel;
   const auto fd = h->front_dims(T);
   const int Tp = fd.Tp, Tr = (Tp + 1) / 2, M = B * Tp;  // Conv1D(stride 2): ceil(T'/2) reduced frames
@@ -913,17 +914,8 @@ ppasr_status sq_run(ppasr_model_s* h, const float* feats, const int64_t* lens, i
   // the time reduction reads full-rate rows 2j - 3 .. 2j + 1, the recovery reduced row t / 2)
   const bool skip = h->skip_padding && lens && !s;
   const int rc = causal ? 0 : (KS - 1) / 2;
-  auto pskip = [&](int Tcur, int mul_cur) {
-    PadSkip p;
-    if (skip) {
-      p.lens = lens;
-      p.Tp = Tcur;
-      p.mul = mul_cur;
-      p.slack = mul_cur == 4 ? 2 * (rc + 4) + rc + 8 : rc + 4;
-    }
-    return p;
-  };
-  const PadSkip psF = pskip(Tp, 4), psH = pskip(Tr, 8);
+  const RaggedPlan ragged{skip, lens, rc, true, 4};
+  const PadSkip psF = ragged.at(Tp, 4), psH = ragged.at(Tr, 8);
   auto ln = [&](const float* in, float* out, const float* gg, const float* bb, float eps, int act, bool mask, int rows, int Ti,
                 int mul) {
     PPASR_LAUNCH(k_g_ln, dim3((rows + 3) / 4), dim3(256), 0, st, in, out, gg, bb, rows, D, eps, act, mask ? lens : nullptr, Ti, mul, 1.0f,
@@ -1012,7 +1004,7 @@ ppasr_status sq_run(ppasr_model_s* h, const float* feats, const int64_t* lens, i
       //  the end of a mapping -- found by the instrumented full suite, round 6)
       at.pos0 = plain_mha ? 0 : plan->pos0;
     }
-    at.pad_skip = skip ? ps.slack + 1 : 0;
+    at.pad_skip = ragged.attn_pad_skip(ps);
     at.dm = D;
     launch_attention(at, B, heads, st);
     dense(ctx, D, W.wo, W.bo, x, Mi, D, D, D, D, st, 1.0f, res_epi(false));
@@ -1064,26 +1056,8 @@ ppasr_status sq_run(ppasr_model_s* h, const float* feats, const int64_t* lens, i
     if (!pre) ln(x, x, W.ln4_g, W.ln4_b, 1e-5f, kActNone, false, Mi, Ti, mul);
   }
   // ---- ctc_lo -> softmax (no after_norm in Squeezeformer, encoder.py:232-235) ----
-  float* lg = logits ? logits : (probs ? probs : ws + wl.lg);
-  {
-    GemmEpi e;
-    e.ps = reduced ? PadSkip{} : psF;  // (without a recovery layer the encoder ends at the reduced rate: every row)
-    dense(x, D, h->gen_head_w, h->gen_head_b, lg, M, D, h->gen_vpad, V, V, st, 1.0f, e);
-  }
-  float* pr = probs;
-  if (!pr && (frame_argmax || frame_maxprob)) pr = (lg == ws + wl.lg) ? lg : ws + wl.lg;
-  if (pr) {
-    if (pr != lg) HIP_TRY(hipMemcpyAsync(pr, lg, (size_t)M * V * sizeof(float), hipMemcpyDeviceToDevice, st));
-    launch_softmax_from_stats(pr, nullptr, nullptr, M, V, st);
-    if (frame_argmax || frame_maxprob) {
-      int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(y);
-      float* fp = frame_maxprob ? frame_maxprob : y + M;
-      launch_frame_argmax(pr, fa, fp, M, V, st);
-    }
-  }
-  if (skip && !reduced) launch_zero_pad_rows(probs, logits, frame_argmax, frame_maxprob, lens, B, Tp, 4, V, st);
-  HIP_TRY(hipGetLastError());
-  return PPASR_OK;
+  // (without a recovery layer the encoder ends at the reduced rate: every row is computed and none zeroed)
+  return dense_head_tail(h, x, probs, logits, frame_argmax, frame_maxprob, ws + wl.lg, y, B, M, reduced ? PadSkip{} : psF, st);
 }
 }  // namespace
 

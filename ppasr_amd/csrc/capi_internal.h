@@ -248,6 +248,9 @@ struct ppasr_model_s : DeviceAllocs {
   const f32x4* embed_w_h3 = nullptr;  // ... and its input projection
   const f32x4* head_w_h3 = nullptr;   // the CTC head's weight [256][32 * n_tiles]
   std::vector<SqLayerW> sq_layers_h3;  // Squeezeformer: sq_layers[] with the two feed-forward modules' weights re-packed
+  // the fp16 x3 mode is on and this family's layers have their re-packed views
+  bool h3_layers() const { return gemm_mode == PPASR_GEMM_F16X3 && !layers_h3.empty(); }
+  bool h3_sq_layers() const { return gemm_mode == PPASR_GEMM_F16X3 && !sq_layers_h3.empty(); }
   int gemm_coverage = 0;      // PPASR_GEMM_COVERS_* of the current mode (ppasr_gemm_coverage)
   // range guard of the fp16 x3 mode (csrc/h3.h, ppasr_set_gemm_guard / ppasr_gemm_guard_stats)
   bool gemm_guard = true;
@@ -366,4 +369,5 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
                                   float* logits, int32_t* frame_argmax, float* frame_maxprob, float* ws,
                                   const WsLayout& wl, hipStream_t st);
 
+#include "encode_common.h"
 #include "weights.h"

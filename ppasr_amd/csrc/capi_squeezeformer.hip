@@ -168,67 +168,29 @@ LayerW sq_conv_view(const SqLayerW& W) {
 ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const int64_t* lens, int B, int T, float* probs,
                                   float* logits, int32_t* frame_argmax, float* frame_maxprob, float* ws,
                                   const WsLayout& wl, hipStream_t st) {
-  const int F = h->desc.input_dim, T1 = (T - 1) / 2, F1 = h->F1, Tp = (T1 - 1) / 2, F2 = h->F2;
+  const int Tp = h->front_dims(T).Tp;
   const int Tr = (Tp + 1) / 2;  // Conv1D(k=1, stride 2): ceil(T'/2) frames (time_reduction.py:186,196-199)
   const int M = B * Tp, L = h->desc.num_blocks, H = h->desc.attention_heads;
   const int n_chunks = h->desc.linear_units / 256, KS = h->desc.cnn_module_kernel;
   float *y1 = ws + wl.y1, *y2 = ws + wl.y2, *xa = ws + wl.xa, *xb = ws + wl.xb, *xc = ws + wl.xc;
   float *qkv = ws + wl.qkv, *ctx = ws + wl.ctx, *g = ws + wl.g, *xs = ws + wl.xs;
-  size_t tap_off = 0;
-  auto tap = [&](const float* src, size_t n) {
-    if (h->taps && tap_off + n <= h->taps_floats)
-      (void)hipMemcpyAsync(h->taps + tap_off, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    tap_off += n;
-  };
-  // ragged batches (ppasr_set_skip_padding, see ppasr_encode): the slack covers the time-reduction layer (reduced row
-  // j reads full-rate rows 2j - 3 .. 2j + 1 at most), the recovery (row t reads reduced row t/2) and, for the
-  // non-streaming model, the right context of the non-causal conv module
+  Taps tap{h->taps, h->taps_floats, st};
+  // ragged batches (ppasr_set_skip_padding, see ppasr_encode; the rule: RaggedPlan -- the rate changes at the time-reduction
+  // layer and back at the recovery)
   const bool skip = h->skip_padding && lens && !h->taps;
   const bool causal = h->desc.causal != 0;
-  const int rc = causal ? 0 : (KS - 1) / 2;
-  auto pskip = [&](int Tcur, int mul_cur) {
-    PadSkip ps;
-    if (skip) {
-      ps.lens = lens;
-      ps.Tp = Tcur;
-      ps.mul = mul_cur;
-      ps.slack = mul_cur == 4 ? 2 * (rc + 4) + rc + 8 : rc + 4;
-    }
-    return ps;
-  };
-  const PadSkip psF = pskip(Tp, 4), psH = pskip(Tr, 8);
-  int* tile_tab = (size_t)B + 2 <= ((size_t)M + 63) / 64 * 64 ? reinterpret_cast<int*>(ws + wl.rmax) : nullptr;
+  const RaggedPlan ragged{skip, lens, causal ? 0 : (KS - 1) / 2, true, 4};
+  const PadSkip psF = ragged.at(Tp, 4), psH = ragged.at(Tr, 8);
   // ragged batch: the active row blocks of the two frame rates as lists (PadSkip::tab), for the layer kernels K_B / K_C --
   // with the beam search of the previous batch on some CUs a padded grid with early exits runs extra rounds (rowblock.h).
-  // The lists live behind conv2's tile table in the CTC head's statistics buffers (2 al(M) floats, unused until the head).
+  // (one list per rate even where T' = 1 makes the two rates the same rows: make, not with_table)
   const int rowsF = h->taps ? 32 : row_block_for(h, B, Tp, 4, psF.slack, skip);
   const int rowsH = h->taps ? 32 : row_block_for(h, B, Tr, 8, psH.slack, skip);
-  PadSkip psF_rb = psF, psH_rb = psH;
-  if (skip && tile_tab && block_tables_enabled()) {
-    const int RF = form_rows(rowsF), RH = form_rows(rowsH);
-    const size_t nF = 1 + ((size_t)M + RF - 1) / RF, nH = 1 + ((size_t)B * Tr + RH - 1) / RH;
-    const size_t o1 = ((size_t)B + 2 + 15) / 16 * 16, o2 = o1 + (nF + 15) / 16 * 16;
-    if (o2 + nH <= 2 * (((size_t)M + 63) / 64 * 64)) {
-      int* base = reinterpret_cast<int*>(ws + wl.rmax);
-      launch_block_table(psF, M, RF, base + o1, st);
-      launch_block_table(psH, B * Tr, RH, base + o2, st);
-      psF_rb.tab = base + o1;
-      psH_rb.tab = base + o2;
-    }
-  }
-  // (fp16 x3 mode, ppasr_set_gemm_mode: conv2 on that route as its own launch behind k_conv1)
-  const f32x4* conv2_h3 = h->gemm_mode == PPASR_GEMM_F16X3 ? h->conv2_w_h3 : nullptr;
-  if (!conv2_h3 && conv12_enabled(h) && conv12_supported(h->front, F, F2)) {  // both convolutions in one launch (front_fused.hip)
-    launch_conv12(feats, h->front, y2, B, T, F, Tp, F2, st, psF, tile_tab);
-  } else {
-    launch_conv1(feats, h->front, y1, B, T, F, T1, F1, st, psF);
-    if (!conv2_h3 && conv2_quad_supported(h->front)) launch_conv2_quad(y1, h->front, y2, B, T1, F1, Tp, F2, st, psF, tile_tab);
-    else launch_conv2(y1, h->front, y2, B, T1, F1, Tp, F2, st, psF, tile_tab, conv2_h3);
-  }
+  BlockTables tables(skip, B, M, ws + wl.rmax, st);
+  const PadSkip psF_rb = tables.make(psF, Tp, form_rows(rowsF)), psH_rb = tables.make(psH, Tr, form_rows(rowsH));
   // (the embed GEMM works on 32-row blocks: it takes the full-rate list when that is the 32-row one)
-  launch_embed(y2, h->front, xa, M, F2 * kD, sqrtf((float)kD), /*scale_before_bias=*/true, st,
-               (rowsF != 16 && ffn_split_for(h, M) == 1) ? psF_rb : psF, ffn_split_for(h, M), y1,
-               conv2_h3 ? h->embed_w_h3 : nullptr);
+  front4_fused(h, feats, B, T, psF, tables.tile_tab(), /*scale_before_bias=*/true, ffn_split_for(h, M),
+               (rowsF != 16 && ffn_split_for(h, M) == 1) ? psF_rb : psF, y1, y2, xa, st, NoSpans{});
   launch_ln_rows(xa, h->preln_g, h->preln_b, M, st, psF);
   tap(xa, (size_t)M * kD);
   float* x = xa;      // current layer input / residual
@@ -258,7 +220,7 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
     // under-filled launches up to kSplitRows16Max rows (one utterance, small batches; fp32): the single-unit launches on
     // the Conformer's 16-row kernels through weight views, as a stream handle's chunk does (capi_stream.hip sq_stream_layers)
     const bool views16 = ffn_split_for(h, Mi) > 1 && !(rowsF == 16 && h->ffn_split < 0) && Mi <= kSplitRows16Max &&
-                         !(h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty());
+                         !h->h3_sq_layers();
     auto qkv_view = [](const SqLayerW& w) {
       LayerW v{};
       v.wqkv = w.wqkv;
@@ -271,7 +233,7 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
     }
     tap(qkv, (size_t)Mi * 3 * kD);
     AttnArgs a{qkv, 768, qkv + 256, 768, qkv + 512, 768, Ti, Ti, 0, lens, ctx, W.pos_u, W.pos_v, W.ptab, reduced ? 2 : 1, mul, Ti, Ti, 1};
-    a.pad_skip = skip ? ps.slack + 1 : 0;
+    a.pad_skip = ragged.attn_pad_skip(ps);
     launch_attention(a, B, H, st);
     tap(ctx, (size_t)Mi * kD);
     // under-filled grid (ppasr_set_ffn_split): K_B / K_C cut at their feed-forward modules, partial sums in the conv1 buffer
@@ -284,7 +246,7 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
     const SqLayerW* Wn = fuse_next ? &h->sq_layers[i + 1] : nullptr;
     if (S > 1) {
       // (fp16 x3 mode: the two feed-forward modules' slices on that route -- the re-packed weights of the layer's h3 view)
-      const bool h3s = h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty();
+      const bool h3s = h->h3_sq_layers();
       const SqLayerW& Ws = h3s ? h->sq_layers_h3[i] : W;
       // x1 = LN1(x + MHA) in `other` (free until this layer's output)
       if (views16) {
@@ -312,8 +274,7 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
       else if (Wn) launch_sq_qkv(other, qkv, Wn->wqkv, Wn->bqkv, Mi, st, ps);
     } else {
       // feed-forward modules on the fp16 x3 route (ppasr_set_gemm_mode): the 8-wave 32-row kernels only
-      const bool h3 = h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty() && rows == 32 && !h->taps &&
-                      sq_h3_supported(KS, Ti);
+      const bool h3 = h->h3_sq_layers() && rows == 32 && !h->taps && sq_h3_supported(KS, Ti);
       const SqLayerW& Wk = h3 ? h->sq_layers_h3[i] : W;
       launch_sq_mid(ctx, x, xc, g, nullptr, Wk, lens, Mi, Ti, mul, n_chunks, st, ps_rb, rows, h3);
       tap(xc, (size_t)Mi * kD);
@@ -325,22 +286,8 @@ ppasr_status squeezeformer_encode(ppasr_model_s* h, const float* feats, const in
     have_qkv = fuse_next;
     tap(x, (size_t)Mi * kD);
   }
-  float* lg = logits ? logits : probs;
-  int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
-  float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;
   // (the encoder ends at the full rate after the recovery; without one it stays reduced and M rows = B * Tp is the
-  //  caller's contract either way)
-  const PadSkip psO = reduced ? PadSkip{} : psF;
-  const bool head_h3 = h->gemm_mode == PPASR_GEMM_F16X3 && h->head_w_h3;
-  HeadW hw = h->head;
-  if (head_h3) hw.w = h->head_w_h3;
-  launch_ctc_head(x, hw, lg, fa, fp, ws + wl.rmax, ws + wl.rsum, M, st, psO, ffn_split_for(h, M), y1, head_h3);
-  if (probs) {
-    if (logits)
-      HIP_TRY(hipMemcpyAsync(probs, logits, (size_t)M * h->head.V * sizeof(float), hipMemcpyDeviceToDevice, st));
-    launch_softmax_from_stats(probs, ws + wl.rmax, ws + wl.rsum, M, h->head.V, st, psO);
-  }
-  if (skip && !reduced) launch_zero_pad_rows(probs, logits, fa, fp, lens, B, Tp, 4, h->head.V, st);
-  HIP_TRY(hipGetLastError());
-  return PPASR_OK;
+  //  caller's contract either way: every row is computed and none zeroed)
+  return fused_head_tail(h, x, probs, logits, frame_argmax, frame_maxprob, ws, wl, B, M, ffn_split_for(h, M),
+                         reduced ? PadSkip{} : psF, st, NoSpans{});
 }

@@ -235,7 +235,7 @@ void stream_head(const ppasr_model_s* h, const StreamRows& v, const StreamWs& w,
 // kernels stay fp32.  Out-of-range activations are saturated and counted (ppasr_gemm_guard_stats); a chunk is not re-run.
 int conformer_stream_layers(const ppasr_model_s* h, const StreamRows& v, const StreamWs& w, hipStream_t st) {
   const int n_chunks = h->desc.linear_units / 256, H = h->desc.attention_heads, n = v.n;
-  const bool h3_mode = h->gemm_mode == PPASR_GEMM_F16X3 && !h->layers_h3.empty();
+  const bool h3_mode = h->h3_layers();
   float *xa = w.xa, *xb = w.xb, *xc = w.xc, *qkv = w.qkv, *ctx = w.ctx, *g = w.g, *xhat = w.xhat, *partial = w.y1;
   int Ti = v.c, mul = 4, pstride = 1;
   bool half = false;
@@ -359,7 +359,7 @@ ppasr_status sq_stream_layers(const ppasr_model_s* h, const StreamRows& v, const
     const int Ti = reduced ? v.c_r : v.c, M = n * Ti;
     const int mul = reduced ? 8 : 4;
     const int S = ffn_split_for(h, M);
-    const bool h3s = S > 1 && h->gemm_mode == PPASR_GEMM_F16X3 && !h->sq_layers_h3.empty();  // (the FFN slices in the mode)
+    const bool h3s = S > 1 && h->h3_sq_layers();  // (the FFN slices in the mode)
     const bool r16 = v.handle() && S > 1 && !h3s && Ti <= kSplitRows16Max;
     if (!have_qkv) {
       if (r16) {

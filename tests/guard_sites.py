@@ -233,8 +233,8 @@ def oracle_kwargs(family):
 
 
 def _routes(family, site, layer):
-    """The routes of `site` at `layer` of the family's fixture, read off capi.hip / capi_stream.hip (encode_impl; conformer_stream_layers /
-    sq_stream_layers, one walk for stream handles and session groups): a grouped-attention
+    """The routes of `site` at `layer` of the family's fixture, read off capi.hip / encode_common.h / capi_stream.hip (encode_impl and its layer_route;
+    conformer_stream_layers / sq_stream_layers, one walk for stream handles and session groups): a grouped-attention
     layer has no fused attention (its out-projection and pointwise_conv1 then keep fp32 on the fused route, and the three
     attention sites do not exist); session groups are exercised on the Conformer."""
     routes = [r for r in SITE[site].routes if r != GROUP or family == "conformer"]
@@ -392,7 +392,7 @@ def set_route(model, route):
 
 def expected_kernels(family, site, layer, kind):
     """The kernels that split `site` at `layer` on route kind FUSED / SPLIT (streams and groups run the SPLIT kind), read
-    off capi.hip's layer loop: the Efficient-Conformer's stride layer runs pointwise_conv2 and, where its halved rows are not
+    off capi.hip's layer loop (encode_impl; a layer's route: layer_route in encode_common.h): the Efficient-Conformer's stride layer runs pointwise_conv2 and, where its halved rows are not
     split over slices, its final feed-forward module in k_conv_ffn_stride; on the fused route a layer's S1 (macaron module,
     Q/K/V, K planes) runs in its own k_ffn_qkv_h3 launch at layer 0 and behind the stride layer, which has no NEXT tail, and
     in the NEXT tail of the layer in front (k_conv_ffn_h3) everywhere else."""
