@@ -620,6 +620,68 @@ PPASR_API int          ppasr_fbank_feature_dim(ppasr_fbank_handle f);
  * computed in double and rounded to float once.  Same refusals as ppasr_mfcc_create, and PPASR_EINVAL for a null pointer. */
 PPASR_API ppasr_status ppasr_mfcc_tables(int n_mels, int n_mfcc, float cepstral_lifter, float* dct, float* lifter);
 
+/* ---- Polyphase FIR resampler: audio at any other rate -> the model's rate, in front of the fbank front-end -------------
+ * AudioSegment.resample (data_utils/audio.py:306-317; audio_featurizer.py:46-47 calls it first).  The reference uses
+ * resampy's 'kaiser_best', which is not installable offline; this is the filter the host route of
+ * data_utils/featurizer.py::resample has always used, scipy.signal.resample_poly(x, up, down, window=("kaiser",
+ * 14.769656459379492)): parity with resampy unpinned, like the host route.
+ *   g = gcd(in_rate, out_rate), up = out_rate / g, down = in_rate / g, half_len = 10 max(up, down), L = 2 half_len + 1,
+ *   h = up * firwin(L, 1 / max(up, down), kaiser beta),  n_pre_pad = down - half_len % down,
+ *   n_pre_remove = (half_len + n_pre_pad) / down,  hp = [0] * n_pre_pad + h,
+ *   y[m] = sum_i hp[(m + n_pre_remove) down - i up] x[i],  0 <= m < out_len = ceil(n_in up / down),  x = 0 outside the stream.
+ * Stored by phase: with k = (m + n_pre_remove) down, q(m) = k / up, p = k % up,  y[m] = sum_t table[p][t] x[q(m) - t] over
+ * t = 0 .. T - 1, table[p][t] = hp[p + t up] (exactly 0 past hp's end), T = taps_per_phase = ceil((L + n_pre_pad) / up):
+ * 21 / 21 / 29 / 32 / 43 / 58 / 64 taps for 8 k / 11.025 k / 22.05 k / 24 k / 32 k / 44.1 k / 48 k -> 16 k.  The table is
+ * computed in double and rounded to float once.
+ * Accumulation (the contract): every output is ONE fp32 accumulator that starts at 0 and takes its T taps in ascending t with
+ * fmaf; a sample outside the stream or outside the window a call was given enters as 0.  The result depends on the output's
+ * absolute index and the samples alone -- not on the call, the segment, in_first or where a packet boundary fell -- so whole
+ * utterances, packed batches and packet-by-packet streams give the same bytes.  Inputs are assumed finite (0 * inf is NaN).
+ * PPASR_EINVAL: a rate <= 0, equal rates (nothing to do), a null pointer, a position or count outside 0 .. 2^40;
+ * PPASR_EUNSUPPORTED: max(up, down) > 1024 (every standard rate to or from 8 k / 16 k lies inside).  A refused call writes
+ * nothing.  There is no host fallback. */
+#define PPASR_RESAMPLE_TILE 256                     /* outputs per workgroup */
+#define PPASR_RESAMPLE_MAX_SAMPLES (1LL << 40)      /* largest stream position / count a call takes */
+typedef struct ppasr_resampler_s* ppasr_resampler_handle;
+/* Host only, no device and no handle. */
+PPASR_API ppasr_status ppasr_resampler_geometry(int in_rate, int out_rate, int* up, int* down, int* taps_per_phase, int* n_pre_pad,
+                                                int* n_pre_remove);
+/* table [up][taps_per_phase]: the very table ppasr_resampler_create uploads */
+PPASR_API ppasr_status ppasr_resampler_table(int in_rate, int out_rate, float* table);
+/* The three below return -1 (and set ppasr_last_error) for what they refuse.
+ * out_len: ceil(n_in up / down).
+ * ready: how many leading outputs have q(m) < n_in_total, i.e. read no sample past the first n_in_total of the stream
+ *        (= max(0, out_len(n_in_total) - n_pre_remove)): what a stream can emit so far.
+ * first_needed: max(0, q(m) - (T - 1)), the lowest sample index output m reads: the tail a stream keeps for output m on. */
+PPASR_API long long    ppasr_resampler_out_len(int in_rate, int out_rate, long long n_in);
+PPASR_API long long    ppasr_resampler_ready(int in_rate, int out_rate, long long n_in_total);
+PPASR_API long long    ppasr_resampler_first_needed(int in_rate, int out_rate, long long m);
+/* Uploads the table to the current device. */
+PPASR_API ppasr_status ppasr_resampler_create(int in_rate, int out_rate, ppasr_resampler_handle* out);
+PPASR_API ppasr_status ppasr_resampler_destroy(ppasr_resampler_handle r);
+/* One call for every use; asynchronous on `stream`; in, out: device f32.  `in` holds the stream's samples with absolute
+ * indices in_first .. in_first + n_in - 1 (everything outside is zero); the call writes out[0 .. n_out), the outputs with
+ * absolute indices out_first .. out_first + n_out - 1, and nothing else.  A whole waveform: in_first = out_first = 0, n_out =
+ * out_len.  A stream packet: the kept tail + the new samples, out_first = the outputs emitted so far.  n_in == 0 and
+ * n_out == 0 are legal (then the buffer may be null). */
+PPASR_API ppasr_status ppasr_resample_compute(ppasr_resampler_handle r, const float* in, long long in_first, long long n_in,
+                                              float* out, long long out_first, long long n_out, void* stream);
+/* Batch form: n independent windows ("segments") of any streams, ONE launch whatever n is (n <= 65535).  Segment s reads
+ * in[in_offset ..] and writes out[out_offset .. out_offset + n_out) as a ppasr_resample_compute call of its own would, byte
+ * for byte.  segments_dev: a device copy of the table; its entries are the caller's to keep inside the buffers.  max_n_out:
+ * the largest n_out in the table (it sizes the grid; outputs past it are not computed). */
+typedef struct {
+  long long in_offset;  /* index in `in` of the segment's first held sample */
+  long long in_first;   /* absolute stream index of that sample */
+  long long n_in;
+  long long out_offset; /* index in `out` of the segment's first output */
+  long long out_first;  /* absolute index of that output */
+  long long n_out;
+} ppasr_resample_segment;
+PPASR_API ppasr_status ppasr_resample_compute_batch(ppasr_resampler_handle r, const float* in,
+                                                    const ppasr_resample_segment* segments_dev, int n, long long max_n_out,
+                                                    float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,15 @@ class FbankSegment(ctypes.Structure):
                 ("first_chunk", ctypes.c_int), ("first_frame", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
+class ResampleSegment(ctypes.Structure):
+    """ppasr_resample_segment: one window of one stream in a batch-form resample call"""
+    _fields_ = [("in_offset", ctypes.c_longlong), ("in_first", ctypes.c_longlong), ("n_in", ctypes.c_longlong),
+                ("out_offset", ctypes.c_longlong), ("out_first", ctypes.c_longlong), ("n_out", ctypes.c_longlong)]
+
+
+RESAMPLE_TILE = 256  # PPASR_RESAMPLE_TILE: outputs per workgroup of the resampler
+
+
 class ModelDesc(ctypes.Structure):
     _fields_ = [("model_type", ctypes.c_int), ("input_dim", ctypes.c_int), ("vocab_size", ctypes.c_int),
                 ("output_size", ctypes.c_int), ("attention_heads", ctypes.c_int), ("linear_units", ctypes.c_int),
@@ -182,6 +191,16 @@ SYMBOLS = [
                                          ctypes.c_float, ctypes.POINTER(_vp)]),
     ("ppasr_fbank_feature_dim", ctypes.c_int, [_vp]),
     ("ppasr_mfcc_tables", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp]),
+    ("ppasr_resampler_geometry", ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 5),
+    ("ppasr_resampler_table", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp]),
+    ("ppasr_resampler_out_len", ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]),
+    ("ppasr_resampler_ready", ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]),
+    ("ppasr_resampler_first_needed", ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]),
+    ("ppasr_resampler_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    ("ppasr_resampler_destroy", ctypes.c_int, [_vp]),
+    ("ppasr_resample_compute", ctypes.c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong,
+                                              ctypes.c_longlong, _vp]),
+    ("ppasr_resample_compute_batch", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_longlong, _vp, _vp]),
 ]
 
 _lib = None

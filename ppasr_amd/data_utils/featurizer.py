@@ -8,6 +8,10 @@ path: without a HIP device ``featurize`` raises.  paddleaudio is not installable
 "parity unpinned" (checked against ``oracle/fbank_oracle.py``, a float64 restatement of Kaldi's algorithm).
 ``feature_method='mfcc'`` is the same kernel with one more stage (``ppasr_mfcc_create``: DCT-II over the mel axis and the
 cepstral lifter, Kaldi's defaults); ``'linear'`` is not built.
+Audio at another rate than the model's is resampled first: on the host by default (``resample``, scipy in float64), or with
+``AudioFeaturizer(resample="device")`` by ``csrc/resample.hip`` behind ``ppasr_resample_*`` -- the same filter as a
+polyphase kernel, for single waveforms, packed batches (``featurize_many(sample_rates=...)``) and streams
+(``StreamResampler``), which all give the same bytes.
 """
 import ctypes
 import io
@@ -16,7 +20,7 @@ import wave
 import numpy as np
 import torch
 
-__all__ = ["AudioFeaturizer", "TextFeaturizer", "load_audio", "db_gain"]
+__all__ = ["AudioFeaturizer", "StreamResampler", "TextFeaturizer", "load_audio", "db_gain"]
 
 
 
@@ -87,7 +91,7 @@ def pcm_bytes_to_float(data, channels=1, samp_width=2):
 
 class AudioFeaturizer:
     def __init__(self, feature_method="fbank", n_mels=80, n_mfcc=40, sample_rate=16000, use_dB_normalization=True,
-                 target_dB=-20, train=False, device=None, **_ignored):
+                 target_dB=-20, train=False, device=None, resample="host", **_ignored):
         if feature_method == "linear":
             # 161 wide: beyond what any front end takes (input_dim <= 128), and a 320-point transform of un-quantised samples
             raise NotImplementedError("feature_method='linear' is not built: its 161-wide rows fit no encoder front end here "
@@ -96,6 +100,10 @@ class AudioFeaturizer:
             raise NotImplementedError(f"feature_method={feature_method!r} is not built: 'fbank' and 'mfcc' are")
         if feature_method == "mfcc" and not 1 <= n_mfcc <= n_mels:  # paddleaudio.compliance.kaldi.mfcc asserts this
             raise AssertionError(f"n_mfcc must be in 1 .. n_mels: {n_mfcc} vs {n_mels}")
+        if resample not in ("host", "device"):
+            raise ValueError(f"resample={resample!r}: 'host' (scipy on the CPU, the default) or 'device' (csrc/resample.hip)")
+        self._resample = resample
+        self._resamplers = {}  # foreign rate -> (ppasr_resampler_handle, its geometry); resample="device" only
         self._feature_method = feature_method
         self._n_mels = n_mels
         self._n_mfcc = n_mfcc
@@ -130,6 +138,82 @@ class AudioFeaturizer:
         if h is not None and h.value:
             self._lib.ppasr_fbank_destroy(h)
             self._h = None
+        for r, _ in getattr(self, "_resamplers", {}).values():
+            self._lib.ppasr_resampler_destroy(r)
+        self._resamplers = {}
+
+    @property
+    def resample_mode(self):
+        """'host' or 'device': where audio at another rate than the featurizer's is resampled"""
+        return self._resample
+
+    def _resampler(self, sample_rate):
+        """-> (handle, rate) of the device resampler sample_rate -> the featurizer's rate, built on first use.  What the
+        library refuses (max(up, down) > 1024, a rate <= 0) raises ``PPASRHipError``: there is no host fallback."""
+        from ppasr_amd import _lib
+        rate = int(sample_rate)
+        if self._resample != "device":
+            raise ValueError(f"audio at {rate} Hz for a featurizer at {self._sr} Hz: this call resamples on the device only, "
+                             'construct the AudioFeaturizer with resample="device"')
+        got = self._resamplers.get(rate)
+        if got is None:
+            self._handle()  # (the library, and the refusal without a device)
+            r = ctypes.c_void_p()
+            with torch.cuda.device(self._device):
+                _lib.check(self._lib.ppasr_resampler_create(rate, int(self._sr), ctypes.byref(r)))
+            got = self._resamplers[rate] = (r, rate)
+        return got
+
+    def _foreign(self, sample_rate):
+        return sample_rate is not None and int(sample_rate) != int(self._sr)
+
+    def resample_device(self, samples, sample_rate):
+        """float32 mono samples at `sample_rate` (numpy or tensor) -> the same audio at the featurizer's rate, a float32
+        DEVICE tensor of ceil(n up / down) samples: uploads the raw samples and resamples them there (``resample="device"``).
+        Samples already at the featurizer's rate are only uploaded."""
+        from ppasr_amd import _lib
+        x = torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self._device).contiguous()
+        if not self._foreign(sample_rate):
+            return x
+        r, rate = self._resampler(sample_rate)
+        n = int(x.numel())
+        n_out = int(self._lib.ppasr_resampler_out_len(rate, int(self._sr), n))
+        y = torch.empty(n_out, dtype=torch.float32, device=self._device)
+        with torch.cuda.device(self._device):
+            cur = torch.cuda.current_stream(self._device)
+            _lib.check(self._lib.ppasr_resample_compute(r, x.data_ptr(), 0, n, y.data_ptr(), 0, n_out, cur.cuda_stream))
+            x.record_stream(cur)  # `x` must outlive the kernel
+        return y
+
+    def _resample_windows(self, sample_rate, windows):
+        """windows = [(held samples (numpy), absolute index of the first one, absolute index of the first output wanted,
+        outputs wanted)] of any streams at `sample_rate` -> their outputs (numpy float32), by one packed upload, ONE batched
+        launch (``ppasr_resample_compute_batch``) and one download."""
+        from ppasr_amd import _lib
+        r, rate = self._resampler(sample_rate)
+        n = len(windows)
+        outs_n = [int(w[3]) for w in windows]
+        total_in, total_out = int(sum(w[0].size for w in windows)), int(sum(outs_n))
+        if n == 0 or total_out == 0:
+            return [np.zeros(0, np.float32) for _ in windows]
+        seg_bytes = ctypes.sizeof(_lib.ResampleSegment) * n
+        host = torch.empty(seg_bytes + 4 * total_in, dtype=torch.uint8, pin_memory=True)
+        table = (_lib.ResampleSegment * n).from_address(host.data_ptr())
+        packed = host[seg_bytes:].view(torch.float32).numpy()
+        off_in = off_out = 0
+        for b, (x, in_first, out_first, n_out) in enumerate(windows):
+            packed[off_in:off_in + x.size] = x
+            table[b] = _lib.ResampleSegment(off_in, int(in_first), int(x.size), off_out, int(out_first), int(n_out))
+            off_in += x.size
+            off_out += int(n_out)
+        with torch.cuda.device(self._device):
+            cur = torch.cuda.current_stream(self._device)
+            dev = host.to(self._device, non_blocking=True)
+            y = torch.empty(total_out, dtype=torch.float32, device=self._device)
+            _lib.check(self._lib.ppasr_resample_compute_batch(r, dev.data_ptr() + seg_bytes, dev.data_ptr(), n, max(outs_n),
+                                                              y.data_ptr(), cur.cuda_stream))
+            y = y.cpu().numpy()  # (synchronises: the pinned buffer and `dev` are free again)
+        return [y[o - k:o] for o, k in zip(np.cumsum(outs_n).tolist(), outs_n)]
 
     @property
     def feature_dim(self):
@@ -148,7 +232,9 @@ class AudioFeaturizer:
         """float32 mono samples in [-1, 1] (numpy or tensor) -> fbank [T, n_mels] (mfcc: [T, n_mfcc]) float32 DEVICE tensor."""
         from ppasr_amd import _lib
         sr = sample_rate or self._sr
-        if sr != self._sr:  # audio_featurizer.py:46-47: up / down-sample to the model's rate first (host side)
+        if sr != self._sr and self._resample == "device":  # the same step on the device: no host round trip
+            samples = self.resample_device(samples, sr)
+        elif sr != self._sr:  # audio_featurizer.py:46-47: up / down-sample to the model's rate first (host side)
             samples = resample(np.asarray(torch.as_tensor(samples).cpu(), np.float32).reshape(-1), sr, self._sr)
         h = self._handle()
         x = torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self._device).contiguous()
@@ -184,8 +270,8 @@ class AudioFeaturizer:
             self._scratch[key] = t
         return t
 
-    def featurize_many(self, waveforms, padded=False):
-        """A list of float32 mono waveforms at the featurizer's rate (numpy or tensor) -> their fbank features on the
+    def featurize_many(self, waveforms, padded=False, sample_rates=None):
+        """A list of float32 mono waveforms (numpy or tensor) -> their fbank features on the
         device, by ONE packed upload and ONE set of launches (``ppasr_fbank_compute_batch``: three with dB normalisation,
         one without, whatever the number of waveforms).  Every waveform's rows equal ``featurize_device`` on it alone,
         byte for byte.
@@ -193,18 +279,41 @@ class AudioFeaturizer:
           padded=True:  (feats [B, Tmax, n_mels], lens [B] int64 tensor) -- what ``get_encoder_out`` takes; the rows
                         past a waveform's frames are zero.
         A waveform shorter than one window has no frame.  ``self.last_gains`` holds the gains ([B] float32) afterwards
-        when dB normalisation is on.  (``feature_method='mfcc'``: read n_mfcc for n_mels.)"""
+        when dB normalisation is on.  (``feature_method='mfcc'``: read n_mfcc for n_mels.)
+        sample_rates: None = every waveform is at the featurizer's rate; one rate for all, or one per waveform.  A foreign
+        rate needs ``resample="device"`` (ValueError otherwise): the raw samples go up in the same packed upload and ONE
+        batched resample launch per distinct foreign rate writes the model-rate samples into the buffer the fbank launches
+        read.  With no foreign rate the call runs what it runs without the argument."""
         from ppasr_amd import _lib
-        h = self._handle()
-        lib, dev = self._lib, self._device
         wavs = [np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w, np.float32).reshape(-1) for w in waveforms]
         n = len(wavs)
-        counts = (ctypes.c_int * max(n, 1))(*[int(w.size) for w in wavs])
+        if sample_rates is None or np.ndim(sample_rates) == 0:
+            rates = [int(sample_rates or self._sr)] * n
+        else:
+            rates = [int(r or self._sr) for r in sample_rates]
+            if len(rates) != n:
+                raise ValueError(f"featurize_many: {len(rates)} sample rates for {n} waveforms")
+        foreign = [b for b in range(n) if rates[b] != int(self._sr)]
+        if foreign and self._resample != "device":
+            raise ValueError(f"featurize_many: waveforms at {sorted({rates[b] for b in foreign})} Hz for a featurizer at "
+                             f'{self._sr} Hz need AudioFeaturizer(resample="device")')
+        h = self._handle()
+        lib, dev = self._lib, self._device
+        by_rate = {}  # foreign rate -> its waveforms, in order
+        for b in foreign:
+            by_rate.setdefault(rates[b], []).append(b)
+        resamplers = {rate: self._resampler(rate)[0] for rate in by_rate}  # (refusals before anything is staged)
+        # samples at the featurizer's rate: a foreign waveform's are made on the device, behind the uploaded ones
+        sizes = [int(w.size) for w in wavs]
+        for b in foreign:
+            sizes[b] = int(lib.ppasr_resampler_out_len(rates[b], int(self._sr), int(wavs[b].size)))
+        counts = (ctypes.c_int * max(n, 1))(*sizes)
         win, shift = int(self._sr * 0.001 * 25.0), int(self._sr * 0.001 * 10.0)
-        frames = np.array([0 if w.size < win else 1 + (w.size - win) // shift for w in wavs], np.int64)
+        frames = np.array([0 if k < win else 1 + (k - win) // shift for k in sizes], np.int64)
         t_max = max(int(frames.max()) if n else 0, 1) if padded else 0
-        total = int(sum(w.size for w in wavs))
-        seg_bytes = ctypes.sizeof(_lib.FbankSegment) * n
+        total = int(sum(w.size for w in wavs))                 # uploaded samples
+        made = int(sum(sizes[b] for b in foreign))             # samples the resampler writes behind them
+        seg_bytes = ctypes.sizeof(_lib.FbankSegment) * n + ctypes.sizeof(_lib.ResampleSegment) * len(foreign)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
             # the pinned buffer: not before the upload that may still read it has finished
@@ -217,24 +326,47 @@ class AudioFeaturizer:
             chunks, n_frames = chunks.value, n_frames.value
             assert n_frames == int(frames.sum())
             packed = host[seg_bytes:seg_bytes + 4 * total].view(torch.float32).numpy()
-            off = 0
+            off, raw_at = 0, []
             for w in wavs:
                 packed[off:off + w.size] = w
+                raw_at.append(off)
                 off += w.size
+            if foreign:
+                # the fbank table's segments: where each waveform's model-rate samples are -- its uploaded samples, or
+                # its slot in the resampled region [total, total + made)
+                fb = (_lib.FbankSegment * n).from_address(host.data_ptr())
+                rs = (_lib.ResampleSegment * len(foreign)).from_address(host.data_ptr() + ctypes.sizeof(_lib.FbankSegment) * n)
+                at, k, launches = total, 0, []
+                for b in range(n):
+                    fb[b].first_sample = raw_at[b]
+                for rate, members in by_rate.items():
+                    launches.append((rate, k, len(members), max(sizes[b] for b in members)))
+                    for b in members:
+                        fb[b].first_sample = at
+                        rs[k] = _lib.ResampleSegment(raw_at[b], 0, int(wavs[b].size), at, 0, sizes[b])
+                        at += sizes[b]
+                        k += 1
             # the device buffers: a call queued on another stream may still read them
             if self._queued is not None:
                 cur.wait_event(self._queued)
-            stage = self._stage("stage", seg_bytes + 4 * total + 4)
+            stage = self._stage("stage", seg_bytes + 4 * (total + made) + 4)
             stage[:seg_bytes + 4 * total].copy_(host[:seg_bytes + 4 * total], non_blocking=True)
             self._uploaded = torch.cuda.Event()
             self._uploaded.record(cur)
+            samples_dev = stage.data_ptr() + seg_bytes
+            if foreign:
+                rs_dev = stage.data_ptr() + ctypes.sizeof(_lib.FbankSegment) * n
+                for rate, k, count, longest in launches:
+                    _lib.check(lib.ppasr_resample_compute_batch(resamplers[rate], samples_dev,
+                                                                rs_dev + ctypes.sizeof(_lib.ResampleSegment) * k, count,
+                                                                longest, samples_dev, cur.cuda_stream))
             ws = self._stage("ws", int(lib.ppasr_fbank_batch_workspace_bytes(n, chunks)))
             feats = (torch.empty(n, t_max, self.feature_dim, dtype=torch.float32, device=dev) if padded
                      else torch.empty(n_frames, self.feature_dim, dtype=torch.float32, device=dev))
             if padded:
                 feats.zero_()  # the padding rows; the kernel writes the others
             if n:
-                _lib.check(lib.ppasr_fbank_compute_batch(h, stage.data_ptr() + seg_bytes, stage.data_ptr(), n, chunks,
+                _lib.check(lib.ppasr_fbank_compute_batch(h, samples_dev, stage.data_ptr(), n, chunks,
                                                          n_frames, int(bool(self._use_db)), float(self._target_db),
                                                          feats.data_ptr() if feats.numel() else ws.data_ptr(),
                                                          ws.data_ptr(), ws.numel(), cur.cuda_stream))
@@ -247,6 +379,65 @@ class AudioFeaturizer:
                         check_gain_db(float(gains[b, 1]), self._target_db)
                 self.last_gains = gains[:, 0].copy()
         return (feats, torch.from_numpy(frames)) if padded else (feats, frames)
+
+
+class StreamResampler:
+    """One stream at `sample_rate`, packet by packet -> the same stream at the featurizer's rate, on the device resampler
+    (``AudioFeaturizer(resample="device")``).  The kernel is stateless and addressed by absolute stream position; this class
+    keeps, on the host, the raw tail the coming outputs still read and the two absolute counters.  Everything ``push``
+    returns followed by what ``flush`` returns equals ``resample_device`` of all the samples pushed, byte for byte,
+    wherever the packets were cut."""
+
+    def __init__(self, featurizer, sample_rate):
+        self._f = featurizer
+        self._rate = int(sample_rate)
+        featurizer._resampler(self._rate)  # (ValueError without resample="device"; the library's refusals)
+        self._lib = featurizer._lib
+        self._tail = np.zeros(0, np.float32)  # raw samples tail_first .. n_in - 1
+        self._tail_first = 0
+        self._n_in = 0    # raw samples pushed so far
+        self._n_out = 0   # outputs handed out so far
+        self._flushed = False
+
+    @property
+    def sample_rate(self):
+        return self._rate
+
+    def _prepare(self, samples, flush=False):
+        """-> (the window a launch needs: (held samples, their first absolute index, first output, outputs), the state
+        after it).  Changes nothing: ``_commit`` takes the state once the outputs exist."""
+        if self._flushed:
+            raise ValueError("StreamResampler: the stream was flushed; make a new one for new audio")
+        x = np.asarray(samples, np.float32).reshape(-1)
+        held = np.concatenate([self._tail, x]) if x.size else self._tail
+        n_in = self._n_in + int(x.size)
+        fr = int(self._f._sr)
+        done = int((self._lib.ppasr_resampler_out_len if flush else self._lib.ppasr_resampler_ready)(self._rate, fr, n_in))
+        assert done >= self._n_out
+        keep = min(int(self._lib.ppasr_resampler_first_needed(self._rate, fr, done)), n_in)  # the next output's first sample
+        keep = max(keep, self._tail_first)
+        state = (held[keep - self._tail_first:], keep, n_in, done, flush)
+        return (held, self._tail_first, self._n_out, done - self._n_out), state
+
+    def _commit(self, state):
+        self._tail, self._tail_first, self._n_in, self._n_out, self._flushed = state
+
+    def push(self, samples):
+        """raw samples -> the model-rate samples that are complete now (numpy float32; possibly none)"""
+        window, state = self._prepare(samples)
+        out = self._f._resample_windows(self._rate, [window])[0]
+        self._commit(state)
+        return out
+
+    def flush(self):
+        """End of the stream: the remaining outputs up to ceil(n up / down) of everything pushed, with zeros for the samples
+        that never came.  The stream takes no more audio afterwards."""
+        if self._flushed:
+            return np.zeros(0, np.float32)
+        window, state = self._prepare(np.zeros(0, np.float32), flush=True)
+        out = self._f._resample_windows(self._rate, [window])[0]
+        self._commit(state)
+        return out
 
 
 class TextFeaturizer:

@@ -12,7 +12,7 @@ no host synchronisation in between."""
 import numpy as np
 import torch
 
-from ppasr_amd.data_utils.featurizer import AudioFeaturizer, db_gain, pcm_bytes_to_float
+from ppasr_amd.data_utils.featurizer import AudioFeaturizer, StreamResampler, db_gain, pcm_bytes_to_float
 from ppasr_amd.model_utils.conformer.model import make_stream_group
 
 __all__ = ["StreamPool"]
@@ -31,6 +31,8 @@ class _Session:
         self.frame_ids = []    # argmax index of every output frame so far
         self.frame_probs = []  # max prob of the non-blank frames
         self.result = None
+        self.sample_rate = None  # fixed by the session's first packet
+        self.resampler = None    # StreamResampler of a session whose rate is not the featurizer's
 
 
 class StreamPool:
@@ -78,11 +80,37 @@ class StreamPool:
             self.beam = BeamSearchSessions(n_sessions, vocab_list=self.vocab, blank_id=blank_index,
                                            compact=bool(beam_compact), **{**_BEAM_DEFAULTS, **conf})
 
-    def feed(self, session, audio_data, channels=1, samp_width=2):
-        """Append PCM bytes or float samples to a session's buffer (what predict_stream does with each packet)."""
+    def _rate_of(self, session, sample_rate):
+        """The rate of a packet for `session` (None = the featurizer's) -> (rate, the session's resampler or None: a new
+        one is returned, not stored).  ValueError, before anything is modified: a rate other than the one the session's
+        first packet fixed; a foreign rate without ``resample="device"`` in preprocess_conf."""
+        s = self.sessions[session]
+        model_rate = int(self.featurizer._sr)
+        rate = model_rate if sample_rate is None else int(sample_rate)
+        if s.sample_rate is not None and rate != s.sample_rate:
+            raise ValueError(f"StreamPool: session {session} is fed at {s.sample_rate} Hz, not {rate} Hz: a session's rate is "
+                             "fixed by its first packet (reset it for a new stream)")
+        if rate == model_rate:
+            return rate, None
+        if self.featurizer.resample_mode != "device":
+            raise ValueError(f"StreamPool: packets at {rate} Hz for a model at {model_rate} Hz need resample=\"device\" in "
+                             "preprocess_conf (AudioFeaturizer(resample=\"device\")): a pool does not resample on the host")
+        return rate, s.resampler if s.resampler is not None else StreamResampler(self.featurizer, rate)
+
+    def feed(self, session, audio_data, channels=1, samp_width=2, sample_rate=None):
+        """Append PCM bytes or float samples to a session's buffer (what predict_stream does with each packet).
+        sample_rate: the packet's rate, None = the featurizer's.  A foreign rate (``resample="device"``) goes through the
+        session's ``StreamResampler`` first; the model-rate samples that are complete then take the path below."""
+        rate, resampler = self._rate_of(session, sample_rate)
         s = self.sessions[session]
         samples = (pcm_bytes_to_float(audio_data, channels, samp_width) if isinstance(audio_data, (bytes, bytearray))
                    else np.asarray(audio_data, np.float32).reshape(-1))
+        if resampler is not None:
+            samples = resampler.push(samples)
+        s.sample_rate, s.resampler = rate, resampler
+        self._feed_model_rate(s, samples)
+
+    def _feed_model_rate(self, s, samples):
         s.remained_wav = samples if s.remained_wav is None else np.concatenate([s.remained_wav, samples])
         feat = self.featurizer.featurize(s.remained_wav)
         # predict_stream's buffered samples are normalised IN PLACE by the reference's featurize() (ppasr_amd/predict.py
@@ -105,8 +133,10 @@ class StreamPool:
         dev = self.featurizer._device
         return torch.cat([torch.as_tensor(cached).to(dev), torch.as_tensor(feat).to(dev)], dim=1)
 
-    def feed_many(self, packets, channels=1, samp_width=2):
-        """``feed`` for many sessions at once: packets = {session: PCM bytes or float samples}.  The listed sessions'
+    def feed_many(self, packets, channels=1, samp_width=2, sample_rate=None):
+        """``feed`` for many sessions at once: packets = {session: PCM bytes or float samples}.  sample_rate: one rate for
+        all packets or {session: rate} (a session not listed: the featurizer's); the packets of one foreign rate are
+        resampled by one batched launch, then everything takes the path below.  The listed sessions'
         buffers go to the device in one upload and are featurized by one set of launches
         (``AudioFeaturizer.featurize_many``); their features stay on the device (``cached_feat`` becomes a device tensor,
         ``step`` / ``finish`` cut the windows there).  Every session ends up exactly where ``feed`` would leave it.  An
@@ -115,13 +145,27 @@ class StreamPool:
         audio = list(packets.values()) if hasattr(packets, "values") else [p[1] for p in packets]
         if len(set(ids)) != len(ids) or any(i < 0 or i >= len(self.sessions) for i in ids):
             raise ValueError(f"StreamPool.feed_many: session indices must be distinct and in 0..{len(self.sessions) - 1}")
+        rates = [self._rate_of(i, sample_rate.get(i) if isinstance(sample_rate, dict) else sample_rate) for i in ids]
+        new = [(pcm_bytes_to_float(a, channels, samp_width) if isinstance(a, (bytes, bytearray))
+                else np.asarray(a, np.float32).reshape(-1)) for a in audio]
+        by_rate = {}  # foreign rate -> positions in `ids`
+        for k, (rate, resampler) in enumerate(rates):
+            if resampler is not None:
+                by_rate.setdefault(rate, []).append(k)
+        states = {}
+        for rate, members in by_rate.items():
+            jobs = [rates[k][1]._prepare(new[k]) for k in members]
+            for k, job, out in zip(members, jobs, self.featurizer._resample_windows(rate, [j[0] for j in jobs])):
+                new[k], states[k] = out, job[1]
         wavs = []
-        for i, a in zip(ids, audio):
+        for i, samples in zip(ids, new):
             s = self.sessions[i]
-            samples = (pcm_bytes_to_float(a, channels, samp_width) if isinstance(a, (bytes, bytearray))
-                       else np.asarray(a, np.float32).reshape(-1))
             wavs.append(samples if s.remained_wav is None else np.concatenate([s.remained_wav, samples]))
         feats, counts = self.featurizer.featurize_many(wavs)
+        for k, i in enumerate(ids):  # nothing raises from here on: the sessions take their new state
+            self.sessions[i].sample_rate, self.sessions[i].resampler = rates[k]
+            if k in states:
+                rates[k][1]._commit(states[k])
         # (the remainder's gain: on the host, as in feed)
         if self.featurizer.use_db_normalization:
             wavs = [w * db_gain(w, self.featurizer.target_db) if w.size else w for w in wavs]
@@ -180,9 +224,14 @@ class StreamPool:
         """End of a session's audio (``predict_stream(..., is_end=True)``, predict.py:291-298): run the buffered full
         windows, then the last, shorter window if at least 7 frames (the conv front-end's context) are left.
         -> the session's final result dict (None if it never produced output).  The session keeps its state until
-        ``reset``."""
-        self.step()
+        ``reset``.  A session fed at a foreign rate flushes its resampler first: the last model-rate samples, which waited
+        for audio that will not come, are fed like a packet."""
         s = self.sessions[session]
+        if s.resampler is not None:
+            rest = s.resampler.flush()
+            if rest.size:
+                self._feed_model_rate(s, rest)
+        self.step()
         if s.cached_feat is not None and s.cached_feat.shape[1] >= _CONTEXT:
             s.result = self._advance([session], s.cached_feat)[0]
             s.cached_feat = s.cached_feat[:, s.cached_feat.shape[1] - _KEEP:]
