@@ -85,6 +85,14 @@ def _rows(lens_out, B, T):
     return [min(int(n), T) for n in (lens_out.cpu().numpy() if isinstance(lens_out, torch.Tensor) else lens_out)]
 
 
+def rel(a, b):
+    """max |a - b| / max |b| in float64 over two arrays of EQUAL shape: a comparison that would go through a broadcast
+    (a [1, c, V] tensor against a [c, V] one) is an error of the test, not a pass."""
+    a, b = _np64(a), _np64(b)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
 def utt_rel(got, ref, lens_out=None):
     """Worst utterance of max |got - ref| / max |ref| over that utterance's rows ([B, T, ...]; lens_out: valid rows per
     utterance, None = all T).  Per utterance, so that a short low-magnitude utterance cannot hide behind a long one."""

@@ -12,17 +12,11 @@ import torch
 from oracle.conformer_oracle import ConformerOracle
 from oracle.ctc_decoders_oracle import greedy_tokens
 from ppasr_amd.utils.synth import conformer_state_dict, synth_features
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 
 TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _model(sd, V, L):
@@ -62,20 +56,20 @@ def test_stage_taps_match_oracle(B, T, lens):
         return out
 
     errs = {}
-    errs["x0"] = _rel(take(M * 256, (B, Tp, 256)), layers[0].numpy())
+    errs["x0"] = rel(take(M * 256, (B, Tp, 256)), layers[0].numpy())
     for i in range(L):
         p = f"encoder.encoders.{i}"
-        errs[f"L{i}.x1"] = _rel(take(M * 256, (B, Tp, 256)), tr[p + ".x1"].numpy())
+        errs[f"L{i}.x1"] = rel(take(M * 256, (B, Tp, 256)), tr[p + ".x1"].numpy())
         qkv = take(M * 768, (B, Tp, 768))
-        errs[f"L{i}.q"] = _rel(qkv[..., :256], tr[p + ".self_attn.q"].numpy())
-        errs[f"L{i}.k"] = _rel(qkv[..., 256:512], tr[p + ".self_attn.k"].numpy())
-        errs[f"L{i}.v"] = _rel(qkv[..., 512:], tr[p + ".self_attn.v"].numpy())
-        errs[f"L{i}.ctx"] = _rel(take(M * 256, (B, Tp, 256)), tr[p + ".self_attn.ctx"].numpy())
-        errs[f"L{i}.x2"] = _rel(take(M * 256, (B, Tp, 256)), tr[p + ".x2"].numpy())
-        errs[f"L{i}.glu"] = _rel(take(M * 256, (B, Tp, 256)), tr[p + ".conv_module.glu"][:, 14:, :].numpy())
-        errs[f"L{i}.out"] = _rel(take(M * 256, (B, Tp, 256)), layers[i + 1].numpy())
-    errs["logits"] = _rel(logits.cpu().numpy(), ref_logits.numpy())
-    errs["probs"] = _rel(probs.cpu().numpy(), ref_probs.numpy())
+        errs[f"L{i}.q"] = rel(qkv[..., :256], tr[p + ".self_attn.q"].numpy())
+        errs[f"L{i}.k"] = rel(qkv[..., 256:512], tr[p + ".self_attn.k"].numpy())
+        errs[f"L{i}.v"] = rel(qkv[..., 512:], tr[p + ".self_attn.v"].numpy())
+        errs[f"L{i}.ctx"] = rel(take(M * 256, (B, Tp, 256)), tr[p + ".self_attn.ctx"].numpy())
+        errs[f"L{i}.x2"] = rel(take(M * 256, (B, Tp, 256)), tr[p + ".x2"].numpy())
+        errs[f"L{i}.glu"] = rel(take(M * 256, (B, Tp, 256)), tr[p + ".conv_module.glu"][:, 14:, :].numpy())
+        errs[f"L{i}.out"] = rel(take(M * 256, (B, Tp, 256)), layers[i + 1].numpy())
+    errs["logits"] = rel(logits.cpu().numpy(), ref_logits.numpy())
+    errs["probs"] = rel(probs.cpu().numpy(), ref_probs.numpy())
     print({k: f"{v:.2e}" for k, v in errs.items()})
     bad = {k: v for k, v in errs.items() if not v < TOL}
     assert not bad, bad

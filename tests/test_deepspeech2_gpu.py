@@ -5,16 +5,10 @@ import torch
 
 from oracle.deepspeech2_oracle import DeepSpeech2Oracle
 from ppasr_amd.utils.synth import deepspeech2_state_dict, synth_features
-from numerics import F32_BUDGET_DS2
+from numerics import F32_BUDGET_DS2, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET_DS2  # fp32 error budget of the recurrences (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _model(sd, V, L, streaming):
@@ -33,8 +27,8 @@ def test_deepspeech2_matches_oracle(streaming):
     torch.cuda.synchronize()
     rp, rl, rh, rc = DeepSpeech2Oracle(sd, L, 1024, streaming).forward(x, lens)
     assert out_lens.cpu().tolist() == rl.tolist()
-    assert _rel(probs.cpu().numpy(), rp.numpy()) < TOL
-    assert _rel(fh.cpu().numpy(), rh.numpy()) < TOL and _rel(fc.cpu().numpy(), rc.numpy()) < TOL
+    assert rel(probs.cpu().numpy(), rp.numpy()) < TOL
+    assert rel(fh.cpu().numpy(), rh.numpy()) < TOL and rel(fc.cpu().numpy(), rc.numpy()) < TOL
 
 
 def test_deepspeech2_streaming_state_carry():
@@ -51,7 +45,7 @@ def test_deepspeech2_streaming_state_carry():
         lens = np.array([67])
         probs, _, h, c = model.get_encoder_out_chunk(chunk, lens, h, c)
         rp, _, rh, rc = oracle.forward(chunk, lens, rh, rc)
-        assert _rel(probs.cpu().numpy(), rp.numpy()) < TOL
+        assert rel(probs.cpu().numpy(), rp.numpy()) < TOL
 
 
 def test_deepspeech2_config1_shape():
@@ -64,7 +58,7 @@ def test_deepspeech2_config1_shape():
     probs = model.get_encoder_out(x, lens)
     assert tuple(probs.shape) == (1, 123, V)
     rp, _, _, _ = DeepSpeech2Oracle(sd, L, 1024, False).forward(x, lens)
-    assert _rel(probs.cpu().numpy(), rp.numpy()) < TOL
+    assert rel(probs.cpu().numpy(), rp.numpy()) < TOL
     tokens, n, score, _, _ = greedy_decode_ids(probs)
     ref = rp[0].numpy().argmax(1)
     keep = np.r_[True, ref[1:] != ref[:-1]]
@@ -89,8 +83,8 @@ def test_deepspeech2_streaming_batch_wavefront_with_state_carry():
         rp, rl, rh, rc = oracle.forward(chunk, la, rh, rc)
         torch.cuda.synchronize()
         assert ol.cpu().tolist() == rl.tolist()
-        assert _rel(probs.cpu().numpy(), rp.numpy()) < TOL
-        assert _rel(h.cpu().numpy(), rh.numpy()) < TOL and _rel(c.cpu().numpy(), rc.numpy()) < TOL
+        assert rel(probs.cpu().numpy(), rp.numpy()) < TOL
+        assert rel(h.cpu().numpy(), rh.numpy()) < TOL and rel(c.cpu().numpy(), rc.numpy()) < TOL
 
 
 @pytest.mark.parametrize("streaming,gru,B", [(True, False, 6), (False, False, 1), (True, True, 3), (False, True, 2)])
@@ -110,10 +104,10 @@ def test_deepspeech2_rnn_size_2048(streaming, gru, B):
     torch.cuda.synchronize()
     rp, rl, rh, rc = DeepSpeech2Oracle(sd, L, H, streaming, use_gru=gru).forward(x, lens)
     assert out_lens.cpu().tolist() == rl.tolist()
-    e = _rel(probs.cpu().numpy(), rp.numpy())
+    e = rel(probs.cpu().numpy(), rp.numpy())
     print(f"H=2048 streaming={streaming} gru={gru} B={B}: probs {e:.2e}")
     assert e < TOL
-    assert _rel(fh.cpu().numpy(), rh.numpy()) < TOL
+    assert rel(fh.cpu().numpy(), rh.numpy()) < TOL
 
 
 @pytest.mark.parametrize("gru,B", [(False, 40), (False, 70), (True, 6), (True, 45), (True, 100)])
@@ -140,12 +134,12 @@ def test_deepspeech2_wavefront_row_tiles_and_gru(gru, B):
         rp, rl, rh, rc = oracle.forward(chunk, la, rh, rc)
         torch.cuda.synchronize()
         assert ol.cpu().tolist() == rl.tolist()
-        e = _rel(probs.cpu().numpy(), rp.numpy())
+        e = rel(probs.cpu().numpy(), rp.numpy())
         print(f"gru={gru} B={B}: probs {e:.2e}")
         assert e < TOL
-        assert _rel(h.cpu().numpy(), rh.numpy()) < TOL
+        assert rel(h.cpu().numpy(), rh.numpy()) < TOL
         if not gru:
-            assert _rel(c.cpu().numpy(), rc.numpy()) < TOL
+            assert rel(c.cpu().numpy(), rc.numpy()) < TOL
 
 
 class _persist:
@@ -190,10 +184,10 @@ def test_single_utterance_persistent_recurrence_equals_per_step_route(streaming,
     rp, rl, rh, rc = DeepSpeech2Oracle(sd, L, 1024, streaming).forward(x, lens, torch.from_numpy(h0), torch.from_numpy(c0))
     for got in outs:
         assert got[1].tolist() == rl.tolist()
-        assert _rel(got[0], rp.numpy()) < TOL and _rel(got[2], rh.numpy()) < TOL and _rel(got[3], rc.numpy()) < TOL
-    e = _rel(outs[0][0], outs[1][0])
-    print(f"persistent vs per-step: probs {e:.2e} h {_rel(outs[0][2], outs[1][2]):.2e} c {_rel(outs[0][3], outs[1][3]):.2e}")
-    assert e < 2e-5 and _rel(outs[0][2], outs[1][2]) < 2e-5 and _rel(outs[0][3], outs[1][3]) < 2e-5
+        assert rel(got[0], rp.numpy()) < TOL and rel(got[2], rh.numpy()) < TOL and rel(got[3], rc.numpy()) < TOL
+    e = rel(outs[0][0], outs[1][0])
+    print(f"persistent vs per-step: probs {e:.2e} h {rel(outs[0][2], outs[1][2]):.2e} c {rel(outs[0][3], outs[1][3]):.2e}")
+    assert e < 2e-5 and rel(outs[0][2], outs[1][2]) < 2e-5 and rel(outs[0][3], outs[1][3]) < 2e-5
     assert model._h is not None
 
 
@@ -222,11 +216,11 @@ def test_single_utterance_gru_persistent_recurrence_equals_per_step_route(stream
     rp, rl, rh, _ = DeepSpeech2Oracle(sd, L, 1024, streaming, use_gru=True).forward(x, lens, torch.from_numpy(h0), torch.from_numpy(c0))
     for got in outs:
         assert got[1].tolist() == rl.tolist()
-        assert _rel(got[0], rp.numpy()) < TOL and _rel(got[2], rh.numpy()) < TOL
+        assert rel(got[0], rp.numpy()) < TOL and rel(got[2], rh.numpy()) < TOL
         assert np.array_equal(got[3], c0)  # handed through
-    e = _rel(outs[0][0], outs[1][0])
-    print(f"GRU persistent vs per-step: probs {e:.2e} h {_rel(outs[0][2], outs[1][2]):.2e}")
-    assert e < 2e-5 and _rel(outs[0][2], outs[1][2]) < 2e-5
+    e = rel(outs[0][0], outs[1][0])
+    print(f"GRU persistent vs per-step: probs {e:.2e} h {rel(outs[0][2], outs[1][2]):.2e}")
+    assert e < 2e-5 and rel(outs[0][2], outs[1][2]) < 2e-5
 
 
 @pytest.mark.parametrize("gru", [False, True])
@@ -260,6 +254,6 @@ def test_persistent_recurrence_gives_up_when_the_chip_is_partly_held(gru):
         side.synchronize()
         after = model.get_encoder_out_chunk(x, lens)[0].cpu().numpy()  # inside the hold period: per-step kernels
     print(f"give-up path ({'GRU' if gru else 'LSTM'}): call took {dt * 1e3:.0f} ms with 224 CUs held")
-    assert _rel(free, want) < 2e-5
+    assert rel(free, want) < 2e-5
     assert np.array_equal(held, want), "the give-up path must return the per-step route's result"
     assert np.array_equal(after, want)

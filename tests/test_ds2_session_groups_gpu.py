@@ -12,9 +12,10 @@ import pytest
 import torch
 
 import ref_cases as rc
-from numerics import F32_BUDGET_DS2, oracle64
+from numerics import F32_BUDGET_DS2, oracle64, rel
 from ppasr_amd import _lib
 from ppasr_amd.utils.synth import deepspeech2_state_dict, synth_features, synth_vocabulary
+from session_groups import predict_stream_reference, status_of
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -37,21 +38,6 @@ def _group(model, n):
 
 def _feats(n, T, seed):
     return torch.from_numpy(synth_features(n, T, seed=seed)[0]).cuda()
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def _status(fn):
-    try:
-        fn()
-    except _lib.PPASRHipError as e:
-        return e.status
-    return _lib.PPASR_OK
 
 
 def _check_frames(fa, fp, probs):
@@ -86,7 +72,7 @@ def test_reference_source_three_sessions(name):
             outs[s].append(probs[k].cpu().numpy())
     assert counts == ref[f"{name}/chunk/n"].tolist()
     got = np.stack([np.concatenate(o, 0) for o in outs])
-    e_p = _rel(got, ref[f"{name}/chunk/probs"])
+    e_p = rel(got, ref[f"{name}/chunk/probs"])
     assert e_p < F32_BUDGET_DS2, e_p
     assert [group.offset(s) for s in range(3)] == [sum(counts)] * 3
     nxt = _feats(3, WINDOW, seed=77)
@@ -94,7 +80,7 @@ def test_reference_source_three_sessions(name):
     h = torch.from_numpy(ref[f"{name}/chunk/h"]).cuda()
     c = torch.from_numpy(ref[f"{name}/chunk/c"]).cuda()
     p_ref, _, _, _ = model.get_encoder_out_chunk(nxt, np.full(3, WINDOW, np.int64), h, c)
-    e_s = _rel(p_group.cpu().numpy(), p_ref.cpu().numpy())
+    e_s = rel(p_group.cpu().numpy(), p_ref.cpu().numpy())
     print(f"{name} ({'GRU' if gru else 'LSTM'}): probs {e_p:.2e}, next window from the final states {e_s:.2e}")
     assert e_s < F32_BUDGET_DS2
 
@@ -152,7 +138,7 @@ def test_staggered_subsets_against_the_float64_oracle(gru):
         for k, s in enumerate(act):
             rp, rl, rh, rc_ = oracle.forward(x[k:k + 1].cpu().double(), np.array([T]), *state[s])
             state[s] = (rh, rc_)
-            e = _rel(probs[k].cpu().numpy(), rp[0].numpy())
+            e = rel(probs[k].cpu().numpy(), rp[0].numpy())
             worst = max(worst, e)
             assert e < F32_BUDGET_DS2, (r, s, e)
             frames[s] += int(rl[0])
@@ -175,7 +161,7 @@ def test_reset_and_refusals():
         for k, s in enumerate(act):
             rp, _, rh, rc_ = oracle.forward(x[k:k + 1].cpu().double(), np.array([T]), *state[s])
             state[s] = (rh, rc_)
-            assert _rel(probs[k].cpu().numpy(), rp[0].numpy()) < F32_BUDGET_DS2, s
+            assert rel(probs[k].cpu().numpy(), rp[0].numpy()) < F32_BUDGET_DS2, s
 
     advance([0, 1, 2], WINDOW, 902)
     # reset(1): session 1 starts again from zero state, the others go on
@@ -193,9 +179,9 @@ def test_reset_and_refusals():
     assert lib.ppasr_ds2_stream_group_create(model._h, 0, 0, ctypes.byref(g)) == _lib.PPASR_EINVAL and not g.value
     # refused rounds change no session
     x2 = _feats(2, WINDOW, seed=905)
-    assert _status(lambda: group.encode_chunks([0, 0], x2)) == _lib.PPASR_EINVAL
-    assert _status(lambda: group.encode_chunks([0, 3], x2)) == _lib.PPASR_EINVAL
-    assert _status(lambda: group.encode_chunks([-1, 1], x2)) == _lib.PPASR_EINVAL
+    assert status_of(lambda: group.encode_chunks([0, 0], x2)) == _lib.PPASR_EINVAL
+    assert status_of(lambda: group.encode_chunks([0, 3], x2)) == _lib.PPASR_EINVAL
+    assert status_of(lambda: group.encode_chunks([-1, 1], x2)) == _lib.PPASR_EINVAL
     x6 = _feats(2, 6, seed=906)
     ids = (ctypes.c_int * 2)(0, 1)
     ws = torch.empty(int(lib.ppasr_group_chunk_workspace_bytes(model._h, 2, WINDOW)), dtype=torch.uint8, device="cuda")
@@ -223,7 +209,6 @@ def test_stream_pool_equals_predict_stream(tmp_path, decoder, scorer):
     from lm_util import write_synthetic_arpa
     from test_predictor_gpu import _audio, _cfg
     from ppasr_amd.model_utils.deepspeech2.model import DeepSpeech2StreamGroup
-    from ppasr_amd.predict import PPASRPredictor
     from ppasr_amd.serving import StreamPool
     V = 300
     vocab = synth_vocabulary(V)
@@ -232,19 +217,9 @@ def test_stream_pool_equals_predict_stream(tmp_path, decoder, scorer):
     conf = cfg["ctc_beam_search_decoder_conf"]
     if scorer:
         conf["language_model_path"] = write_synthetic_arpa(str(tmp_path / "lm.arpa"), vocab[2:150], order=3, seed=6)
-    p = PPASRPredictor(configs=cfg, state_dict=sd, vocab_list=vocab, warmup=False)
     n = 3
-    wavs = [_audio(2.4, seed=21), _audio(1.93, seed=22), _audio(3.1, seed=23)]
-    pcms = [(np.clip(w, -1, 1) * 32767).astype(np.int16).tobytes() for w in wavs]
+    p, pcms, want = predict_stream_reference(cfg, sd, vocab, [_audio(2.4, seed=21), _audio(1.93, seed=22), _audio(3.1, seed=23)])
     step = 16000  # 0.5 s packets
-    want = []
-    for pcm in pcms:
-        p.reset_stream()
-        out = None
-        for i in range(0, len(pcm), step):
-            out = p.predict_stream(audio_data=pcm[i:i + step], is_end=(i + step >= len(pcm))) or out
-        want.append(out)
-    p.reset_stream()
     model = p.predictor.model
     kw = dict(decoder="ctc_beam_search", decoder_conf=dict(conf)) if decoder == "ctc_beam_search" else {}
     pool = StreamPool(model, vocab, n_sessions=n, preprocess_conf=cfg["preprocess_conf"], **kw)

@@ -7,16 +7,10 @@ import torch
 from oracle.conformer_oracle import ConformerOracle
 from oracle.ctc_decoders_oracle import greedy_tokens
 from ppasr_amd.utils.synth import conformer_state_dict, synth_features
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _model(sd, V, L):
@@ -42,7 +36,7 @@ def test_ragged_and_extreme_lengths_match_oracle(B, T, lens):
     ref_probs, ref_logits = ConformerOracle(sd, num_blocks=L).get_encoder_out(x, lens, return_logits=True)
     assert tuple(probs.shape) == tuple(ref_probs.shape)
     assert torch.isfinite(probs).all()
-    assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
+    assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
 
 
 def test_too_short_input_is_refused():
@@ -114,7 +108,7 @@ def test_maximum_length_and_one_past_it():
     probs, logits = model.get_encoder_out(x, lens, return_logits=True)
     torch.cuda.synchronize()
     ref_probs, ref_logits = ConformerOracle(sd, num_blocks=L).get_encoder_out(x, lens, return_logits=True)
-    assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
+    assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
     tokens, n_tokens, _ = model.encode_greedy(x, lens)
     ids, _, _ = greedy_tokens(ref_probs[0].numpy())
     assert np.array_equal(ids, tokens[0, : int(n_tokens[0])].cpu().numpy())
@@ -147,14 +141,14 @@ def test_wider_front_ends_edges(input_layer, t_min, rate):
         ref_probs, ref_logits = oracle.get_encoder_out(x, la, return_logits=True)
         torch.cuda.synchronize()
         assert tuple(probs.shape) == tuple(ref_probs.shape)
-        assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
+        assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
         nv = model.valid_out_frames(la, T).cpu().numpy()
         assert list(nv) == [min(probs.shape[1], (ln + rate - 1) // rate) for ln in lens]
     x, _ = synth_features(1, 67, seed=3)
     p, att, cnn = model.get_encoder_out_chunk(x, 0, -1)
     ref_p, _, _ = oracle.get_encoder_out_chunk(x, 0, -1)
     assert tuple(p.shape) == tuple(ref_p.shape) == (1, model.out_frames(67), V)
-    assert _rel(p.cpu().numpy(), ref_p.numpy()) < TOL
+    assert rel(p.cpu().numpy(), ref_p.numpy()) < TOL
 
 
 @pytest.mark.parametrize("streaming,norm", [(True, "layer_norm"), (False, "batch_norm")])
@@ -178,7 +172,7 @@ def test_generic_width_512_with_8_heads(streaming, norm):
         tokens, n, _ = model.encode_greedy(x, la)
         torch.cuda.synchronize()
         assert torch.isfinite(probs).all()
-        assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
+        assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
         for b in range(B):
             ids, _, _ = greedy_tokens(ref_probs[b].numpy())
             assert np.array_equal(ids, tokens[b, :int(n[b])].cpu().numpy()), b
@@ -190,9 +184,9 @@ def test_generic_width_512_with_8_heads(streaming, norm):
             p, att, cnn = model.get_encoder_out_chunk(x[:, a:b], off, 20, att, cnn)
             rp, r_att, r_cnn = oracle.get_encoder_out_chunk(x[:, a:b], off, 20, r_att, r_cnn)
             off += p.shape[1]
-            assert _rel(p.cpu().numpy(), rp.numpy()) < TOL
+            assert rel(p.cpu().numpy(), rp.numpy()) < TOL
         assert tuple(att.shape) == tuple(r_att.shape) == (L, 8, 20, 128)
-        assert _rel(att.cpu().numpy(), r_att.numpy()) < TOL and _rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
+        assert rel(att.cpu().numpy(), r_att.numpy()) < TOL and rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
         with pytest.raises(_lib.PPASRHipError):  # session groups stay on the fused route
             from ppasr_amd.model_utils.conformer.model import ConformerStreamGroup
             ConformerStreamGroup(model, 2)

@@ -6,16 +6,10 @@ import torch
 from oracle.ctc_decoders_oracle import greedy_tokens
 from oracle.efficient_conformer_oracle import EfficientConformerOracle
 from ppasr_amd.utils.synth import efficient_conformer_state_dict, synth_features
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _model(sd, V, L, stride_idx, groups):
@@ -45,7 +39,7 @@ def test_efficient_conformer_matches_oracle(B, T, lens, L, stride_idx, groups):
     oracle = EfficientConformerOracle(sd, num_blocks=L, stride_layer_idx=stride_idx, group_layer_idx=groups)
     ref_probs, ref_logits = oracle.get_encoder_out(x, lens, return_logits=True)
     assert tuple(logits.shape) == tuple(ref_logits.shape)
-    e = _rel(logits.cpu().numpy(), ref_logits.numpy())
+    e = rel(logits.cpu().numpy(), ref_logits.numpy())
     print("logits", e)
     assert e < TOL
     tokens, n_tokens, score = model.encode_greedy(x, lens)
@@ -64,7 +58,7 @@ def test_efficient_conformer_full_config_beam_search():
     probs, logits = model.get_encoder_out(x, lens, return_logits=True)
     ref_probs, ref_logits = EfficientConformerOracle(sd, num_blocks=L).get_encoder_out(x, lens, return_logits=True)
     assert probs.shape[1] == 63  # T'=125 -> ceil(125/2)
-    assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
+    assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
     tokens, ln, sc, _ = beam_search_ids(probs, 10, 0.99, 40, 0)
     assert int(ln[0, 0]) > 0
 
@@ -90,10 +84,10 @@ def test_efficient_conformer_non_streaming_matches_oracle(B, T, lens, route):
     ref_probs, ref_logits = oracle.get_encoder_out(x, la, return_logits=True)
     torch.cuda.synchronize()
     assert tuple(logits.shape) == tuple(ref_logits.shape)
-    assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
+    assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
     # the non-causal modules must actually differ from the causal ones
     causal = EfficientConformerOracle(sd, num_blocks=L, stride_layer_idx=1, group_layer_idx=(0, 1)).get_encoder_out(
         x, la, return_logits=True)[1]
-    assert _rel(causal.numpy(), ref_logits.numpy()) > 1e-2
+    assert rel(causal.numpy(), ref_logits.numpy()) > 1e-2
     with pytest.raises(Exception):
         model.new_stream()  # forward_chunk needs the causal module

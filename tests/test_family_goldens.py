@@ -8,19 +8,13 @@ import os
 import numpy as np
 import pytest
 import torch
-from numerics import F32_BUDGET, F32_BUDGET_DS2
+from numerics import F32_BUDGET, F32_BUDGET_DS2, rel
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "family_oracle_golden.npz")
 _spec = importlib.util.spec_from_file_location("make_family_goldens", os.path.join(HERE, "golden", "make_family_goldens.py"))
 mk = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(mk)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def test_oracles_reproduce_the_committed_fixtures():
@@ -33,7 +27,7 @@ def test_oracles_reproduce_the_committed_fixtures():
         elif k.endswith("_score"):
             assert abs(float(got[k]) - float(g[k])) <= 1e-6 * max(1.0, abs(float(g[k]))), k
         else:
-            assert _rel(got[k], g[k]) < 1e-4, k
+            assert rel(got[k], g[k]) < 1e-4, k
 
 
 @pytest.mark.gpu
@@ -45,12 +39,12 @@ def test_squeezeformer_and_efficient_conformer_match_fixtures():
     for mode in (-1, 0):
         m.set_ffn_split(mode)
         _, lg = m.get_encoder_out(c["sq_x"], c["sq_lens"], return_logits=True)
-        assert _rel(lg.cpu().numpy(), g["sq_logits"]) < F32_BUDGET, mode
+        assert rel(lg.cpu().numpy(), g["sq_logits"]) < F32_BUDGET, mode
     m = EfficientConformerModel(80, 53, streaming=True, encoder_conf=c["eff_conf"], state_dict=c["eff_sd"], device="cuda:0")
     for mode in (-1, 0):
         m.set_ffn_split(mode)
         _, lg = m.get_encoder_out(c["eff_x"], c["eff_lens"], return_logits=True)
-        assert _rel(lg.cpu().numpy(), g["eff_logits"]) < F32_BUDGET, mode
+        assert rel(lg.cpu().numpy(), g["eff_logits"]) < F32_BUDGET, mode
 
 
 @pytest.mark.gpu
@@ -62,8 +56,8 @@ def test_deepspeech2_matches_fixtures(key, streaming):
                          state_dict=c[key + "_sd"], device="cuda:0")
     probs, lens, h, _ = m.get_encoder_out_chunk(c[key + "_x"], c[key + "_lens"])
     assert lens.cpu().tolist() == g[key + "_lens"].tolist()
-    assert _rel(probs.cpu().numpy(), g[key + "_probs"]) < F32_BUDGET_DS2
-    assert _rel(h.cpu().numpy(), g[key + "_h"]) < F32_BUDGET_DS2
+    assert rel(probs.cpu().numpy(), g[key + "_probs"]) < F32_BUDGET_DS2
+    assert rel(h.cpu().numpy(), g[key + "_h"]) < F32_BUDGET_DS2
 
 
 @pytest.mark.gpu

@@ -9,16 +9,10 @@ import torch
 from oracle.ctc_decoders_oracle import greedy_tokens
 from ppasr_amd.utils.synth import (conformer_state_dict, efficient_conformer_state_dict, squeezeformer_state_dict,
                                    synth_features)
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _conformer(streaming):
@@ -68,14 +62,14 @@ def test_every_split_mode_matches_the_oracle(family, lens):
         probs, logits = model.get_encoder_out(x, la, return_logits=True)
         tokens, n, _ = model.encode_greedy(x, la)
         torch.cuda.synchronize()
-        assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL, mode
+        assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL, mode
         for b in range(len(lens)):
             ids, _, _ = greedy_tokens(ref_probs[b].numpy())
             assert np.array_equal(ids, tokens[b, :int(n[b])].cpu().numpy()), (mode, b)
         outs[mode] = logits
     model.set_ffn_split(-1)
     # the routes differ only in the order of the final sum over hidden chunks
-    assert _rel(outs[8].cpu().numpy(), outs[0].cpu().numpy()) < 1e-5
+    assert rel(outs[8].cpu().numpy(), outs[0].cpu().numpy()) < 1e-5
     assert torch.equal(outs[-1], outs[8])  # <= 128 row blocks and n_chunks = 8: the default picks 8 slices here
 
 
@@ -109,5 +103,5 @@ def test_forced_split_on_a_batch_above_the_fused_attention_threshold():
         model.set_ffn_split(mode)
         got = model.get_encoder_out(x, la, return_logits=True)[1]
         torch.cuda.synchronize()
-        assert _rel(got.cpu().numpy(), ref.cpu().numpy()) < 1e-5, mode
+        assert rel(got.cpu().numpy(), ref.cpu().numpy()) < 1e-5, mode
     model.set_ffn_split(-1)

@@ -5,7 +5,7 @@ logits within 1e-3 of the oracle, the fp32 route within the fp32 budget of tests
 import numpy as np
 import pytest
 import torch
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +20,6 @@ def _model(V, blocks, seed, causal=True):
     sd = conformer_state_dict(vocab_size=V, num_blocks=blocks, seed=seed, perturb_norm=True)
     conf = dict(output_size=256, attention_heads=4, linear_units=2048, num_blocks=blocks, cnn_module_kernel=15)
     return sd, ConformerModel(80, V, streaming=causal, encoder_conf=conf, state_dict=sd, device="cuda:0")
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
 
 
 @pytest.mark.parametrize("B,T,lens", [(3, 331, [331, 200, 57]), (9, 403, None), (16, 611, None)])  # conv2 tiles: 32, 96, 128 + 64
@@ -43,7 +39,7 @@ def test_f16x3_mode_against_the_oracle_and_the_fp32_mode(B, T, lens):
     orc = ConformerOracle(sd, num_blocks=blocks)
     _, lo = orc.get_encoder_out(torch.as_tensor(x), torch.as_tensor(la), return_logits=True)
     lo = lo.numpy()
-    e32, eh = _rel(l32, lo), _rel(lh, lo)
+    e32, eh = rel(l32, lo), rel(lh, lo)
     assert e32 < F32_BUDGET and eh < 1e-3, (e32, eh)
     assert eh < 2e-5, eh  # (measured 1e-6 .. 3e-6: the same class as the fp32 kernels)
     assert np.array_equal(lh.argmax(-1), l32.argmax(-1))
@@ -76,7 +72,7 @@ def test_f16x3_mode_on_the_efficient_conformer():
     orc = EfficientConformerOracle(sd, num_blocks=L, stride_layer_idx=stride_idx, group_layer_idx=groups)
     _, lo = orc.get_encoder_out(x, la, return_logits=True)
     assert np.isfinite(lh).all() and not np.array_equal(lh, l32)
-    assert _rel(lh, lo.numpy()) < 2e-5 and _rel(l32, lo.numpy()) < 2e-5
+    assert rel(lh, lo.numpy()) < 2e-5 and rel(l32, lo.numpy()) < 2e-5
     assert np.array_equal(lh.argmax(-1), l32.argmax(-1))
 
 
@@ -97,7 +93,7 @@ def test_f16x3_mode_at_the_baseline_shape_with_ragged_lengths():
     m.set_skip_padding(False)
     l32, lh, lhs = l32.cpu().numpy(), lh.cpu().numpy(), lhs.cpu().numpy()
     assert np.isfinite(lh).all() and not np.array_equal(lh, l32)
-    assert _rel(lh, l32) < 2e-5
+    assert rel(lh, l32) < 2e-5
     tp = lh.shape[1]
     tv = [min(tp, (int(n) + 3) // 4) for n in la]  # frame t is valid iff 4 t < len (subsampling.py:115)
     for b in range(32):
@@ -121,12 +117,12 @@ def test_f16x3_mode_on_the_squeezeformer():
     _, lh = sm.get_encoder_out(x, la, return_logits=True)
     orc = SqueezeformerOracle(sq_sd, num_blocks=2, cnn_module_kernel=31, reduce_idx=None, recover_idx=None)
     _, lo = orc.get_encoder_out(x, la, return_logits=True)
-    assert _rel(lh.cpu().numpy(), lo.numpy()) < 2e-5
+    assert rel(lh.cpu().numpy(), lo.numpy()) < 2e-5
     sm.set_skip_padding(True)
     _, lhs = sm.get_encoder_out(x, la, return_logits=True)
     l32, lh, lhs = l32.cpu().numpy(), lh.cpu().numpy(), lhs.cpu().numpy()
     assert np.isfinite(lh).all() and not np.array_equal(lh, l32)
-    assert _rel(lh, l32) < 2e-5
+    assert rel(lh, l32) < 2e-5
     assert np.array_equal(lh.argmax(-1), l32.argmax(-1))
     for b, n in enumerate(la):
         tv = min(lh.shape[1], (int(n) + 3) // 4)
@@ -166,7 +162,7 @@ def test_f16x3_range_guard_falls_back_to_fp32_and_counts():
     # in range: the mode runs, nothing is counted
     _, lh = m.get_encoder_out(x, la, return_logits=True)
     lh = lh.cpu().numpy()
-    assert not np.array_equal(lh, ref) and _rel(lh, ref) < 2e-5
+    assert not np.array_equal(lh, ref) and rel(lh, ref) < 2e-5
     assert m.gemm_guard_stats() == (0, 0)
     # out of range, guard on (default)
     _, lb = m.get_encoder_out(big, la, return_logits=True)
@@ -356,7 +352,7 @@ def test_f16x3_mode_on_the_squeezeformer_split_route_and_stream():
     assert any(k.startswith("k_ffn_part<true>") for k in kp.kernels), sorted(kp.kernels)
     _, lo = SqueezeformerOracle(sd, num_blocks=L, cnn_module_kernel=31, reduce_idx=1, recover_idx=2).get_encoder_out(
         x, la, return_logits=True)
-    assert _rel(lh.cpu().numpy(), lo.numpy()) < 2e-5
+    assert rel(lh.cpu().numpy(), lo.numpy()) < 2e-5
     for a, b in zip(got_chunks, base_chunks):
         assert a.shape == b.shape and np.abs(a - b).max() < 1e-5
         assert np.array_equal(a.argmax(-1), b.argmax(-1))

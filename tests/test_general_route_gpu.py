@@ -9,7 +9,7 @@ import torch
 
 from oracle.conformer_oracle import ConformerOracle
 from ppasr_amd.utils.synth import conformer_state_dict, synth_features
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
@@ -17,12 +17,6 @@ TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
 #  |x| = 0.5 -- turns a 1e-7 difference in a pre-activation next to the threshold into a 0.5 step, so two correct fp32
 #  implementations agree only as far as no value happens to sit there; seen here: 8e-3 on one draw)
 ACTS = ["swish", "relu", "gelu", "tanh", "hardtanh", "relu6", "leakyrelu", "selu", "elu", "hardswish"]
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _draw(seed, streaming=False):
@@ -67,10 +61,10 @@ def test_random_options_batched(seed):
         ref_probs, ref_logits = oracle.get_encoder_out(x, la, return_logits=True)
         torch.cuda.synchronize()
         assert torch.isfinite(probs).all()
-        e = _rel(logits.cpu().numpy(), ref_logits.numpy())
+        e = rel(logits.cpu().numpy(), ref_logits.numpy())
         print(f"seed {seed} {conf} B={B} T={Tb}: logits {e:.2e}")
         assert e < TOL, conf
-        assert _rel(probs.cpu().numpy(), ref_probs.numpy()) < TOL
+        assert rel(probs.cpu().numpy(), ref_probs.numpy()) < TOL
 
 
 @pytest.mark.parametrize("seed", range(14))
@@ -89,15 +83,15 @@ def test_random_options_chunked(seed):
         rp, r_att, r_cnn = oracle.get_encoder_out_chunk(x[:, pos:pos + frames], off, required, r_att, r_cnn)
         pos += frames
         off += p.shape[1]
-        e = _rel(p.cpu().numpy(), rp.numpy())
+        e = rel(p.cpu().numpy(), rp.numpy())
         print(f"seed {seed} chunk {i} ({frames} frames, required {required}): probs {e:.2e}")
         assert e < TOL, conf
         assert tuple(att.shape) == tuple(r_att.shape), (att.shape, r_att.shape)
         if r_att.numel():
-            assert _rel(att.cpu().numpy(), r_att.numpy()) < TOL
+            assert rel(att.cpu().numpy(), r_att.numpy()) < TOL
         assert tuple(cnn.shape) == tuple(r_cnn.shape), (cnn.shape, r_cnn.shape)
         if r_cnn.numel():
-            assert _rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
+            assert rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
 
 
 # ---- the other *former families at widths the fused kernels do not cover (Squeezeformer encoder_dim, Efficient-Conformer
@@ -150,7 +144,7 @@ def test_width_512_families_batched(family, seed):
         ref_probs, ref_logits = oracle.get_encoder_out(x, la, return_logits=True)
         torch.cuda.synchronize()
         assert torch.isfinite(probs).all()
-        e = _rel(logits.cpu().numpy(), ref_logits.numpy())
+        e = rel(logits.cpu().numpy(), ref_logits.numpy())
         print(f"{family} seed {seed} {conf} B={B} T={Tb}: logits {e:.2e}")
         assert e < TOL, conf
 
@@ -170,11 +164,11 @@ def test_width_512_families_chunked(family, seed):
         p, att, cnn = model.get_encoder_out_chunk(chunk, off, required, att, cnn)
         rp, r_att, r_cnn = oracle.get_encoder_out_chunk(chunk, off, required, r_att, r_cnn)
         off += p.shape[1]
-        e = _rel(p.cpu().numpy(), rp.numpy())
+        e = rel(p.cpu().numpy(), rp.numpy())
         print(f"{family} seed {seed} window {cur} required {required}: probs {e:.2e}")
         assert e < TOL, conf
         assert tuple(att.shape) == tuple(r_att.shape), (att.shape, r_att.shape)
-        assert _rel(att.cpu().numpy(), r_att.numpy()) < TOL and _rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
+        assert rel(att.cpu().numpy(), r_att.numpy()) < TOL and rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
 
 
 def test_ragged_decode_on_a_route_without_the_ragged_mode():

@@ -7,16 +7,10 @@ import torch
 from oracle.ctc_decoders_oracle import greedy_tokens
 from ppasr_amd.utils.synth import (conformer_state_dict, deepspeech2_state_dict, efficient_conformer_state_dict,
                                    squeezeformer_state_dict, synth_features)
-from numerics import F32_BUDGET, F32_BUDGET_DS2
+from numerics import F32_BUDGET, F32_BUDGET_DS2, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET  # fp32 error budgets (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _cases(seed, n, t_lo=40, t_hi=900):
@@ -36,7 +30,7 @@ def _check(model, oracle, x, lens, V):
     torch.cuda.synchronize()
     ref_probs, ref_logits = oracle.get_encoder_out(x, lens, return_logits=True)
     assert tuple(logits.shape) == tuple(ref_logits.shape)
-    assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
+    assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
     tokens, n_tokens, _ = model.encode_greedy(x, lens)
     for b in range(x.shape[0]):
         ids, _, _ = greedy_tokens(ref_probs[b].numpy())
@@ -96,4 +90,4 @@ def test_deepspeech2_sweep(B, T, lens, streaming):
     probs = model.get_encoder_out(x, lens)
     torch.cuda.synchronize()
     ref, _, _, _ = DeepSpeech2Oracle(sd, 2, 1024, streaming).forward(x, lens)
-    assert _rel(probs.cpu().numpy(), np.asarray(ref)) < F32_BUDGET_DS2
+    assert rel(probs.cpu().numpy(), np.asarray(ref)) < F32_BUDGET_DS2

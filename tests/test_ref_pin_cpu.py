@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import ref_cases as rc
+from numerics import rel
 from oracle.conformer_oracle import ConformerOracle
 from oracle.deepspeech2_oracle import DeepSpeech2Oracle
 from oracle.efficient_conformer_oracle import EfficientConformerOracle
@@ -23,13 +24,6 @@ TOL = 2e-5
 def ref():
     with np.load(os.path.join(HERE, "golden", "ref_small.npz")) as z:
         return {k: z[k] for k in z.files}
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def make_oracle(case, sd):
@@ -64,7 +58,7 @@ def test_former_oracle_matches_reference_source(ref, name):
     oracle = make_oracle(case, sd)
     x, lens = rc.features(case)
     probs, logits = oracle.get_encoder_out(x, lens, return_logits=True)
-    e_l, e_p = _rel(logits.numpy(), ref[f"{name}/logits"]), _rel(probs.numpy(), ref[f"{name}/probs"])
+    e_l, e_p = rel(logits.numpy(), ref[f"{name}/logits"]), rel(probs.numpy(), ref[f"{name}/probs"])
     print(f"{name}: logits {e_l:.2e} probs {e_p:.2e}")
     assert e_l < TOL and e_p < TOL
     # greedy ids of every frame (padded ones too, like greedy_decoder_batch) are identical
@@ -85,9 +79,9 @@ def test_former_oracle_chunks_match_reference_source(ref, name, required):
         offset += p.shape[1]
     k = f"{name}/chunk{required}"
     assert [o.shape[1] for o in outs] == ref[k + "/n"].tolist()
-    e_p = _rel(np.concatenate(outs, 1), ref[k + "/probs"])
-    e_a = _rel(att.numpy(), ref[k + "/att"]) if ref[k + "/att"].size else 0.0
-    e_c = _rel(cnn.numpy(), ref[k + "/cnn"]) if ref[k + "/cnn"].size else 0.0  # (use_cnn_module=False: empty)
+    e_p = rel(np.concatenate(outs, 1), ref[k + "/probs"])
+    e_a = rel(att.numpy(), ref[k + "/att"]) if ref[k + "/att"].size else 0.0
+    e_c = rel(cnn.numpy(), ref[k + "/cnn"]) if ref[k + "/cnn"].size else 0.0  # (use_cnn_module=False: empty)
     print(f"{k}: probs {e_p:.2e} att {e_a:.2e} cnn {e_c:.2e}")
     assert tuple(att.shape) == ref[k + "/att"].shape and tuple(cnn.shape) == ref[k + "/cnn"].shape
     assert e_p < TOL and e_a < TOL and e_c < TOL
@@ -100,7 +94,7 @@ def test_ds2_oracle_matches_reference_source(ref, name):
     oracle = make_oracle(case, sd)
     x, lens = rc.features(case)
     probs, out_lens, h, c = oracle.forward(x, lens)
-    e = _rel(probs.numpy(), ref[f"{name}/probs"])
+    e = rel(probs.numpy(), ref[f"{name}/probs"])
     print(f"{name}: probs {e:.2e}")
     assert e < TOL
     if case["chunk_frames"]:
@@ -113,11 +107,11 @@ def test_ds2_oracle_matches_reference_source(ref, name):
             p, _, h, c = oracle.forward(xc[:, a:b], np.full(B, b - a, np.int64), h, c)
             outs.append(p.numpy())
         assert [o.shape[1] for o in outs] == ref[f"{name}/chunk/n"].tolist()
-        e_p, e_h = _rel(np.concatenate(outs, 1), ref[f"{name}/chunk/probs"]), _rel(h.numpy(), ref[f"{name}/chunk/h"])
+        e_p, e_h = rel(np.concatenate(outs, 1), ref[f"{name}/chunk/probs"]), rel(h.numpy(), ref[f"{name}/chunk/h"])
         print(f"{name}/chunk: probs {e_p:.2e} h {e_h:.2e}")
         assert e_p < TOL and e_h < TOL
         if not case["kw"].get("use_gru"):
-            assert _rel(c.numpy(), ref[f"{name}/chunk/c"]) < TOL
+            assert rel(c.numpy(), ref[f"{name}/chunk/c"]) < TOL
 
 
 def test_full_size_conformer_oracle_matches_reference_source():

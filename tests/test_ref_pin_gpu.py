@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import ref_cases as rc
-from numerics import F32_BUDGET, F32_BUDGET_DS2
+from numerics import F32_BUDGET, F32_BUDGET_DS2, rel
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -32,13 +32,6 @@ def ref():
 def ref_full():
     with np.load(os.path.join(HERE, "golden", "ref_full.npz")) as z:
         return {k: z[k] for k in z.files}
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 GEMM_MODES = ["f32", "f16x3"]
@@ -88,7 +81,7 @@ def test_former_batched_matches_reference_source(ref, name, gemm):
     x, lens = rc.features(case)
     probs, logits = model.get_encoder_out(x, lens, return_logits=True)
     torch.cuda.synchronize()
-    e_l, e_p = _rel(logits.cpu().numpy(), ref[f"{name}/logits"]), _rel(probs.cpu().numpy(), ref[f"{name}/probs"])
+    e_l, e_p = rel(logits.cpu().numpy(), ref[f"{name}/logits"]), rel(probs.cpu().numpy(), ref[f"{name}/probs"])
     print(f"{name} [{gemm}]: logits {e_l:.2e} probs {e_p:.2e}")
     assert e_l < TOL[gemm] and e_p < TOL[gemm]
     got, want = probs.cpu().numpy().argmax(-1), ref[f"{name}/probs"].argmax(-1)
@@ -114,11 +107,11 @@ def test_former_chunks_match_reference_source(ref, name, required, gemm):
         outs.append(stream.encode_chunk(x[:, a:b], required).cpu().numpy())
     k = f"{name}/chunk{required}"
     assert [o.shape[1] for o in outs] == ref[k + "/n"].tolist()
-    e_p = _rel(np.concatenate(outs, 1), ref[k + "/probs"])
+    e_p = rel(np.concatenate(outs, 1), ref[k + "/probs"])
     att, cnn = stream.export_caches()
     assert tuple(att.shape) == ref[k + "/att"].shape and tuple(cnn.shape) == ref[k + "/cnn"].shape
-    e_a = _rel(att.cpu().numpy(), ref[k + "/att"]) if ref[k + "/att"].size else 0.0
-    e_c = _rel(cnn.cpu().numpy(), ref[k + "/cnn"]) if ref[k + "/cnn"].size else 0.0  # (use_cnn_module=False: empty)
+    e_a = rel(att.cpu().numpy(), ref[k + "/att"]) if ref[k + "/att"].size else 0.0
+    e_c = rel(cnn.cpu().numpy(), ref[k + "/cnn"]) if ref[k + "/cnn"].size else 0.0  # (use_cnn_module=False: empty)
     print(f"{k} [{gemm}]: probs {e_p:.2e} att {e_a:.2e} cnn {e_c:.2e}")
     assert e_p < TOL[gemm] and e_a < TOL[gemm] and e_c < TOL[gemm]
 
@@ -130,7 +123,7 @@ def test_ds2_matches_reference_source(ref, name):
     x, lens = rc.features(case)
     probs = model.get_encoder_out(x, lens)
     torch.cuda.synchronize()
-    e = _rel(probs.cpu().numpy(), ref[f"{name}/probs"])
+    e = rel(probs.cpu().numpy(), ref[f"{name}/probs"])
     print(f"{name}: probs {e:.2e}")
     assert e < F32_BUDGET_DS2
     assert np.array_equal(probs.cpu().numpy().argmax(-1), ref[f"{name}/probs"].argmax(-1))
@@ -144,12 +137,12 @@ def test_ds2_matches_reference_source(ref, name):
             p, _, h, c = model.get_encoder_out_chunk(xc[:, a:b], np.full(B, b - a, np.int64), h, c)
             outs.append(p.cpu().numpy())
         assert [o.shape[1] for o in outs] == ref[f"{name}/chunk/n"].tolist()
-        e_p = _rel(np.concatenate(outs, 1), ref[f"{name}/chunk/probs"])
-        e_h = _rel(h.cpu().numpy(), ref[f"{name}/chunk/h"])
+        e_p = rel(np.concatenate(outs, 1), ref[f"{name}/chunk/probs"])
+        e_h = rel(h.cpu().numpy(), ref[f"{name}/chunk/h"])
         print(f"{name}/chunk: probs {e_p:.2e} h {e_h:.2e}")
         assert e_p < F32_BUDGET_DS2 and e_h < F32_BUDGET_DS2
         if not case["kw"].get("use_gru"):
-            assert _rel(c.cpu().numpy(), ref[f"{name}/chunk/c"]) < F32_BUDGET_DS2
+            assert rel(c.cpu().numpy(), ref[f"{name}/chunk/c"]) < F32_BUDGET_DS2
 
 
 # ---- BASELINE.json configs at full size ------------------------------------------------------------------------------

@@ -8,14 +8,9 @@ import torch
 
 from ppasr_amd.utils.synth import (conformer_state_dict, deepspeech2_state_dict, efficient_conformer_state_dict,
                                    squeezeformer_state_dict, synth_features)
-from numerics import F32_BUDGET, F32_BUDGET_DS2
+from numerics import F32_BUDGET, F32_BUDGET_DS2, rel
 
 pytestmark = pytest.mark.gpu
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _windows(n_frames, window=67, stride=64):
@@ -64,7 +59,7 @@ def test_stream_chunks_on_the_fused_route_equal_the_split_route(family, ks):
     assert len(outs[-1]) == len(outs[0]) == 4
     for i, (s, f) in enumerate(zip(outs[-1], outs[0])):
         assert s.shape == f.shape and np.isfinite(f).all()
-        assert _rel(f, s) < 2e-5, (family, ks, i, _rel(f, s))
+        assert rel(f, s) < 2e-5, (family, ks, i, rel(f, s))
 
 
 @pytest.mark.parametrize("mode", ["rows32", "rows16", "rows32_w16", "f16x3"])
@@ -89,7 +84,7 @@ def test_squeezeformer_with_15_tap_conv_modules(mode):
     _, ref = SqueezeformerOracle(sd, num_blocks=L, cnn_module_kernel=15, reduce_idx=1, recover_idx=3).get_encoder_out(
         x, la, return_logits=True)
     torch.cuda.synchronize()
-    e = _rel(logits.cpu().numpy(), ref.numpy())
+    e = rel(logits.cpu().numpy(), ref.numpy())
     print(f"squeezeformer, 15 taps, {mode}: logits {e:.2e}")
     assert e < F32_BUDGET
 
@@ -112,7 +107,7 @@ def test_squeezeformer_utterances_of_three_frames(ks):
         x, la, return_logits=True)
     torch.cuda.synchronize()
     assert tuple(logits.shape) == tuple(ref.shape) and logits.shape[1] == 3
-    assert _rel(logits.cpu().numpy(), ref.numpy()) < F32_BUDGET
+    assert rel(logits.cpu().numpy(), ref.numpy()) < F32_BUDGET
 
 
 def test_gru_single_utterance_step_kernel():
@@ -131,8 +126,8 @@ def test_gru_single_utterance_step_kernel():
         torch.cuda.synchronize()
         rp, rl, rh, _rc = DeepSpeech2Oracle(sd, L, H, streaming, use_gru=True).forward(x, lens)
         assert out_lens.cpu().tolist() == rl.tolist()
-        assert _rel(probs.cpu().numpy(), rp.numpy()) < F32_BUDGET_DS2
-        assert _rel(fh.cpu().numpy(), rh.numpy()) < F32_BUDGET_DS2
+        assert rel(probs.cpu().numpy(), rp.numpy()) < F32_BUDGET_DS2
+        assert rel(fh.cpu().numpy(), rh.numpy()) < F32_BUDGET_DS2
 
 
 def test_probabilities_of_a_vocabulary_beyond_5120_characters():
@@ -149,5 +144,5 @@ def test_probabilities_of_a_vocabulary_beyond_5120_characters():
     got = model.get_encoder_out(x, lens).cpu().numpy()
     want = ConformerOracle(sd, num_blocks=L).get_encoder_out(x, lens).numpy()
     assert got.shape == want.shape
-    assert _rel(got, want) < F32_BUDGET
+    assert rel(got, want) < F32_BUDGET
     assert np.abs(got.sum(-1) - 1.0).max() < 1e-5

@@ -12,7 +12,7 @@ import torch
 
 from oracle.squeezeformer_oracle import SqueezeformerOracle
 from ppasr_amd.utils.synth import squeezeformer_state_dict, synth_features
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,11 +30,6 @@ def _model(streaming=True, kernel=31, norm="layer_norm"):
     conf = dict(encoder_dim=256, output_size=256, attention_heads=4, num_blocks=L, reduce_idx=RED, recover_idx=REC,
                 feed_forward_expansion_factor=8, cnn_module_kernel=kernel, cnn_norm_type=norm)
     return SqueezeformerModel(80, V, streaming=streaming, encoder_conf=conf, state_dict=sd, device="cuda:0"), sd
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _run(model, x, lens, rows):
@@ -56,14 +51,14 @@ def test_16_row_blocks_match_32_row_blocks_and_the_oracle(streaming, kernel, nor
     pw, lw = _run(model, x, lens, W16)
     pa, la = _run(model, x, lens, -1)   # the grid-size rule picks the 16-row kernels for every layer of this batch
     assert np.array_equal(la, l16)
-    e, ew = _rel(l16, l32), _rel(lw, l32)
+    e, ew = rel(l16, l32), rel(lw, l32)
     print("16 vs 32 rows: max rel logit diff", e, " 32 rows on 16 waves vs 8:", ew)
     assert e < 2e-5 and ew < 2e-5
     oracle = SqueezeformerOracle(sd, num_blocks=L, cnn_module_kernel=kernel, reduce_idx=RED, recover_idx=REC, causal=streaming)
     with torch.no_grad():
         enc, _ = oracle.encoder_forward(x, lens)[:2]
         ref = oracle.ctc_logits(enc).numpy()
-    e16, e32, ew16 = _rel(l16, ref), _rel(l32, ref), _rel(lw, ref)
+    e16, e32, ew16 = rel(l16, ref), rel(l32, ref), rel(lw, ref)
     print("vs oracle: 16-row", e16, "32-row", e32, "32 rows on 16 waves", ew16)
     assert e16 < F32_BUDGET and e32 < F32_BUDGET and ew16 < F32_BUDGET
     near_tie = (np.sort(p32, -1)[..., -1] - np.sort(p32, -1)[..., -2]).min() < 1e-5
@@ -86,7 +81,7 @@ def test_16_wave_kernels_on_a_full_launch_with_a_partial_last_block():
     # the auto route mixes forms per layer; both it and the forced form stay within rounding of the 8-wave kernels
     for u in range(len(lens_l)):
         n = int(fl[u])
-        assert _rel(la[u, :n], l32[u, :n]) < 2e-5 and _rel(lw[u, :n], l32[u, :n]) < 2e-5
+        assert rel(la[u, :n], l32[u, :n]) < 2e-5 and rel(lw[u, :n], l32[u, :n]) < 2e-5
     assert not np.array_equal(lw, l32)   # (a different summation order: the 16-wave kernels did run)
 
 
@@ -118,7 +113,7 @@ def test_ragged_mode_with_hint_computes_the_same_valid_rows():
     for u in range(len(LENS)):
         n = int(fl[u])
         assert np.array_equal(a[u, :n], b[u, :n])
-        assert _rel(a[u, :n], c[u, :n]) < 2e-5 and _rel(d[u, :n], c[u, :n]) < 2e-5
+        assert rel(a[u, :n], c[u, :n]) < 2e-5 and rel(d[u, :n], c[u, :n]) < 2e-5
         assert not a[u, n:].any() and not b[u, n:].any() and not c[u, n:].any() and not d[u, n:].any()
 
 
@@ -161,9 +156,9 @@ def test_conformer_family_16_row_blocks(family):
     model.set_ffn_split(0)
     pw, lw = _run(model, x, la, W16)
     model.set_ffn_split(-1)
-    e, ew = _rel(l16, l32), _rel(lw, l32)
+    e, ew = rel(l16, l32), rel(lw, l32)
     ref = oracle.get_encoder_out(x, la, return_logits=True)[1].numpy()
-    e16, e32, ew16 = _rel(l16, ref), _rel(l32, ref), _rel(lw, ref)
+    e16, e32, ew16 = rel(l16, ref), rel(l32, ref), rel(lw, ref)
     print(family, "16 vs 32 rows", e, "16 waves vs 8", ew, "vs oracle: 16-row", e16, "32-row", e32, "16 waves", ew16)
     assert e < 2e-5 and ew < 2e-5 and e16 < F32_BUDGET and e32 < F32_BUDGET and ew16 < F32_BUDGET
     assert not np.array_equal(lw, l32)
@@ -195,6 +190,6 @@ def test_conformer_16_wave_kernels_around_the_fused_attention():
         assert not np.array_equal(lw, l32)
         for u in range(len(lens_l)):
             n = int(fl[u])
-            assert _rel(lw[u, :n], l32[u, :n]) < 2e-5
+            assert rel(lw[u, :n], l32[u, :n]) < 2e-5
             if skip:
                 assert not lw[u, n:].any()

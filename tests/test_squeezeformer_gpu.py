@@ -6,16 +6,10 @@ import torch
 from oracle.ctc_decoders_oracle import greedy_tokens
 from oracle.squeezeformer_oracle import SqueezeformerOracle
 from ppasr_amd.utils.synth import squeezeformer_state_dict, synth_features
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _model(sd, V, L, reduce_idx, recover_idx):
@@ -42,8 +36,8 @@ def test_squeezeformer_layers_and_logits_match_oracle(B, T, lens, L, red, rec):
         enc, _, layers = oracle.encoder_forward(x, lens, return_layers=True)
         ref_logits = oracle.ctc_logits(enc)
         ref_probs = torch.softmax(ref_logits, dim=2)
-    e_logits = _rel(logits.cpu().numpy(), ref_logits.numpy())
-    e_probs = _rel(probs.cpu().numpy(), ref_probs.numpy())
+    e_logits = rel(logits.cpu().numpy(), ref_logits.numpy())
+    e_probs = rel(probs.cpu().numpy(), ref_probs.numpy())
     print("logits", e_logits, "probs", e_probs)
     assert e_logits < TOL and e_probs < TOL
     tokens, n_tokens, score = model.encode_greedy(x, lens)
@@ -60,7 +54,7 @@ def test_squeezeformer_full_config_runs():
     model = _model(sd, V, L, 5, 11)
     probs, logits = model.get_encoder_out(x, lens, return_logits=True)
     ref_probs, ref_logits = SqueezeformerOracle(sd, num_blocks=L).get_encoder_out(x, lens, return_logits=True)
-    assert _rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
+    assert rel(logits.cpu().numpy(), ref_logits.numpy()) < TOL
 
 
 @pytest.mark.parametrize("B,T,lens", [(3, 203, [203, 150, 67]), (2, 411, [411, 300]), (1, 131, [131])])

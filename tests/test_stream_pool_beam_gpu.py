@@ -9,6 +9,8 @@ from lm_util import write_synthetic_arpa
 from ppasr_amd.utils.synth import (conformer_state_dict, efficient_conformer_state_dict, squeezeformer_state_dict,
                                    synth_vocabulary)
 
+from session_groups import predict_stream_reference
+
 pytestmark = pytest.mark.gpu
 V = 300
 
@@ -51,7 +53,6 @@ def _group(family, model, n):
 def test_stream_pool_beam_search_equals_predict_stream(tmp_path, family, scorer, beam):
     from test_predictor_gpu import _audio
     from ppasr_amd.decoders.beam_search_decoder import BeamSearchDecoder
-    from ppasr_amd.predict import PPASRPredictor
     from ppasr_amd.serving import StreamPool
     vocab = synth_vocabulary(V)
     cfg, sd = _setup("conformer" if family == "handles" else family)
@@ -60,19 +61,9 @@ def test_stream_pool_beam_search_equals_predict_stream(tmp_path, family, scorer,
     conf["beam_size"] = beam
     if scorer:
         conf["language_model_path"] = write_synthetic_arpa(str(tmp_path / "lm.arpa"), vocab[2:150], order=3, seed=6)
-    p = PPASRPredictor(configs=cfg, state_dict=sd, vocab_list=vocab, warmup=False)
     n = 3
-    wavs = [_audio(2.4, seed=21), _audio(1.93, seed=22), _audio(3.1, seed=23)]
-    pcms = [(np.clip(w, -1, 1) * 32767).astype(np.int16).tobytes() for w in wavs]
+    p, pcms, want = predict_stream_reference(cfg, sd, vocab, [_audio(2.4, seed=21), _audio(1.93, seed=22), _audio(3.1, seed=23)])
     step = 16000  # 0.5 s packets
-    want = []
-    for pcm in pcms:
-        p.reset_stream()
-        out = None
-        for i in range(0, len(pcm), step):
-            out = p.predict_stream(audio_data=pcm[i:i + step], is_end=(i + step >= len(pcm))) or out
-        want.append(out)
-    p.reset_stream()
     model = p.predictor.model
     pool = StreamPool(model, vocab, n_sessions=n, preprocess_conf=cfg["preprocess_conf"], group=_group(family, model, n),
                       decoder="ctc_beam_search", decoder_conf=dict(conf))

@@ -1,23 +1,16 @@
 """GPU parity of forward_chunk for the Squeezeformer and Efficient-Conformer families (device-resident caches, half-rate
 layers held once) vs the oracles' restatements of squeezeformer/encoder.py:260-381 and
 efficient_conformer/encoder.py:266-393, chunk by chunk with predict_stream's windowing (predict.py:277-283,306-307)."""
-import numpy as np
 import pytest
 import torch
 
 from oracle.efficient_conformer_oracle import EfficientConformerOracle
 from oracle.squeezeformer_oracle import SqueezeformerOracle
 from ppasr_amd.utils.synth import efficient_conformer_state_dict, squeezeformer_state_dict, synth_features
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _windows(n_frames, window=67, stride=64):
@@ -51,14 +44,14 @@ def _run_stream(model, oracle, x, required, frames_per_chunk):
         got = stream.encode_chunk(chunk, required)
         torch.cuda.synchronize()
         assert tuple(got.shape) == tuple(ref.shape), (a, b)
-        e = _rel(got.cpu().numpy(), ref.numpy())
+        e = rel(got.cpu().numpy(), ref.numpy())
         assert e < TOL, (a, b, e)
         offset += ref.shape[1]
         assert stream.offset == offset and stream.cache_frames == att.shape[2]
         g_att, g_cnn = stream.export_caches()
         assert tuple(g_att.shape) == tuple(att.shape) and tuple(g_cnn.shape) == tuple(cnn.shape)
-        assert _rel(g_att.cpu().numpy(), att.numpy()) < TOL
-        assert _rel(g_cnn.cpu().numpy(), cnn.numpy()) < TOL
+        assert rel(g_att.cpu().numpy(), att.numpy()) < TOL
+        assert rel(g_cnn.cpu().numpy(), cnn.numpy()) < TOL
     return stream
 
 
@@ -78,7 +71,7 @@ def test_squeezeformer_chunks_match_oracle(L, red, rec, required):
     first_ref, _, _ = oracle.get_encoder_out_chunk(x[:, :67], 0, required)
     stream.reset()
     again = stream.encode_chunk(x[:, :67], required)
-    assert _rel(again.cpu().numpy(), first_ref.numpy()) < TOL
+    assert rel(again.cpu().numpy(), first_ref.numpy()) < TOL
 
 
 @pytest.mark.parametrize("L,stride_idx,groups,required", [
@@ -116,13 +109,13 @@ def test_stateless_signature_and_one_giant_chunk(family):
     full = model.get_encoder_out(x, lens)
     one, att, cnn = model.get_encoder_out_chunk(x, 0, -1)
     torch.cuda.synchronize()
-    assert _rel(one.cpu().numpy(), full.cpu().numpy()) < 1e-5
+    assert rel(one.cpu().numpy(), full.cpu().numpy()) < 1e-5
     r_probs, r_att, r_cnn = oracle.get_encoder_out_chunk(x, 0, -1)
     assert tuple(att.shape) == tuple(r_att.shape)
-    assert _rel(att.cpu().numpy(), r_att.numpy()) < TOL and _rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
+    assert rel(att.cpu().numpy(), r_att.numpy()) < TOL and rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
     x2, _ = synth_features(1, 67, seed=93)
     ref2, ratt2, _ = oracle.get_encoder_out_chunk(x2, r_probs.shape[1], -1, r_att, r_cnn)
     got2, att2, _ = model.get_encoder_out_chunk(x2, r_probs.shape[1], -1, r_att, r_cnn)
     torch.cuda.synchronize()
-    assert _rel(got2.cpu().numpy(), ref2.numpy()) < TOL
+    assert rel(got2.cpu().numpy(), ref2.numpy()) < TOL
     assert tuple(att2.shape) == tuple(ratt2.shape)

@@ -7,16 +7,10 @@ import torch
 
 from oracle.conformer_oracle import ConformerOracle
 from ppasr_amd.utils.synth import conformer_state_dict, synth_features
-from numerics import F32_BUDGET
+from numerics import F32_BUDGET, rel
 
 pytestmark = pytest.mark.gpu
 TOL = F32_BUDGET  # fp32 error budget (tests/numerics.py)
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 def _model(sd, V, L):
@@ -48,18 +42,18 @@ def test_chunked_stream_matches_oracle(required):
         got = stream.encode_chunk(chunk, required)
         torch.cuda.synchronize()
         assert got.shape == ref.shape
-        assert _rel(got.cpu().numpy(), ref.numpy()) < TOL, (a, b)
+        assert rel(got.cpu().numpy(), ref.numpy()) < TOL, (a, b)
         offset += ref.shape[1]
         assert stream.offset == offset and stream.cache_frames == att.shape[2]
         g_att, g_cnn = stream.export_caches()
-        assert _rel(g_att.cpu().numpy(), att.numpy()) < TOL
-        assert _rel(g_cnn.cpu().numpy(), cnn.numpy()) < TOL
+        assert rel(g_att.cpu().numpy(), att.numpy()) < TOL
+        assert rel(g_cnn.cpu().numpy(), cnn.numpy()) < TOL
     # reset -> the first chunk again gives the first result again
     first_ref, _, _ = oracle.get_encoder_out_chunk(x[:, :67], 0, required)
     stream.reset()
     assert stream.offset == 0 and stream.cache_frames == 0
     again = stream.encode_chunk(x[:, :67], required)
-    assert _rel(again.cpu().numpy(), first_ref.numpy()) < TOL
+    assert rel(again.cpu().numpy(), first_ref.numpy()) < TOL
 
 
 def test_stateless_chunk_signature_and_one_giant_chunk():
@@ -74,15 +68,15 @@ def test_stateless_chunk_signature_and_one_giant_chunk():
     full = model.get_encoder_out(x, lens)
     one, att, cnn = model.get_encoder_out_chunk(x, 0, -1)
     torch.cuda.synchronize()
-    assert _rel(one.cpu().numpy(), full.cpu().numpy()) < 1e-5
+    assert rel(one.cpu().numpy(), full.cpu().numpy()) < 1e-5
     r_probs, r_att, r_cnn = oracle.get_encoder_out_chunk(x, 0, -1)
-    assert _rel(att.cpu().numpy(), r_att.numpy()) < TOL and _rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
+    assert rel(att.cpu().numpy(), r_att.numpy()) < TOL and rel(cnn.cpu().numpy(), r_cnn.numpy()) < TOL
     # continue from explicitly passed (host) caches
     x2, _ = synth_features(1, 67, seed=43)
     ref2, _, _ = oracle.get_encoder_out_chunk(x2, r_probs.shape[1], -1, r_att, r_cnn)
     got2, att2, _ = model.get_encoder_out_chunk(x2, r_probs.shape[1], -1, r_att, r_cnn)
     torch.cuda.synchronize()
-    assert _rel(got2.cpu().numpy(), ref2.numpy()) < TOL
+    assert rel(got2.cpu().numpy(), ref2.numpy()) < TOL
     assert att2.shape[2] == r_att.shape[2] + 16
 
 
@@ -110,7 +104,7 @@ def test_session_group_equals_independent_streams():
             ref = singles[s].encode_chunk(chunks[i:i + 1], -16)
             torch.cuda.synchronize()
             assert group.offset(s) == singles[s].offset
-            err = _rel(probs[i].cpu().numpy(), ref[0].cpu().numpy())
+            err = rel(probs[i].cpu().numpy(), ref[0].cpu().numpy())
             # (not bit-equal: the single-session route runs 16-row units and splits the front end's contractions over
             #  more workgroups than the group route -- another order of the fp32 sums; both sit within TOL of the oracle)
             assert err < 3e-5, (r, s, err)
@@ -122,7 +116,7 @@ def test_session_group_equals_independent_streams():
                                         want_probs=True)
     ref2 = singles[2].encode_chunk(feats[2][:, :67], -16)
     torch.cuda.synchronize()
-    assert group.offset(2) == 16 and _rel(probs[0].cpu().numpy(), ref2[0].cpu().numpy()) < 3e-5
+    assert group.offset(2) == 16 and rel(probs[0].cpu().numpy(), ref2[0].cpu().numpy()) < 3e-5
     with pytest.raises(Exception):
         group.encode_chunks([1, 1], np.concatenate([feats[1][:, :67]] * 2))
 
