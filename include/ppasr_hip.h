@@ -682,6 +682,62 @@ PPASR_API ppasr_status ppasr_resample_compute_batch(ppasr_resampler_handle r, co
                                                     const ppasr_resample_segment* segments_dev, int n, long long max_n_out,
                                                     float* out, void* stream);
 
+/* ---- attention rescoring of CTC n-best lists with the checkpoint's attention decoder ----
+ * The reference trains a BiTransformerDecoder with every Conformer-family model (conformer/model.py:48,
+ * transformer/decoder.py) and never calls it at inference; the use defined here is WeNet's `attention_rescoring`:
+ * score every hypothesis of the CTC prefix beam search with the left (and right) decoder over the encoder output and add
+ * the CTC score.
+ *
+ * Encoder output.  While `memory_dev` is set (host call; NULL clears), every offline ppasr_encode on the handle also
+ * writes memory [B,T',D] f32 = the first return value of the reference's encoder(xs, lens, -1, -1): behind after_norm
+ * (Conformer, Efficient-Conformer), the last layer's output (Squeezeformer).  n_floats: capacity of the buffer; a call
+ * that needs more returns PPASR_ENOSPACE.  The route and every other output are unchanged, bit for bit.  With
+ * ppasr_set_skip_padding, rows behind an utterance's valid frames are 0.  Streaming calls do not write it.
+ * PPASR_EUNSUPPORTED on DeepSpeech2 handles and on a Squeezeformer with final_proj (folded into the CTC head). */
+PPASR_API ppasr_status ppasr_set_memory_out(ppasr_handle h, float* memory_dev, size_t n_floats);
+
+typedef struct ppasr_rescorer_s* ppasr_rescorer;
+/* decoder_conf of the reference's YAML + the model's vocabulary.  Built for d_model 256 with 4 heads, linear_units a
+ * multiple of 256 up to 4096, num_blocks 1..6, r_num_blocks 0..6, vocab_size >= 2, normalize_before = True and
+ * concat_after = False (the constructor defaults, the only ones the reference's configurations use); anything else is
+ * PPASR_EUNSUPPORTED. */
+typedef struct {
+  int vocab_size;
+  int d_model;
+  int attention_heads;
+  int linear_units;
+  int num_blocks;
+  int r_num_blocks;
+  int max_len;          /* positional table length, 0 = 5000 */
+} ppasr_rescorer_desc;
+/* Weights by the reference's names: decoder.{left,right}_decoder.{embed.0.weight, after_norm.*, output_layer.*,
+ * decoders.N.{self_attn,src_attn}.linear_{q,k,v,out}.*, decoders.N.feed_forward.w_{1,2}.*, decoders.N.norm{1,2,3}.*}; a
+ * missing one is PPASR_EMISSING with its name in ppasr_last_error(). */
+PPASR_API ppasr_status ppasr_rescorer_create(const ppasr_rescorer_desc* desc, const ppasr_weight_blob* weights_host,
+                                             int n_weights, ppasr_rescorer* out);
+PPASR_API ppasr_status ppasr_rescorer_destroy(ppasr_rescorer r);
+PPASR_API size_t ppasr_rescorer_workspace_bytes(ppasr_rescorer r, int B, int Tp, int nbest, int max_tokens);
+/* One call, asynchronous on `stream`, no read-back: the decoders run over one packed row per (utterance, hypothesis,
+ * direction, position) that exists (a device-side row table made from `lens`).
+ *   memory [B,Tp,D] f32; out_lens [B] i32 valid memory frames (NULL: all Tp; cross-attention sees t < out_lens[b] only)
+ *   tokens [B,nbest,max_tokens] i32, lens [B,nbest] i32 (-1: no such hypothesis), ctc_scores [B,nbest] f64 (-log P):
+ *     the three outputs of ppasr_ctc_beam_search as they are
+ *   sos = eos = V - 1.  att = sum_j logp_left[j][y_j] + logp_left[n][eos] over the input [sos, y0 .. y(n-1)]; r_att the
+ *   same over the reversed tokens with the right decoder; total = (1 - reverse_weight) att + reverse_weight r_att +
+ *   ctc_weight (-ctc_scores).
+ *   att_scores, r_att_scores, total_scores [B,nbest] f64 (absent hypothesis: total = -inf; r_att = 0 when
+ *     reverse_weight == 0, and then the right decoder does not run); best [B] i32: the largest total, lowest index on a tie
+ *   token_logp [B,nbest,2,max_tokens+1] f32 or NULL: the summed log-probabilities (0: left, 1: right; 0.0 where no row)
+ *   logits_tap [B,nbest,2,max_tokens+1,V] f32 or NULL: the decoders' pre-softmax outputs (parity tests; 0.0 where no row)
+ * Refused before any device work: reverse_weight > 0 on a rescorer without right blocks (PPASR_EINVAL); max_tokens + 1
+ * above max_len or above 256 rows per hypothesis (PPASR_EUNSUPPORTED); a workspace below
+ * ppasr_rescorer_workspace_bytes (PPASR_ENOSPACE). */
+PPASR_API ppasr_status ppasr_rescore(ppasr_rescorer r, const float* memory, const int32_t* out_lens, int B, int Tp,
+                                     const int32_t* tokens, const int32_t* lens, const double* ctc_scores, int nbest,
+                                     int max_tokens, double ctc_weight, double reverse_weight, double* att_scores,
+                                     double* r_att_scores, double* total_scores, int32_t* best, float* token_logp,
+                                     float* logits_tap, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

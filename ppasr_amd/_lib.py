@@ -63,6 +63,13 @@ class ModelDesc(ctypes.Structure):
                 ("stride_layer_mask", ctypes.c_int)]
 
 
+class RescorerDesc(ctypes.Structure):
+    """ppasr_rescorer_desc: the attention decoder's shape"""
+    _fields_ = [("vocab_size", ctypes.c_int), ("d_model", ctypes.c_int), ("attention_heads", ctypes.c_int),
+                ("linear_units", ctypes.c_int), ("num_blocks", ctypes.c_int), ("r_num_blocks", ctypes.c_int),
+                ("max_len", ctypes.c_int)]
+
+
 # every symbol include/ppasr_hip.h declares: (name, restype, argtypes)
 _vp = ctypes.c_void_p
 SYMBOLS = [
@@ -201,6 +208,14 @@ SYMBOLS = [
     ("ppasr_resample_compute", ctypes.c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong,
                                               ctypes.c_longlong, _vp]),
     ("ppasr_resample_compute_batch", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_longlong, _vp, _vp]),
+    ("ppasr_set_memory_out", ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
+    ("ppasr_rescorer_create", ctypes.c_int, [ctypes.POINTER(RescorerDesc), ctypes.POINTER(WeightBlob), ctypes.c_int,
+                                             ctypes.POINTER(_vp)]),
+    ("ppasr_rescorer_destroy", ctypes.c_int, [_vp]),
+    ("ppasr_rescorer_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("ppasr_rescore", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                     _vp]),
 ]
 
 _lib = None

@@ -277,6 +277,17 @@ ppasr_status ppasr_set_debug_taps(ppasr_handle h, float* taps, size_t n_floats) 
   return PPASR_OK;
 }
 
+ppasr_status ppasr_set_memory_out(ppasr_handle h, float* memory_dev, size_t n_floats) {
+  if (!h) return fail(PPASR_EINVAL, "null handle");
+  if (h->desc.model_type == PPASR_MODEL_DEEPSPEECH2 && memory_dev)
+    return fail(PPASR_EUNSUPPORTED, "memory output: DeepSpeech2 has no attention decoder");
+  if (h->sq_final_proj && memory_dev)
+    return fail(PPASR_EUNSUPPORTED, "memory output: final_proj is folded into the CTC head, its output is not formed");
+  h->memory_out = memory_dev;
+  h->memory_floats = memory_dev ? n_floats : 0;
+  return PPASR_OK;
+}
+
 ppasr_status ppasr_set_ffn_split(ppasr_handle h, int mode) {
   if (!h) return fail(PPASR_EINVAL, "null handle");
   if (mode != -1 && mode != 0 && mode != 2 && mode != 4 && mode != 8) return fail(PPASR_EINVAL, "ffn split: -1, 0, 2, 4 or 8");

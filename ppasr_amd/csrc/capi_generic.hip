@@ -601,8 +601,10 @@ struct GenRun {
 // when asked for (missing one of the two: its half of the scratch y); ragged batches (ps.lens): outputs behind the valid
 // frames are zeroed.
 ppasr_status dense_head_tail(const ppasr_model_s* h, const float* enc, float* probs, float* logits, int32_t* frame_argmax,
-                             float* frame_maxprob, float* lg_ws, float* y, int B, int M, const PadSkip& ps, hipStream_t st) {
+                             float* frame_maxprob, float* lg_ws, float* y, int B, int M, const PadSkip& ps, hipStream_t st,
+                             bool offline) {
   const int D = h->desc.output_size, V = h->desc.vocab_size;
+  if (offline) LOAD_TRY(memory_out(h, enc, nullptr, nullptr, M, D, ps, st));  // (enc: already behind after_norm)
   float* lg = logits ? logits : (probs ? probs : lg_ws);
   GemmEpi e;
   e.ps = ps;
@@ -810,7 +812,7 @@ ppasr_status gen_layers(const GenRun& r, float* probs, float* logits, int32_t* f
     ln(x, a, h->head.ln_g, h->head.ln_b, 1e-5f, kActNone, false, M);
     enc = a;
   }
-  return dense_head_tail(h, enc, probs, logits, frame_argmax, frame_maxprob, r.lg, y, B, M, ps, st);
+  return dense_head_tail(h, enc, probs, logits, frame_argmax, frame_maxprob, r.lg, y, B, M, ps, st, !r.s && !r.sess);
 }
 
 // front end: GlobalCMVN + the subsampling class + the positional encoding's scaling (subsampling.py, embedding.py)
@@ -1057,7 +1059,7 @@ ppasr_status sq_run(ppasr_model_s* h, const float* feats, const int64_t* lens, i
   }
   // ---- ctc_lo -> softmax (no after_norm in Squeezeformer, encoder.py:232-235) ----
   // (without a recovery layer the encoder ends at the reduced rate: every row is computed and none zeroed)
-  return dense_head_tail(h, x, probs, logits, frame_argmax, frame_maxprob, ws + wl.lg, y, B, M, reduced ? PadSkip{} : psF, st);
+  return dense_head_tail(h, x, probs, logits, frame_argmax, frame_maxprob, ws + wl.lg, y, B, M, reduced ? PadSkip{} : psF, st, !s);
 }
 }  // namespace
 

@@ -19,6 +19,7 @@ using namespace ppasr;
 
 #include "squeezeformer_kernels.h"
 #include "ds2_kernels.h"
+#include "rescore_kernels.h"
 
 std::string& ppasr_err_slot();  // thread-local error string (defined in capi.hip)
 inline ppasr_status fail(ppasr_status s, const std::string& msg) {
@@ -237,6 +238,9 @@ struct ppasr_model_s : DeviceAllocs {
   std::vector<Ds2LayerW> ds2_layers;
   float* taps = nullptr;
   size_t taps_floats = 0;
+  float* memory_out = nullptr;  // ppasr_set_memory_out: the encoder output of offline encodes, [B][T'][D]
+  size_t memory_floats = 0;
+  bool sq_final_proj = false;  // Squeezeformer with final_proj: folded into the CTC head, its output rows are never formed
   // optional per-kernel timing (bench.py roofline leg): one event pair per launch on the caller's stream
   bool prof = false;
   int front_fused = -1;  // ppasr_set_front_fused: -1 / 1 = conv1 + conv2 of the 4x front end as one launch, 0 = two launches

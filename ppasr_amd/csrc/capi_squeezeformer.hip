@@ -136,6 +136,7 @@ ppasr_status squeezeformer_create(ppasr_model_s* m, Loader& ld) {
       for (int n = 0; n < V; ++n) cb_f[n] = (float)acc[n];
       cw = cw_f.data();
       cb = cb_f.data();
+      m->sq_final_proj = true;  // (the encoder's own output is then never formed: ppasr_set_memory_out refuses)
     } else {
       GETW(cw_d, "ctc.ctc_lo.weight", (size_t)d * V);
       GETW(cb_d, "ctc.ctc_lo.bias", V);

@@ -113,6 +113,17 @@ inline void front4_fused(const ppasr_model_s* h, const float* feats, int B, int 
   });
 }
 
+// ppasr_set_memory_out: the encoder output [M][D] of an offline encode, from the rows x the head reads (g / b: the after_norm
+// the head applies to them, nullptr: none or already applied); ragged batches (ps.lens): 0 behind the valid frames.  One
+// small launch of its own beside the head; nothing when the pointer is clear.
+inline ppasr_status memory_out(const ppasr_model_s* h, const float* x, const float* g, const float* b, int M, int D,
+                               const PadSkip& ps, hipStream_t st) {
+  if (!h->memory_out) return PPASR_OK;
+  if ((size_t)M * D > h->memory_floats) return fail(PPASR_ENOSPACE, "memory buffer too small (ppasr_set_memory_out)");
+  launch_memory_out(x, g, b, h->memory_out, M, D, ps, st);
+  return PPASR_OK;
+}
+
 // The head of the fused walks over the M = B x ps.Tp rows of x: CTC head (its re-packed weight in the fp16 x3 mode; on an
 // under-filled launch the vocabulary tiles over `slices` workgroups per row block, scratch = the conv1 buffer y1) ->
 // logits, frame argmax / maxprob (into the workspace when the caller wants none), probabilities in place from the logits
@@ -122,6 +133,7 @@ template <typename Spans>
 inline ppasr_status fused_head_tail(const ppasr_model_s* h, const float* x, float* probs, float* logits, int32_t* frame_argmax,
                                     float* frame_maxprob, float* ws, const WsLayout& wl, int B, int M, int slices,
                                     const PadSkip& ps, hipStream_t st, Spans&& spans) {
+  if (ppasr_status ms = memory_out(h, x, h->head.ln_g, h->head.ln_b, M, kD, ps, st)) return ms;
   float* lg = logits ? logits : probs;  // probs are produced in place from the logits tap
   int32_t* fa = frame_argmax ? frame_argmax : reinterpret_cast<int32_t*>(ws + wl.fa);
   float* fp = frame_maxprob ? frame_maxprob : ws + wl.fp;

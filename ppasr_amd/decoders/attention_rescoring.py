@@ -1,0 +1,144 @@
+"""Attention rescoring of CTC n-best lists with the checkpoint's own attention decoder (``decoder.left_decoder.*`` /
+``decoder.right_decoder.*``, the reference's ``BiTransformerDecoder``), on the HIP kernels behind ``ppasr_rescore``.
+
+The reference trains this decoder with every Conformer-family model and never calls it at inference; the decode mode is
+WeNet's ``attention_rescoring``: n-best of the CTC prefix beam search -> score each hypothesis with the left and right
+decoder over the encoder output -> add the CTC score -> best.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from ppasr_amd import _lib
+from ppasr_amd.decoders.beam_search_decoder import _text, beam_search_ids
+
+__all__ = ["AttentionRescorer", "attention_rescoring", "MAX_ROWS"]
+
+MAX_ROWS = 256  # rows per hypothesis (tokens + 1) the kernels are built for
+
+
+class AttentionRescorer:
+    """``state_dict``: the Paddle-layout checkpoint (only its ``decoder.*`` entries are read); ``decoder_conf``: the
+    section of the reference YAML (attention_heads, linear_units, num_blocks, r_num_blocks; dropout keys are accepted and
+    ignored).  Anything the kernels are not built for is refused at construction (``PPASR_EUNSUPPORTED``), a checkpoint
+    without the decoder's weights with ``PPASR_EMISSING``."""
+
+    _IGNORED = ("dropout_rate", "positional_dropout_rate", "self_attention_dropout_rate", "src_attention_dropout_rate")
+
+    def __init__(self, state_dict, vocab_size, decoder_conf=None, device="cuda:0", d_model=256, max_len=5000):
+        if not torch.cuda.is_available():
+            raise _lib.PPASRHipError("no HIP device visible: ppasr_amd has no CPU fallback")
+        conf = dict(decoder_conf or {})
+        for k in self._IGNORED:
+            conf.pop(k, None)
+        if not conf.pop("normalize_before", True):
+            raise _lib.PPASRHipError("attention decoder: normalize_before = False is not built", _lib.PPASR_EUNSUPPORTED)
+        if conf.pop("concat_after", False):
+            raise _lib.PPASRHipError("attention decoder: concat_after = True is not built", _lib.PPASR_EUNSUPPORTED)
+        if conf.pop("input_layer", "embed") != "embed" or not conf.pop("use_output_layer", True):
+            raise ValueError("attention decoder: input_layer 'embed' with an output layer only")  # decoder.py:171
+        self.heads = int(conf.pop("attention_heads", 4))
+        self.linear_units = int(conf.pop("linear_units", 2048))
+        self.num_blocks = int(conf.pop("num_blocks", 6))
+        self.r_num_blocks = int(conf.pop("r_num_blocks", 0))
+        max_len = int(conf.pop("max_len", max_len))
+        if conf:
+            raise ValueError("unknown decoder_conf keys: " + ", ".join(sorted(conf)))
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.vocab_size = int(vocab_size)
+        self.d_model = int(d_model)
+        sd = {k: v for k, v in state_dict.items() if k.startswith("decoder.")}
+        if not sd:  # (the library names the first weight it misses)
+            sd = {"__none__": np.zeros(1, np.float32)}
+        keep = []
+        blobs = (_lib.WeightBlob * len(sd))()
+        for i, (name, arr) in enumerate(sd.items()):
+            a = np.ascontiguousarray(arr, dtype=np.float32)
+            keep.append(a)
+            blobs[i].name = name.encode()
+            blobs[i].data_host = a.ctypes.data
+            blobs[i].ndim = a.ndim
+            for j in range(a.ndim):
+                blobs[i].shape[j] = a.shape[j]
+        desc = _lib.RescorerDesc(self.vocab_size, self.d_model, self.heads, self.linear_units, self.num_blocks,
+                                 self.r_num_blocks, max_len)
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.ppasr_rescorer_create(ctypes.byref(desc), blobs, len(sd), ctypes.byref(handle)))
+        self._h = handle
+        self._ws = {}
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self.lib.ppasr_rescorer_destroy(h)
+            self._h = None
+
+    def _workspace(self, B, Tp, nbest, max_tokens):
+        need = int(self.lib.ppasr_rescorer_workspace_bytes(self._h, B, Tp, nbest, max_tokens))
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def rescore(self, memory, out_lens, tokens, lens, ctc_scores, ctc_weight=0.5, reverse_weight=0.0,
+                return_token_logp=False, return_logits=False, workspace=None, out=None):
+        """memory [B, Tp, D] f32, out_lens [B] i32 or None, tokens [B, nbest, max_tokens] i32, lens [B, nbest] i32,
+        ctc_scores [B, nbest] f64 (the outputs of ``beam_search_ids``) -> dict of device tensors: att, r_att, total
+        [B, nbest] f64, best [B] i32 (+ token_logp [B, nbest, 2, max_tokens + 1], logits [.., V] when asked for).
+        Asynchronous on the current stream.  ``workspace`` / ``out``: caller-owned buffers (tests)."""
+        dev = self.device
+        memory = torch.as_tensor(memory, dtype=torch.float32).to(dev).contiguous()
+        tokens = torch.as_tensor(tokens, dtype=torch.int32).to(dev).contiguous()
+        lens = torch.as_tensor(lens, dtype=torch.int32).to(dev).contiguous()
+        ctc_scores = torch.as_tensor(ctc_scores, dtype=torch.float64).to(dev).contiguous()
+        ol = None if out_lens is None else torch.as_tensor(out_lens, dtype=torch.int32).to(dev).contiguous()
+        B, Tp, D = memory.shape
+        _, nbest, mt = tokens.shape
+        assert D == self.d_model and lens.shape == (B, nbest) and ctc_scores.shape == (B, nbest)
+        o = {} if out is None else out
+        new = lambda name, shape, dt: o[name] if name in o else torch.empty(shape, dtype=dt, device=dev)
+        res = dict(att=new("att", (B, nbest), torch.float64), r_att=new("r_att", (B, nbest), torch.float64),
+                   total=new("total", (B, nbest), torch.float64), best=new("best", (B,), torch.int32))
+        if return_token_logp:
+            res["token_logp"] = new("token_logp", (B, nbest, 2, mt + 1), torch.float32)
+        if return_logits:
+            res["logits"] = new("logits", (B, nbest, 2, mt + 1, self.vocab_size), torch.float32)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            ws = workspace if workspace is not None else self._workspace(B, Tp, nbest, mt)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(self.lib.ppasr_rescore(self._h, memory.data_ptr(), ptr(ol), B, Tp, ptr(tokens) if mt else None,
+                                              lens.data_ptr(), ctc_scores.data_ptr(), nbest, mt, float(ctc_weight),
+                                              float(reverse_weight), res["att"].data_ptr(), res["r_att"].data_ptr(),
+                                              res["total"].data_ptr(), res["best"].data_ptr(), ptr(res.get("token_logp")),
+                                              ptr(res.get("logits")), ws.data_ptr(), ws.numel(), stream))
+        return res
+
+
+def attention_rescoring(model, rescorer, probs, memory, out_lens, vocabulary, beam_size=10, ctc_weight=0.5,
+                        reverse_weight=0.0, cutoff_prob=0.99, cutoff_top_n=40, blank_id=0):
+    """probs [B, T', V] and memory [B, T', D] of one encode (``model.get_encoder_out(..., return_memory=True)``),
+    out_lens [B] valid frames or None -> per utterance ``(score, text)`` of the hypothesis with the largest total score.
+    The n-best list is the plain CTC prefix beam search's (no external scorer); search and rescoring are queued on the
+    current stream and read back once."""
+    del model  # (kept in the signature for symmetry with the other decoders: the encode already happened)
+    fl = None if out_lens is None else torch.as_tensor(out_lens, dtype=torch.int32)
+    tokens, lens, scores, _ = beam_search_ids(probs, beam_size, cutoff_prob, cutoff_top_n, blank_id, frame_lens=fl,
+                                              nbest=beam_size)
+    if tokens.shape[2] > MAX_ROWS - 1:  # the kernels take 255 tokens per hypothesis; longer ones are refused below
+        tokens = tokens[:, :, :MAX_ROWS - 1].contiguous()
+    res = rescorer.rescore(memory, fl, tokens, lens, scores, ctc_weight, reverse_weight)
+    best = res["best"].to(torch.int64)
+    idx = best[:, None, None].expand(-1, 1, tokens.shape[2])
+    pack = (tokens.gather(1, idx)[:, 0], lens.gather(1, best[:, None])[:, 0], res["total"].gather(1, best[:, None])[:, 0],
+            lens.max())
+    tk, ln, sc, longest = [t.cpu().numpy() for t in pack]  # (the read-back)
+    if int(longest) > tokens.shape[2]:
+        raise _lib.PPASRHipError(f"attention rescoring: a hypothesis of {int(longest)} tokens exceeds the "
+                                 f"{MAX_ROWS - 1} the kernels are built for; decode shorter segments",
+                                 _lib.PPASR_EUNSUPPORTED)
+    return [(float(sc[b]), _text(tk[b, :max(int(ln[b]), 0)].tolist(), vocabulary)) for b in range(tk.shape[0])]

@@ -58,7 +58,8 @@ def decoder_result(outs, vocabulary, decoder="ctc_greedy", beam_search_decoder=N
 
 
 def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer", beam_search_decoder=None,
-             display_result=False, trim_padding=False, overlap_decode=True, shard="batches"):
+             display_result=False, trim_padding=False, overlap_decode=True, shard="batches", rescorer=None,
+             rescoring_conf=None):
     """model: any ppasr_amd model with ``get_encoder_out(inputs, input_lens)``;
     batches: iterable of (inputs [B,T,F], labels [B,U] (-1 padded), input_lens [B], label_lens [B]) like the reference's
     test_loader.  -> mean error rate (float), -1 if there is nothing to score (trainer.py:643).
@@ -69,7 +70,13 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
     dealt to the ranks by padded work (ragged batches).  "buckets" ALWAYS has ``trim_padding=True`` semantics -- the
     encoder skips the padding and decoding covers each utterance's valid frames only, whatever ``trim_padding`` says --
     so for batches with padding its error rate equals ``shard="batches", trim_padding=True``, not the reference's
-    padded-row decoding; with ``decoder != "ctc_greedy"`` a ``beam_search_decoder`` is required (no silent greedy)."""
+    padded-row decoding; with ``decoder != "ctc_greedy"`` a ``beam_search_decoder`` is required (no silent greedy).
+    ``decoder="attention_rescoring"``: ``rescorer`` (an ``AttentionRescorer`` of the same checkpoint) is required and
+    ``rescoring_conf`` holds the keyword arguments of ``decoders.attention_rescoring.attention_rescoring`` (beam_size,
+    ctc_weight, reverse_weight, cutoff_prob, cutoff_top_n); ``shard="batches"`` only, encode and decode on one stream."""
+    rescoring = decoder == "attention_rescoring"
+    if rescoring and (rescorer is None or shard != "batches"):
+        raise ValueError("decoder='attention_rescoring' needs a rescorer and shard='batches'")
     dist = torch.distributed.is_available() and torch.distributed.is_initialized()
     if shard == "buckets":
         return _evaluate_bucketed(model, batches, vocab_list, decoder, metrics_type, beam_search_decoder, display_result,
@@ -81,7 +88,7 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
     eos = len(vocab_list) - 1
     total, count = 0.0, 0
     dev = getattr(model, "device", None)
-    pipelined = overlap_decode and dev is not None and torch.device(dev).type == "cuda"
+    pipelined = overlap_decode and dev is not None and torch.device(dev).type == "cuda" and not rescoring
     enc_stream = torch.cuda.Stream(device=dev) if pipelined else None
 
     def encode(inputs, input_lens):
@@ -90,7 +97,8 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
             set_skip_padding_if_built(model, True)
             frame_lens = model.valid_out_frames(input_lens, inputs.shape[1])
         try:
-            outs = model.get_encoder_out(inputs, input_lens)
+            outs = model.get_encoder_out(inputs, input_lens, return_memory=True) if rescoring else model.get_encoder_out(
+                inputs, input_lens)
         finally:
             if trim_padding:
                 set_skip_padding_if_built(model, False)
@@ -98,7 +106,12 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
 
     def score(outs, frame_lens, labels):
         nonlocal total, count
-        out_strings = decoder_result(outs, vocab_list, decoder, beam_search_decoder, frame_lens)
+        if rescoring:
+            from ppasr_amd.decoders.attention_rescoring import attention_rescoring
+            out_strings = [t for _, t in attention_rescoring(model, rescorer, outs[0], outs[1], frame_lens, vocab_list,
+                                                             **dict(rescoring_conf or {}))]
+        else:
+            out_strings = decoder_result(outs, vocab_list, decoder, beam_search_decoder, frame_lens)
         labels_str = labels_to_string(labels, vocab_list, eos=eos)
         for out_string, label in zip(out_strings, labels_str):
             err = wer(out_string, label) if metrics_type == "wer" else cer(out_string, label)

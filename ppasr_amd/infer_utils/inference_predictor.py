@@ -62,6 +62,17 @@ class InferencePredictor:
             from ppasr_amd.model_utils.deepspeech2.model import DeepSpeech2Model as cls
         self.model = cls(input_dim, vocab_size, streaming=streaming, encoder_conf=enc, state_dict=state_dict,
                          device=device)
+        # decoder: attention_rescoring -- the checkpoint's attention decoder (decoder.left_decoder.* / right_decoder.*,
+        # shaped by the YAML's decoder_conf) next to the encoder; a checkpoint without those weights raises here
+        self.rescorer = None
+        if _get(configs, "decoder") == "attention_rescoring":
+            if use_model == "deepspeech2":
+                raise ValueError("decoder: attention_rescoring needs a Conformer-family model (DeepSpeech2 has no "
+                                 "attention decoder)")
+            from ppasr_amd.decoders.attention_rescoring import AttentionRescorer
+            dec = _get(configs, "decoder_conf", {}) or {}
+            dec = dict(dec) if isinstance(dec, dict) else dict(vars(dec))
+            self.rescorer = AttentionRescorer(state_dict, vocab_size, dec, device=device, d_model=self.model.output_size)
         # (a configuration whose forward_chunk the library does not build -- input_layer: linear, an Efficient-Conformer
         #  behind conv2d6 / conv2d8 -- still serves predict(); predict_chunk_conformer then raises NotImplementedError)
         self._stream = None
@@ -96,6 +107,11 @@ class InferencePredictor:
     def predict_device(self, speech, speech_lengths):
         """-> probs [B,T',V] device tensor (no host round trip)."""
         return self.model.get_encoder_out(speech, speech_lengths)
+
+    def predict_device_memory(self, speech, speech_lengths):
+        """-> (probs [B,T',V], memory [B,T',D]) device tensors: the encoder output next to the probabilities, for the
+        attention decoder (Conformer families)."""
+        return self.model.get_encoder_out(speech, speech_lengths, return_memory=True)
 
     def predict_greedy(self, speech, speech_lengths, trim_to_length=False):
         """Fused encoder + greedy decode: -> (tokens, n_tokens, score) device tensors."""

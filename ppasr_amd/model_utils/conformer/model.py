@@ -35,7 +35,8 @@ class ConformerModel:
     """Drop-in for the inference half of the reference ``ConformerModel``.
 
     Args mirror ``conformer/model.py:17-29``; the training-only arguments
-    (decoder_conf, ctc_weight, ...) are accepted and ignored.  ``state_dict`` is a
+    (ctc_weight, ...) are accepted and ignored; ``decoder_conf`` is kept for ``decoders/attention_rescoring.py``, which
+    runs the checkpoint's attention decoder over ``get_encoder_out(..., return_memory=True)``.  ``state_dict`` is a
     Paddle-layout ``{name: np.ndarray}`` (what ``paddle.load('model.pdparams')`` holds).
     """
 
@@ -50,6 +51,7 @@ class ConformerModel:
         self.input_dim = input_dim
         self.vocab_size = vocab_size
         self.streaming = streaming
+        self.decoder_conf = dict(decoder_conf or {})
         conf = dict(encoder_conf or {})
         self.output_size = int(conf.get("output_size", 256))
         self.attention_heads = int(conf.get("attention_heads", 4))
@@ -154,16 +156,29 @@ class ConformerModel:
         _lib.check(self.lib.ppasr_encode(self._h, speech.data_ptr(), lens.data_ptr(), B, T, ptr(probs), ptr(logits),
                                          ptr(fa), ptr(fp), ws.data_ptr(), ws.numel(), stream))
 
-    def get_encoder_out(self, speech, speech_lengths, return_logits=False):
-        """-> ctc_probs [B, T', V] (device tensor).  conformer/model.py:148-162"""
+    def get_encoder_out(self, speech, speech_lengths, return_logits=False, return_memory=False):
+        """-> ctc_probs [B, T', V] (device tensor).  conformer/model.py:148-162
+        ``return_memory``: also the encoder output [B, T', D] (the first return value of the reference's
+        ``encoder(xs, lens, -1, -1)``, what the attention decoder attends to) -> (probs, memory); the same launches plus
+        one small kernel, probs bit-identical (``ppasr_set_memory_out``)."""
         speech, lens = self._prep(speech, speech_lengths)
         B, T, _ = speech.shape
         Tp = self.out_frames(T)
         probs = torch.empty(B, Tp, self.vocab_size, dtype=torch.float32, device=self.device)
         logits = torch.empty_like(probs) if return_logits else None
+        memory = torch.empty(B, Tp, self.output_size, dtype=torch.float32, device=self.device) if return_memory else None
         with torch.cuda.device(self.device):
-            self._encode(speech, lens, probs=probs, logits=logits)
-        return (probs, logits) if return_logits else probs
+            if return_memory:
+                _lib.check(self.lib.ppasr_set_memory_out(self._h, memory.data_ptr(), memory.numel()))
+            try:
+                self._encode(speech, lens, probs=probs, logits=logits)
+            finally:
+                if return_memory:
+                    _lib.check(self.lib.ppasr_set_memory_out(self._h, None, 0))
+        out = (probs, logits) if return_logits else (probs,)
+        if return_memory:
+            out = out + (memory,)
+        return out if len(out) > 1 else out[0]
 
     def encode_greedy(self, speech, speech_lengths, trim_to_length=False, blank=0):
         """Fused path: features -> (tokens [B,T'] i32 (-1 padded), n_tokens [B] i32, score [B] f64), all on

@@ -52,6 +52,13 @@ class PPASRPredictor:
         self.greedy_last_max_prob_list = None
         self.greedy_last_max_index_list = None
         self.beam_search_decoder = None
+        if self.configs.decoder == "attention_rescoring":
+            if self.configs.use_model == "deepspeech2":
+                raise ValueError("decoder: attention_rescoring needs a Conformer-family model (DeepSpeech2 has no "
+                                 "attention decoder)")
+            # WeNet's decode defaults with the shipped reverse_weight (configs/conformer.yml)
+            self._rescoring_conf = dict(beam_size=10, ctc_weight=0.5, reverse_weight=0.3, cutoff_prob=0.99, cutoff_top_n=40)
+            self._rescoring_conf.update(dict(self.configs.get("attention_rescoring_decoder_conf") or {}))
         if self.configs.decoder == "ctc_beam_search":
             from ppasr_amd.decoders.beam_search_decoder import BeamSearchDecoder
             self.beam_search_decoder = BeamSearchDecoder(vocab_list=self._text_featurizer.vocab_list,
@@ -78,6 +85,14 @@ class PPASRPredictor:
         feat = self._audio_featurizer.featurize(samples, sr)
         input_data = np.asarray(feat, np.float32)[np.newaxis, :]
         audio_len = np.array([input_data.shape[1]]).astype(np.int64)
+        if self.configs.decoder == "attention_rescoring":
+            if use_pun or is_itn:
+                raise NotImplementedError("punctuation / ITN are outside the hot path")
+            from ppasr_amd.decoders.attention_rescoring import attention_rescoring
+            probs, memory = self.predictor.predict_device_memory(input_data, audio_len)
+            score, text = attention_rescoring(self.predictor.model, self.predictor.rescorer, probs, memory, None,
+                                              self._text_featurizer.vocab_list, **self._rescoring_conf)[0]
+            return {"text": text, "score": score}
         probs = self.predictor.predict_device(input_data, audio_len)[0]  # stays on the device
         score, text = self.decode(output_data=probs, use_pun=use_pun, is_itn=is_itn)
         return {"text": text, "score": score}
@@ -114,6 +129,10 @@ class PPASRPredictor:
         3 cached feature frames, required_cache_size = -16)."""
         if not self.configs.streaming:
             raise Exception(f"不支持改该模型流式识别，当前模型：{self.configs.use_model}")
+        if self.configs.decoder == "attention_rescoring":
+            raise NotImplementedError("decoder: attention_rescoring scores whole utterances (it attends to the encoder "
+                                      "output of every frame): use predict / predict_long, or ctc_greedy / "
+                                      "ctc_beam_search for predict_stream")
         if isinstance(audio_data, np.ndarray):
             samples, _ = load_audio(audio_data, sample_rate)
         elif isinstance(audio_data, bytes):
