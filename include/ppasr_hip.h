@@ -721,7 +721,8 @@ PPASR_API size_t ppasr_rescorer_workspace_bytes(ppasr_rescorer r, int B, int Tp,
  * direction, position) that exists (a device-side row table made from `lens`).
  *   memory [B,Tp,D] f32; out_lens [B] i32 valid memory frames (NULL: all Tp; cross-attention sees t < out_lens[b] only)
  *   tokens [B,nbest,max_tokens] i32, lens [B,nbest] i32 (-1: no such hypothesis), ctc_scores [B,nbest] f64 (-log P):
- *     the three outputs of ppasr_ctc_beam_search as they are
+ *     the three outputs of ppasr_ctc_beam_search as they are.  Out-of-range values are clamped, not refused: a lens
+ *     entry above max_tokens counts as max_tokens, and a token id outside [0, V - 1] inside a hypothesis as 0 or V - 1.
  *   sos = eos = V - 1.  att = sum_j logp_left[j][y_j] + logp_left[n][eos] over the input [sos, y0 .. y(n-1)]; r_att the
  *   same over the reversed tokens with the right decoder; total = (1 - reverse_weight) att + reverse_weight r_att +
  *   ctc_weight (-ctc_scores).

@@ -6,7 +6,12 @@ log-probabilities of a row spread over several nats.
 
 A case is admitted only if, for every utterance, the float64 top-2 margin of `total` exceeds MARGIN_FACTOR x the score
 tolerance (score_tol): then `best` must equal the float64 argmax (tests/test_rescore_oracle_cpu.py asserts it for the
-whole table, so nothing is skipped at run time)."""
+whole table, so nothing is skipped at run time).
+
+EDGE_CASES (constructed inputs on the kernels' tile edges) and TRAINED_CASES (weights that leave the random
+initialisation in one respect: trained_like) follow the drawn table; tests/test_rescore_edges_gpu.py runs them."""
+import contextlib
+
 import numpy as np
 
 import numerics
@@ -69,7 +74,10 @@ FIXTURE_CASES = ("v67_l17_n3_b3_t33", "v67_l2_n3_b1_t31", "v67_l33_n3_b1_t33")  
 
 
 def weights(case):
-    return decoder_state_dict(1000 + case["seed"], case["V"], case["units"], *case["blocks"])
+    sd = decoder_state_dict(1000 + case["seed"], case["V"], case["units"], *case["blocks"])
+    if case.get("trained"):
+        sd = trained_like(sd, *case["trained"])
+    return sd
 
 
 def inputs(case):
@@ -141,3 +149,186 @@ def errors(case, got, ref):
         d = max(np.abs(got[k][b][fin] - ref[k][b][fin]).max() if fin.any() else 0.0 for k in ("att", "r_att", "total"))
         e_sc = max(e_sc, float(d / (case["L"] * max(scale, 1.0))))
     return e_lg, e_lp, e_sc
+
+
+# ---- edge cases: constructed, not drawn -----------------------------------------------------------------------------------
+# Each case places its inputs on one edge of the kernels of csrc/rescore_kernels.hip, at the smallest shape that reaches
+# it.  Fields beyond those of CASES:
+#   group     what the case is about (tests/test_rescore_oracle_cpu.py pairs each oracle mutation with a group)
+#   out_lens  explicit valid memory frames per utterance (default: all Tp)
+#   over      (utterance, value): a second call with out_lens[utterance] = value > Tp must equal this one byte for byte
+#   lens      explicit hypothesis lengths [B][nbest] (default: the longest, the empty one, ..., an absent one)
+#   force     token ids every utterance's first hypothesis carries, so that each occurs as a target of both directions
+#   tie       (i, j): hypothesis j is a copy of hypothesis i -- tokens, length and CTC score -- and the pair leads the rest
+#   lead      per utterance the hypothesis whose CTC score is set 400 below the others', so that it wins
+#   ctc_step  scale of the CTC score steps between hypotheses (default 1)
+#   max_len   positional table length of the rescorer (default: the library's)
+#   trained   (kind, level) of trained_like()
+def _e(group, seed, V=67, L=9, nbest=3, B=2, Tp=33, blocks=(1, 1), units=256, rw=0.3, cw=0.5, **kw):
+    return dict(group=group, seed=seed, V=V, L=L, nbest=nbest, B=B, Tp=Tp, blocks=blocks, units=units, reverse_weight=rw,
+                ctc_weight=cw, short=False, **kw)
+
+
+KEY_COUNTS = (0, 1, 7, 8, 9, 63, 64, 65, 128, 129)  # around the 8 key slices of a row and the 64-key tile of k_dec_cross_attn
+FORCED_COLUMNS = (1, 31, 32, 255, 256)  # and V - 2: wave and tile edges of k_dec_output's columns
+
+
+def _forced(V):
+    return tuple(sorted({c for c in FORCED_COLUMNS + (V - 2,) if 1 <= c <= V - 2}))
+
+
+def _vocab(seed, V):
+    if V == 2:  # no token between blank and sos / eos: only empty and absent hypotheses
+        return _e("vocab", seed, V=2, L=3, lens=[[0, 0, -1], [0, -1, 0]])
+    return _e("vocab", seed, V=V, force=_forced(V))
+
+
+EDGE_CASES = {
+    # cross-attention key tiles
+    "keys_b10_t129": _e("keys", 101, L=5, B=10, Tp=129, out_lens=list(KEY_COUNTS), over=(9, 1000)),
+    # right decoder deeper than the left; total without att; total without the CTC score
+    "blocks_1_3": _e("blocks", 111, blocks=(1, 3), rw=0.3),
+    "blocks_2_6_rw1": _e("blocks", 112, blocks=(2, 6), rw=1.0, lead=[0, 1]),
+    "blocks_3_3_cw0": _e("blocks", 113, blocks=(3, 3), cw=0.0),
+    # FFN width: one chunk, an odd multiple, the limit
+    "units_256": _e("units", 121, units=256),
+    "units_768": _e("units", 122, units=768, lead=[0, 0]),
+    "units_4096": _e("units", 123, units=4096),
+    # vocabulary tiles of the output layer
+    "vocab_2": _vocab(131, 2),
+    "vocab_3": _vocab(132, 3),
+    "vocab_32": _vocab(133, 32),
+    "vocab_33": _vocab(134, 33),
+    "vocab_256": _vocab(135, 256),
+    "vocab_257": _vocab(136, 257),
+    "vocab_512": _vocab(137, 512),
+    # the row table: a group without rows first / in the middle / last, no row at all, nbest beyond k_dec_score's block,
+    # groups that end exactly on a tile (17 + 8 + 7 = 32 rows, 17 + 17 + 17 + 13 = 64 rows), L = max_len
+    "rows_absent_u0": _e("rows", 141, B=4, lens=[[-1, -1, -1], [8, 0, 3], [8, 2, -1], [8, 0, 5]]),
+    "rows_absent_u2": _e("rows", 141, B=4, lens=[[8, 0, 3], [8, 2, -1], [-1, -1, -1], [8, 0, 5]]),
+    "rows_absent_u3": _e("rows", 141, B=4, lens=[[8, 0, 3], [8, 2, -1], [8, 0, 5], [-1, -1, -1]]),
+    "rows_all_absent": _e("rows", 142, B=4, lens=[[-1, -1, -1]] * 4),
+    "rows_n70_l2": _e("rows", 143, L=2, nbest=70, lead=[66, 68]),  # the winners sit behind the block's first stride
+    "rows_32_and_64": _e("rows", 144, L=17, nbest=4, lens=[[16, 7, 6, -1], [16, 16, 16, 12]]),
+    "rows_l17_maxlen17": _e("rows", 145, L=17, max_len=17),
+    # exact ties: `best` is the lower index
+    "tie_0_1": _e("tie", 151, L=5, nbest=4, lens=[[4, 4, 2, 0], [3, 3, 4, -1]], tie=(0, 1)),
+    "tie_1_3": _e("tie", 152, L=5, nbest=4, lens=[[4, 2, 0, 2], [0, 4, 3, 4]], tie=(1, 3)),
+    "tie_8_9": _e("tie", 153, L=5, nbest=10, lens=[[4, 0, 1, 2, 3, 4, -1, 2, 3, 3], [1, 2, 3, 4, 0, -1, 4, 3, 4, 4]], tie=(8, 9)),
+    # the reordering test's case: (3, 3) blocks, mixed lengths with an empty and an absent hypothesis
+    "reorder_b3_n5": _e("reorder", 161, B=3, nbest=5, blocks=(3, 3), units=1024,
+                        lens=[[8, 0, 3, -1, 5], [2, 8, -1, 0, 7], [0, 6, 8, 1, -1]], out_lens=[33, 20, 29]),
+}
+
+
+def edge_inputs(case):
+    """inputs() for a case of EDGE_CASES / TRAINED_CASES: the same dict, built from the case's explicit fields; only the
+    memory, the free tokens and the CTC score steps are drawn."""
+    rng = np.random.default_rng(case["seed"])
+    B, nbest, L, Tp, V = case["B"], case["nbest"], case["L"], case["Tp"], case["V"]
+    mt = L - 1
+    memory = rng.standard_normal((B, Tp, D)).astype(np.float32)
+    out_lens = np.asarray(case.get("out_lens", [Tp] * B), np.int32)
+    assert out_lens.shape == (B,)
+    if "lens" in case:
+        lens = np.asarray(case["lens"], np.int32)
+    else:
+        lens = rng.integers(0, mt + 1, (B, nbest)).astype(np.int32)
+        lens[:, 0] = mt
+        if nbest >= 3:
+            lens[:, 1] = 0
+            lens[:, nbest - 1] = -1
+    assert lens.shape == (B, nbest) and lens.max() <= mt
+    tokens = np.full((B, nbest, max(mt, 1)), -1, np.int32)[:, :, :mt]
+    for b in range(B):
+        for k in range(nbest):
+            n = int(lens[b, k])
+            if n > 0:
+                tokens[b, k, :n] = rng.integers(1, V - 1, n)
+        force = case.get("force", ())
+        if force:
+            assert lens[b, 0] == mt >= len(force)
+            tokens[b, 0, (np.arange(len(force)) + b) % mt] = force
+    ctc = np.cumsum(rng.uniform(0.5, 6.0, (B, nbest)) * case.get("ctc_step", 1.0), axis=1) + rng.uniform(0.0, 30.0, (B, 1))
+    for b, k in enumerate(case.get("lead", ())):
+        assert lens[b, k] >= 0
+        ctc[b, k] = ctc[b].min() - 400.0  # (a random decoder gives a token about -7)
+    if "tie" in case:
+        i, j = case["tie"]
+        others = [k for k in range(nbest) if k not in (i, j)]
+        ctc[:, others] += 200.0  # the pair leads whatever the decoders say about <= L tokens
+        tokens[:, j], lens[:, j], ctc[:, j] = tokens[:, i], lens[:, i], ctc[:, i]
+    return dict(memory=memory, out_lens=out_lens, tokens=np.ascontiguousarray(tokens), lens=lens,
+                ctc_scores=ctc.astype(np.float64))
+
+
+def case_inputs(case):
+    return edge_inputs(case) if "group" in case else inputs(case)
+
+
+def expected_best(case, ref):
+    """the float64 argmax (numpy: the lowest index of the largest total, which is the lower duplicate of a tie case)"""
+    return np.asarray(ref["total"]).argmax(1).astype(np.int32)
+
+
+# ---- trained-like weights --------------------------------------------------------------------------------------------------
+def trained_like(sd, kind, level):
+    """A new state dict that leaves the random initialisation in ONE respect (the arrays it changes are copies):
+      offset  `level` added to every embedding column and to every linear_out / w_2 bias: the residual stream of every
+              row moves by 16 x level at the embedding and by 3 x level per block, so every LayerNorm sees
+              |row mean| >> row std
+      sharp   linear_q / linear_k weights of both attentions x level: scores grow by level^2, attention is near one-hot
+      wide    output_layer.weight x level: logits of about +- 8 x level"""
+    ends = {"offset": ("embed.0.weight", ".linear_out.bias", ".w_2.bias"), "sharp": (".linear_q.weight", ".linear_k.weight"),
+            "wide": ("output_layer.weight",)}[kind]
+    out = dict(sd)
+    for k, v in sd.items():
+        if k.endswith(ends):
+            a = np.asarray(v, np.float32)
+            out[k] = np.ascontiguousarray(a + np.float32(level) if kind == "offset" else a * np.float32(level))
+    return out
+
+
+@contextlib.contextmanager
+def conditioning(oracle):
+    """Records on `oracle` (float64) while the block runs -> dict: "ln" the smallest |row mean| / row std over every
+    LayerNorm input row, "score" the largest max - min of an attention row's scores over the keys it sees, "logit" the
+    largest max - min of a row's logits."""
+    rec = {"ln": np.inf, "score": 0.0, "logit": 0.0}
+    oracle.rec = rec
+    try:
+        yield rec
+    finally:
+        oracle.rec = None
+
+
+REACHED = {"offset": lambda rec: rec["ln"], "sharp": lambda rec: rec["score"], "wide": lambda rec: rec["logit"]}
+
+
+def _t(seed, kind, level, floor, **kw):
+    return _e("trained", seed, L=17, B=2, blocks=(2, 2), units=1024, trained=(kind, level), floor=floor, **kw)
+
+
+# Levels, chosen on the CPU (V 67, L 17, nbest 3, B 2, Tp 33, blocks (2, 2)); e32 = the float32 oracle's (logits,
+# log-probabilities, scores) errors against float64, `reached` what conditioning() measured, `floor` what the CPU test
+# asserts of it:
+#   plain      e32 (5e-7, 5e-7, 3e-8); reached: |mean| / std 4e-4, score spread 16, logit spread 16
+#   offset 16  e32 (8.0e-6, 5.1e-6, 1.0e-6)  |mean| / std >= 48    ln_one_pass 18 / 21 / 3 x tol
+#   offset 64  e32 (3.7e-5, 3.0e-5, 3.8e-6)  |mean| / std >= 193   ln_one_pass 67 / 63 / 21 x tol
+#   sharp 4    e32 (2.0e-6, 2.5e-6, 1.2e-7)  score spread 277      softmax_without_max > 1000 x tol
+#   sharp 8    e32 (4.8e-6, 2.7e-6, 1.3e-7)  score spread 1088     softmax_without_max > 1000 x tol
+#   wide 12    e32 (7.6e-7, 6.1e-7, 5.8e-8)  logit spread 199, lowest log-probability -136   softmax_without_max: NaN
+#   wide 16    e32 (6.6e-7, 7.3e-7, 4.8e-8)  logit spread 265, lowest log-probability -181   softmax_without_max: NaN
+# Not chosen: offset 8 (|mean| / std 24) leaves ln_one_pass at 6.7 x tol only; sharp 3 (spread 156) keeps every
+# |score| under 88, where an fp32 softmax without its maximum is still exact, and wide 6 (spread 99) likewise.  Every
+# tolerance stays far below numerics.TOL_CAP (the largest is 4 x 3.7e-5).  The kinds are not combined: all three at once
+# (offset 32, sharp 8, wide 12) measured a logits e32 of 3.8e-4, four times which is above TOL_CAP.
+TRAINED_CASES = {
+    "offset_16": _t(171, "offset", 16.0, 40.0),
+    "offset_64": _t(171, "offset", 64.0, 150.0),
+    "sharp_4": _t(171, "sharp", 4.0, 200.0),
+    "sharp_8": _t(171, "sharp", 8.0, 800.0),
+    "wide_12": _t(171, "wide", 12.0, 150.0, ctc_step=10.0),
+    "wide_16": _t(171, "wide", 16.0, 200.0, ctc_step=10.0),
+}
+ALL_EDGE_CASES = dict(EDGE_CASES, **TRAINED_CASES)

@@ -9,7 +9,12 @@ that no padding, batch mask or launch shape takes part.
     att   = sum_j log_softmax(logits[j])[target_j]
     total = (1 - reverse_weight) * att + reverse_weight * r_att + ctc_weight * (-ctc_score)
 
-`mut` names one deliberate bug (tests/test_rescore_oracle_cpu.py)."""
+`mut` names one deliberate bug (tests/test_rescore_oracle_cpu.py): MUTATIONS are bugs of the decoder's definition, EDGE_MUTATIONS
+what a kernel could plausibly get wrong at a tile edge (a key tile, a key slice, a key / value slot, an FFN chunk, a
+vocabulary tile, a tie) or on trained-like weights (fp32 one-pass LayerNorm statistics, a softmax without its maximum).
+
+`rec` (a dict, set by decoder_cases.conditioning) collects what the trained-like cases state about themselves: the
+smallest |row mean| / row std a LayerNorm saw, the widest attention-score row and the widest logit row."""
 import math
 
 import numpy as np
@@ -17,6 +22,9 @@ import torch
 
 MUTATIONS = ("causal_no_diagonal", "one_frame_past_out_lens", "no_eos", "left_embedding_for_right", "no_after_norm",
              "no_sqrt_d")
+EDGE_MUTATIONS = ("cross_keys_first_tile_only", "cross_every_eighth_slice_dropped", "right_reads_left_kv_slot",
+                  "ffn_last_chunk_dropped", "target_column_mod_256", "vocab_padded_columns_counted", "last_index_on_tie",
+                  "best_among_first_64", "ln_one_pass", "softmax_without_max")
 EPS = 1e-12  # LayerNorm(epsilon=1e-12) of decoder.py
 
 
@@ -32,8 +40,9 @@ def pe_table(n, d, dtype):
 
 class DecoderOracle:
     def __init__(self, sd, vocab_size, num_blocks, r_num_blocks, heads=4, dtype=torch.float64, mut=None):
-        assert mut is None or mut in MUTATIONS, mut
+        assert mut is None or mut in MUTATIONS + EDGE_MUTATIONS, mut
         self.V, self.H, self.dtype, self.mut = vocab_size, heads, dtype, mut
+        self.rec = None
         self.blocks = {"left": num_blocks, "right": r_num_blocks}
         self.w = {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in sd.items() if k.startswith("decoder.")}
         self.d = self.w["decoder.left_decoder.embed.0.weight"].shape[1]
@@ -41,23 +50,47 @@ class DecoderOracle:
 
     def _ln(self, x, prefix):
         g, b = self.w[prefix + ".weight"], self.w[prefix + ".bias"]
+        if self.rec is not None:
+            r = x.double()
+            ratio = r.mean(-1).abs() / r.std(-1, unbiased=False).clamp_min(1e-300)
+            self.rec["ln"] = min(self.rec["ln"], float(ratio.min()))
+        if self.mut == "ln_one_pass":  # fp32 statistics, var = max(E[x^2] - E[x]^2, 0)
+            x32 = x.to(torch.float32)
+            mu = x32.mean(-1, keepdim=True)
+            var = ((x32 * x32).mean(-1, keepdim=True) - mu * mu).clamp_min(0.0)
+            return ((x32 - mu) * torch.rsqrt(var + np.float32(EPS))).to(x.dtype) * g + b
         mu = x.mean(-1, keepdim=True)
         var = ((x - mu) ** 2).mean(-1, keepdim=True)
         return (x - mu) / torch.sqrt(var + EPS) * g + b
 
+    def _softmax(self, s, mask):
+        """softmax over the last axis of s [.., Lk] with mask (True = attend) already applied as -inf"""
+        if self.mut == "softmax_without_max":  # fp32 exp(s) / sum exp(s): inf / inf or 0 / 0 once |s| passes ~88
+            e = torch.exp(s.to(torch.float32)).masked_fill(~mask, 0.0)
+            return (e / e.sum(-1, keepdim=True)).to(s.dtype)
+        return torch.softmax(s, -1)
+
     def _lin(self, x, prefix):
         return x @ self.w[prefix + ".weight"] + self.w[prefix + ".bias"]  # Paddle Linear: weight [in, out]
 
-    def _mha(self, q_in, kv_in, mask, prefix):
-        """MultiHeadedAttention.forward (conformer/attention.py): mask [Lq, Lk] bool, True = attend"""
+    def _mha(self, q_in, kv_in, mask, prefix, kv_prefix=None):
+        """MultiHeadedAttention.forward (conformer/attention.py): mask [Lq, Lk] bool, True = attend; kv_prefix: the
+        attention whose linear_k / linear_v are used (a mutation; None: the attention's own)"""
         Lq, Lk, H = q_in.shape[0], kv_in.shape[0], self.H
         dk = self.d // H
+        kvp = kv_prefix or prefix
         q = self._lin(q_in, prefix + ".linear_q").reshape(Lq, H, dk).transpose(0, 1)
-        k = self._lin(kv_in, prefix + ".linear_k").reshape(Lk, H, dk).transpose(0, 1)
-        v = self._lin(kv_in, prefix + ".linear_v").reshape(Lk, H, dk).transpose(0, 1)
+        k = self._lin(kv_in, kvp + ".linear_k").reshape(Lk, H, dk).transpose(0, 1)
+        v = self._lin(kv_in, kvp + ".linear_v").reshape(Lk, H, dk).transpose(0, 1)
         s = q @ k.transpose(1, 2) / math.sqrt(dk)
+        if self.rec is not None and Lk > 0:
+            hi = s.masked_fill(~mask[None], float("-inf")).amax(-1)
+            lo = s.masked_fill(~mask[None], float("inf")).amin(-1)
+            spread = (hi - lo)[torch.isfinite(hi - lo)]
+            if spread.numel():
+                self.rec["score"] = max(self.rec["score"], float(spread.max()))
         s = s.masked_fill(~mask[None], float("-inf"))
-        a = torch.softmax(s, -1)
+        a = self._softmax(s, mask[None].expand_as(s))
         a = torch.nan_to_num(a, nan=0.0).masked_fill(~mask[None], 0.0)  # a row without keys attends to nothing
         ctx = (a @ v).transpose(0, 1).reshape(Lq, self.d)
         return self._lin(ctx, prefix + ".linear_out")
@@ -75,15 +108,26 @@ class DecoderOracle:
         Tp = memory.shape[0]
         keys = min(int(out_len) + (1 if self.mut == "one_frame_past_out_lens" else 0), Tp)
         mem = torch.as_tensor(np.asarray(memory)).to(self.dtype)[:keys]
+        if self.mut == "cross_keys_first_tile_only":
+            mem = mem[:64]
+        elif self.mut == "cross_every_eighth_slice_dropped":
+            mem = mem[torch.arange(mem.shape[0]) % 8 != 7]
+        keys = mem.shape[0]
         causal = torch.tril(torch.ones(n, n, dtype=torch.bool), diagonal=-1 if self.mut == "causal_no_diagonal" else 0)
         full = torch.ones(n, keys, dtype=torch.bool)
         for i in range(self.blocks[side]):
             lp = f"{p}.decoders.{i}"
             y = self._ln(x, lp + ".norm1")
             x = x + self._mha(y, y, causal, lp + ".self_attn")
-            x = x + self._mha(self._ln(x, lp + ".norm2"), mem, full, lp + ".src_attn")
+            kvp = None
+            if right and self.mut == "right_reads_left_kv_slot":
+                kvp = f"decoder.left_decoder.decoders.{min(i, self.blocks['left'] - 1)}.src_attn"
+            x = x + self._mha(self._ln(x, lp + ".norm2"), mem, full, lp + ".src_attn", kvp)
             y = self._ln(x, lp + ".norm3")
-            x = x + self._lin(torch.relu(self._lin(y, lp + ".feed_forward.w_1")), lp + ".feed_forward.w_2")
+            h = torch.relu(self._lin(y, lp + ".feed_forward.w_1"))
+            if self.mut == "ffn_last_chunk_dropped":
+                h = torch.cat([h[:, :-256], torch.zeros_like(h[:, -256:])], 1)
+            x = x + self._lin(h, lp + ".feed_forward.w_2")
         if self.mut != "no_after_norm":
             x = self._ln(x, p + ".after_norm")
         return self._lin(x, p + ".output_layer")
@@ -93,7 +137,20 @@ class DecoderOracle:
         lg = self.logits(memory, out_len, tokens, right)
         toks = list(tokens)[::-1] if right else list(tokens)
         tgt = torch.tensor(toks + [self.V - 1], dtype=torch.long)
-        lp = torch.log_softmax(lg, -1).gather(1, tgt[:, None])[:, 0]
+        if self.rec is not None:
+            self.rec["logit"] = max(self.rec["logit"], float((lg.amax(-1) - lg.amin(-1)).max()))
+        if self.mut == "softmax_without_max":  # fp32 log(exp(v) / sum exp(v))
+            e = torch.exp(lg.to(torch.float32))
+            lsm = torch.log(e / e.sum(-1, keepdim=True)).to(lg.dtype)
+        elif self.mut == "vocab_padded_columns_counted":  # the columns V .. Vp - 1 of the last 256-column tile, logit 0
+            pad = (self.V + 255) // 256 * 256 - self.V
+            lsm = lg - torch.logsumexp(torch.cat([lg, torch.zeros(lg.shape[0], pad, dtype=lg.dtype)], 1), -1, keepdim=True)
+        else:
+            lsm = torch.log_softmax(lg, -1)
+        if self.mut == "target_column_mod_256":  # the target's logit from the column's place in its tile
+            lp = lg.gather(1, (tgt % 256)[:, None])[:, 0] - (lg - lsm)[:, 0]
+        else:
+            lp = lsm.gather(1, tgt[:, None])[:, 0]
         if self.mut == "no_eos":
             lp = torch.cat([lp[:-1], torch.zeros(1, dtype=lp.dtype)])
         return lp, lg
@@ -184,4 +241,9 @@ class DecoderOracle:
                     (r_att if side else att)[b, k] = float(lp.double().sum())
                 total[b, k] = ((1.0 - reverse_weight) * att[b, k] + reverse_weight * r_att[b, k]
                                + ctc_weight * (-float(ctc_scores[b, k])))
-        return dict(att=att, r_att=r_att, total=total, best=total.argmax(1).astype(np.int32), token_logp=tlp, logits=lgs)
+        best = total.argmax(1)  # the lowest index on a tie
+        if self.mut == "last_index_on_tie":
+            best = total.shape[1] - 1 - total[:, ::-1].argmax(1)
+        elif self.mut == "best_among_first_64":  # the argmax without the stride over k_dec_score's 64 threads
+            best = total[:, :64].argmax(1)
+        return dict(att=att, r_att=r_att, total=total, best=best.astype(np.int32), token_logp=tlp, logits=lgs)
