@@ -327,6 +327,18 @@ PPASR_API int          ppasr_lm_eos(ppasr_lm_handle lm);
  * Scorer::get_log_cond_prob for a window of `order` LM word indices (oldest first) on that table. */
 PPASR_API ppasr_status ppasr_lm_debug_load_host(const char* model_path, const char* const* vocab_utf8, int V, ppasr_lm_handle* out);
 PPASR_API double       ppasr_lm_debug_host_score(ppasr_lm_handle lm, const int32_t* window);
+/* Verification hooks of the device scorer (csrc/lm.h).  ppasr_lm_debug_table copies out the host mirror of the n-gram
+ * table as it is laid out for the device: 16-byte slots (uint64 key, 0 = empty; float log10 prob; float log10 back-off),
+ * `mask + 2` of them -- the power-of-two table and, behind it, the copy of slot 0.  It returns that slot count; with
+ * slots_out == NULL it only returns it, otherwise n_slots must equal it (else -1).  Works on a host-only handle.
+ * ppasr_lm_debug_device_score evaluates Scorer::get_log_cond_prob of n_windows windows ([n_windows][order] int32 LM word
+ * indices, oldest first, device memory) with the device functions, one thread per window, into out_dev[n_windows]
+ * (doubles, device memory): form 0 = the plain back-off walk, 1 = the factorised form the search uses per (hypothesis,
+ * candidate) pair, 2 = the same with the candidate's unigram handed in by the caller.  PPASR_EINVAL for a host-only
+ * handle, a null pointer, n_windows < 0 or another form; n_windows == 0 launches nothing. */
+PPASR_API long long    ppasr_lm_debug_table(ppasr_lm_handle lm, void* slots_out, long long n_slots);
+PPASR_API ppasr_status ppasr_lm_debug_device_score(ppasr_lm_handle lm, const int32_t* windows_dev, int n_windows, int form,
+                                                   double* out_dev, void* stream);
 PPASR_API ppasr_status ppasr_lm_destroy(ppasr_lm_handle lm);
 PPASR_API int          ppasr_lm_order(ppasr_lm_handle lm);
 PPASR_API int          ppasr_lm_is_character_based(ppasr_lm_handle lm);

@@ -140,6 +140,8 @@ SYMBOLS = [
     ("ppasr_lm_debug_load_host", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                                 ctypes.POINTER(_vp)]),
     ("ppasr_lm_debug_host_score", ctypes.c_double, [_vp, _vp]),
+    ("ppasr_lm_debug_table", ctypes.c_longlong, [_vp, _vp, ctypes.c_longlong]),
+    ("ppasr_lm_debug_device_score", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     ("ppasr_lm_format", ctypes.c_char_p, [_vp]),
     ("ppasr_lm_word_index", ctypes.c_int, [_vp, ctypes.c_int]),
     ("ppasr_lm_bos", ctypes.c_int, [_vp]),

@@ -21,6 +21,28 @@
 
 namespace {
 
+// ppasr_lm_debug_device_score: one window per thread through the device functions of lm.h, unchanged
+__global__ void __launch_bounds__(256) k_lm_debug_score(LmDev lm, const int32_t* __restrict__ windows, int n_windows,
+                                                        int form, double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_windows) return;
+  const int order = lm.order;
+  const int32_t* win = windows + (size_t)i * order;
+  if (form == 0) {
+    out[i] = lm_log_cond_prob(lm, win);
+    return;
+  }
+  float acc[kLmMaxOrder + 1];
+  lm_context_acc(lm, win, acc);
+  const int32_t word = win[order - 1];
+  if (form == 1) {
+    out[i] = lm_pair_log_cond_prob(lm, win, acc, word);
+    return;
+  }
+  const float uni = (word > 0 && word < lm.n_words) ? lm.uni_prob[word] : __builtin_nanf("");
+  out[i] = lm_pair_log_cond_prob(lm, win, acc, word, uni);
+}
+
 int utf8_len(const std::string& s) {
   int n = 0;
   for (unsigned char c : s) n += (c & 0xc0) != 0x80;
@@ -309,6 +331,36 @@ double ppasr_lm_debug_host_score(ppasr_lm_handle lm, const int32_t* win) {
     if (n > 1 && find(win + order - n, n - 1, p, b)) acc += b;
   }
   return kLmOovScore;
+}
+
+// The host mirror of the table as lm_build_table laid it out: mask + 2 slots of 16 bytes (key, prob, back-off), the last
+// one the copy of slot 0 that lm_probe_many reads behind the last slot.  Returns the slot count; copies when `slots_out`
+// is given and `n_slots` is that count (else -1).  Works on a host-only handle.
+long long ppasr_lm_debug_table(ppasr_lm_handle lm, void* slots_out, long long n_slots) {
+  if (!lm) return -1;
+  const long long n = (long long)lm->slots.size();
+  if (!slots_out) return n;
+  if (n_slots != n) return -1;
+  std::memcpy(slots_out, lm->slots.data(), (size_t)n * sizeof(LmSlot));
+  return n;
+}
+
+// Scorer::get_log_cond_prob of n_windows windows ([n_windows][order] LM word indices, oldest first; device memory)
+// evaluated by the DEVICE functions of lm.h, one window per thread: form 0 = lm_log_cond_prob, 1 = lm_context_acc +
+// lm_pair_log_cond_prob reading uni_prob itself, 2 = the same with the unigram handed in by the caller (the narrow
+// search's way).  out_dev: [n_windows] doubles; nothing else is written.
+ppasr_status ppasr_lm_debug_device_score(ppasr_lm_handle lm, const int32_t* windows_dev, int n_windows, int form,
+                                         double* out_dev, void* stream) {
+  if (!lm || !windows_dev || !out_dev) return fail(PPASR_EINVAL, "lm: null argument");
+  if (!lm->dev.slots) return fail(PPASR_EINVAL, "lm: host-only handle (ppasr_lm_debug_load_host) has no device table");
+  if (n_windows < 0) return fail(PPASR_EINVAL, "lm: negative n_windows");
+  if (form < 0 || form > 2) return fail(PPASR_EINVAL, "lm: form must be 0, 1 or 2");
+  if (n_windows == 0) return PPASR_OK;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  PPASR_LAUNCH(k_lm_debug_score, dim3((unsigned)(((long long)n_windows + 255) / 256)), dim3(256), 0, hs, lm->dev,
+               windows_dev, n_windows, form, out_dev);
+  HIP_TRY(hipGetLastError());
+  return PPASR_OK;
 }
 
 int ppasr_lm_word_index(ppasr_lm_handle lm, int token) {

@@ -1,6 +1,6 @@
 // lm_host.h -- host side of the language-model object shared by the model-file readers (lm.hip: ARPA text,
-// klm.hip: KenLM binaries): the flattened n-gram table is built on the host, kept there for the verification hook
-// ppasr_lm_debug_host_score, and uploaded to the device for the beam-search kernel.
+// klm.hip: KenLM binaries): the flattened n-gram table is built on the host, kept there for the verification hooks
+// ppasr_lm_debug_host_score / ppasr_lm_debug_table, and uploaded to the device for the beam-search kernel.
 #pragma once
 #include <cstdint>
 #include <string>

@@ -59,6 +59,10 @@ def _oracle_lm_decode(lib, chunks, V, beam, cutoff_prob, top_n, lm, alpha, beta,
     (70, 200, 16, 2, 1.9, 0.3, "peaky"),
     (70, 200, 8, 5, 0.5, -1.5, "flat"),
     (70, 200, 8, 5, 0.5, -1.5, "peaky"),
+    (40, 120, 10, 6, 2.2, 4.3, "peaky"),     # kLmMaxOrder: the second round of probes holds two keys and an idle lane
+    (40, 120, 10, 6, 2.2, 4.3, "flat"),
+    (40, 120, 10, 1, 2.2, 4.3, "peaky"),     # a unigram-only model: no context words at all
+    (40, 120, 10, 1, 2.2, 4.3, "flat"),
 ])
 def test_beam_search_with_scorer_matches_c_oracle(tmp_path, T, V, beam, order, alpha, beta, kind):
     from ppasr_amd.decoders.beam_search_decoder import Scorer, beam_search_ids
@@ -91,6 +95,44 @@ def test_beam_search_with_scorer_matches_c_oracle(tmp_path, T, V, beam, order, a
         differs += tokens[b, 0, :lens[b, 0]].tolist() != t0[b, 0, :int(l0[b, 0])].cpu().numpy().tolist()
     if T >= 40 and kind == "flat":
         assert differs > 0  # the scorer must actually steer the search on ambiguous posteriors
+
+
+@pytest.mark.parametrize("V,cutoff_prob", [(40, 0.99),      # narrow: the candidates' unigrams come from the LDS table
+                                           (200, 1.0)])     # the whole vocabulary: the wide form, with a character model
+@pytest.mark.parametrize("beam", [5, 30])
+def test_beam_search_on_a_table_with_a_wrapping_cluster(tmp_path, V, cutoff_prob, beam):
+    """The order-5, five-character model of the zoo (tests/lm_cases.py): a table of 256 slots whose last slot is occupied
+    and whose clusters run through the table's end -- the probes of lm_probe_many that read the wrap copy and continue
+    with `& mask` (test_lm_reference_cpu.py asserts that the windows of this model reach them).  Most characters of the
+    acoustic vocabulary are OOV for it.  Compared with the C oracle exactly as the rows above."""
+    import lm_cases
+    from ppasr_amd.decoders.beam_search_decoder import Scorer, beam_search_ids
+    lib = _oracle()
+    T, alpha, beta, top_n, B = 40, 2.2, 4.3, 40, 3
+    vocab = _vocab(V)
+    assert vocab[2:7] == lm_cases.chars_of(lm_cases.WRAP_MODEL)
+    arpa = lm_cases.write_model(lm_cases.WRAP_MODEL, tmp_path)
+    lm = read_arpa(arpa, vocab)
+    scorer = Scorer(alpha, beta, arpa, vocab)
+    assert scorer.get_max_order() == 5 and scorer.is_character_based() and scorer.ngram_count() == len(lm["gram_n"])
+    rng = np.random.Generator(np.random.PCG64(T * 13 + V + beam + 5))
+    batch = np.stack([_probs(rng, T, V, kind) for kind in ("peaky", "flat", "flat")])
+    nbest = min(beam, 4)
+    tokens, lens, scores, _ = beam_search_ids(torch.from_numpy(batch).cuda(), beam, cutoff_prob, top_n, 0, nbest=nbest,
+                                              ext_scorer=scorer)
+    t0, l0, _, _ = beam_search_ids(torch.from_numpy(batch).cuda(), beam, cutoff_prob, top_n, 0, nbest=1)
+    torch.cuda.synchronize()
+    tokens, lens, scores = tokens.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy()
+    differs = 0
+    for b in range(B):
+        ref = _oracle_lm_decode(lib, [batch[b]], V, beam, cutoff_prob, top_n, lm, alpha, beta, nbest)
+        assert tokens[b, 0, :lens[b, 0]].tolist() == ref[0][0], (b, ref[0])
+        assert abs(scores[b, 0] - ref[0][1]) <= 2e-4 * max(1.0, abs(ref[0][1]))
+        for r in range(1, len(ref)):
+            if abs(ref[r][1] - ref[r - 1][1]) > 1e-3 and (r + 1 >= len(ref) or abs(ref[r + 1][1] - ref[r][1]) > 1e-3):
+                assert tokens[b, r, :lens[b, r]].tolist() == ref[r][0], (b, r)
+        differs += tokens[b, 0, :lens[b, 0]].tolist() != t0[b, 0, :int(l0[b, 0])].cpu().numpy().tolist()
+    assert differs > 0  # the scorer must actually steer the search on ambiguous posteriors
 
 
 def test_scorer_streaming_and_decoder_object(tmp_path):
@@ -162,7 +204,7 @@ def test_seeded_fuzz_against_oracle(tmp_path):
         assert abs(float(sc[0, 0]) - ref[0][1]) <= 2e-4 * max(1.0, abs(ref[0][1])), (seed, float(sc[0, 0]), ref[0][1])
 
 
-@pytest.mark.parametrize("model_type,order", [("probing", 3), ("trie", 4), ("rest_probing", 2)])
+@pytest.mark.parametrize("model_type,order", [("probing", 3), ("trie", 4), ("rest_probing", 2), ("probing", 6)])
 def test_scorer_from_klm_binary_equals_scorer_from_arpa(tmp_path, model_type, order):
     """`Scorer(alpha, beta, 'lm.klm', vocab)` -- the file type PPASR ships (decoders/beam_search_decoder.py:19-29): the
     KenLM binary (written by tests/klm_writer.py from the same ARPA model) gives the SAME hypotheses and scores as the
