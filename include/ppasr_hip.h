@@ -751,6 +751,30 @@ PPASR_API ppasr_status ppasr_rescore(ppasr_rescorer r, const float* memory, cons
                                      double* r_att_scores, double* total_scores, int32_t* best, float* token_logp,
                                      float* logits_tap, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC forced alignment: when each token of a transcript was spoken (no reference counterpart) ----
+ * The Viterbi path of tokens[b, 0..n_tokens[b]) through the CTC trellis of probs[b], and per token its frames and its
+ * confidence.  The transcript may be a decoder's own output (greedy, beam search, rescoring) or the caller's.  The
+ * trellis, the clamp of the emissions, the tie rule and the feasibility rule are defined once, in the header comment of
+ * csrc/ctc_align.hip.  One call, asynchronous on `stream`, no read-back; every pointer is a device pointer.
+ *   probs [B,Tp,V] f32 (the head's softmax output); frame_lens [B] i32 or NULL (all Tp rows; clamped to [0, Tp])
+ *   tokens [B,max_tokens] i32 (only the first n_tokens[b] of a row are read), n_tokens [B] i32; max_tokens <= 255
+ *   frame_token [B,Tp] i32: the index l of the token the path emits at that frame, -1 on blank frames and for t >= frame_lens
+ *   begin, end [B,max_tokens] i32 or NULL: first frame of token l, one past its last; peak [B,max_tokens] i32 and
+ *   conf [B,max_tokens] f32 or NULL: the largest probs[b, t, tokens[b, l]] over begin <= t < end, copied from the table,
+ *   and the first frame that attains it.  Entries l >= n_tokens[b] are -1 (conf: 0.0).
+ *   score [B] f32: the path's log-probability (fp32, one add per frame); status [B] i32:
+ *     0 aligned; 1 infeasible (frame_lens < n_tokens + adjacent repeats); 2 bad input (n_tokens outside [0, max_tokens], a
+ *     token id outside [0, V) or equal to blank).  Status 1 and 2 are results, not errors: score -inf, every entry -1.
+ * Refused before any launch: a NULL required pointer, B <= 0, Tp < 0, V < 2, blank outside [0, V), max_tokens < 0, a
+ * workspace below ppasr_ctc_align_workspace_bytes or not 16-byte aligned (PPASR_EINVAL); max_tokens > 255
+ * (PPASR_EUNSUPPORTED).  Tp = 0 is a valid call that writes status and score only.  tokens may be NULL when max_tokens
+ * is 0, probs and frame_token when Tp is 0. */
+PPASR_API size_t ppasr_ctc_align_workspace_bytes(int B, int Tp, int max_tokens);
+PPASR_API ppasr_status ppasr_ctc_align(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank,
+                                       const int32_t* tokens, const int32_t* n_tokens, int max_tokens, int32_t* frame_token,
+                                       int32_t* begin, int32_t* end, int32_t* peak, float* conf, float* score,
+                                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,11 +120,12 @@ class AttentionRescorer:
 
 
 def attention_rescoring(model, rescorer, probs, memory, out_lens, vocabulary, beam_size=10, ctc_weight=0.5,
-                        reverse_weight=0.0, cutoff_prob=0.99, cutoff_top_n=40, blank_id=0):
+                        reverse_weight=0.0, cutoff_prob=0.99, cutoff_top_n=40, blank_id=0, return_ids=False):
     """probs [B, T', V] and memory [B, T', D] of one encode (``model.get_encoder_out(..., return_memory=True)``),
     out_lens [B] valid frames or None -> per utterance ``(score, text)`` of the hypothesis with the largest total score.
     The n-best list is the plain CTC prefix beam search's (no external scorer); search and rescoring are queued on the
-    current stream and read back once."""
+    current stream and read back once.  ``return_ids``: ``(score, text, ids)``, the token ids the text was made of (for
+    ``ctc_alignment``)."""
     del model  # (kept in the signature for symmetry with the other decoders: the encode already happened)
     fl = None if out_lens is None else torch.as_tensor(out_lens, dtype=torch.int32)
     tokens, lens, scores, _ = beam_search_ids(probs, beam_size, cutoff_prob, cutoff_top_n, blank_id, frame_lens=fl,
@@ -141,4 +142,5 @@ def attention_rescoring(model, rescorer, probs, memory, out_lens, vocabulary, be
         raise _lib.PPASRHipError(f"attention rescoring: a hypothesis of {int(longest)} tokens exceeds the "
                                  f"{MAX_ROWS - 1} the kernels are built for; decode shorter segments",
                                  _lib.PPASR_EUNSUPPORTED)
-    return [(float(sc[b]), _text(tk[b, :max(int(ln[b]), 0)].tolist(), vocabulary)) for b in range(tk.shape[0])]
+    ids = [tk[b, :max(int(ln[b]), 0)].tolist() for b in range(tk.shape[0])]
+    return [(float(sc[b]), _text(ids[b], vocabulary)) + ((ids[b],) if return_ids else ()) for b in range(tk.shape[0])]

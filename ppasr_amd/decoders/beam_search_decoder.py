@@ -194,13 +194,14 @@ def beam_search_ids(probs, beam_size, cutoff_prob=1.0, cutoff_top_n=40, blank_id
     return tokens, lens, scores, state
 
 
-def _results(tokens, lens, scores, vocabulary, b):
+def _results(tokens, lens, scores, vocabulary, b, with_ids=False):
     tk, ln, sc = tokens[b].cpu().numpy(), lens[b].cpu().numpy(), scores[b].cpu().numpy()
     out = []
     for r in range(tk.shape[0]):
         if ln[r] < 0:
             continue
-        out.append((float(sc[r]), _text(tk[r, :ln[r]].tolist(), vocabulary)))
+        ids = tk[r, :ln[r]].tolist()
+        out.append((float(sc[r]), _text(ids, vocabulary)) + ((ids,) if with_ids else ()))
     return out
 
 
@@ -252,14 +253,15 @@ class BeamSearchDecoder:
         self._max_stream_frames = int(max_stream_frames)
         self._state = None
 
-    def decode_beam_search_offline(self, probs_split):
-        """-> (score, text) of the best hypothesis.  beam_search_decoder.py:45-56"""
+    def decode_beam_search_offline(self, probs_split, return_ids=False):
+        """-> (score, text) of the best hypothesis.  beam_search_decoder.py:45-56
+        ``return_ids``: (score, text, ids), the token ids the text was made of (for ``ctc_alignment``)."""
         if self._ext_scorer is not None:
             self._ext_scorer.reset_params(self.alpha, self.beta)  # beam_search_decoder.py:46-47
         p = probs_split if isinstance(probs_split, torch.Tensor) else np.asarray(probs_split, np.float32)
         tokens, lens, scores, _ = beam_search_ids(torch.as_tensor(p)[None], self.beam_size, self.cutoff_prob,
                                                   self.cutoff_top_n, self.blank_id, nbest=1, ext_scorer=self._ext_scorer)
-        return _results(tokens, lens, scores, self.vocab_list, 0)[0]
+        return _results(tokens, lens, scores, self.vocab_list, 0, with_ids=return_ids)[0]
 
     def decode_batch_beam_search_offline(self, probs_split):
         """-> list[str].  beam_search_decoder.py:59-73 (every row of every table is decoded)."""

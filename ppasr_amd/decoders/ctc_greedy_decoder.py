@@ -45,15 +45,19 @@ def _text(ids, vocabulary):
     return "".join(vocabulary[i] for i in ids).replace("<space>", " ")
 
 
-def greedy_decoder(probs_seq, vocabulary, blank_index=0):
-    """(score, text) of one [T, V] probability table.  ctc_greedy_decoder.py:6-31"""
+def greedy_decoder(probs_seq, vocabulary, blank_index=0, return_ids=False):
+    """(score, text) of one [T, V] probability table.  ctc_greedy_decoder.py:6-31
+    ``return_ids``: (score, text, ids), the token ids the text was made of (for ``ctc_alignment``)."""
     p = probs_seq if isinstance(probs_seq, torch.Tensor) else np.asarray(probs_seq, np.float32)
     if p.shape[0] == 0:
-        return 0, ""
+        return (0, "", []) if return_ids else (0, "")
     tokens, n, score, _, _ = greedy_decode_ids(torch.as_tensor(p)[None], None, blank_index)
     n0 = int(n[0])
     s = float(score[0])
-    return (s if s != 0.0 else 0), _text(tokens[0, :n0].tolist(), vocabulary)
+    ids = tokens[0, :n0].tolist()
+    if return_ids:
+        return (s if s != 0.0 else 0), _text(ids, vocabulary), ids
+    return (s if s != 0.0 else 0), _text(ids, vocabulary)
 
 
 def greedy_decoder_batch(probs_split, vocabulary, blank_index=0):

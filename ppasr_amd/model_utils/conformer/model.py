@@ -205,12 +205,17 @@ class ConformerModel:
                                                    stream))
         return tokens, n_tokens, score
 
+    @property
+    def total_subsampling(self):
+        """Feature frames per output frame: the front end's rate (4, 6 or 8), doubled behind each stride layer."""
+        return getattr(self, "subsampling_rate", 4) * (2 ** len(getattr(self, "_stride_layers", ())))
+
     def valid_out_frames(self, speech_lengths, T):
         """Output frames that are not padding, per utterance (int32 device tensor): frame t of the output is valid iff
         ``mul * t < len`` with ``mul`` = the model's total time reduction (the reference's mask slicing,
         subsampling.py:115; x2 behind the Efficient-Conformer's stride layer)."""
         lens = torch.as_tensor(speech_lengths, dtype=torch.int64).to(self.device)
-        mul = getattr(self, "subsampling_rate", 4) * (2 ** len(getattr(self, "_stride_layers", ())))
+        mul = self.total_subsampling
         return torch.clamp((lens + mul - 1) // mul, min=0, max=self.out_frames(int(T))).to(torch.int32)
 
     def set_skip_padding(self, enable=True):

@@ -55,6 +55,8 @@ class DeepSpeech2Model:
     def out_frames(self, T):
         return ((T - 1) // 2 - 1) // 2
 
+    total_subsampling = 4  # feature frames per output frame: two stride-2 convolutions (out_frames above)
+
     def _run(self, speech, speech_lengths, init_h=None, init_c=None, want_states=False):
         x = torch.as_tensor(speech, dtype=torch.float32).to(self.device).contiguous()
         lens = torch.as_tensor(speech_lengths, dtype=torch.int64).to(self.device).contiguous()

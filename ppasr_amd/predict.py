@@ -1,6 +1,7 @@
 """Drop-in for ``ppasr/predict.py`` (``PPASRPredictor``): ``predict`` (:163-187), ``predict_stream``
 (:232-337), ``reset_stream`` (:340-347), ``decode`` (:114-140) with the same arguments and return
-dicts.  Audio -> fbank is host-side glue (``data_utils/featurizer.py``); encoder + CTC decode run in
+dicts, plus token timestamps (``predict(..., timestamps=True)``, ``align``: ``decoders/ctc_alignment.py``, no reference
+counterpart).  Audio -> fbank is host-side glue (``data_utils/featurizer.py``); encoder + CTC decode run in
 the HIP library.  VAD (`predict_long`), punctuation and ITN are separate models outside the hot
 path and are not provided (``use_pun=True`` / ``is_itn=True`` raise).
 """
@@ -13,6 +14,8 @@ from ppasr_amd.decoders.ctc_greedy_decoder import greedy_decoder, greedy_decoder
 from ppasr_amd.infer_utils.inference_predictor import InferencePredictor
 
 __all__ = ["PPASRPredictor"]
+
+FRAME_SHIFT = 0.010  # seconds per feature frame (the Kaldi fbank / MFCC hop)
 
 
 class _Cfg(dict):
@@ -79,12 +82,19 @@ class PPASRPredictor:
             result = greedy_decoder(probs_seq=output_data, vocabulary=self._text_featurizer.vocab_list)
         return result[0], result[1]
 
-    def predict(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000):
-        """-> {'text': str, 'score': float}.  predict.py:163-187"""
+    def predict(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, timestamps=False):
+        """-> {'text': str, 'score': float}.  predict.py:163-187
+        ``timestamps=True`` adds ``'timestamps': [{'text', 'start', 'end', 'score'}, ...]``, one entry per token of the
+        text: ``start`` / ``end`` in seconds on the encoder's frame grid (``_token_times``), ``score`` the largest
+        probability of the token inside its span."""
         samples, sr = load_audio(audio_data, sample_rate)
         feat = self._audio_featurizer.featurize(samples, sr)
         input_data = np.asarray(feat, np.float32)[np.newaxis, :]
         audio_len = np.array([input_data.shape[1]]).astype(np.int64)
+        if timestamps:
+            if use_pun or is_itn:
+                raise NotImplementedError("punctuation / ITN are outside the hot path")
+            return self._predict_timestamps(input_data, audio_len, len(samples) / float(sr))
         if self.configs.decoder == "attention_rescoring":
             if use_pun or is_itn:
                 raise NotImplementedError("punctuation / ITN are outside the hot path")
@@ -97,13 +107,62 @@ class PPASRPredictor:
         score, text = self.decode(output_data=probs, use_pun=use_pun, is_itn=is_itn)
         return {"text": text, "score": score}
 
+    # ---- token timestamps (CTC forced alignment on the device, decoders/ctc_alignment.py) ----
+    def _blank(self):
+        return self.beam_search_decoder.blank_id if self.beam_search_decoder is not None else 0
+
+    def _token_times(self, probs, ids, duration):
+        """The Viterbi alignment of ``ids`` through ``probs`` [T', V] (device) -> one {'text', 'start', 'end', 'score'} per
+        token.  start = begin x m x frame shift, end = min(end x m x frame shift, duration), with m the model's total
+        subsampling: the times lie on the encoder's frame grid, and the receptive-field offset of the convolutional front
+        end is not corrected."""
+        from ppasr_amd.decoders.ctc_alignment import align_one
+        step = self.predictor.model.total_subsampling * FRAME_SHIFT
+        vocab = self._text_featurizer.vocab_list
+        greedy = self.configs.decoder == "ctc_greedy"  # (the only decoder whose text shows <space> as a blank character)
+        return [{"text": vocab[i].replace("<space>", " ") if greedy else vocab[i], "start": b * step,
+                 "end": min(e * step, duration), "score": c}
+                for i, (b, e, c) in zip(ids, align_one(probs, ids, self._blank()))]
+
+    def _predict_timestamps(self, input_data, audio_len, duration):
+        """predict() with the winning hypothesis aligned against the same device-resident table: one more call and one
+        more read-back than predict()."""
+        vocab = self._text_featurizer.vocab_list
+        if self.configs.decoder == "attention_rescoring":
+            from ppasr_amd.decoders.attention_rescoring import attention_rescoring
+            probs, memory = self.predictor.predict_device_memory(input_data, audio_len)
+            score, text, ids = attention_rescoring(self.predictor.model, self.predictor.rescorer, probs, memory, None, vocab,
+                                                   return_ids=True, **self._rescoring_conf)[0]
+            probs = probs[0]
+        else:
+            probs = self.predictor.predict_device(input_data, audio_len)[0]
+            if self.configs.decoder == "ctc_beam_search":
+                score, text, ids = self.beam_search_decoder.decode_beam_search_offline(probs_split=probs, return_ids=True)
+            else:
+                score, text, ids = greedy_decoder(probs_seq=probs, vocabulary=vocab, return_ids=True)
+        return {"text": text, "score": score, "timestamps": self._token_times(probs, ids, duration)}
+
+    def align(self, audio_data, text, sample_rate=16000):
+        """Forced alignment of a transcript the caller supplies: the list ``predict(..., timestamps=True)`` returns under
+        ``'timestamps'``, for ``text``.  ValueError for a character that is not in the vocabulary and for a transcript
+        that does not fit into the utterance's frames."""
+        from ppasr_amd.decoders.ctc_alignment import text_to_ids
+        samples, sr = load_audio(audio_data, sample_rate)
+        feat = self._audio_featurizer.featurize(samples, sr)
+        input_data = np.asarray(feat, np.float32)[np.newaxis, :]
+        audio_len = np.array([input_data.shape[1]]).astype(np.int64)
+        ids = text_to_ids(text, self._text_featurizer.vocab_list, space_token=self.configs.decoder == "ctc_greedy")
+        probs = self.predictor.predict_device(input_data, audio_len)[0]
+        return self._token_times(probs, ids, len(samples) / float(sr))
+
     def predict_long(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, speech_timestamps=None,
-                     vad_predictor=None):
+                     vad_predictor=None, timestamps=False):
         """predict.py:190-229: recognise the speech segments of a long recording one by one and join the texts with
         '，'; score = mean of the segment scores (2 decimals).  The reference finds the segments with its Silero VAD
         model (``init_vad``), which is a separate model outside this path: pass the segments as ``speech_timestamps``
         (``[{'start': sample, 'end': sample}, ...]``, what ``get_speech_timestamps`` returns) or an object with that
-        method as ``vad_predictor``."""
+        method as ``vad_predictor``.  ``timestamps=True``: the segments' token timestamps (``predict``), each moved by its
+        segment's start, in one list under ``'timestamps'``."""
         if use_pun:
             raise NotImplementedError("punctuation is a separate model outside the hot path")
         samples, sr = load_audio(audio_data, sample_rate)
@@ -112,16 +171,25 @@ class PPASRPredictor:
                 raise NotImplementedError("predict_long needs speech_timestamps or a vad_predictor: the Silero VAD "
                                           "model is not part of this library")
             speech_timestamps = vad_predictor.get_speech_timestamps(samples, sr)
-        texts, scores = "", []
+        texts, scores, stamps = "", [], []
         for t in speech_timestamps:
-            result = self.predict(audio_data=samples[t["start"]:t["end"]], use_pun=False, is_itn=is_itn, sample_rate=sr)
+            if timestamps:
+                result = self.predict(audio_data=samples[t["start"]:t["end"]], use_pun=False, is_itn=is_itn, sample_rate=sr,
+                                      timestamps=True)
+                at = t["start"] / float(sr)
+                stamps += [dict(e, start=e["start"] + at, end=e["end"] + at) for e in result["timestamps"]]
+            else:
+                result = self.predict(audio_data=samples[t["start"]:t["end"]], use_pun=False, is_itn=is_itn, sample_rate=sr)
             score, text = result["score"], result["text"]
             if text != "":
                 texts = texts + "，" + text
             scores.append(score)
         if texts[:1] == "，":
             texts = texts[1:]
-        return {"text": texts, "score": round(sum(scores) / len(scores), 2) if scores else 0}
+        out = {"text": texts, "score": round(sum(scores) / len(scores), 2) if scores else 0}
+        if timestamps:
+            out["timestamps"] = stamps
+        return out
 
     def predict_stream(self, audio_data, is_end=False, use_pun=False, is_itn=False, channels=1, samp_width=2,
                        sample_rate=16000):
