@@ -775,6 +775,32 @@ PPASR_API ppasr_status ppasr_ctc_align(const float* probs, const int32_t* frame_
                                        int32_t* begin, int32_t* end, int32_t* peak, float* conf, float* score,
                                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the loss half of evaluation: CTC and attention losses, forward only (the reference's ConformerModel.forward) ----
+ * CTC negative log-likelihood: nll[b] = -log P_ctc(tokens[b] | probs[b]), the sum over every alignment where
+ * ppasr_ctc_align takes the best one.  Inputs, trellis, emission clamp, statuses and refusals are ppasr_ctc_align's; the
+ * definition is the header comment of csrc/ctc_loss.hip.  One call, asynchronous on `stream`, no read-back.
+ *   nll [B] f32; status [B] i32: 0 ok; 1 infeasible and 2 bad input, both with nll = +inf.  n_tokens = 0 with
+ *   frame_lens = 0 gives nll = 0.  A result depends on its own utterance only (the same bits alone and in any batch). */
+PPASR_API size_t ppasr_ctc_loss_workspace_bytes(int B, int Tp, int max_tokens);
+PPASR_API ppasr_status ppasr_ctc_loss(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank,
+                                      const int32_t* tokens, const int32_t* n_tokens, int max_tokens, float* nll,
+                                      int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Label-smoothing loss of the attention decoder (loss/label_smoothing_loss.py of the reference), teacher-forced over one
+ * label per utterance: the decoder walk is ppasr_rescore's with nbest = 1.
+ *   memory, out_lens: as ppasr_rescore; labels [B,max_tokens] i32, label_lens [B] i32 (clamped as ppasr_rescore clamps)
+ *   att_kl, r_att_kl [B] f64: the sum over the label_lens[b] + 1 target rows (tokens, then eos) of
+ *     kl_row = sum_v t_v (ln t_v - logp_v),  t = (1 - lsm_weight) at the target and lsm_weight / (V - 1) elsewhere, 0 ln 0 = 0
+ *   of the left decoder and of the right decoder over the reversed label (0 when reverse_weight == 0: it does not run);
+ *   row terms are summed in double in row order.  rows [B] i32: label_lens[b] + 1.
+ *   At lsm_weight = 0, att_kl[b] is -att_scores[b] of ppasr_rescore on the same label, bit for bit.
+ * Refusals as ppasr_rescore; lsm_weight outside [0, 1) is PPASR_EINVAL. */
+PPASR_API size_t ppasr_rescorer_loss_workspace_bytes(ppasr_rescorer r, int B, int Tp, int max_tokens);
+PPASR_API ppasr_status ppasr_rescorer_loss(ppasr_rescorer r, const float* memory, const int32_t* out_lens, int B, int Tp,
+                                           const int32_t* labels, const int32_t* label_lens, int max_tokens,
+                                           double lsm_weight, double reverse_weight, double* att_kl, double* r_att_kl,
+                                           int32_t* rows, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

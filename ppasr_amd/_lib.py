@@ -221,6 +221,12 @@ SYMBOLS = [
     ("ppasr_ctc_align_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("ppasr_ctc_align", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp,
                                        ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("ppasr_ctc_loss_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("ppasr_ctc_loss", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                      ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("ppasr_rescorer_loss_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("ppasr_rescorer_loss", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int,
+                                           ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 ]
 
 _lib = None

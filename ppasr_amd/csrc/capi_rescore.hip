@@ -16,6 +16,7 @@ constexpr size_t al64(size_t n) { return (n + 63) / 64 * 64; }
 // workspace offsets in floats
 struct RescoreLayout {
   size_t x, qkv, ctx, qc, kv, logp, counts, tile_info, row_info, hyp_row0, total;
+  size_t stat, total_loss;  // ppasr_rescorer_loss: the row statistics behind everything ppasr_rescore uses
 };
 RescoreLayout rescore_layout(const ppasr_rescorer_s* r, const RescoreDims& d) {
   RescoreLayout l;
@@ -37,7 +38,24 @@ RescoreLayout rescore_layout(const ppasr_rescorer_s* r, const RescoreDims& d) {
   l.row_info = take(2 * rows);
   l.hyp_row0 = take((size_t)2 * d.B * d.nbest);
   l.total = o;
+  l.stat = take(2 * rows);
+  l.total_loss = o;
   return l;
+}
+
+RescoreBufs rescore_bufs(float* ws, const RescoreLayout& l) {
+  RescoreBufs bf;
+  bf.x = ws + l.x;
+  bf.qkv = ws + l.qkv;
+  bf.ctx = ws + l.ctx;
+  bf.qc = ws + l.qc;
+  bf.kv = ws + l.kv;
+  bf.logp = ws + l.logp;
+  bf.tab.counts = reinterpret_cast<int*>(ws + l.counts);
+  bf.tab.tile_info = reinterpret_cast<int*>(ws + l.tile_info);
+  bf.tab.row_info = reinterpret_cast<int2*>(ws + l.row_info);
+  bf.tab.hyp_row0 = reinterpret_cast<int*>(ws + l.hyp_row0);
+  return bf;
 }
 
 ppasr_status load_side(ppasr_rescorer_s* r, Loader& ld, const std::string& p, int nblk, DecSideW* side,
@@ -160,23 +178,48 @@ ppasr_status ppasr_rescore(ppasr_rescorer r, const float* memory, const int32_t*
   const RescoreDims d{B, Tp, nbest, max_tokens, reverse_weight > 0.0 ? 2 : 1};
   const RescoreLayout l = rescore_layout(r, RescoreDims{B, Tp, nbest, max_tokens, 2});
   float* ws = static_cast<float*>(workspace);
-  RescoreBufs bf;
-  bf.x = ws + l.x;
-  bf.qkv = ws + l.qkv;
-  bf.ctx = ws + l.ctx;
-  bf.qc = ws + l.qc;
-  bf.kv = ws + l.kv;
-  bf.logp = ws + l.logp;
-  bf.tab.counts = reinterpret_cast<int*>(ws + l.counts);
-  bf.tab.tile_info = reinterpret_cast<int*>(ws + l.tile_info);
-  bf.tab.row_info = reinterpret_cast<int2*>(ws + l.row_info);
-  bf.tab.hyp_row0 = reinterpret_cast<int*>(ws + l.hyp_row0);
+  const RescoreBufs bf = rescore_bufs(ws, l);
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(configure_rescore_kernels());  // (a per-device attribute: the call may run on another device than create did)
   if (logits_tap)
     HIP_TRY(hipMemsetAsync(logits_tap, 0, (size_t)B * nbest * 2 * (max_tokens + 1) * r->desc.vocab_size * sizeof(float), st));
   launch_rescore(r->W, d, bf, memory, out_lens, tokens, lens, ctc_scores, ctc_weight, reverse_weight, att_scores, r_att_scores,
-                 total_scores, best, token_logp, logits_tap, st);
+                 total_scores, best, token_logp, logits_tap, nullptr, st);
+  HIP_TRY(hipGetLastError());
+  return PPASR_OK;
+}
+
+size_t ppasr_rescorer_loss_workspace_bytes(ppasr_rescorer r, int B, int Tp, int max_tokens) {
+  if (!r || B <= 0 || Tp <= 0 || max_tokens < 0 || max_tokens + 1 > kRescoreMaxRows) return 0;
+  return rescore_layout(r, RescoreDims{B, Tp, 1, max_tokens, 2}).total_loss * sizeof(float);
+}
+
+ppasr_status ppasr_rescorer_loss(ppasr_rescorer r, const float* memory, const int32_t* out_lens, int B, int Tp,
+                                 const int32_t* labels, const int32_t* label_lens, int max_tokens, double lsm_weight,
+                                 double reverse_weight, double* att_kl, double* r_att_kl, int32_t* rows, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  if (!r) return fail(PPASR_EINVAL, "null rescorer");
+  if (!memory || !label_lens || !att_kl || !r_att_kl || !rows || !workspace) return fail(PPASR_EINVAL, "null argument");
+  if (B <= 0 || Tp <= 0 || max_tokens < 0 || (max_tokens > 0 && !labels)) return fail(PPASR_EINVAL, "bad shape");
+  if (!(lsm_weight >= 0.0 && lsm_weight < 1.0)) return fail(PPASR_EINVAL, "lsm_weight outside [0, 1)");
+  if (!(reverse_weight >= 0.0 && reverse_weight <= 1.0)) return fail(PPASR_EINVAL, "reverse_weight outside [0, 1]");
+  if (reverse_weight > 0.0 && r->desc.r_num_blocks == 0)
+    return fail(PPASR_EINVAL, "reverse_weight > 0 needs a right decoder (r_num_blocks is 0)");
+  if (max_tokens + 1 > r->desc.max_len)
+    return fail(PPASR_EUNSUPPORTED, "max_tokens + 1 exceeds the positional table (max_len)");
+  if (max_tokens + 1 > kRescoreMaxRows)
+    return fail(PPASR_EUNSUPPORTED, "max_tokens + 1 exceeds the 256 rows per label the kernels are built for");
+  if ((size_t)B > 65535u * 16u || (size_t)B * Tp > (size_t)1 << 24) return fail(PPASR_EUNSUPPORTED, "batch too large");
+  if (workspace_bytes < ppasr_rescorer_loss_workspace_bytes(r, B, Tp, max_tokens))
+    return fail(PPASR_ENOSPACE, "workspace too small (ppasr_rescorer_loss_workspace_bytes)");
+  const RescoreDims d{B, Tp, 1, max_tokens, reverse_weight > 0.0 ? 2 : 1};
+  const RescoreLayout l = rescore_layout(r, RescoreDims{B, Tp, 1, max_tokens, 2});
+  float* ws = static_cast<float*>(workspace);
+  const RescoreBufs bf = rescore_bufs(ws, l);
+  const RescoreLoss loss{lsm_weight, ws + l.stat, att_kl, r_att_kl, rows};
+  HIP_TRY(configure_rescore_kernels());
+  launch_rescore(r->W, d, bf, memory, out_lens, labels, label_lens, nullptr, 0.0, reverse_weight, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, nullptr, &loss, static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return PPASR_OK;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstddef>
 #include <cstdint>
 
@@ -33,6 +34,27 @@ inline AlignLayout align_layout(int B, int Tp, int max_tokens) {
   l.total = o > 0 ? o : 256;
   return l;
 }
+
+// ---- what the alignment (ctc_align.hip) and the loss (ctc_loss.hip) share: the emission, the frame clamp, the lane move ----
+#if defined(__HIPCC__)
+constexpr float kNegInf = -__builtin_huge_valf();
+
+__device__ __forceinline__ float emission(float p) { return logf(fmaxf(p, FLT_MIN)); }
+
+__device__ __forceinline__ int clamp_frames(const int32_t* frame_lens, int b, int Tp) {
+  const int T = frame_lens ? frame_lens[b] : Tp;
+  return min(max(T, 0), Tp);
+}
+
+// lane i <- lane i-1 across the whole wave (DPP wave_shr:1); lane 0 gets `edge`
+__device__ __forceinline__ float lane_shr1(float x, float edge) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(x), 0x138, 0xf, 0xf, false));
+}
+#endif
+
+// Queues the gather alone: emis [B][Tp][align_row_stride(max_tokens)] = e(t, .) of every row t < T and token l < L.
+void launch_ctc_gather(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank, const int32_t* tokens,
+                       const int32_t* n_tokens, int max_tokens, float* emis, hipStream_t st);
 
 // Queues the gather and the chain on `st`.  Arguments as ppasr_ctc_align (include/ppasr_hip.h), already validated.
 void launch_ctc_align(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank, const int32_t* tokens,

@@ -31,27 +31,12 @@
 //   Nothing is accumulated with atomics, and no word of the workspace or of an output is read before this call wrote it.
 #include "ctc_align.h"
 
-#include <cfloat>
-
 #include "launch.h"
 
 namespace ppasr {
 namespace {
 
-constexpr float kNegInf = -__builtin_huge_valf();
 constexpr int kAhead = 16;  // frames of emissions in flight per lane (5 registers each)
-
-__device__ __forceinline__ float emission(float p) { return logf(fmaxf(p, FLT_MIN)); }
-
-__device__ __forceinline__ int clamp_frames(const int32_t* frame_lens, int b, int Tp) {
-  const int T = frame_lens ? frame_lens[b] : Tp;
-  return min(max(T, 0), Tp);
-}
-
-// lane i <- lane i-1 across the whole wave (DPP wave_shr:1); lane 0 gets `edge`
-__device__ __forceinline__ float lane_shr1(float x, float edge) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(x), 0x138, 0xf, 0xf, false));
-}
 
 __global__ __launch_bounds__(256) void align_gather_kernel(const float* __restrict__ probs, const int32_t* __restrict__ frame_lens,
                                                            long long rows, int Tp, int V, int blank,
@@ -268,6 +253,14 @@ __global__ __launch_bounds__(64) void align_chain_kernel(const float* __restrict
 
 }  // namespace
 
+void launch_ctc_gather(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank, const int32_t* tokens,
+                       const int32_t* n_tokens, int max_tokens, float* emis, hipStream_t st) {
+  const long long rows = (long long)B * Tp;
+  if (rows > 0)
+    PPASR_LAUNCH(align_gather_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, probs, frame_lens, rows, Tp, V, blank,
+                 tokens, n_tokens, max_tokens, align_row_stride(max_tokens), emis);
+}
+
 void launch_ctc_align(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank, const int32_t* tokens,
                       const int32_t* n_tokens, int max_tokens, int32_t* frame_token, int32_t* begin, int32_t* end, int32_t* peak,
                       float* conf, float* score, int32_t* status, void* workspace, hipStream_t st) {
@@ -277,10 +270,7 @@ void launch_ctc_align(const float* probs, const int32_t* frame_lens, int B, int 
   uint16_t* bp = reinterpret_cast<uint16_t*>(ws + l.bp);
   int32_t* span = reinterpret_cast<int32_t*>(ws + l.span);
   const int stride = align_row_stride(max_tokens);
-  const long long rows = (long long)B * Tp;
-  if (rows > 0)
-    PPASR_LAUNCH(align_gather_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, probs, frame_lens, rows, Tp, V, blank,
-                 tokens, n_tokens, max_tokens, stride, emis);
+  launch_ctc_gather(probs, frame_lens, B, Tp, V, blank, tokens, n_tokens, max_tokens, emis, st);
   PPASR_LAUNCH(align_chain_kernel, dim3(B), dim3(64), 0, st, probs, frame_lens, Tp, V, blank, tokens, n_tokens, max_tokens, stride,
                emis, bp, span, frame_token, begin, end, peak, conf, score, status);
 }

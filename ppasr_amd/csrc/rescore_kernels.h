@@ -58,12 +58,20 @@ struct RescoreBufs {
 };
 
 // ppasr_set_memory_out: out [M][D] = LayerNorm(x) (g == nullptr: x itself); ragged batches (ps.lens): 0 behind the valid frames
+// ppasr_rescorer_loss: what launch_rescore computes in place of the hypothesis scores (nbest = 1; the labels are `tokens`)
+struct RescoreLoss {
+  double lsm_weight;
+  float* stat;         // workspace [rows_cap][2]: per row the logit sum over v < V and the log-sum-exp
+  double *att_kl, *r_att_kl;  // [B]
+  int32_t* rows;       // [B]
+};
+
 void launch_memory_out(const float* x, const float* g, const float* b, float* out, int M, int D, const PadSkip& ps,
                        hipStream_t st);
 hipError_t configure_rescore_kernels();
 void launch_rescore(const RescoreW& W, const RescoreDims& d, const RescoreBufs& bf, const float* memory, const int32_t* out_lens,
                     const int32_t* tokens, const int32_t* lens, const double* ctc_scores, double ctc_weight,
                     double reverse_weight, double* att, double* r_att, double* total, int32_t* best, float* token_logp,
-                    float* logits_tap, hipStream_t st);
+                    float* logits_tap, const RescoreLoss* loss, hipStream_t st);
 
 }  // namespace ppasr

@@ -9,6 +9,7 @@
 //   k_dec_output (1)  after_norm -> output_layer with running max / sum over the vocabulary tiles; keeps the target's
 //                     log-probability only (the logits leave the chip only into the parity tests' tap)
 //   k_dec_score (1)   per-hypothesis sums in double, the combine with the CTC score and the argmax
+// ppasr_rescorer_loss makes the same walk with nbest = 1 and ends in k_dec_output<true> + k_dec_loss instead.
 // Left and right decoder share every launch (a tile belongs to one direction and reads that direction's weights).
 // Grids are sized from B * nbest * 2 * (max_tokens + 1); blocks behind the device-side tile count exit.
 // Dense layers: rowblock.h (exact fp32 on the matrix core, weights streamed in fragment order).
@@ -376,12 +377,17 @@ __global__ __launch_bounds__(kThreads) void k_dec_crossout_ffn(RescoreW W, Resco
 
 // after_norm -> output_layer over the vocabulary 256 columns at a time; per row only the running max / sum and the target's
 // logit are kept.  tap (parity tests): the logits themselves, [B * nbest][2][L][V].
+// kLoss (ppasr_rescorer_loss): the row also keeps X, the sum of its logits over the real columns v < V, and writes
+// stat [row][2] = (X, log-sum-exp); the padded columns up to Vp never enter X.  Lanes are summed as a tree, waves in order.
+template <bool kLoss>
 __global__ __launch_bounds__(kThreads) void k_dec_output(RescoreW W, RescoreDims d, RowTab tab, const float* __restrict__ x,
                                                          const int32_t* __restrict__ tokens, const int32_t* __restrict__ lens,
-                                                         float* __restrict__ logp, float* __restrict__ tap) {
+                                                         float* __restrict__ logp, float* __restrict__ tap,
+                                                         float* __restrict__ stat) {
   __shared__ float a[kTileLds];
   __shared__ int s_tgt[32], s_hyp[32], s_pos[32];
   __shared__ float s_tv[32], s_m[kWaves][32], s_s[kWaves][32];
+  __shared__ float s_x[kLoss ? kWaves : 1][32];
   const int t = blockIdx.x;
   if (t >= tab.counts[0]) return;
   const int dir = tab.tile_info[t] / d.B;
@@ -404,6 +410,7 @@ __global__ __launch_bounds__(kThreads) void k_dec_output(RescoreW W, RescoreDims
   rb_layernorm(a, a, kLda, 32, S.ang, S.anb, kLnEps);
   __syncthreads();
   float m[16], s[16];
+  [[maybe_unused]] float xs[16];
   int tgt[16];
   size_t tap_row[16];
 #pragma unroll
@@ -411,6 +418,7 @@ __global__ __launch_bounds__(kThreads) void k_dec_output(RescoreW W, RescoreDims
     const int row = acc_row(r, lane);
     m[r] = -INFINITY;
     s[r] = 0.f;
+    if constexpr (kLoss) xs[r] = 0.f;
     tgt[r] = s_tgt[row];
     tap_row[r] = (((size_t)max(s_hyp[row], 0) * 2 + dir) * d.L() + s_pos[row]) * W.V;
   }
@@ -430,6 +438,7 @@ __global__ __launch_bounds__(kThreads) void k_dec_output(RescoreW W, RescoreDims
         const float mn = fmaxf(m[r], v);
         s[r] = s[r] * expf(m[r] - mn) + expf(v - mn);
         m[r] = mn;
+        if constexpr (kLoss) xs[r] += v;
       }
     }
   }
@@ -443,10 +452,12 @@ __global__ __launch_bounds__(kThreads) void k_dec_output(RescoreW W, RescoreDims
       const float f1 = m[r] == -INFINITY ? 0.f : expf(m[r] - mn), f2 = m2 == -INFINITY ? 0.f : expf(m2 - mn);
       s[r] = s[r] * f1 + s2 * f2;
       m[r] = mn;
+      if constexpr (kLoss) xs[r] += __shfl_xor(xs[r], o);
     }
     if ((lane & 31) == 0) {
       s_m[w][acc_row(r, lane)] = m[r];
       s_s[w][acc_row(r, lane)] = s[r];
+      if constexpr (kLoss) s_x[w][acc_row(r, lane)] = xs[r];
     }
   }
   __syncthreads();
@@ -457,7 +468,44 @@ __global__ __launch_bounds__(kThreads) void k_dec_output(RescoreW W, RescoreDims
     float sum = 0.f;
     for (int k = 0; k < kWaves; ++k) sum += s_m[k][row] == -INFINITY ? 0.f : s_s[k][row] * expf(s_m[k][row] - M);
     logp[t * 32 + row] = s_tgt[row] >= 0 ? s_tv[row] - (M + logf(sum)) : 0.f;
+    if constexpr (kLoss) {
+      float X = 0.f;
+      for (int k = 0; k < kWaves; ++k) X += s_x[k][row];
+      stat[(size_t)(t * 32 + row) * 2] = s_tgt[row] >= 0 ? X : 0.f;
+      stat[(size_t)(t * 32 + row) * 2 + 1] = s_tgt[row] >= 0 ? M + logf(sum) : 0.f;
+    }
   }
+}
+
+// ppasr_rescorer_loss: per utterance (nbest = 1) and direction the label-smoothing KL of its L + 1 target rows, summed in
+// double in row order.  With c = 1 - s:  kl_row = c ln c + s ln(s / (V - 1)) - c logp_y - s / (V - 1) (X - x_y - (V - 1) lse),
+// 0 ln 0 = 0, and x_y = logp_y + lse.  At s = 0 the row term is -logp_y exactly.
+__global__ __launch_bounds__(64) void k_dec_loss(RescoreDims d, RowTab tab, const int32_t* __restrict__ lens,
+                                                 const float* __restrict__ logp, const float* __restrict__ stat, int V, double lsm,
+                                                 double* __restrict__ att_kl, double* __restrict__ r_att_kl,
+                                                 int32_t* __restrict__ rows) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= d.B) return;
+  const int len = min(lens[b], d.max_tokens);
+  const double c = 1.0 - lsm, low = lsm / (double)(V - 1);
+  const double k0 = (c > 0.0 ? c * log(c) : 0.0) + (lsm > 0.0 ? lsm * log(low) : 0.0);
+  double kl[2] = {0.0, 0.0};
+  for (int dir = 0; dir < d.ndir; ++dir) {
+    const int r0 = len >= 0 ? tab.hyp_row0[dir * d.B + b] : -1;
+    if (r0 < 0) continue;
+    for (int p = 0; p <= len; ++p) {
+      const double lp = (double)logp[r0 + p];
+      double row = k0 - c * lp;
+      if (lsm > 0.0) {
+        const double X = (double)stat[(size_t)(r0 + p) * 2], lse = (double)stat[(size_t)(r0 + p) * 2 + 1];
+        row -= low * (X - lp - (double)V * lse);
+      }
+      kl[dir] += row;
+    }
+  }
+  att_kl[b] = kl[0];
+  r_att_kl[b] = kl[1];
+  rows[b] = len >= 0 ? len + 1 : 0;
 }
 
 // per-hypothesis sums (double), total = (1 - rw) att + rw r_att - cw ctc, best = first largest total; also the
@@ -549,7 +597,7 @@ hipError_t configure_rescore_kernels() {
 void launch_rescore(const RescoreW& W, const RescoreDims& d, const RescoreBufs& bf, const float* memory, const int32_t* out_lens,
                     const int32_t* tokens, const int32_t* lens, const double* ctc_scores, double ctc_weight,
                     double reverse_weight, double* att, double* r_att, double* total, int32_t* best, float* token_logp,
-                    float* logits_tap, hipStream_t st) {
+                    float* logits_tap, const RescoreLoss* loss, hipStream_t st) {
   const int tiles = d.tiles_cap();
   const int slots = W.n_left + (d.ndir == 2 ? W.side[1].nblk : 0);
   const int kvw = 512 * (W.n_left + W.side[1].nblk);
@@ -564,7 +612,15 @@ void launch_rescore(const RescoreW& W, const RescoreDims& d, const RescoreBufs& 
     PPASR_LAUNCH(k_dec_cross_attn, dim3(tiles, 4), dim3(256), 0, st, W, d, bf.tab, l, out_lens, bf.qc, bf.kv, kvw, bf.ctx);
     PPASR_LAUNCH(k_dec_crossout_ffn, dim3(tiles), dim3(kThreads), kFfnLds, st, W, d, bf.tab, l, bf.ctx, bf.x);
   }
-  PPASR_LAUNCH(k_dec_output, dim3(tiles), dim3(kThreads), 0, st, W, d, bf.tab, bf.x, tokens, lens, bf.logp, logits_tap);
+  if (loss) {  // ppasr_rescorer_loss: the same walk (nbest = 1), the row statistics of the smoothed target on top
+    PPASR_LAUNCH(k_dec_output<true>, dim3(tiles), dim3(kThreads), 0, st, W, d, bf.tab, bf.x, tokens, lens, bf.logp, logits_tap,
+                 loss->stat);
+    PPASR_LAUNCH(k_dec_loss, dim3((d.B + 63) / 64), dim3(64), 0, st, d, bf.tab, lens, bf.logp, loss->stat, W.V, loss->lsm_weight,
+                 loss->att_kl, loss->r_att_kl, loss->rows);
+    return;
+  }
+  PPASR_LAUNCH(k_dec_output<false>, dim3(tiles), dim3(kThreads), 0, st, W, d, bf.tab, bf.x, tokens, lens, bf.logp, logits_tap,
+               static_cast<float*>(nullptr));
   PPASR_LAUNCH(k_dec_score, dim3(d.B), dim3(64), 0, st, d, bf.tab, lens, bf.logp, ctc_scores, ctc_weight, reverse_weight, att,
                r_att, total, best, token_logp);
 }

@@ -118,6 +118,39 @@ class AttentionRescorer:
                                               ptr(res.get("logits")), ws.data_ptr(), ws.numel(), stream))
         return res
 
+    def loss(self, memory, out_lens, labels, label_lens, lsm_weight=0.0, reverse_weight=0.0, workspace=None, out=None):
+        """The label-smoothing loss of the decoder, teacher-forced over one label per utterance (``ppasr_rescorer_loss``):
+        memory [B, Tp, D] f32, out_lens [B] i32 or None, labels [B, max_tokens] i32 (only the first label_lens[b] of a row
+        are read), label_lens [B] i32 -> dict of device tensors: att_kl, r_att_kl [B] f64 (the sums of the row KL terms
+        over the label_lens[b] + 1 target rows of the left decoder, and of the right decoder over the reversed label; 0
+        when ``reverse_weight`` is 0), rows [B] i32.  At ``lsm_weight = 0``, att_kl is ``-att`` of ``rescore`` on the same
+        label.  Asynchronous on the current stream.  ``workspace`` / ``out``: caller-owned buffers (tests)."""
+        dev = self.device
+        memory = torch.as_tensor(memory, dtype=torch.float32).to(dev).contiguous()
+        labels = torch.as_tensor(labels, dtype=torch.int32).to(dev).contiguous()
+        label_lens = torch.as_tensor(label_lens, dtype=torch.int32).to(dev).contiguous()
+        ol = None if out_lens is None else torch.as_tensor(out_lens, dtype=torch.int32).to(dev).contiguous()
+        B, Tp, D = memory.shape
+        mt = labels.shape[1]
+        assert D == self.d_model and labels.shape[0] == B and label_lens.shape == (B,)
+        o = {} if out is None else out
+        new = lambda name, dt: o[name] if name in o else torch.empty((B,), dtype=dt, device=dev)
+        res = dict(att_kl=new("att_kl", torch.float64), r_att_kl=new("r_att_kl", torch.float64), rows=new("rows", torch.int32))
+        with torch.cuda.device(dev):
+            if workspace is None:
+                need = int(self.lib.ppasr_rescorer_loss_workspace_bytes(self._h, B, Tp, mt))
+                key = torch.cuda.current_stream(dev).cuda_stream
+                workspace = self._ws.get(key)
+                if workspace is None or workspace.numel() < need:
+                    workspace = self._ws[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(self.lib.ppasr_rescorer_loss(self._h, memory.data_ptr(), None if ol is None else ol.data_ptr(), B, Tp,
+                                                    labels.data_ptr() if mt else None, label_lens.data_ptr(), mt,
+                                                    float(lsm_weight), float(reverse_weight), res["att_kl"].data_ptr(),
+                                                    res["r_att_kl"].data_ptr(), res["rows"].data_ptr(),
+                                                    workspace.data_ptr(), workspace.numel(), stream))
+        return res
+
 
 def attention_rescoring(model, rescorer, probs, memory, out_lens, vocabulary, beam_size=10, ctc_weight=0.5,
                         reverse_weight=0.0, cutoff_prob=0.99, cutoff_top_n=40, blank_id=0, return_ids=False):

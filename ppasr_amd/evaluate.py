@@ -1,6 +1,7 @@
-"""Batched evaluation harness: the decode half of ``PPASRTrainer.evaluate`` (ppasr/trainer.py:592-645) and
-``__decoder_result`` (:330-352) on top of the HIP hot path.  The loss half needs the training graph (attention decoder,
-CTC loss) and is out of scope; ``evaluate`` returns the mean CER / WER only.
+"""Batched evaluation harness: ``PPASRTrainer.evaluate`` (ppasr/trainer.py:592-645) and ``__decoder_result`` (:330-352)
+on top of the HIP hot path.  ``evaluate`` returns the mean CER / WER; with ``return_loss=True`` it returns the
+reference's pair ``(loss, error_rate)``, the loss being ``model.forward``'s (CTC and attention losses, forward only:
+``model_utils/loss``).  Training itself (backward pass, dropout) is not built.
 
 With ``torch.distributed`` initialised, every rank evaluates the batches ``rank::world`` and the per-utterance error
 rates are summed with one all-reduce (utterance data parallelism, NOTES.md §6).  For variable-length batches
@@ -59,7 +60,7 @@ def decoder_result(outs, vocabulary, decoder="ctc_greedy", beam_search_decoder=N
 
 def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer", beam_search_decoder=None,
              display_result=False, trim_padding=False, overlap_decode=True, shard="batches", rescorer=None,
-             rescoring_conf=None):
+             rescoring_conf=None, return_loss=False, loss_conf=None):
     """model: any ppasr_amd model with ``get_encoder_out(inputs, input_lens)``;
     batches: iterable of (inputs [B,T,F], labels [B,U] (-1 padded), input_lens [B], label_lens [B]) like the reference's
     test_loader.  -> mean error rate (float), -1 if there is nothing to score (trainer.py:643).
@@ -73,10 +74,30 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
     padded-row decoding; with ``decoder != "ctc_greedy"`` a ``beam_search_decoder`` is required (no silent greedy).
     ``decoder="attention_rescoring"``: ``rescorer`` (an ``AttentionRescorer`` of the same checkpoint) is required and
     ``rescoring_conf`` holds the keyword arguments of ``decoders.attention_rescoring.attention_rescoring`` (beam_size,
-    ctc_weight, reverse_weight, cutoff_prob, cutoff_top_n); ``shard="batches"`` only, encode and decode on one stream."""
+    ctc_weight, reverse_weight, cutoff_prob, cutoff_top_n); ``shard="batches"`` only, encode and decode on one stream.
+    ``return_loss=True``: -> ``(loss, error_rate)`` like the reference; ``loss`` is the mean over batches of
+    ``model_loss(...)["loss"] / accum_grad`` (trainer.py:624, 642; -1 without batches) with ``loss_conf`` holding
+    ``ctc_weight`` (default 0.5; a DeepSpeech2 model's loss is its CTC loss alone), ``lsm_weight``, ``reverse_weight``,
+    ``length_normalized_loss`` and ``accum_grad``.  ``ctc_weight < 1`` needs ``rescorer``; ``shard="batches"`` only, encode
+    and decode on one stream.  The error rate is the one the same call returns without ``return_loss``."""
     rescoring = decoder == "attention_rescoring"
     if rescoring and (rescorer is None or shard != "batches"):
         raise ValueError("decoder='attention_rescoring' needs a rescorer and shard='batches'")
+    if return_loss:
+        from ppasr_amd.model_utils.loss import _branches, encode_for_loss, loss_of_encoded
+        if shard != "batches":
+            raise ValueError("return_loss=True needs shard='batches'")
+        lc = dict(loss_conf or {})
+        accum_grad = float(lc.pop("accum_grad", 1))
+        loss_kw = dict(lsm_weight=float(lc.pop("lsm_weight", 0.0)), reverse_weight=float(lc.pop("reverse_weight", 0.0)),
+                       length_normalized_loss=bool(lc.pop("length_normalized_loss", False)))
+        loss_cw = _branches(model, rescorer, lc.pop("ctc_weight", 0.5))
+        if lc:
+            raise ValueError("unknown loss_conf keys: " + ", ".join(sorted(lc)))
+        want_memory = loss_cw != 1.0
+    else:
+        want_memory = False
+    loss_total, loss_batches = 0.0, 0
     dist = torch.distributed.is_available() and torch.distributed.is_initialized()
     if shard == "buckets":
         return _evaluate_bucketed(model, batches, vocab_list, decoder, metrics_type, beam_search_decoder, display_result,
@@ -88,7 +109,7 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
     eos = len(vocab_list) - 1
     total, count = 0.0, 0
     dev = getattr(model, "device", None)
-    pipelined = overlap_decode and dev is not None and torch.device(dev).type == "cuda" and not rescoring
+    pipelined = overlap_decode and dev is not None and torch.device(dev).type == "cuda" and not rescoring and not return_loss
     enc_stream = torch.cuda.Stream(device=dev) if pipelined else None
 
     def encode(inputs, input_lens):
@@ -97,8 +118,8 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
             set_skip_padding_if_built(model, True)
             frame_lens = model.valid_out_frames(input_lens, inputs.shape[1])
         try:
-            outs = model.get_encoder_out(inputs, input_lens, return_memory=True) if rescoring else model.get_encoder_out(
-                inputs, input_lens)
+            outs = model.get_encoder_out(inputs, input_lens, return_memory=True) if rescoring or want_memory else \
+                model.get_encoder_out(inputs, input_lens)
         finally:
             if trim_padding:
                 set_skip_padding_if_built(model, False)
@@ -127,7 +148,20 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
         if batch_id % world != rank:
             continue
         if not pipelined:
-            outs, frame_lens = encode(inputs, input_lens)
+            if return_loss and not hasattr(model, "valid_out_frames"):  # DeepSpeech2: the encode itself returns the frames
+                probs, memory, frames = encode_for_loss(model, inputs, input_lens, False)
+                outs, frame_lens = probs, None
+            else:
+                outs, frame_lens = encode(inputs, input_lens)
+            if return_loss:  # the loss reads the probabilities (and the encoder output) the decode below reads
+                if hasattr(model, "valid_out_frames"):
+                    probs, memory = outs if rescoring or want_memory else (outs, None)
+                    frames = model.valid_out_frames(input_lens, inputs.shape[1])
+                loss_total += loss_of_encoded(rescorer, probs, memory, frames, labels, _label_lens, loss_cw,
+                                              **loss_kw)["loss"] / accum_grad
+                loss_batches += 1
+                if not rescoring:
+                    outs = probs
             score(outs, frame_lens, labels)
             continue
         dec_stream = torch.cuda.current_stream(dev)
@@ -147,9 +181,11 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
         score(*pending[:3])
     if dist:
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.distributed.get_backend() == "nccl" else "cpu"
-        t = torch.tensor([total, float(count)], dtype=torch.float64, device=dev)
+        t = torch.tensor([total, float(count), loss_total, float(loss_batches)], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t)
-        total, count = float(t[0]), int(t[1])
+        total, count, loss_total, loss_batches = float(t[0]), int(t[1]), float(t[2]), int(t[3])
+    if return_loss:
+        return (loss_total / loss_batches if loss_batches > 0 else -1), (total / count if count > 0 else -1)
     return total / count if count > 0 else -1
 
 

@@ -155,6 +155,41 @@ class PPASRPredictor:
         probs = self.predictor.predict_device(input_data, audio_len)[0]
         return self._token_times(probs, ids, len(samples) / float(sr))
 
+    def score(self, audio_data, text, sample_rate=16000):
+        """How likely is this transcript given this audio: ``{'ctc_nll', 'att_nll', 'tokens', 'frames'}`` with
+        ``ctc_nll = -log P_ctc(text | audio)`` (``model_utils/loss.ctc_nll``) and ``att_nll`` the left attention decoder's
+        ``-log P(text, eos | audio)`` (``AttentionRescorer.loss`` without smoothing; ``None`` when the predictor holds no
+        decoder weights, i.e. was not configured with ``decoder: attention_rescoring``).  The transcript is split as in
+        ``align``.  ValueError for a character that is not in the vocabulary and for a transcript that does not fit into
+        the utterance's frames."""
+        from ppasr_amd.decoders.ctc_alignment import frames_needed, text_to_ids
+        from ppasr_amd.model_utils.loss import STATUS_OK, ctc_nll
+        samples, sr = load_audio(audio_data, sample_rate)
+        feat = self._audio_featurizer.featurize(samples, sr)
+        input_data = np.asarray(feat, np.float32)[np.newaxis, :]
+        audio_len = np.array([input_data.shape[1]]).astype(np.int64)
+        ids = text_to_ids(text, self._text_featurizer.vocab_list, space_token=self.configs.decoder == "ctc_greedy")
+        rescorer = self.predictor.rescorer
+        if rescorer is not None:
+            probs, memory = self.predictor.predict_device_memory(input_data, audio_len)
+        else:
+            probs, memory = self.predictor.predict_device(input_data, audio_len), None
+        T, need = int(probs.shape[1]), frames_needed(ids)
+        if T < need:
+            raise ValueError(f"score: the transcript does not fit: T = {T} frames, {need} needed "
+                             f"({len(ids)} tokens, {need - len(ids)} repeats)")
+        lab = np.asarray(ids, np.int32).reshape(1, len(ids))
+        n = np.asarray([len(ids)], np.int32)
+        c = ctc_nll(probs, lab, n, None, self._blank())
+        pack = [c["nll"].to(torch.float64), c["status"].to(torch.float64)]
+        if rescorer is not None:
+            pack.append(rescorer.loss(memory, None, lab, n, 0.0, 0.0)["att_kl"])
+        host = torch.cat(pack).cpu().numpy()  # (the read-back)
+        if int(host[1]) != STATUS_OK:
+            raise ValueError(f"score: the transcript cannot be scored (status {int(host[1])})")
+        return {"ctc_nll": float(host[0]), "att_nll": float(host[2]) if rescorer is not None else None, "tokens": len(ids),
+                "frames": T}
+
     def predict_long(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, speech_timestamps=None,
                      vad_predictor=None, timestamps=False):
         """predict.py:190-229: recognise the speech segments of a long recording one by one and join the texts with
