@@ -775,6 +775,46 @@ PPASR_API ppasr_status ppasr_ctc_align(const float* probs, const int32_t* frame_
                                        int32_t* begin, int32_t* end, int32_t* peak, float* conf, float* score,
                                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- probability arena: the CTC tables of many streaming sessions, kept on the device so that a stream can be aligned ----
+ * A stream's table arrives one chunk per round.  The arena keeps the rows of every session in pages of page_frames rows
+ * inside one slab [n_pages][page_frames][V] f32 that is allocated once; the page list of every session and the free list
+ * live on the host.  ALL CALLS ON ONE ARENA GO ON ONE STREAM: reset and append are ordered against the launches that still
+ * read a page only by that stream's order.  The calls are not thread-safe.
+ *   create: n_sessions >= 1, V >= 2, page_frames >= 1, n_pages >= 1, the slab below 2^40 bytes (PPASR_EINVAL otherwise,
+ *     checked before any device call).
+ *   append: rows 0 .. frames_host[k] - 1 (NULL: all c) of probs_dev[k] ([n][c][V], device) go behind the last frame of
+ *     session sessions_host[k].  One kernel launch for all n sessions, plus one asynchronous upload of the call's table
+ *     from pinned memory; nothing is read back and the host does not wait for the device (the upload slots are a ring of
+ *     8: the ninth call waits for the first one's launch).  All or nothing: a call that needs more pages than are free
+ *     returns PPASR_ENOSPACE and changes no session, frame count or free page.  PPASR_EINVAL: n < 1, a session outside
+ *     [0, n_sessions) or listed twice, c < 0, a frames_host[k] outside [0, c], a NULL list or table.
+ *   reset: the session's (session < 0: every session's) pages go back to the free list; host bookkeeping only.
+ *   frames / free_pages: frames held for the session / pages not in use (-1 for a bad argument).
+ *   read: dense_dev [frames][V] = the session's table, one launch.
+ *   ppasr_ctc_align_arena: ppasr_ctc_align with B = n, Tp = the longest listed session and every session's own frame
+ *     count as its frame_lens; the emissions are read through the page lists, the chain and the workspace layout are
+ *     ppasr_ctc_align's, and every output equals, bit for bit, ppasr_ctc_align on the dense tables of the same sessions
+ *     (frame_token [n][Tp]).  tokens, n_tokens and the outputs are device pointers; sessions_host is a host list.
+ *     ppasr_ctc_align_arena_workspace_bytes(n, Tp, max_tokens) = ppasr_ctc_align_workspace_bytes.  Refusals: a session
+ *     outside the arena or listed twice, n < 1, blank outside [0, V), a NULL required pointer, a workspace that is not
+ *     16-byte aligned (PPASR_EINVAL); max_tokens > 255, n * Tp > 2^26 (PPASR_EUNSUPPORTED; an append: n * c > 2^30); a workspace below
+ *     ppasr_ctc_align_arena_workspace_bytes (PPASR_ENOSPACE).  A refused call leaves the arena as it was. */
+typedef struct ppasr_prob_arena_s* ppasr_prob_arena;
+PPASR_API ppasr_status ppasr_prob_arena_create(int n_sessions, int V, int page_frames, int n_pages, ppasr_prob_arena* out);
+PPASR_API ppasr_status ppasr_prob_arena_destroy(ppasr_prob_arena arena);
+PPASR_API ppasr_status ppasr_prob_arena_append(ppasr_prob_arena arena, const int* sessions_host, int n, const float* probs_dev,
+                                               int c, const int* frames_host, void* stream);
+PPASR_API ppasr_status ppasr_prob_arena_reset(ppasr_prob_arena arena, int session);
+PPASR_API long long    ppasr_prob_arena_frames(ppasr_prob_arena arena, int session);
+PPASR_API long long    ppasr_prob_arena_free_pages(ppasr_prob_arena arena);
+PPASR_API ppasr_status ppasr_prob_arena_read(ppasr_prob_arena arena, int session, float* dense_dev, void* stream);
+PPASR_API size_t ppasr_ctc_align_arena_workspace_bytes(int n, int Tp, int max_tokens);
+PPASR_API ppasr_status ppasr_ctc_align_arena(ppasr_prob_arena arena, const int* sessions_host, int n, int blank,
+                                             const int32_t* tokens, const int32_t* n_tokens, int max_tokens,
+                                             int32_t* frame_token, int32_t* begin, int32_t* end, int32_t* peak, float* conf,
+                                             float* score, int32_t* status, void* workspace, size_t workspace_bytes,
+                                             void* stream);
+
 /* ---- the loss half of evaluation: CTC and attention losses, forward only (the reference's ConformerModel.forward) ----
  * CTC negative log-likelihood: nll[b] = -log P_ctc(tokens[b] | probs[b]), the sum over every alignment where
  * ppasr_ctc_align takes the best one.  Inputs, trellis, emission clamp, statuses and refusals are ppasr_ctc_align's; the

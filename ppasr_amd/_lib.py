@@ -221,6 +221,17 @@ SYMBOLS = [
     ("ppasr_ctc_align_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("ppasr_ctc_align", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp,
                                        ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("ppasr_prob_arena_create", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    ("ppasr_prob_arena_destroy", ctypes.c_int, [_vp]),
+    ("ppasr_prob_arena_append", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _vp, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_int), _vp]),
+    ("ppasr_prob_arena_reset", ctypes.c_int, [_vp, ctypes.c_int]),
+    ("ppasr_prob_arena_frames", ctypes.c_longlong, [_vp, ctypes.c_int]),
+    ("ppasr_prob_arena_free_pages", ctypes.c_longlong, [_vp]),
+    ("ppasr_prob_arena_read", ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    ("ppasr_ctc_align_arena_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("ppasr_ctc_align_arena", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                             ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     ("ppasr_ctc_loss_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("ppasr_ctc_loss", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp,
                                       ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),

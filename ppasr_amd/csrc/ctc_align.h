@@ -61,4 +61,18 @@ void launch_ctc_align(const float* probs, const int32_t* frame_lens, int B, int 
                       const int32_t* n_tokens, int max_tokens, int32_t* frame_token, int32_t* begin, int32_t* end, int32_t* peak,
                       float* conf, float* score, int32_t* status, void* workspace, hipStream_t st);
 
+// ---- probability arena (ppasr_prob_arena_*): a slab [n_pages][P][V]; every table below is a device array ----
+// The alignment of B sessions held in pages: utterance b has frame_lens[b] <= Tp frames, frame t in row t % P of page
+// pages[page_off[b] + t / P].  The paged gather, then the chain of launch_ctc_align; same workspace, same outputs.
+void launch_ctc_align_paged(const float* slab, int V, int P, const int32_t* page_off, const int32_t* pages,
+                            const int32_t* frame_lens, int B, int Tp, int blank, const int32_t* tokens, const int32_t* n_tokens,
+                            int max_tokens, int32_t* frame_token, int32_t* begin, int32_t* end, int32_t* peak, float* conf,
+                            float* score, int32_t* status, void* workspace, hipStream_t st);
+// One launch: rows 0 .. count[k] - 1 of probs[k] ([n][c][V], n * c > 0) become frames first[k] .. of entry k's session, whose
+// pages from page first[k] / P on are pages[page_off[k] ..].
+void launch_arena_append(const float* probs, int n, int c, int V, int P, const int32_t* first, const int32_t* count,
+                         const int32_t* page_off, const int32_t* pages, float* slab, hipStream_t st);
+// dense [T][V] (T > 0) = the frames held in pages[0 .. (T - 1) / P]
+void launch_arena_read(const float* slab, int V, int P, const int32_t* pages, int T, float* dense, hipStream_t st);
+
 }  // namespace ppasr

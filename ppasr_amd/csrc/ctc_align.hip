@@ -29,6 +29,13 @@
 //     back-pointers, 64 frames at a time through an 8 KB LDS copy (a dependent LDS read per frame, not a dependent global
 //     one), then the wave fills begin / end over frames and peak / conf over tokens in parallel.
 //   Nothing is accumulated with atomics, and no word of the workspace or of an output is read before this call wrote it.
+//
+// PAGED TABLES (ppasr_prob_arena_*, capi_align.hip).  A stream's table grows by one chunk per round, so it is kept in pages
+//   of page_frames rows inside one slab: frame t of session b is row t % page_frames of page pages[page_off[b] + t /
+//   page_frames].  arena_append_kernel copies one round's rows of every listed session behind their last frames with one
+//   launch (one workgroup per row; words, so every bit pattern survives).  align_gather_paged_kernel is the gather above
+//   with the row found through the page list, and the chain is the same kernel: the only place where it reads the table
+//   itself (peak / conf) finds the row through DenseRows or PagedRows.  Rows behind a session's last frame are never read.
 #include "ctc_align.h"
 
 #include "launch.h"
@@ -59,12 +66,75 @@ __global__ __launch_bounds__(256) void align_gather_kernel(const float* __restri
   }
 }
 
+// where row t of utterance b lies: a dense [B][Tp][V] table, or the pages of a probability arena
+struct DenseRows {
+  const float* probs;
+  int Tp, V;
+  __device__ __forceinline__ const float* row(int b, int t) const { return probs + ((size_t)b * Tp + t) * V; }
+};
+struct PagedRows {
+  const float* slab;         // [n_pages][P][V]
+  const int32_t* page_off;   // [B]: where utterance b's page list starts in `pages`
+  const int32_t* pages;      // page of frames jP .. jP + P - 1 of utterance b at [page_off[b] + j]
+  int P, V;
+  __device__ __forceinline__ const float* row(int b, int t) const {
+    return slab + ((size_t)pages[page_off[b] + t / P] * P + t % P) * V;
+  }
+};
+
+// align_gather_kernel over an arena: frame_lens [B] are the sessions' own frame counts (never NULL, all <= Tp)
+__global__ __launch_bounds__(256) void align_gather_paged_kernel(PagedRows table, const int32_t* __restrict__ frame_lens,
+                                                                 long long rows, int Tp, int blank,
+                                                                 const int32_t* __restrict__ tokens,
+                                                                 const int32_t* __restrict__ n_tokens, int max_tokens,
+                                                                 int stride, float* __restrict__ emis) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const int b = (int)(row / Tp), t = (int)(row - (long long)b * Tp);
+  if (t >= clamp_frames(frame_lens, b, Tp)) return;
+  const int L = n_tokens[b];
+  if (L < 0 || L > max_tokens) return;
+  const float* p = table.row(b, t);
+  float* e = emis + (size_t)row * stride;
+  if (lane == 0) e[stride - 4] = emission(p[blank]);
+  for (int l = lane; l < L; l += 64) {
+    const int tok = tokens[(size_t)b * max_tokens + l];
+    if ((unsigned)tok < (unsigned)table.V) e[l] = emission(p[tok]);
+  }
+}
+
+// One round's rows into the arena: workgroup (k, r) copies row r of entry k to frame first[k] + r of its session, whose
+// pages from page first[k] / P on are pages[page_off[k] ..].  Rows r >= count[k] are not appended.
+__global__ __launch_bounds__(256) void arena_append_kernel(const uint32_t* __restrict__ probs, int c, int V, int P,
+                                                           const int32_t* __restrict__ first, const int32_t* __restrict__ count,
+                                                           const int32_t* __restrict__ page_off,
+                                                           const int32_t* __restrict__ pages, uint32_t* __restrict__ slab) {
+  const int k = blockIdx.x / c, r = blockIdx.x - k * c;
+  if (r >= count[k]) return;
+  const int f = first[k] + r;
+  const int page = pages[page_off[k] + f / P - first[k] / P];
+  const uint32_t* src = probs + (size_t)blockIdx.x * V;
+  uint32_t* dst = slab + ((size_t)page * P + f % P) * V;
+  for (int v = threadIdx.x; v < V; v += 256) dst[v] = src[v];
+}
+
+// a session's pages as one dense [T][V] table: workgroup t copies frame t
+__global__ __launch_bounds__(256) void arena_read_kernel(const uint32_t* __restrict__ slab, int V, int P,
+                                                         const int32_t* __restrict__ pages, uint32_t* __restrict__ dense) {
+  const int t = blockIdx.x;
+  const uint32_t* src = slab + ((size_t)pages[t / P] * P + t % P) * V;
+  uint32_t* dst = dense + (size_t)t * V;
+  for (int v = threadIdx.x; v < V; v += 256) dst[v] = src[v];
+}
+
 struct Emis {
   float4 v;  // e(t, token 4i .. 4i+3) of lane i
   float eb;  // e(t, blank)
 };
 
-__global__ __launch_bounds__(64) void align_chain_kernel(const float* __restrict__ probs, const int32_t* __restrict__ frame_lens,
+template <class Rows>
+__global__ __launch_bounds__(64) void align_chain_kernel(const Rows table, const int32_t* __restrict__ frame_lens,
                                                          int Tp, int V, int blank, const int32_t* __restrict__ tokens,
                                                          const int32_t* __restrict__ n_tokens, int max_tokens, int stride,
                                                          const float* emis, uint16_t* bp, int32_t* span, int32_t* frame_token,
@@ -230,14 +300,13 @@ __global__ __launch_bounds__(64) void align_chain_kernel(const float* __restrict
   __syncthreads();
 
   // ---- peak / conf over tokens ----
-  const float* pu = probs + (size_t)b * Tp * V;
   for (int l = lane; l < L; l += 64) {
     const int t0 = min(max(sb[l], 0), T - 1), t1 = min(se[l], T);  // (in range as written; the clamp bounds the reads below)
     const int id = tk[l];
-    float best = pu[(size_t)t0 * V + id];
+    float best = table.row(b, t0)[id];
     int at_t = t0;
     for (int t = t0 + 1; t < t1; ++t) {
-      const float p = pu[(size_t)t * V + id];
+      const float p = table.row(b, t)[id];
       if (p > best) {
         best = p;
         at_t = t;
@@ -261,18 +330,51 @@ void launch_ctc_gather(const float* probs, const int32_t* frame_lens, int B, int
                  tokens, n_tokens, max_tokens, align_row_stride(max_tokens), emis);
 }
 
-void launch_ctc_align(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank, const int32_t* tokens,
+namespace {
+template <class Rows>
+void launch_ctc_chain(const Rows& table, const int32_t* frame_lens, int B, int Tp, int V, int blank, const int32_t* tokens,
                       const int32_t* n_tokens, int max_tokens, int32_t* frame_token, int32_t* begin, int32_t* end, int32_t* peak,
                       float* conf, float* score, int32_t* status, void* workspace, hipStream_t st) {
   const AlignLayout l = align_layout(B, Tp, max_tokens);
   char* ws = static_cast<char*>(workspace);
-  float* emis = reinterpret_cast<float*>(ws + l.emis);
-  uint16_t* bp = reinterpret_cast<uint16_t*>(ws + l.bp);
-  int32_t* span = reinterpret_cast<int32_t*>(ws + l.span);
-  const int stride = align_row_stride(max_tokens);
+  PPASR_LAUNCH(align_chain_kernel<Rows>, dim3(B), dim3(64), 0, st, table, frame_lens, Tp, V, blank, tokens, n_tokens, max_tokens,
+               align_row_stride(max_tokens), reinterpret_cast<const float*>(ws + l.emis), reinterpret_cast<uint16_t*>(ws + l.bp),
+               reinterpret_cast<int32_t*>(ws + l.span), frame_token, begin, end, peak, conf, score, status);
+}
+}  // namespace
+
+void launch_ctc_align(const float* probs, const int32_t* frame_lens, int B, int Tp, int V, int blank, const int32_t* tokens,
+                      const int32_t* n_tokens, int max_tokens, int32_t* frame_token, int32_t* begin, int32_t* end, int32_t* peak,
+                      float* conf, float* score, int32_t* status, void* workspace, hipStream_t st) {
+  float* emis = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_layout(B, Tp, max_tokens).emis);
   launch_ctc_gather(probs, frame_lens, B, Tp, V, blank, tokens, n_tokens, max_tokens, emis, st);
-  PPASR_LAUNCH(align_chain_kernel, dim3(B), dim3(64), 0, st, probs, frame_lens, Tp, V, blank, tokens, n_tokens, max_tokens, stride,
-               emis, bp, span, frame_token, begin, end, peak, conf, score, status);
+  launch_ctc_chain(DenseRows{probs, Tp, V}, frame_lens, B, Tp, V, blank, tokens, n_tokens, max_tokens, frame_token, begin, end,
+                   peak, conf, score, status, workspace, st);
+}
+
+void launch_ctc_align_paged(const float* slab, int V, int P, const int32_t* page_off, const int32_t* pages,
+                            const int32_t* frame_lens, int B, int Tp, int blank, const int32_t* tokens, const int32_t* n_tokens,
+                            int max_tokens, int32_t* frame_token, int32_t* begin, int32_t* end, int32_t* peak, float* conf,
+                            float* score, int32_t* status, void* workspace, hipStream_t st) {
+  float* emis = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_layout(B, Tp, max_tokens).emis);
+  const PagedRows table{slab, page_off, pages, P, V};
+  const long long rows = (long long)B * Tp;
+  if (rows > 0)
+    PPASR_LAUNCH(align_gather_paged_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, table, frame_lens, rows, Tp, blank,
+                 tokens, n_tokens, max_tokens, align_row_stride(max_tokens), emis);
+  launch_ctc_chain(table, frame_lens, B, Tp, V, blank, tokens, n_tokens, max_tokens, frame_token, begin, end, peak, conf, score,
+                   status, workspace, st);
+}
+
+void launch_arena_append(const float* probs, int n, int c, int V, int P, const int32_t* first, const int32_t* count,
+                         const int32_t* page_off, const int32_t* pages, float* slab, hipStream_t st) {
+  PPASR_LAUNCH(arena_append_kernel, dim3((unsigned)n * c), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(probs), c, V, P,
+               first, count, page_off, pages, reinterpret_cast<uint32_t*>(slab));
+}
+
+void launch_arena_read(const float* slab, int V, int P, const int32_t* pages, int T, float* dense, hipStream_t st) {
+  PPASR_LAUNCH(arena_read_kernel, dim3((unsigned)T), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(slab), V, P, pages,
+               reinterpret_cast<uint32_t*>(dense));
 }
 
 }  // namespace ppasr

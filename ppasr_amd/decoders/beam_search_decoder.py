@@ -278,9 +278,9 @@ class BeamSearchDecoder:
                                              self.cutoff_prob, self.cutoff_top_n, self.blank_id, self._ext_scorer)
         return [r[0][1] for r in res]
 
-    def decode_chunk(self, probs, logits_lens):
+    def decode_chunk(self, probs, logits_lens, return_ids=False):
         """Streaming: feed one chunk [B=1,c,V], return the current best (score, text).
-        beam_search_decoder.py:75-91"""
+        beam_search_decoder.py:75-91.  ``return_ids``: (score, text, ids)."""
         p = torch.as_tensor(probs, dtype=torch.float32)
         if p.dim() == 2:
             p = p[None]
@@ -293,7 +293,7 @@ class BeamSearchDecoder:
         lens = np.asarray(logits_lens).astype(np.int32)
         tokens, ln, scores, _ = beam_search_ids(p, self.beam_size, self.cutoff_prob, self.cutoff_top_n, self.blank_id,
                                                 frame_lens=lens, nbest=1, state=self._state, ext_scorer=self._ext_scorer)
-        return _results(tokens, ln, scores, self.vocab_list, 0)[0]
+        return _results(tokens, ln, scores, self.vocab_list, 0, with_ids=return_ids)[0]
 
     def reset_decoder(self):
         """beam_search_decoder.py:93-96"""
@@ -407,10 +407,10 @@ class BeamSearchSessions:
             self._lib.ppasr_beam_pool_status(self._h, out.ctypes.data_as(ctypes.c_void_p), self._stream())
         return out
 
-    def decode_chunks(self, sessions, probs, lens=None):
+    def decode_chunks(self, sessions, probs, lens=None, return_ids=False):
         """sessions: distinct indices (n); probs [n,c,V] (device tensor or array); lens [n] frames of each chunk (None:
         all c).  -> [(score, text)] by list position: each session's current best after this chunk.  One device-to-host
-        copy per call."""
+        copy per call.  ``return_ids``: (score, text, ids), the token ids the text was made of (for ``ctc_alignment``)."""
         ids = [int(s) for s in sessions]
         n = len(ids)
         if n < 1 or len(set(ids)) != n or any(not 0 <= s < self.n_sessions for s in ids):
@@ -442,4 +442,5 @@ class BeamSearchSessions:
         scores = host[:8 * n].view(np.float64)
         ln = host[8 * n:12 * n].view(np.int32)
         tk = host[12 * n:].view(np.int32).reshape(n, L)
-        return [(float(scores[k]), _text(tk[k, :max(int(ln[k]), 0)].tolist(), self.vocab_list)) for k in range(n)]
+        ids = [tk[k, :max(int(ln[k]), 0)].tolist() for k in range(n)]
+        return [(float(scores[k]), _text(ids[k], self.vocab_list)) + ((ids[k],) if return_ids else ()) for k in range(n)]

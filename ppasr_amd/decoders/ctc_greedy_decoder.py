@@ -70,10 +70,12 @@ def greedy_decoder_batch(probs_split, vocabulary, blank_index=0):
     return [greedy_decoder(p, vocabulary, blank_index)[1] for p in probs_split]
 
 
-def greedy_decoder_chunk(probs_seq, vocabulary, last_max_prob_list=None, last_max_index_list=None, blank_index=0):
+def greedy_decoder_chunk(probs_seq, vocabulary, last_max_prob_list=None, last_max_index_list=None, blank_index=0,
+                         frame_maxprob_list=None):
     """Streaming variant, ctc_greedy_decoder.py:52-89: the per-frame stage (argmax + max prob) runs on
     the GPU for the new chunk; the reference's stateful lists are kept with its (swapped) naming:
-    ``last_max_prob_list`` holds argmax indices, ``last_max_index_list`` holds non-blank max probs."""
+    ``last_max_prob_list`` holds argmax indices, ``last_max_index_list`` holds non-blank max probs.
+    ``frame_maxprob_list``: a list that takes the max prob of EVERY new frame (``ctc_alignment.greedy_runs`` reads it)."""
     if last_max_prob_list is None:
         last_max_prob_list = []
     if last_max_index_list is None:
@@ -85,6 +87,8 @@ def greedy_decoder_chunk(probs_seq, vocabulary, last_max_prob_list=None, last_ma
         prob = fp[0].cpu().numpy()
         last_max_prob_list.extend(list(idx))
         last_max_index_list.extend(list(prob[idx != blank_index]))
+        if frame_maxprob_list is not None:
+            frame_maxprob_list.extend(prob.tolist())
     hist = np.asarray(last_max_prob_list, np.int64)
     keep = np.ones(len(hist), bool)
     keep[1:] = hist[1:] != hist[:-1]

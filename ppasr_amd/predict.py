@@ -54,6 +54,9 @@ class PPASRPredictor:
         self.cached_feat = None
         self.greedy_last_max_prob_list = None
         self.greedy_last_max_index_list = None
+        # predict_stream(timestamps=True): audio fed so far, greedy's per-frame max probs, the beam's best ids and table
+        self._stream_seconds, self._stream_maxprob, self._stream_ids = 0.0, None, []
+        self._stream_arena, self._stream_overflow = None, False
         self.beam_search_decoder = None
         if self.configs.decoder == "attention_rescoring":
             if self.configs.use_model == "deepspeech2":
@@ -227,21 +230,31 @@ class PPASRPredictor:
         return out
 
     def predict_stream(self, audio_data, is_end=False, use_pun=False, is_itn=False, channels=1, samp_width=2,
-                       sample_rate=16000):
+                       sample_rate=16000, timestamps=False):
         """predict.py:232-337 (same windowing constants: 16 output frames per 67-frame window, stride 64,
-        3 cached feature frames, required_cache_size = -16)."""
+        3 cached feature frames, required_cache_size = -16).
+        ``timestamps=True`` (every call of the stream alike) adds ``'timestamps'``, the list ``predict(...,
+        timestamps=True)`` returns, for the current text: beam search keeps the stream's probabilities in a one-session
+        ``ProbArena`` and aligns against it, greedy reads its own frame lists.  None (with ``'table_overflow': True``)
+        once the stream outgrows the arena, and for more than 255 tokens.  Not built for DeepSpeech2, whose chunk
+        probabilities reach this method on the host."""
         if not self.configs.streaming:
             raise Exception(f"不支持改该模型流式识别，当前模型：{self.configs.use_model}")
         if self.configs.decoder == "attention_rescoring":
             raise NotImplementedError("decoder: attention_rescoring scores whole utterances (it attends to the encoder "
                                       "output of every frame): use predict / predict_long, or ctc_greedy / "
                                       "ctc_beam_search for predict_stream")
+        if timestamps and self.configs.use_model == "deepspeech2":
+            raise NotImplementedError("predict_stream(timestamps=True) is not built for DeepSpeech2 (its chunk probabilities "
+                                      "come back on the host): use serving.StreamPool(timestamps=True)")
+        rate = sample_rate
         if isinstance(audio_data, np.ndarray):
-            samples, _ = load_audio(audio_data, sample_rate)
+            samples, rate = load_audio(audio_data, sample_rate)
         elif isinstance(audio_data, bytes):
             samples = pcm_bytes_to_float(audio_data, channels, samp_width)
         else:
             raise Exception(f"不支持该数据类型，当前数据类型为：{type(audio_data)}")
+        self._stream_seconds += len(samples) / float(rate)
         self.remained_wav = samples if self.remained_wav is None else np.concatenate([self.remained_wav, samples])
         x_chunk = self._audio_featurizer.featurize(self.remained_wav, sample_rate)
         x_chunk = np.asarray(x_chunk, np.float32)[np.newaxis, :]
@@ -285,16 +298,60 @@ class PPASRPredictor:
                 probs = self.predictor._stream.encode_chunk(x, required_cache_size)  # device tensor [1,c,V]
                 lens = np.array([probs.shape[1]])
             if self.configs.decoder == "ctc_beam_search":
-                score, text = self.beam_search_decoder.decode_chunk(probs=probs, logits_lens=lens)
+                if timestamps:
+                    self._stream_keep(probs)
+                    score, text, self._stream_ids = self.beam_search_decoder.decode_chunk(probs=probs, logits_lens=lens,
+                                                                                          return_ids=True)
+                else:
+                    score, text = self.beam_search_decoder.decode_chunk(probs=probs, logits_lens=lens)
             else:
+                if timestamps and self._stream_maxprob is None:
+                    self._stream_maxprob = []
                 score, text, self.greedy_last_max_prob_list, self.greedy_last_max_index_list = greedy_decoder_chunk(
                     probs_seq=probs[0], vocabulary=self._text_featurizer.vocab_list,
                     last_max_index_list=self.greedy_last_max_index_list,
-                    last_max_prob_list=self.greedy_last_max_prob_list)
+                    last_max_prob_list=self.greedy_last_max_prob_list,
+                    frame_maxprob_list=self._stream_maxprob if timestamps else None)
         self.cached_feat = self.cached_feat[:, end - cached_feature_num:, :]
         if use_pun or is_itn:
             raise NotImplementedError("punctuation / ITN are outside the hot path")
+        if timestamps:
+            return self._stream_timestamps({"text": text, "score": score})
         return {"text": text, "score": score}
+
+    # ---- token timestamps of a stream ----
+    def _stream_keep(self, probs):
+        """One chunk's probabilities [1, c, V] (device) go behind the stream's table: a one-session arena sized for the
+        model's longest stream.  A stream that outgrows it loses its table until ``reset_stream``."""
+        from ppasr_amd.decoders.ctc_alignment import ProbArena
+        if self._stream_arena is None:
+            frames = int(getattr(self.predictor.model, "max_len", 5000))
+            self._stream_arena = ProbArena(1, int(probs.shape[2]), page_frames=16, n_pages=(frames + 15) // 16,
+                                           device=probs.device)
+        a = self._stream_arena
+        if not self._stream_overflow and a.frames(0) + int(probs.shape[1]) > a.n_pages * a.page_frames:
+            self._stream_overflow = True
+            a.reset(0)
+        if not self._stream_overflow:
+            a.append([0], probs)
+
+    def _stream_timestamps(self, result):
+        from ppasr_amd.decoders.ctc_alignment import MAX_TOKENS, greedy_runs, token_entries
+        step = self.predictor.model.total_subsampling * FRAME_SHIFT
+        vocab = self._text_featurizer.vocab_list
+        if self.configs.decoder == "ctc_beam_search":
+            ids = self._stream_ids
+            if self._stream_overflow or len(ids) > MAX_TOKENS:
+                result["timestamps"] = None
+                if self._stream_overflow:
+                    result["table_overflow"] = True
+                return result
+            spans = self._stream_arena.align([0], [ids], self._blank())[0] if ids else []
+            result["timestamps"] = token_entries(ids, spans, vocab, step, self._stream_seconds)
+        else:
+            ids, spans = greedy_runs(self.greedy_last_max_prob_list, self._stream_maxprob, 0)  # (the swapped naming: ids)
+            result["timestamps"] = token_entries(ids, spans, vocab, step, self._stream_seconds, space_as_blank=True)
+        return result
 
     def reset_stream(self):
         """predict.py:340-347"""
@@ -303,5 +360,9 @@ class PPASRPredictor:
         self.cached_feat = None
         self.greedy_last_max_prob_list = None
         self.greedy_last_max_index_list = None
+        self._stream_seconds, self._stream_maxprob, self._stream_ids = 0.0, None, []
+        self._stream_overflow = False
+        if self._stream_arena is not None:
+            self._stream_arena.reset(0)
         if self.configs.decoder == "ctc_beam_search" and self.beam_search_decoder is not None:
             self.beam_search_decoder.reset_decoder()

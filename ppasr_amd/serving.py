@@ -8,7 +8,15 @@ greedy_decoder_chunk's running lists) for N sessions and advances every session 
 set of kernel launches per round.  Each session's result equals what its own ``PPASRPredictor.predict_stream`` returns
 with the same decoder: ``ctc_greedy`` (the default), or ``ctc_beam_search``, where every round's CTC probabilities go to a
 ``BeamSearchSessions`` pool -- one beam-search launch for all sessions of the round, on the same stream as the encoder, with
-no host synchronisation in between."""
+no host synchronisation in between.
+
+``timestamps=True`` adds token times to a pool (``finish(...)["timestamps"]``, ``pool.timestamps(session)``).  A beam
+search's tokens are aligned against the session's probability table, which a ``ProbArena`` keeps on the device: one more
+launch per round, whatever the number of sessions.  Greedy keeps no table: its tokens are the runs of the frame ids the
+pool downloads anyway, which is their alignment whenever no frame is a near-tie.  Their confidences are read off the
+round's table before it is dropped (``ppasr_ctc_greedy``'s per-frame stage, a fixed number of launches per round): the
+head's own per-frame maximum is 1 / sum of its running statistics and may differ from the table's entry, which the
+alignment copies, in the last bit."""
 import numpy as np
 import torch
 
@@ -33,18 +41,37 @@ class _Session:
         self.result = None
         self.sample_rate = None  # fixed by the session's first packet
         self.resampler = None    # StreamResampler of a session whose rate is not the featurizer's
+        # timestamps=True only
+        self.seconds = 0.0       # audio fed so far
+        self.frame_maxprob = []  # greedy: largest entry of every output frame's table row so far
+        self.ids = []            # beam search: token ids of the current best hypothesis
+        self.overflow = False    # beam search: the session outgrew its share of the probability arena
 
 
 class StreamPool:
     def __init__(self, model, vocab_list, n_sessions, preprocess_conf=None, max_seconds=200.0, blank_index=0, group=None,
-                 decoder="ctc_greedy", decoder_conf=None, beam_compact=False):
+                 decoder="ctc_greedy", decoder_conf=None, beam_compact=False, timestamps=False, table_seconds=30.0,
+                 page_frames=16):
         """group: a ready session group for `model` with `n_sessions` slots (e.g. ``SqueezeformerStreamGroup``,
         ``GeneralConformerStreamGroup``); None =
         ``make_stream_group``'s choice.  decoder: "ctc_greedy" or "ctc_beam_search"; decoder_conf: keys of
         ``ctc_beam_search_decoder_conf`` (alpha, beta, beam_size, num_processes, cutoff_prob, cutoff_top_n,
         language_model_path), over the shipped values without a language model.  beam_compact: the beam-search pool
         compacts a session's prefix arena before it would grow its block (``BeamSearchSessions(compact=True)``), so that
-        long streams stay in bounded memory; not a decoder_conf key, which mirror the YAML."""
+        long streams stay in bounded memory; not a decoder_conf key, which mirror the YAML.
+        timestamps: ``finish`` adds ``"timestamps": [{"text", "start", "end", "score"}, ...]`` and ``timestamps(session)``
+        gives the same for the current partial text.  With beam search every session may keep ``table_seconds`` of
+        probabilities in an arena of ``page_frames``-row pages (n_sessions x ceil(table_seconds x frames per second /
+        page_frames) pages of page_frames x V floats, allocated once); a session that outgrows its share, or whose
+        hypothesis exceeds 255 tokens, gets ``"timestamps": None`` (with ``"table_overflow": True`` in the first case)
+        and keeps its text and score.  Off (the default): no arena, no extra launch, results as before."""
+        if not isinstance(timestamps, (bool, np.bool_)):
+            raise ValueError("StreamPool: timestamps must be True or False")
+        if isinstance(table_seconds, (bool, np.bool_)) or not isinstance(table_seconds, (int, float, np.integer, np.floating)) \
+                or not 0 < float(table_seconds) < float("inf"):
+            raise ValueError("StreamPool: table_seconds must be a positive number of seconds")
+        if isinstance(page_frames, (bool, np.bool_)) or not isinstance(page_frames, (int, np.integer)) or page_frames < 1:
+            raise ValueError("StreamPool: page_frames must be an integer >= 1")
         if decoder not in _DECODERS:
             raise ValueError(f"StreamPool: unknown decoder {decoder!r} (one of {', '.join(_DECODERS)})")
         if not isinstance(beam_compact, (bool, np.bool_)):
@@ -79,6 +106,16 @@ class StreamPool:
             from ppasr_amd.decoders.beam_search_decoder import BeamSearchSessions
             self.beam = BeamSearchSessions(n_sessions, vocab_list=self.vocab, blank_id=blank_index,
                                            compact=bool(beam_compact), **{**_BEAM_DEFAULTS, **conf})
+        self.with_timestamps = bool(timestamps)
+        self.frame_seconds = float(getattr(model, "total_subsampling", 4)) * 0.010  # (PPASRPredictor._token_times' step)
+        self.arena = None
+        self.session_pages = 0  # pages a session may hold
+        if self.with_timestamps and self.beam is not None:
+            from ppasr_amd.decoders.ctc_alignment import ProbArena
+            frames = int(np.ceil(float(table_seconds) / self.frame_seconds - 1e-6))  # (2.56 s / 0.04 s is 64 frames, not 65)
+            self.session_pages = max(1, -(-frames // int(page_frames)))
+            self.arena = ProbArena(n_sessions, len(self.vocab), page_frames=int(page_frames),
+                                   n_pages=int(n_sessions) * self.session_pages, device=self.beam._device)
 
     def _rate_of(self, session, sample_rate):
         """The rate of a packet for `session` (None = the featurizer's) -> (rate, the session's resampler or None: a new
@@ -105,6 +142,7 @@ class StreamPool:
         s = self.sessions[session]
         samples = (pcm_bytes_to_float(audio_data, channels, samp_width) if isinstance(audio_data, (bytes, bytearray))
                    else np.asarray(audio_data, np.float32).reshape(-1))
+        s.seconds += samples.size / float(rate)
         if resampler is not None:
             samples = resampler.push(samples)
         s.sample_rate, s.resampler = rate, resampler
@@ -148,6 +186,7 @@ class StreamPool:
         rates = [self._rate_of(i, sample_rate.get(i) if isinstance(sample_rate, dict) else sample_rate) for i in ids]
         new = [(pcm_bytes_to_float(a, channels, samp_width) if isinstance(a, (bytes, bytearray))
                 else np.asarray(a, np.float32).reshape(-1)) for a in audio]
+        seconds = [x.size / float(rate) for x, (rate, _) in zip(new, rates)]
         by_rate = {}  # foreign rate -> positions in `ids`
         for k, (rate, resampler) in enumerate(rates):
             if resampler is not None:
@@ -164,6 +203,7 @@ class StreamPool:
         feats, counts = self.featurizer.featurize_many(wavs)
         for k, i in enumerate(ids):  # nothing raises from here on: the sessions take their new state
             self.sessions[i].sample_rate, self.sessions[i].resampler = rates[k]
+            self.sessions[i].seconds += seconds[k]
             if k in states:
                 rates[k][1]._commit(states[k])
         # (the remainder's gain: on the host, as in feed)
@@ -209,22 +249,78 @@ class StreamPool:
         if self.beam is not None:
             # the probabilities stay on the device: the search is queued behind the encoder on the same stream
             _, _, probs = self.group.encode_chunks(ids, chunks, want_probs=True)
-            return [{"text": text, "score": score} for score, text in self.beam.decode_chunks(ids, probs)]
-        fa, fp = self.group.encode_chunks(ids, chunks)
+            if self.arena is None:
+                return [{"text": text, "score": score} for score, text in self.beam.decode_chunks(ids, probs)]
+            self._keep_table(ids, probs)
+            out = []
+            for i, (score, text, tokens) in zip(ids, self.beam.decode_chunks(ids, probs, return_ids=True)):
+                self.sessions[i].ids = tokens
+                out.append({"text": text, "score": score})
+            return out
+        if self.with_timestamps:
+            from ppasr_amd.decoders.ctc_greedy_decoder import greedy_decode_ids
+            fa, fp, probs = self.group.encode_chunks(ids, chunks, want_probs=True)
+            table_max = greedy_decode_ids(probs, None, self.blank)[4].cpu().numpy()  # each frame's largest table entry
+        else:
+            fa, fp = self.group.encode_chunks(ids, chunks)
         fa, fp = fa.cpu().numpy(), fp.cpu().numpy()
         out = []
         for k, i in enumerate(ids):
             s = self.sessions[i]
             s.frame_ids.extend(fa[k].tolist())
             s.frame_probs.extend(fp[k][fa[k] != self.blank].tolist())
+            if self.with_timestamps:
+                s.frame_maxprob.extend(table_max[k].tolist())
             out.append(self._result(s))
         return out
+
+    def _keep_table(self, ids, probs):
+        """The round's probabilities go behind the listed sessions' tables: one launch.  A session whose table would
+        outgrow its share of the arena gives its pages back and appends nothing from then on (until ``reset``); the
+        shares add up to the arena, so the others always fit."""
+        c = int(probs.shape[1])
+        room = self.session_pages * self.arena.page_frames
+        frames = []
+        for i in ids:
+            s = self.sessions[i]
+            if not s.overflow and self.arena.frames(i) + c > room:
+                s.overflow = True
+                self.arena.reset(i)
+            frames.append(0 if s.overflow else c)
+        self.arena.append(ids, probs, frames)
+
+    def timestamps(self, session):
+        """[{"text", "start", "end", "score"}, ...], one entry per token of the session's current text: start = first
+        frame x the model's frame step, end = one past the last frame x the step, clipped to the audio fed so far, score
+        = the token's largest probability in between.  None for a beam-search session without a table (it outgrew
+        ``table_seconds``) or with more than 255 tokens.  Beam search: one alignment call and one read-back."""
+        from ppasr_amd.decoders.ctc_alignment import MAX_TOKENS, greedy_runs, token_entries
+        if not self.with_timestamps:
+            raise ValueError("StreamPool.timestamps: the pool was built with timestamps=False")
+        s = self.sessions[session]
+        if self.arena is None:
+            ids, spans = greedy_runs(s.frame_ids, s.frame_maxprob, self.blank)
+            return token_entries(ids, spans, self.vocab, self.frame_seconds, s.seconds, space_as_blank=True)
+        if s.overflow or len(s.ids) > MAX_TOKENS:
+            return None
+        if not s.ids:
+            return []
+        spans = self.arena.align([session], [s.ids], self.blank)[0]
+        return token_entries(s.ids, spans, self.vocab, self.frame_seconds, s.seconds)
+
+    def session_probs(self, session):
+        """The session's probability table so far, a dense device tensor [frames, V] (beam search with timestamps=True;
+        [0, V] for a session that outgrew ``table_seconds``)."""
+        if self.arena is None:
+            raise ValueError("StreamPool.session_probs: no table is kept (timestamps=True with decoder='ctc_beam_search')")
+        return self.arena.read(session)
 
     def finish(self, session):
         """End of a session's audio (``predict_stream(..., is_end=True)``, predict.py:291-298): run the buffered full
         windows, then the last, shorter window if at least 7 frames (the conv front-end's context) are left.
-        -> the session's final result dict (None if it never produced output).  The session keeps its state until
-        ``reset``.  A session fed at a foreign rate flushes its resampler first: the last model-rate samples, which waited
+        -> the session's final result dict (None if it never produced output); with ``timestamps=True`` a copy of it
+        with ``"timestamps"`` (``timestamps(session)``) and, for a session that outgrew its table, ``"table_overflow":
+        True``.  The session keeps its state until ``reset``.  A session fed at a foreign rate flushes its resampler first: the last model-rate samples, which waited
         for audio that will not come, are fed like a packet."""
         s = self.sessions[session]
         if s.resampler is not None:
@@ -235,7 +331,12 @@ class StreamPool:
         if s.cached_feat is not None and s.cached_feat.shape[1] >= _CONTEXT:
             s.result = self._advance([session], s.cached_feat)[0]
             s.cached_feat = s.cached_feat[:, s.cached_feat.shape[1] - _KEEP:]
-        return s.result
+        if not self.with_timestamps or s.result is None:
+            return s.result
+        out = dict(s.result, timestamps=self.timestamps(session))
+        if s.overflow:
+            out["table_overflow"] = True
+        return out
 
     def _result(self, s):
         hist = np.asarray(s.frame_ids, np.int64)
@@ -251,4 +352,6 @@ class StreamPool:
         self.group.reset(session)
         if self.beam is not None:
             self.beam.reset(session)
+        if self.arena is not None:
+            self.arena.reset(session)
         self.sessions[session] = _Session()
