@@ -495,6 +495,9 @@ ppasr_status ppasr_stream_create(ppasr_handle h, ppasr_stream* out) {
   s->offset = 0;
   hipError_t e5 = hipMemset(s->xh_hist, 0, L * lo_alloc * D * sizeof(float));
   if (e5 == hipSuccess) e5 = upload_hist_table(h, s->hist_tab);
+  // (hipMemset on device memory and a pageable upload go to the null stream and may return before they have landed; the
+  // first chunk runs on the caller's stream, which need not wait for the null stream: create-time only)
+  if (e5 == hipSuccess) e5 = hipStreamSynchronize(nullptr);
   if (e5 != hipSuccess) {
     (void)ppasr_stream_destroy(s);
     return fail(PPASR_EHIP, "initialising the stream caches failed");
@@ -701,6 +704,10 @@ ppasr_status group_alloc(ppasr_handle h, int n_sessions, int max_frames, GroupFa
     e = upload_hist_table(h, g->hist_tab);
     if (e != hipSuccess) return bail("uploading the session-group history table failed", e);
   }
+  // (as in ppasr_stream_create: the clear and the upload above are null-stream work that a round on the caller's
+  // non-blocking stream does not wait for)
+  e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) return bail("waiting for the session-group clears failed", e);
   g->cache_t.assign(n_sessions, 0);
   g->cache_r.assign(n_sessions, 0);
   g->offset.assign(n_sessions, 0);
