@@ -841,6 +841,27 @@ PPASR_API ppasr_status ppasr_rescorer_loss(ppasr_rescorer r, const float* memory
                                            double lsm_weight, double reverse_weight, double* att_kl, double* r_att_kl,
                                            int32_t* rows, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- attention beam-search decoding: WeNet's `attention` decode mode with the checkpoint's left decoder ----
+ * An autoregressive beam search driven by the attention decoder itself (the reference's forward_one_step); the hypotheses
+ * are not limited to what the CTC head proposed.  The semantics -- candidates, tie rules, the eos carry-over, stopping and
+ * the outputs -- are defined once, in the header comment of csrc/attn_decode.hip.  One call, asynchronous on `stream`, no
+ * read-back: every one of the max_steps steps is enqueued, and the steps behind the end of the search return at once.
+ * `r`: any rescorer (r_num_blocks = 0 is fine: only the left decoder runs).  sos = eos = V - 1.
+ *   memory [B,Tp,D] f32, out_lens [B] i32 or NULL: as ppasr_rescore
+ *   tokens [B,beam_size,max_steps] i32 (-1 behind the hypothesis), lens [B,beam_size] i32, scores [B,beam_size] f64 (best
+ *     first), ended [B,beam_size] i32 (0: cut at max_steps), steps_run [1] i32
+ *   token_logp [B,beam_size,max_steps+1] f32 or NULL; trace_parent, trace_token [max_steps,B,beam_size] i32 and
+ *     trace_score [max_steps,B,beam_size] f64, each or NULL: -1 / 0.0 where nothing happened
+ * Refused before any device work: beam_size < 1 or > V, max_steps < 1, a NULL required pointer, a workspace that is not
+ * 16-byte aligned (PPASR_EINVAL); beam_size > 32, max_steps + 1 above max_len or above 256 rows (PPASR_EUNSUPPORTED); a
+ * workspace below ppasr_attention_decode_workspace_bytes (PPASR_ENOSPACE). */
+PPASR_API size_t ppasr_attention_decode_workspace_bytes(ppasr_rescorer r, int B, int Tp, int beam_size, int max_steps);
+PPASR_API ppasr_status ppasr_attention_decode(ppasr_rescorer r, const float* memory, const int32_t* out_lens, int B, int Tp,
+                                              int beam_size, int max_steps, int32_t* tokens, int32_t* lens, double* scores,
+                                              int32_t* ended, int32_t* steps_run, float* token_logp, int32_t* trace_parent,
+                                              int32_t* trace_token, double* trace_score, void* workspace,
+                                              size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

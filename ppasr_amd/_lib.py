@@ -238,6 +238,9 @@ SYMBOLS = [
     ("ppasr_rescorer_loss_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("ppasr_rescorer_loss", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                            ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("ppasr_attention_decode_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("ppasr_attention_decode", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 ]
 
 _lib = None

@@ -1,0 +1,48 @@
+// attn_decode.h -- attention beam-search decoding with the left decoder (attn_decode.hip, capi_attdecode.hip): the
+// workspace views and the launcher of one ppasr_attention_decode call.  Semantics: header comment of attn_decode.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rescore_kernels.h"
+
+namespace ppasr {
+
+constexpr int kAttDecMaxBeam = 32;
+
+struct AttDecDims {
+  int B, Tp, N, P;  // utterances, memory frames, beam_size, max_steps
+  __host__ __device__ int R() const { return B * N; }                   // rows, dense: r = b * N + k
+  __host__ __device__ int Rp() const { return (B * N + 31) / 32 * 32; }  // rows of the activation buffers (whole tiles)
+};
+
+struct AttDecBufs {
+  float *x, *q, *ctx, *qc;   // [Rp][256]: the new position's activations
+  float* kv;                 // [B * Tp][512 * n_left]: cross-attention k | v per layer
+  float* cache;              // [n_left][P][R][512]: self-attention k | v by (layer, position, utterance, slot)
+  float* logits;             // [Rp][Vp]
+  float* cand_lp;            // [R][N] the row's N largest log-probabilities, largest first
+  int32_t* cand_tok;         // [R][N]
+  double* score[2];          // [R]   (beam state, double-buffered: step i reads (i - 1) & 1 and writes i & 1)
+  int32_t* ended[2];         // [R]
+  uint8_t* anc[2];           // [R][256]: slot of the row's ancestor at every earlier position
+  int32_t *live, *last_tok;  // [Rp]: row runs the decoder at this step / its newest token
+  int32_t *utt_live, *utt_steps;  // [B]: live rows of the utterance / steps it has run
+  int32_t *tr_par, *tr_tok;  // [P][R]: the back-pointers the final hypotheses are read from
+  float* tr_lp;              // [P][R]: the summand of that step (0 on a carried-over ended row)
+};
+
+struct AttDecOut {
+  int32_t *tokens, *lens;
+  double* scores;
+  int32_t *ended, *steps_run;
+  float* token_logp;                      // or nullptr
+  int32_t *trace_parent, *trace_token;    // or nullptr
+  double* trace_score;                    // or nullptr
+};
+
+hipError_t configure_attention_decode_kernels();
+void launch_attention_decode(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
+                             const int32_t* out_lens, const AttDecOut& out, hipStream_t st);
+
+}  // namespace ppasr

@@ -2,12 +2,7 @@
 // one loader of weights.h) and ppasr_rescore (rescore_kernels.hip).
 #include "capi_internal.h"
 #include "rescore_kernels.h"
-
-struct ppasr_rescorer_s {
-  ppasr_rescorer_desc desc;
-  ppasr_model_s store;  // owns the device memory (the loader uploads through it)
-  RescoreW W{};
-};
+#include "rescorer_handle.h"
 
 namespace {
 

@@ -69,6 +69,9 @@ struct RescoreLoss {
 void launch_memory_out(const float* x, const float* g, const float* b, float* out, int M, int D, const PadSkip& ps,
                        hipStream_t st);
 hipError_t configure_rescore_kernels();
+// k_dec_kv alone, over the first `slots` layer slots (the left decoder's when slots = n_left): kv [B * Tp][512 * slots]
+void launch_dec_kv(const RescoreW& W, int B, int Tp, int slots, const float* memory, const int32_t* out_lens, float* kv,
+                   hipStream_t st);
 void launch_rescore(const RescoreW& W, const RescoreDims& d, const RescoreBufs& bf, const float* memory, const int32_t* out_lens,
                     const int32_t* tokens, const int32_t* lens, const double* ctc_scores, double ctc_weight,
                     double reverse_weight, double* att, double* r_att, double* total, int32_t* best, float* token_logp,

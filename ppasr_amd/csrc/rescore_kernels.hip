@@ -17,13 +17,11 @@
 
 #include <math.h>
 
+#include "dec_tile.h"
 #include "launch.h"
 
 namespace ppasr {
 namespace {
-
-constexpr float kLnEps = 1e-12f;  // LayerNorm(epsilon=1e-12) of decoder.py
-constexpr int kTileLds = kRows * kLda;  // floats of one [32][256] LDS tile
 
 // ---- row table ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_row_table(const int32_t* __restrict__ lens, RescoreDims d, RowTab tab) {
@@ -81,14 +79,6 @@ __global__ __launch_bounds__(256) void k_dec_embed(RescoreW W, RescoreDims d, Ro
     }
     *reinterpret_cast<f32x4*>(x + (size_t)r * kD + 4 * lane) = v;
   }
-}
-
-// acc = A[32 x 256] (LDS) x one 32-column tile of a packed K = 256 weight (positioned at the tile)
-__device__ __forceinline__ void gemm256(const float* a, const f32x4* __restrict__ wtile, f32x16 (&acc)[1][1]) {
-  BRing<1> ring;
-  acc_zero<1, 1>(acc);
-  ring_prime<1, kPF>(ring, wtile, 0);
-  rb_gemm<1, 1, kG256>(a, kLda, wtile, 0, nullptr, 0, ring, acc);
 }
 
 // ---- cross-attention keys / values of every layer --------------------------------------------------------------------
@@ -587,6 +577,12 @@ __global__ __launch_bounds__(256) void k_memory_out(const float* __restrict__ x,
 void launch_memory_out(const float* x, const float* g, const float* b, float* out, int M, int D, const PadSkip& ps,
                        hipStream_t st) {
   PPASR_LAUNCH(k_memory_out, dim3((M + 3) / 4), dim3(256), 0, st, x, g, b, out, M, D, ps.lens, ps.Tp, ps.mul);
+}
+
+void launch_dec_kv(const RescoreW& W, int B, int Tp, int slots, const float* memory, const int32_t* out_lens, float* kv,
+                   hipStream_t st) {
+  const RescoreDims d{B, Tp, 1, 0, 1};
+  PPASR_LAUNCH(k_dec_kv, dim3((B * Tp + 31) / 32, 2 * slots), dim3(kThreads), 0, st, W, d, memory, out_lens, 512 * slots, kv);
 }
 
 hipError_t configure_rescore_kernels() {

@@ -43,6 +43,7 @@ class AttentionRescorer:
         self.num_blocks = int(conf.pop("num_blocks", 6))
         self.r_num_blocks = int(conf.pop("r_num_blocks", 0))
         max_len = int(conf.pop("max_len", max_len))
+        self.max_len = max_len if max_len > 0 else 5000  # (0: the library's default table length)
         if conf:
             raise ValueError("unknown decoder_conf keys: " + ", ".join(sorted(conf)))
         self.lib = _lib.load()
@@ -116,6 +117,57 @@ class AttentionRescorer:
                                               float(reverse_weight), res["att"].data_ptr(), res["r_att"].data_ptr(),
                                               res["total"].data_ptr(), res["best"].data_ptr(), ptr(res.get("token_logp")),
                                               ptr(res.get("logits")), ws.data_ptr(), ws.numel(), stream))
+        return res
+
+    def default_max_steps(self, Tp):
+        """WeNet's ``maxlen = T'``, within what the kernels and the positional table take."""
+        return max(1, min(int(Tp), MAX_ROWS - 1, self.max_len - 1))
+
+    def decode_workspace_bytes(self, B, Tp, beam_size, max_steps):
+        return int(self.lib.ppasr_attention_decode_workspace_bytes(self._h, B, Tp, beam_size, max_steps))
+
+    def decode(self, memory, out_lens, beam_size=10, max_steps=None, return_token_logp=False, return_trace=False,
+               workspace=None, out=None):
+        """Attention beam search with the left decoder (``ppasr_attention_decode``; the semantics are the header comment
+        of ``csrc/attn_decode.hip``): memory [B, Tp, D] f32, out_lens [B] i32 or None -> dict of device tensors: tokens
+        [B, beam_size, max_steps] i32 (-1 behind the hypothesis), lens [B, beam_size] i32, scores [B, beam_size] f64 (best
+        first), ended [B, beam_size] i32, steps_run [1] i32 (+ token_logp [B, beam_size, max_steps + 1] f32; trace_parent,
+        trace_token i32 and trace_score f64 [max_steps, B, beam_size] when asked for).  ``max_steps=None``:
+        ``min(Tp, 255, max_len - 1)``.  Asynchronous on the current stream, nothing is read back.  ``workspace`` / ``out``:
+        caller-owned buffers (tests)."""
+        dev = self.device
+        memory = torch.as_tensor(memory, dtype=torch.float32).to(dev).contiguous()
+        ol = None if out_lens is None else torch.as_tensor(out_lens, dtype=torch.int32).to(dev).contiguous()
+        B, Tp, D = memory.shape
+        assert D == self.d_model and (ol is None or ol.shape == (B,))
+        N = int(beam_size)
+        P = self.default_max_steps(Tp) if max_steps is None else int(max_steps)
+        o = {} if out is None else out
+        new = lambda name, shape, dt: o[name] if name in o else torch.empty(shape, dtype=dt, device=dev)
+        shp = lambda *s: tuple(max(int(v), 0) for v in s)
+        res = dict(tokens=new("tokens", shp(B, N, P), torch.int32), lens=new("lens", shp(B, N), torch.int32),
+                   scores=new("scores", shp(B, N), torch.float64), ended=new("ended", shp(B, N), torch.int32),
+                   steps_run=new("steps_run", (1,), torch.int32))
+        if return_token_logp:
+            res["token_logp"] = new("token_logp", shp(B, N, P + 1), torch.float32)
+        if return_trace:
+            res["trace_parent"] = new("trace_parent", shp(P, B, N), torch.int32)
+            res["trace_token"] = new("trace_token", shp(P, B, N), torch.int32)
+            res["trace_score"] = new("trace_score", shp(P, B, N), torch.float64)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            if workspace is None:
+                need = self.decode_workspace_bytes(B, Tp, N, P)
+                key = torch.cuda.current_stream(dev).cuda_stream
+                workspace = self._ws.get(key)
+                if workspace is None or workspace.numel() < need:
+                    workspace = self._ws[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(self.lib.ppasr_attention_decode(
+                self._h, memory.data_ptr(), ptr(ol), B, Tp, N, P, res["tokens"].data_ptr(), res["lens"].data_ptr(),
+                res["scores"].data_ptr(), res["ended"].data_ptr(), res["steps_run"].data_ptr(), ptr(res.get("token_logp")),
+                ptr(res.get("trace_parent")), ptr(res.get("trace_token")), ptr(res.get("trace_score")),
+                workspace.data_ptr(), workspace.numel(), stream))
         return res
 
     def loss(self, memory, out_lens, labels, label_lens, lsm_weight=0.0, reverse_weight=0.0, workspace=None, out=None):

@@ -60,7 +60,7 @@ def decoder_result(outs, vocabulary, decoder="ctc_greedy", beam_search_decoder=N
 
 def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer", beam_search_decoder=None,
              display_result=False, trim_padding=False, overlap_decode=True, shard="batches", rescorer=None,
-             rescoring_conf=None, return_loss=False, loss_conf=None):
+             rescoring_conf=None, return_loss=False, loss_conf=None, attention_conf=None):
     """model: any ppasr_amd model with ``get_encoder_out(inputs, input_lens)``;
     batches: iterable of (inputs [B,T,F], labels [B,U] (-1 padded), input_lens [B], label_lens [B]) like the reference's
     test_loader.  -> mean error rate (float), -1 if there is nothing to score (trainer.py:643).
@@ -75,14 +75,17 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
     ``decoder="attention_rescoring"``: ``rescorer`` (an ``AttentionRescorer`` of the same checkpoint) is required and
     ``rescoring_conf`` holds the keyword arguments of ``decoders.attention_rescoring.attention_rescoring`` (beam_size,
     ctc_weight, reverse_weight, cutoff_prob, cutoff_top_n); ``shard="batches"`` only, encode and decode on one stream.
+    ``decoder="attention"``: the attention beam search (``decoders.attention_decoder.attention_decode``); ``rescorer`` is
+    required likewise and ``attention_conf`` holds ``beam_size`` and ``max_steps``; ``shard="batches"`` only, one stream.
     ``return_loss=True``: -> ``(loss, error_rate)`` like the reference; ``loss`` is the mean over batches of
     ``model_loss(...)["loss"] / accum_grad`` (trainer.py:624, 642; -1 without batches) with ``loss_conf`` holding
     ``ctc_weight`` (default 0.5; a DeepSpeech2 model's loss is its CTC loss alone), ``lsm_weight``, ``reverse_weight``,
     ``length_normalized_loss`` and ``accum_grad``.  ``ctc_weight < 1`` needs ``rescorer``; ``shard="batches"`` only, encode
     and decode on one stream.  The error rate is the one the same call returns without ``return_loss``."""
-    rescoring = decoder == "attention_rescoring"
+    attention = decoder == "attention"
+    rescoring = decoder == "attention_rescoring" or attention  # (what follows: the decode reads the encoder output)
     if rescoring and (rescorer is None or shard != "batches"):
-        raise ValueError("decoder='attention_rescoring' needs a rescorer and shard='batches'")
+        raise ValueError(f"decoder={decoder!r} needs a rescorer and shard='batches'")
     if return_loss:
         from ppasr_amd.model_utils.loss import _branches, encode_for_loss, loss_of_encoded
         if shard != "batches":
@@ -127,7 +130,11 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
 
     def score(outs, frame_lens, labels):
         nonlocal total, count
-        if rescoring:
+        if attention:
+            from ppasr_amd.decoders.attention_decoder import attention_decode
+            out_strings = [t for _, t in attention_decode(model, rescorer, outs[1], frame_lens, vocab_list,
+                                                          **dict(attention_conf or {}))]
+        elif rescoring:
             from ppasr_amd.decoders.attention_rescoring import attention_rescoring
             out_strings = [t for _, t in attention_rescoring(model, rescorer, outs[0], outs[1], frame_lens, vocab_list,
                                                              **dict(rescoring_conf or {}))]

@@ -62,12 +62,13 @@ class InferencePredictor:
             from ppasr_amd.model_utils.deepspeech2.model import DeepSpeech2Model as cls
         self.model = cls(input_dim, vocab_size, streaming=streaming, encoder_conf=enc, state_dict=state_dict,
                          device=device)
-        # decoder: attention_rescoring -- the checkpoint's attention decoder (decoder.left_decoder.* / right_decoder.*,
-        # shaped by the YAML's decoder_conf) next to the encoder; a checkpoint without those weights raises here
+        # decoder: attention_rescoring / attention -- the checkpoint's attention decoder (decoder.left_decoder.* /
+        # right_decoder.*, shaped by the YAML's decoder_conf) next to the encoder; a checkpoint without those weights
+        # raises here
         self.rescorer = None
-        if _get(configs, "decoder") == "attention_rescoring":
+        if _get(configs, "decoder") in ("attention_rescoring", "attention"):
             if use_model == "deepspeech2":
-                raise ValueError("decoder: attention_rescoring needs a Conformer-family model (DeepSpeech2 has no "
+                raise ValueError(f"decoder: {_get(configs, 'decoder')} needs a Conformer-family model (DeepSpeech2 has no "
                                  "attention decoder)")
             from ppasr_amd.decoders.attention_rescoring import AttentionRescorer
             dec = _get(configs, "decoder_conf", {}) or {}

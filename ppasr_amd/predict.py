@@ -65,6 +65,11 @@ class PPASRPredictor:
             # WeNet's decode defaults with the shipped reverse_weight (configs/conformer.yml)
             self._rescoring_conf = dict(beam_size=10, ctc_weight=0.5, reverse_weight=0.3, cutoff_prob=0.99, cutoff_top_n=40)
             self._rescoring_conf.update(dict(self.configs.get("attention_rescoring_decoder_conf") or {}))
+        if self.configs.decoder == "attention":
+            if self.configs.use_model == "deepspeech2":
+                raise ValueError("decoder: attention needs a Conformer-family model (DeepSpeech2 has no attention decoder)")
+            self._attention_conf = dict(beam_size=10, max_steps=None)  # WeNet's decode defaults (maxlen = T')
+            self._attention_conf.update(dict(self.configs.get("attention_decoder_conf") or {}))
         if self.configs.decoder == "ctc_beam_search":
             from ppasr_amd.decoders.beam_search_decoder import BeamSearchDecoder
             self.beam_search_decoder = BeamSearchDecoder(vocab_list=self._text_featurizer.vocab_list,
@@ -106,6 +111,14 @@ class PPASRPredictor:
             score, text = attention_rescoring(self.predictor.model, self.predictor.rescorer, probs, memory, None,
                                               self._text_featurizer.vocab_list, **self._rescoring_conf)[0]
             return {"text": text, "score": score}
+        if self.configs.decoder == "attention":
+            if use_pun or is_itn:
+                raise NotImplementedError("punctuation / ITN are outside the hot path")
+            from ppasr_amd.decoders.attention_decoder import attention_decode
+            _, memory = self.predictor.predict_device_memory(input_data, audio_len)
+            score, text = attention_decode(self.predictor.model, self.predictor.rescorer, memory, None,
+                                           self._text_featurizer.vocab_list, **self._attention_conf)[0]
+            return {"text": text, "score": score}
         probs = self.predictor.predict_device(input_data, audio_len)[0]  # stays on the device
         score, text = self.decode(output_data=probs, use_pun=use_pun, is_itn=is_itn)
         return {"text": text, "score": score}
@@ -137,6 +150,12 @@ class PPASRPredictor:
             score, text, ids = attention_rescoring(self.predictor.model, self.predictor.rescorer, probs, memory, None, vocab,
                                                    return_ids=True, **self._rescoring_conf)[0]
             probs = probs[0]
+        elif self.configs.decoder == "attention":
+            from ppasr_amd.decoders.attention_decoder import attention_decode
+            probs, memory = self.predictor.predict_device_memory(input_data, audio_len)
+            score, text, ids = attention_decode(self.predictor.model, self.predictor.rescorer, memory, None, vocab,
+                                                return_ids=True, **self._attention_conf)[0]
+            probs = probs[0]
         else:
             probs = self.predictor.predict_device(input_data, audio_len)[0]
             if self.configs.decoder == "ctc_beam_search":
@@ -162,7 +181,7 @@ class PPASRPredictor:
         """How likely is this transcript given this audio: ``{'ctc_nll', 'att_nll', 'tokens', 'frames'}`` with
         ``ctc_nll = -log P_ctc(text | audio)`` (``model_utils/loss.ctc_nll``) and ``att_nll`` the left attention decoder's
         ``-log P(text, eos | audio)`` (``AttentionRescorer.loss`` without smoothing; ``None`` when the predictor holds no
-        decoder weights, i.e. was not configured with ``decoder: attention_rescoring``).  The transcript is split as in
+        decoder weights, i.e. was not configured with ``decoder: attention_rescoring`` or ``attention``).  The transcript is split as in
         ``align``.  ValueError for a character that is not in the vocabulary and for a transcript that does not fit into
         the utterance's frames."""
         from ppasr_amd.decoders.ctc_alignment import frames_needed, text_to_ids
@@ -240,8 +259,8 @@ class PPASRPredictor:
         probabilities reach this method on the host."""
         if not self.configs.streaming:
             raise Exception(f"不支持改该模型流式识别，当前模型：{self.configs.use_model}")
-        if self.configs.decoder == "attention_rescoring":
-            raise NotImplementedError("decoder: attention_rescoring scores whole utterances (it attends to the encoder "
+        if self.configs.decoder in ("attention_rescoring", "attention"):
+            raise NotImplementedError(f"decoder: {self.configs.decoder} scores whole utterances (it attends to the encoder "
                                       "output of every frame): use predict / predict_long, or ctc_greedy / "
                                       "ctc_beam_search for predict_stream")
         if timestamps and self.configs.use_model == "deepspeech2":
