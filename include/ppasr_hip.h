@@ -862,6 +862,32 @@ PPASR_API ppasr_status ppasr_attention_decode(ppasr_rescorer r, const float* mem
                                               int32_t* trace_token, double* trace_score, void* workspace,
                                               size_t workspace_bytes, void* stream);
 
+/* ---- CTC-joint scoring inside the attention beam search (WeNet's ctc_weight in its attention beam search) ----
+ * ppasr_attention_decode with the CTC prefix score of every candidate added inside the search:
+ *   comb[v] = logp_att[v] + (float)ctc_weight * (Psi(g.v) - Psi(g)),
+ * Psi(h) the log-probability, under the CTC table, that the transcript starts with h (for eos: that it IS g).  The
+ * semantics are defined once, in the header comment of csrc/attn_decode_joint.hip.  One call, asynchronous on `stream`, no
+ * read-back, every step enqueued.
+ *   the arguments of ppasr_attention_decode, and
+ *   ctc_probs [B,Tp,V_ctc] f32: the CTC head's softmax output of the same encode (frames t >= out_lens[b] are not read);
+ *     V_ctc must equal the decoder's vocab_size; blank in [0, V - 1); ctc_weight >= 0
+ *   token_ctc [B,beam_size,max_steps+1] f32 or NULL: Psi(g.v) - Psi(g) at every position of the final hypotheses (then
+ *     token_logp holds logp_att); trace_ctc [max_steps,B,beam_size] f32 or NULL: Psi of each new row's hypothesis; 0.0
+ *     where nothing happened
+ * A row may offer, and an utterance may keep, fewer than beam_size finite candidates: the rest of the beam is at -inf
+ * (scores -inf, lens 0, ended 0).  ctc_weight == 0 (or one that rounds to 0 in fp32): ppasr_attention_decode itself runs,
+ * every output equals its output bit for bit, the workspace it needs suffices and ctc_probs may be NULL.
+ * Refused before any device work, beside the refusals of ppasr_attention_decode: NULL ctc_probs with ctc_weight > 0, blank
+ * outside [0, V - 1), V_ctc != vocab_size, ctc_weight negative or NaN (PPASR_EINVAL). */
+PPASR_API size_t ppasr_attention_decode_joint_workspace_bytes(ppasr_rescorer r, int B, int Tp, int beam_size, int max_steps);
+PPASR_API ppasr_status ppasr_attention_decode_joint(ppasr_rescorer r, const float* memory, const int32_t* out_lens, int B,
+                                                    int Tp, int beam_size, int max_steps, const float* ctc_probs, int V_ctc,
+                                                    int blank, double ctc_weight, int32_t* tokens, int32_t* lens,
+                                                    double* scores, int32_t* ended, int32_t* steps_run, float* token_logp,
+                                                    float* token_ctc, int32_t* trace_parent, int32_t* trace_token,
+                                                    double* trace_score, float* trace_ctc, void* workspace,
+                                                    size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,11 @@ SYMBOLS = [
     ("ppasr_attention_decode_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("ppasr_attention_decode", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp,
                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("ppasr_attention_decode_joint_workspace_bytes", ctypes.c_size_t, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                                       ctypes.c_int]),
+    ("ppasr_attention_decode_joint", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_double] + [_vp] * 12
+     + [ctypes.c_size_t, _vp]),
 ]
 
 _lib = None

@@ -41,7 +41,29 @@ struct AttDecOut {
   double* trace_score;                    // or nullptr
 };
 
+// the joint mode's share of the workspace and its taps (attn_decode_joint.hip)
+struct AttJointBufs {
+  const float* probs;   // [B][Tp][V] the CTC head's softmax output
+  const int32_t* out_lens;
+  int V, blank;
+  float weight;         // (float)ctc_weight
+  float* state[2];      // [R][Tp][2]: (rn, rb) of the row's hypothesis per frame, double-buffered like the scores
+  float* psi[2];        // [R]: Psi of the row's hypothesis
+  float* cpsi;          // [R][Vp]: Psi(g . v) of every candidate of a live row
+  float *cand_att, *cand_psi;  // [R][N]: the attention log-probability and Psi(g . v) of the row's offers
+  float* tr_ctc;        // [P][R]: Psi(g . v) - Psi(g) of that step (0 on a carried-over ended row); tr_lp: logp_att
+  float *token_ctc, *trace_ctc;  // taps, or nullptr
+};
+
 hipError_t configure_attention_decode_kernels();
+// the two halves of a plain step's launches that the joint mode shares: k_dec_kv + k_ad_init, and the decoder's layers
+// with the output GEMM of step `step` (logits of every live row in bf.logits)
+void launch_attdec_begin(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
+                         const int32_t* out_lens, hipStream_t st);
+void launch_attdec_decoder(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const int32_t* out_lens, int step,
+                           hipStream_t st);
+void launch_attention_decode_joint(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb,
+                                   const float* memory, const int32_t* out_lens, const AttDecOut& out, hipStream_t st);
 void launch_attention_decode(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
                              const int32_t* out_lens, const AttDecOut& out, hipStream_t st);
 

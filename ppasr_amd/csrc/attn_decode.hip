@@ -51,6 +51,7 @@
 
 #include <math.h>
 
+#include "attn_decode_dev.h"
 #include "dec_tile.h"
 #include "launch.h"
 
@@ -298,35 +299,6 @@ __global__ __launch_bounds__(kThreads) void k_ad_output(RescoreW W, AttDecDims d
   }
 }
 
-// (value, id) pairs ordered by larger value, then lower id
-__device__ __forceinline__ bool cand_before(float v1, int i1, float v2, int i2) { return v1 > v2 || (v1 == v2 && i1 < i2); }
-
-// the first pair of the workgroup's 256 in that order, to every thread (id V: none)
-__device__ __forceinline__ void block_first(float& v, int& id, float* s_v, int* s_i) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float v2 = __shfl_xor(v, o);
-    const int i2 = __shfl_xor(id, o);
-    if (cand_before(v2, i2, v, id)) {
-      v = v2;
-      id = i2;
-    }
-  }
-  __syncthreads();
-  if (lane_id() == 0) {
-    s_v[threadIdx.x >> 6] = v;
-    s_i[threadIdx.x >> 6] = id;
-  }
-  __syncthreads();
-  v = s_v[0];
-  id = s_i[0];
-  for (int k = 1; k < 4; ++k)
-    if (cand_before(s_v[k], s_i[k], v, id)) {
-      v = s_v[k];
-      id = s_i[k];
-    }
-}
-
 // log-softmax over v < V of a live row and its N largest entries, largest first, lower id first on equal values
 __global__ __launch_bounds__(256) void k_ad_topn(AttDecDims d, AttDecBufs bf, int V, int Vp) {
   __shared__ float s_v[4];
@@ -475,22 +447,32 @@ __global__ __launch_bounds__(64) void k_ad_finish(AttDecDims d, AttDecBufs bf, i
 
 }  // namespace
 
+void launch_attdec_begin(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
+                         const int32_t* out_lens, hipStream_t st) {
+  launch_dec_kv(W, d.B, d.Tp, W.n_left, memory, out_lens, bf.kv, st);
+  PPASR_LAUNCH(k_ad_init, dim3(((d.Rp() > d.B ? d.Rp() : d.B) + 255) / 256), dim3(256), 0, st, d, bf, W.V);
+}
+
+void launch_attdec_decoder(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const int32_t* out_lens, int step,
+                           hipStream_t st) {
+  const int L = W.n_left, R = d.R(), tiles = d.Rp() / 32;
+  const int p = step - 1, cur = (step - 1) & 1;
+  for (int l = 0; l < L; ++l) {
+    PPASR_LAUNCH(k_ad_qkv, dim3(tiles), dim3(kThreads), 0, st, W, d, bf, l, p);
+    PPASR_LAUNCH(k_ad_attn<true>, dim3(R), dim3(256), 0, st, d, bf, l, p, cur, L, out_lens);
+    PPASR_LAUNCH(k_ad_selfout_q, dim3(tiles), dim3(kThreads), 0, st, W, d, bf, l);
+    PPASR_LAUNCH(k_ad_attn<false>, dim3(R), dim3(256), 0, st, d, bf, l, p, cur, L, out_lens);
+    PPASR_LAUNCH(k_ad_crossout_ffn, dim3(tiles), dim3(kThreads), kAdFfnLds, st, W, d, bf, l);
+  }
+  PPASR_LAUNCH(k_ad_output, dim3(tiles, W.Vp / 256), dim3(kThreads), 0, st, W, d, bf);
+}
+
 void launch_attention_decode(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
                              const int32_t* out_lens, const AttDecOut& out, hipStream_t st) {
-  const int L = W.n_left, R = d.R(), tiles = d.Rp() / 32;
-  launch_dec_kv(W, d.B, d.Tp, L, memory, out_lens, bf.kv, st);
-  PPASR_LAUNCH(k_ad_init, dim3(((d.Rp() > d.B ? d.Rp() : d.B) + 255) / 256), dim3(256), 0, st, d, bf, W.V);
+  launch_attdec_begin(W, d, bf, memory, out_lens, st);
   for (int step = 1; step <= d.P; ++step) {
-    const int p = step - 1, cur = (step - 1) & 1;
-    for (int l = 0; l < L; ++l) {
-      PPASR_LAUNCH(k_ad_qkv, dim3(tiles), dim3(kThreads), 0, st, W, d, bf, l, p);
-      PPASR_LAUNCH(k_ad_attn<true>, dim3(R), dim3(256), 0, st, d, bf, l, p, cur, L, out_lens);
-      PPASR_LAUNCH(k_ad_selfout_q, dim3(tiles), dim3(kThreads), 0, st, W, d, bf, l);
-      PPASR_LAUNCH(k_ad_attn<false>, dim3(R), dim3(256), 0, st, d, bf, l, p, cur, L, out_lens);
-      PPASR_LAUNCH(k_ad_crossout_ffn, dim3(tiles), dim3(kThreads), kAdFfnLds, st, W, d, bf, l);
-    }
-    PPASR_LAUNCH(k_ad_output, dim3(tiles, W.Vp / 256), dim3(kThreads), 0, st, W, d, bf);
-    PPASR_LAUNCH(k_ad_topn, dim3(R), dim3(256), 0, st, d, bf, W.V, W.Vp);
+    launch_attdec_decoder(W, d, bf, out_lens, step, st);
+    PPASR_LAUNCH(k_ad_topn, dim3(d.R()), dim3(256), 0, st, d, bf, W.V, W.Vp);
     PPASR_LAUNCH(k_ad_select, dim3(d.B), dim3(1024), 0, st, d, bf, step, W.V, out);
   }
   PPASR_LAUNCH(k_ad_finish, dim3(d.B), dim3(64), 0, st, d, bf, W.V, out);

@@ -1,4 +1,5 @@
-// capi_attdecode.hip -- C-ABI of attention beam-search decoding on an existing rescorer (attn_decode.hip).
+// capi_attdecode.hip -- C-ABI of attention beam-search decoding on an existing rescorer (attn_decode.hip) and of its
+// CTC-joint mode (attn_decode_joint.hip).
 #include "attn_decode.h"
 #include "capi_internal.h"
 #include "rescorer_handle.h"
@@ -46,6 +47,60 @@ AttDecLayout attdec_layout(const ppasr_rescorer_s* r, const AttDecDims& d) {
   return l;
 }
 
+AttDecBufs attdec_bufs(void* workspace, const AttDecLayout& l) {
+  char* ws = static_cast<char*>(workspace);
+  auto f = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  auto i32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
+  AttDecBufs bf;
+  bf.x = f(l.x);
+  bf.q = f(l.q);
+  bf.ctx = f(l.ctx);
+  bf.qc = f(l.qc);
+  bf.kv = f(l.kv);
+  bf.cache = f(l.cache);
+  bf.logits = f(l.logits);
+  bf.cand_lp = f(l.cand_lp);
+  bf.cand_tok = i32(l.cand_tok);
+  for (int i = 0; i < 2; ++i) {
+    bf.score[i] = reinterpret_cast<double*>(ws + l.score[i]);
+    bf.ended[i] = i32(l.ended[i]);
+    bf.anc[i] = reinterpret_cast<uint8_t*>(ws + l.anc[i]);
+  }
+  bf.live = i32(l.live);
+  bf.last_tok = i32(l.last_tok);
+  bf.utt_live = i32(l.utt_live);
+  bf.utt_steps = i32(l.utt_steps);
+  bf.tr_par = i32(l.tr_par);
+  bf.tr_tok = i32(l.tr_tok);
+  bf.tr_lp = f(l.tr_lp);
+  return bf;
+}
+
+// the joint mode's share, behind the plain layout (whose offsets stay as they are)
+struct AttJointLayout {
+  size_t state[2], psi[2], cpsi, cand_att, cand_psi, tr_ctc, total;
+};
+AttJointLayout attjoint_layout(const ppasr_rescorer_s* r, const AttDecDims& d, size_t base) {
+  AttJointLayout l;
+  const size_t R = d.R();
+  size_t o = base;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += al256(bytes);
+    return at;
+  };
+  for (int i = 0; i < 2; ++i) {
+    l.state[i] = take(R * d.Tp * 2 * 4);
+    l.psi[i] = take(R * 4);
+  }
+  l.cpsi = take(R * r->W.Vp * 4);
+  l.cand_att = take(R * d.N * 4);
+  l.cand_psi = take(R * d.N * 4);
+  l.tr_ctc = take((size_t)d.P * R * 4);
+  l.total = o;
+  return l;
+}
+
 bool attdec_shape_ok(int B, int Tp, int beam_size, int max_steps) {
   return B > 0 && Tp > 0 && beam_size >= 1 && beam_size <= kAttDecMaxBeam && max_steps >= 1 && max_steps + 1 <= kRescoreMaxRows &&
          (size_t)B * beam_size <= ((size_t)1 << 20) && (size_t)B * Tp <= ((size_t)1 << 24);
@@ -77,31 +132,7 @@ ppasr_status ppasr_attention_decode(ppasr_rescorer r, const float* memory, const
   const AttDecDims d{B, Tp, beam_size, max_steps};
   const AttDecLayout l = attdec_layout(r, d);
   if (workspace_bytes < l.total) return fail(PPASR_ENOSPACE, "workspace too small (ppasr_attention_decode_workspace_bytes)");
-  char* ws = static_cast<char*>(workspace);
-  auto f = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  auto i32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
-  AttDecBufs bf;
-  bf.x = f(l.x);
-  bf.q = f(l.q);
-  bf.ctx = f(l.ctx);
-  bf.qc = f(l.qc);
-  bf.kv = f(l.kv);
-  bf.cache = f(l.cache);
-  bf.logits = f(l.logits);
-  bf.cand_lp = f(l.cand_lp);
-  bf.cand_tok = i32(l.cand_tok);
-  for (int i = 0; i < 2; ++i) {
-    bf.score[i] = reinterpret_cast<double*>(ws + l.score[i]);
-    bf.ended[i] = i32(l.ended[i]);
-    bf.anc[i] = reinterpret_cast<uint8_t*>(ws + l.anc[i]);
-  }
-  bf.live = i32(l.live);
-  bf.last_tok = i32(l.last_tok);
-  bf.utt_live = i32(l.utt_live);
-  bf.utt_steps = i32(l.utt_steps);
-  bf.tr_par = i32(l.tr_par);
-  bf.tr_tok = i32(l.tr_tok);
-  bf.tr_lp = f(l.tr_lp);
+  const AttDecBufs bf = attdec_bufs(workspace, l);
   const AttDecOut out{tokens, lens, scores, ended, steps_run, token_logp, trace_parent, trace_token, trace_score};
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(configure_attention_decode_kernels());  // (a per-device attribute)
@@ -111,6 +142,79 @@ ppasr_status ppasr_attention_decode(ppasr_rescorer r, const float* memory, const
   if (trace_token) HIP_TRY(hipMemsetAsync(trace_token, 0xff, tn * sizeof(int32_t), st));
   if (trace_score) HIP_TRY(hipMemsetAsync(trace_score, 0, tn * sizeof(double), st));
   launch_attention_decode(r->W, d, bf, memory, out_lens, out, st);
+  HIP_TRY(hipGetLastError());
+  return PPASR_OK;
+}
+
+size_t ppasr_attention_decode_joint_workspace_bytes(ppasr_rescorer r, int B, int Tp, int beam_size, int max_steps) {
+  if (!r || !attdec_shape_ok(B, Tp, beam_size, max_steps)) return 0;
+  const AttDecDims d{B, Tp, beam_size, max_steps};
+  return attjoint_layout(r, d, attdec_layout(r, d).total).total;
+}
+
+ppasr_status ppasr_attention_decode_joint(ppasr_rescorer r, const float* memory, const int32_t* out_lens, int B, int Tp,
+                                          int beam_size, int max_steps, const float* ctc_probs, int V_ctc, int blank,
+                                          double ctc_weight, int32_t* tokens, int32_t* lens, double* scores, int32_t* ended,
+                                          int32_t* steps_run, float* token_logp, float* token_ctc, int32_t* trace_parent,
+                                          int32_t* trace_token, double* trace_score, float* trace_ctc, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  if (!r) return fail(PPASR_EINVAL, "null rescorer");
+  if (!(ctc_weight >= 0.0)) return fail(PPASR_EINVAL, "ctc_weight negative or NaN");
+  if (V_ctc != r->desc.vocab_size) return fail(PPASR_EINVAL, "V_ctc differs from the decoder's vocab_size");
+  if (blank < 0 || blank >= V_ctc - 1) return fail(PPASR_EINVAL, "blank outside [0, V - 1)");
+  if (!ctc_probs && ctc_weight > 0.0) return fail(PPASR_EINVAL, "null ctc_probs with ctc_weight > 0");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const float w = (float)ctc_weight;
+  if (w == 0.0f) {  // the plain search, bit for bit: no CTC kernel, no 0 * inf
+    const ppasr_status rc = ppasr_attention_decode(r, memory, out_lens, B, Tp, beam_size, max_steps, tokens, lens, scores, ended,
+                                                   steps_run, token_logp, trace_parent, trace_token, trace_score, workspace,
+                                                   workspace_bytes, stream);
+    if (rc != PPASR_OK) return rc;
+    if (token_ctc) HIP_TRY(hipMemsetAsync(token_ctc, 0, (size_t)B * beam_size * (max_steps + 1) * sizeof(float), st));
+    if (trace_ctc) HIP_TRY(hipMemsetAsync(trace_ctc, 0, (size_t)max_steps * B * beam_size * sizeof(float), st));
+    return PPASR_OK;
+  }
+  if (!memory || !tokens || !lens || !scores || !ended || !steps_run || !workspace) return fail(PPASR_EINVAL, "null argument");
+  if (B <= 0 || Tp <= 0 || max_steps < 1) return fail(PPASR_EINVAL, "bad shape");
+  if (beam_size < 1 || beam_size > r->desc.vocab_size) return fail(PPASR_EINVAL, "beam_size outside [1, vocab_size]");
+  if (beam_size > kAttDecMaxBeam) return fail(PPASR_EUNSUPPORTED, "beam_size above the 32 the selection is built for");
+  if (max_steps + 1 > r->desc.max_len) return fail(PPASR_EUNSUPPORTED, "max_steps + 1 exceeds the positional table (max_len)");
+  if (max_steps + 1 > kRescoreMaxRows)
+    return fail(PPASR_EUNSUPPORTED, "max_steps + 1 exceeds the 256 rows per hypothesis the kernels are built for");
+  if (!attdec_shape_ok(B, Tp, beam_size, max_steps)) return fail(PPASR_EUNSUPPORTED, "batch too large");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(PPASR_EINVAL, "workspace not 16-byte aligned");
+  const AttDecDims d{B, Tp, beam_size, max_steps};
+  const AttDecLayout l = attdec_layout(r, d);
+  const AttJointLayout jl = attjoint_layout(r, d, l.total);
+  if (workspace_bytes < jl.total)
+    return fail(PPASR_ENOSPACE, "workspace too small (ppasr_attention_decode_joint_workspace_bytes)");
+  const AttDecBufs bf = attdec_bufs(workspace, l);
+  char* ws = static_cast<char*>(workspace);
+  auto f = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  AttJointBufs jb;
+  jb.probs = ctc_probs;
+  jb.out_lens = out_lens;
+  jb.V = V_ctc;
+  jb.blank = blank;
+  jb.weight = w;
+  for (int i = 0; i < 2; ++i) {
+    jb.state[i] = f(jl.state[i]);
+    jb.psi[i] = f(jl.psi[i]);
+  }
+  jb.cpsi = f(jl.cpsi);
+  jb.cand_att = f(jl.cand_att);
+  jb.cand_psi = f(jl.cand_psi);
+  jb.tr_ctc = f(jl.tr_ctc);
+  jb.token_ctc = token_ctc;
+  jb.trace_ctc = trace_ctc;
+  const AttDecOut out{tokens, lens, scores, ended, steps_run, token_logp, trace_parent, trace_token, trace_score};
+  HIP_TRY(configure_attention_decode_kernels());
+  const size_t tn = (size_t)max_steps * B * beam_size;
+  if (trace_parent) HIP_TRY(hipMemsetAsync(trace_parent, 0xff, tn * sizeof(int32_t), st));
+  if (trace_token) HIP_TRY(hipMemsetAsync(trace_token, 0xff, tn * sizeof(int32_t), st));
+  if (trace_score) HIP_TRY(hipMemsetAsync(trace_score, 0, tn * sizeof(double), st));
+  if (trace_ctc) HIP_TRY(hipMemsetAsync(trace_ctc, 0, tn * sizeof(float), st));
+  launch_attention_decode_joint(r->W, d, bf, jb, memory, out_lens, out, st);
   HIP_TRY(hipGetLastError());
   return PPASR_OK;
 }

@@ -123,18 +123,26 @@ class AttentionRescorer:
         """WeNet's ``maxlen = T'``, within what the kernels and the positional table take."""
         return max(1, min(int(Tp), MAX_ROWS - 1, self.max_len - 1))
 
-    def decode_workspace_bytes(self, B, Tp, beam_size, max_steps):
-        return int(self.lib.ppasr_attention_decode_workspace_bytes(self._h, B, Tp, beam_size, max_steps))
+    def decode_workspace_bytes(self, B, Tp, beam_size, max_steps, joint=False):
+        fn = self.lib.ppasr_attention_decode_joint_workspace_bytes if joint else self.lib.ppasr_attention_decode_workspace_bytes
+        return int(fn(self._h, B, Tp, beam_size, max_steps))
 
     def decode(self, memory, out_lens, beam_size=10, max_steps=None, return_token_logp=False, return_trace=False,
-               workspace=None, out=None):
+               workspace=None, out=None, ctc_probs=None, ctc_weight=0.0, blank=0):
         """Attention beam search with the left decoder (``ppasr_attention_decode``; the semantics are the header comment
         of ``csrc/attn_decode.hip``): memory [B, Tp, D] f32, out_lens [B] i32 or None -> dict of device tensors: tokens
         [B, beam_size, max_steps] i32 (-1 behind the hypothesis), lens [B, beam_size] i32, scores [B, beam_size] f64 (best
         first), ended [B, beam_size] i32, steps_run [1] i32 (+ token_logp [B, beam_size, max_steps + 1] f32; trace_parent,
         trace_token i32 and trace_score f64 [max_steps, B, beam_size] when asked for).  ``max_steps=None``:
         ``min(Tp, 255, max_len - 1)``.  Asynchronous on the current stream, nothing is read back.  ``workspace`` / ``out``:
-        caller-owned buffers (tests)."""
+        caller-owned buffers (tests).
+
+        ``ctc_probs`` [B, Tp, V] f32 (the CTC head's softmax output of the same encode), ``ctc_weight`` and ``blank``
+        select the CTC-joint search (``ppasr_attention_decode_joint``, semantics: the header comment of
+        ``csrc/attn_decode_joint.hip``): every candidate also gets ``ctc_weight`` x its CTC prefix score.  Then the beam may
+        hold rows at -inf (lens 0), token_logp holds the attention summands, and token_ctc [B, beam_size, max_steps + 1]
+        f32 / trace_ctc [max_steps, B, beam_size] f32 come with token_logp / the trace.  With ``ctc_probs=None`` and
+        ``ctc_weight=0`` (the defaults) the plain entry point runs, as before."""
         dev = self.device
         memory = torch.as_tensor(memory, dtype=torch.float32).to(dev).contiguous()
         ol = None if out_lens is None else torch.as_tensor(out_lens, dtype=torch.int32).to(dev).contiguous()
@@ -154,15 +162,31 @@ class AttentionRescorer:
             res["trace_parent"] = new("trace_parent", shp(P, B, N), torch.int32)
             res["trace_token"] = new("trace_token", shp(P, B, N), torch.int32)
             res["trace_score"] = new("trace_score", shp(P, B, N), torch.float64)
+        joint = ctc_probs is not None or ctc_weight != 0.0
+        if joint:
+            cp = None if ctc_probs is None else torch.as_tensor(ctc_probs, dtype=torch.float32).to(dev).contiguous()
+            assert cp is None or (cp.dim() == 3 and cp.shape[:2] == (B, Tp)), "ctc_probs is [B, Tp, V] of the same encode"
+            if return_token_logp:
+                res["token_ctc"] = new("token_ctc", shp(B, N, P + 1), torch.float32)
+            if return_trace:
+                res["trace_ctc"] = new("trace_ctc", shp(P, B, N), torch.float32)
         ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
             if workspace is None:
-                need = self.decode_workspace_bytes(B, Tp, N, P)
+                need = self.decode_workspace_bytes(B, Tp, N, P, joint=joint)
                 key = torch.cuda.current_stream(dev).cuda_stream
                 workspace = self._ws.get(key)
                 if workspace is None or workspace.numel() < need:
                     workspace = self._ws[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
+            if joint:
+                _lib.check(self.lib.ppasr_attention_decode_joint(
+                    self._h, memory.data_ptr(), ptr(ol), B, Tp, N, P, ptr(cp), self.vocab_size if cp is None else cp.shape[2],
+                    int(blank), float(ctc_weight), res["tokens"].data_ptr(), res["lens"].data_ptr(), res["scores"].data_ptr(),
+                    res["ended"].data_ptr(), res["steps_run"].data_ptr(), ptr(res.get("token_logp")),
+                    ptr(res.get("token_ctc")), ptr(res.get("trace_parent")), ptr(res.get("trace_token")),
+                    ptr(res.get("trace_score")), ptr(res.get("trace_ctc")), workspace.data_ptr(), workspace.numel(), stream))
+                return res
             _lib.check(self.lib.ppasr_attention_decode(
                 self._h, memory.data_ptr(), ptr(ol), B, Tp, N, P, res["tokens"].data_ptr(), res["lens"].data_ptr(),
                 res["scores"].data_ptr(), res["ended"].data_ptr(), res["steps_run"].data_ptr(), ptr(res.get("token_logp")),

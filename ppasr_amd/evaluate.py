@@ -76,7 +76,8 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
     ``rescoring_conf`` holds the keyword arguments of ``decoders.attention_rescoring.attention_rescoring`` (beam_size,
     ctc_weight, reverse_weight, cutoff_prob, cutoff_top_n); ``shard="batches"`` only, encode and decode on one stream.
     ``decoder="attention"``: the attention beam search (``decoders.attention_decoder.attention_decode``); ``rescorer`` is
-    required likewise and ``attention_conf`` holds ``beam_size`` and ``max_steps``; ``shard="batches"`` only, one stream.
+    required likewise and ``attention_conf`` holds ``beam_size``, ``max_steps`` and ``ctc_weight`` (above 0: CTC-joint scoring
+    inside the search, on the table of the same encode); ``shard="batches"`` only, one stream.
     ``return_loss=True``: -> ``(loss, error_rate)`` like the reference; ``loss`` is the mean over batches of
     ``model_loss(...)["loss"] / accum_grad`` (trainer.py:624, 642; -1 without batches) with ``loss_conf`` holding
     ``ctc_weight`` (default 0.5; a DeepSpeech2 model's loss is its CTC loss alone), ``lsm_weight``, ``reverse_weight``,
@@ -132,7 +133,7 @@ def evaluate(model, batches, vocab_list, decoder="ctc_greedy", metrics_type="cer
         nonlocal total, count
         if attention:
             from ppasr_amd.decoders.attention_decoder import attention_decode
-            out_strings = [t for _, t in attention_decode(model, rescorer, outs[1], frame_lens, vocab_list,
+            out_strings = [t for _, t in attention_decode(model, rescorer, outs[1], frame_lens, vocab_list, probs=outs[0],
                                                           **dict(attention_conf or {}))]
         elif rescoring:
             from ppasr_amd.decoders.attention_rescoring import attention_rescoring

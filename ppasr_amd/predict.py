@@ -68,7 +68,8 @@ class PPASRPredictor:
         if self.configs.decoder == "attention":
             if self.configs.use_model == "deepspeech2":
                 raise ValueError("decoder: attention needs a Conformer-family model (DeepSpeech2 has no attention decoder)")
-            self._attention_conf = dict(beam_size=10, max_steps=None)  # WeNet's decode defaults (maxlen = T')
+            # WeNet's decode defaults (maxlen = T'); ctc_weight > 0: CTC-joint scoring inside the search
+            self._attention_conf = dict(beam_size=10, max_steps=None, ctc_weight=0.0)
             self._attention_conf.update(dict(self.configs.get("attention_decoder_conf") or {}))
         if self.configs.decoder == "ctc_beam_search":
             from ppasr_amd.decoders.beam_search_decoder import BeamSearchDecoder
@@ -115,9 +116,9 @@ class PPASRPredictor:
             if use_pun or is_itn:
                 raise NotImplementedError("punctuation / ITN are outside the hot path")
             from ppasr_amd.decoders.attention_decoder import attention_decode
-            _, memory = self.predictor.predict_device_memory(input_data, audio_len)
+            probs, memory = self.predictor.predict_device_memory(input_data, audio_len)
             score, text = attention_decode(self.predictor.model, self.predictor.rescorer, memory, None,
-                                           self._text_featurizer.vocab_list, **self._attention_conf)[0]
+                                           self._text_featurizer.vocab_list, probs=probs, **self._attention_conf)[0]
             return {"text": text, "score": score}
         probs = self.predictor.predict_device(input_data, audio_len)[0]  # stays on the device
         score, text = self.decode(output_data=probs, use_pun=use_pun, is_itn=is_itn)
@@ -154,7 +155,7 @@ class PPASRPredictor:
             from ppasr_amd.decoders.attention_decoder import attention_decode
             probs, memory = self.predictor.predict_device_memory(input_data, audio_len)
             score, text, ids = attention_decode(self.predictor.model, self.predictor.rescorer, memory, None, vocab,
-                                                return_ids=True, **self._attention_conf)[0]
+                                                return_ids=True, probs=probs, **self._attention_conf)[0]
             probs = probs[0]
         else:
             probs = self.predictor.predict_device(input_data, audio_len)[0]

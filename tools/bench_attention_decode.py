@@ -1,6 +1,7 @@
 """Attention beam-search decoding (csrc/attn_decode.hip) measured; one JSON line, run on one otherwise idle MI355X:
 
-    python tools/bench_attention_decode.py [--reps R] [--warmup W] [--B 32] [--out profiles/attention_decode.jsonl]
+    python tools/bench_attention_decode.py [--reps R] [--warmup W] [--B 32] [--ctc-weight 0.5]
+                                           [--out profiles/attention_decode.jsonl]
 
 Workload: B = 32 utterances x T' = 250 x beam 10 x V = 4233, 3 + 3 decoder blocks of 1024 units, max_steps = T'.  The
 decoder is synthetic (tests/decoder_cases.py); the output bias of the eos column is chosen by a scan, the first value at
@@ -15,6 +16,12 @@ which the search of this batch ends after 30 to 50 steps.
                read-back per step for the stopping test (WeNet's ``recognize``).  The cross-attention keys and values are
                computed once, which the reference does not do: the stand-in is given that much.
   rescore      for scale: ``ppasr_rescore`` (left decoder only) of the hypotheses the search returned
+``--ctc-weight W`` (W > 0) adds the CTC-joint search (csrc/attn_decode_joint.hip) of the same batch and decoder: the CTC table
+is peaked (0.9) on a seeded transcript of 30 to 40 tokens per utterance, so the joint search follows the transcripts.
+  hip_joint / hip_joint_live   ``AttentionRescorer.decode(..., ctc_probs, ctc_weight=W)``, as hip / hip_live
+  torch_joint_f32              torch_search with the CTC prefix score in torch float32 on the same device: Psi of every
+               (row, v) as one logsumexp over a [B, N, T, V] tensor per step, the state of the N new rows by a loop over
+               the frames (the recurrence is sequential in t)
 A host clock around work that ends in a device synchronise; W warm-up calls, then median and 10th / 90th percentile over R."""
 import json
 import os
@@ -53,9 +60,10 @@ def _timed(fn, reps, warmup):
 
 
 @torch.no_grad()
-def torch_search(o, memory, out_lens, N, P):
+def torch_search(o, memory, out_lens, N, P, ctc=None):
     """the beam search over DecoderOracle's weights (float32, on the device), a step computed as forward_one_step does
-    -> (tokens [B, N, <= P], scores [B, N], steps)"""
+    -> (tokens [B, N, <= P], scores [B, N], steps).  ctc = (x [B, T, V] log emissions, blank, weight): the CTC-joint search
+    (every frame valid)"""
     dev = memory.device
     B, Tp, d = memory.shape
     R, Vv, H = B * N, o.V, o.H
@@ -73,6 +81,15 @@ def torch_search(o, memory, out_lens, N, P):
     base = (torch.arange(B, device=dev) * N)[:, None]
     neg = torch.full((B, N, N - 1), float("-inf"), dtype=torch.float64, device=dev)
     steps = 0
+    if ctc is not None:
+        assert out_lens is None
+        xc, blank, w = ctc
+        ninf = float("-inf")
+        rn = torch.full((R, Tp), ninf, device=dev)
+        rb = xc[:, :, blank].cumsum(1).repeat_interleave(N, 0)
+        psi_g = torch.zeros(B, N, device=dev)
+        last = torch.full((R,), -1, dtype=torch.long, device=dev)
+        bidx = torch.arange(B, device=dev).repeat_interleave(N)
     for i in range(1, P + 1):
         x = o.w[p + ".embed.0.weight"][toks] * (d ** 0.5) + o.pe[:i]
         new_cache = []
@@ -92,6 +109,16 @@ def torch_search(o, memory, out_lens, N, P):
             x = xl if cache[l] is None else torch.cat([cache[l], xl], 1)
             new_cache.append(x)
         logp = torch.log_softmax(o._lin(o._ln(x[:, -1], p + ".after_norm"), p + ".output_layer"), -1).reshape(B, N, Vv)
+        if ctc is not None:
+            first = torch.full((R, 1), 0.0 if i == 1 else ninf, device=dev)
+            php = torch.cat([first, torch.logaddexp(rn, rb)[:, :-1]], 1)  # phi[t - 1]
+            pbp = torch.cat([first, rb[:, :-1]], 1)
+            psi = torch.logsumexp(php.reshape(B, N, Tp, 1) + xc[:, None], 2)  # [B, N, V]
+            at_last = torch.logsumexp(pbp + xc[bidx, :, last.clamp(min=0)], 1)
+            psi.view(R, Vv)[last >= 0, last[last >= 0]] = at_last[last >= 0]
+            psi[:, :, blank] = ninf
+            psi[:, :, eos] = torch.logaddexp(rn[:, -1], rb[:, -1]).reshape(B, N)
+            logp = logp + w * (psi - psi_g[:, :, None])
         top_lp, top_id = logp.topk(N, -1)
         cand = scores[:, :, None] + top_lp.double()
         cand = torch.where(ended[:, :, None], torch.cat([scores[:, :, None], neg], 2), cand)
@@ -102,9 +129,27 @@ def torch_search(o, memory, out_lens, N, P):
         gidx = (base + par).reshape(-1)
         toks = torch.cat([toks[gidx], tok_new.reshape(R, 1)], 1)
         cache = [c[gidx] for c in new_cache]
+        if ctc is not None:
+            was = ended.gather(1, par).reshape(R)
+            c = tok_new.reshape(R)
+            keep = was | (c == eos) | ~torch.isfinite(scores.reshape(R))  # rows that take no token keep their parent's state
+            cc = torch.where(keep, torch.zeros_like(c), c)
+            ph = torch.where((cc == last[gidx])[:, None], pbp[gidx], php[gidx])
+            x_c, x_b = xc[bidx, :, cc], xc[bidx, :, blank]
+            prn = prb = torch.full((R,), ninf, device=dev)
+            nrn, nrb = [], []
+            for t in range(Tp):  # the recurrence is sequential in t
+                prn, prb = torch.logaddexp(prn, ph[:, t]) + x_c[:, t], torch.logaddexp(prn, prb) + x_b[:, t]
+                nrn.append(prn)
+                nrb.append(prb)
+            rn = torch.where(keep[:, None], rn[gidx], torch.stack(nrn, 1))
+            rb = torch.where(keep[:, None], rb[gidx], torch.stack(nrb, 1))
+            new_psi = psi.reshape(B, N * Vv).gather(1, par * Vv + tok_new)
+            psi_g = torch.where(was.reshape(B, N), psi_g.gather(1, par), new_psi)
+            last = torch.where(keep, last[gidx], c)
         ended = ended.gather(1, par) | (tok_new == eos)
         steps = i
-        if bool(ended.all()):  # (the read-back of WeNet's loop)
+        if bool((ended | ~torch.isfinite(scores)).all()):  # (the read-back of WeNet's loop)
             break
     return toks[:, 1:].reshape(B, N, -1), scores, steps
 
@@ -164,6 +209,37 @@ def main():
            "workspace_bytes": r.decode_workspace_bytes(B, TP, BEAM, TP),
            "same_best_hypothesis_as_torch": f"{same}/{B}",
            "max_abs_best_score_difference_to_torch": round(float((res["scores"][:, 0] - t_sc[:, 0]).abs().max()), 6)}
+    cw = _arg("--ctc-weight", 0.0, float)
+    if cw > 0:
+        import joint_search_cases as jc
+        rng = np.random.default_rng(1000 + B)
+        tab = np.stack([jc._peaked(rng, TP, TP, V, 0, rng.integers(1, V - 1, int(rng.integers(30, 41))).tolist(), 0.9)
+                        for _ in range(B)]).astype(np.float32)
+        probs = torch.from_numpy(tab).cuda()
+        jres = r.decode(memory, None, BEAM, TP, ctc_probs=probs, ctc_weight=cw)
+        jsteps = int(jres["steps_run"].cpu()[0])
+        jlens = jres["lens"].cpu().numpy()
+        jhip = _timed(lambda: r.decode(memory, None, BEAM, TP, ctc_probs=probs, ctc_weight=cw), reps, warmup)
+        jlive = _timed(lambda: r.decode(memory, None, BEAM, jsteps, ctc_probs=probs, ctc_weight=cw), reps, warmup)
+        xlog = torch.log(probs.clamp(min=float(np.finfo(np.float32).tiny)))
+        jtor = _timed(lambda: torch_search(o32, memory, None, BEAM, TP, (xlog, 0, cw)), reps, warmup)
+        j_tok, j_sc, j_steps = torch_search(o32, memory, None, BEAM, TP, (xlog, 0, cw))
+        jsame = 0
+        for b in range(B):
+            n = int(jlens[b, 0])
+            row = j_tok[b, 0].cpu().numpy()
+            jsame += int(row[:n].tolist() == jres["tokens"][b, 0, :n].cpu().tolist() and (row[n:] == V - 1).all())
+        rec.update({"ctc_weight": cw, "joint_steps_run": jsteps, "torch_joint_steps": j_steps,
+                    "joint_best_hypothesis_tokens_min_mean_max": [int(jlens[:, 0].min()), round(float(jlens[:, 0].mean()), 1),
+                                                                  int(jlens[:, 0].max())],
+                    "hip_joint": _stats(jhip), "hip_joint_live": _stats(jlive),
+                    "torch_joint_f32": _stats(jtor),
+                    "ratio_torch_joint_over_hip_joint": round(float(np.median(jtor) / np.median(jhip)), 2),
+                    "joint_launches_per_step": 5 * BLOCKS[0] + 5,
+                    "joint_ms_per_live_step": round(float(np.median(jlive)) / jsteps, 4),
+                    "joint_workspace_bytes": r.decode_workspace_bytes(B, TP, BEAM, TP, joint=True),
+                    "joint_same_best_hypothesis_as_torch": f"{jsame}/{B}",
+                    "joint_max_abs_best_score_difference_to_torch": round(float((jres["scores"][:, 0] - j_sc[:, 0]).abs().max()), 6)})
     line = json.dumps(rec)
     print(line, flush=True)
     if path:
