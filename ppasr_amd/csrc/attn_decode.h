@@ -1,5 +1,6 @@
 // attn_decode.h -- attention beam-search decoding with the left decoder (attn_decode.hip, capi_attdecode.hip): the
-// workspace views and the launcher of one ppasr_attention_decode call.  Semantics: header comment of attn_decode.hip.
+// workspace views and the launcher of one ppasr_attention_decode / ppasr_attention_decode_joint call.  Semantics: header
+// comments of attn_decode.hip and attn_decode_joint.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,15 +57,13 @@ struct AttJointBufs {
 };
 
 hipError_t configure_attention_decode_kernels();
-// the two halves of a plain step's launches that the joint mode shares: k_dec_kv + k_ad_init, and the decoder's layers
-// with the output GEMM of step `step` (logits of every live row in bf.logits)
-void launch_attdec_begin(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
-                         const int32_t* out_lens, hipStream_t st);
-void launch_attdec_decoder(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const int32_t* out_lens, int step,
-                           hipStream_t st);
-void launch_attention_decode_joint(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb,
-                                   const float* memory, const int32_t* out_lens, const AttDecOut& out, hipStream_t st);
-void launch_attention_decode(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
-                             const int32_t* out_lens, const AttDecOut& out, hipStream_t st);
+// every launch of one call; joint == nullptr: the plain search
+void launch_attention_decode(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs* joint,
+                             const float* memory, const int32_t* out_lens, const AttDecOut& out, hipStream_t st);
+// the joint mode's own kernels (attn_decode_joint.hip), for that loop: the empty hypothesis' state before the first step,
+// Psi(g . v) of every candidate behind the output GEMM, and the new rows' states behind the selection
+void launch_aj_init(const AttDecDims& d, const AttJointBufs& jb, hipStream_t st);
+void launch_aj_psi(const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb, int step, int Vp, hipStream_t st);
+void launch_aj_update(const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb, int step, hipStream_t st);
 
 }  // namespace ppasr

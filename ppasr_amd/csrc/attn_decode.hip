@@ -36,6 +36,9 @@
 //   k_ad_crossout_ffn output projection + residual + feed-forward
 // then k_ad_output (after_norm + the [256, Vp] output GEMM), k_ad_topn (log-softmax and the row's N largest) and
 // k_ad_select (per utterance: selection, ancestry, end flags): 5 L + 3 launches per step, and k_ad_finish once at the end.
+// launch_attention_decode is the one loop of both modes: with joint buffers it adds the CTC prefix launches of
+// attn_decode_joint.hip (k_aj_init once, k_aj_psi and k_aj_update per step: 5 L + 5) and runs the three search kernels as
+// <true>.
 //
 // ROWS are dense: r = b * N + k, 32 per MFMA tile whatever utterance they belong to (the dense layers are row-local, and
 // the one-query attentions do not need rows of one utterance in one tile).  A row's result depends on its own inputs only:
@@ -57,8 +60,6 @@
 
 namespace ppasr {
 namespace {
-
-constexpr size_t kAdFfnLds = 2 * (size_t)kTileLds * sizeof(float);
 
 // does tile t hold a live row?  (a barrier: every thread of the workgroup calls it)
 __device__ __forceinline__ bool tile_live(const int32_t* __restrict__ live, int R, int t) {
@@ -200,33 +201,7 @@ __global__ __launch_bounds__(kThreads) void k_ad_selfout_q(RescoreW W, AttDecDim
   __shared__ float a[kTileLds];
   const int t = blockIdx.x;
   if (!tile_live(bf.live, d.R(), t)) return;
-  const DecLayerW lw = W.side[0].layers[layer];
-  const int lane = lane_id(), w = wave_id();
-  float* x = bf.x;
-  rb_load_rows(a, kLda, bf.ctx + (size_t)t * 32 * kD, 32, 32);
-  __syncthreads();
-  f32x16 acc[1][1];
-  gemm256(a, lw.wo + (size_t)w * kTs256, acc);
-  const int col = w * 32 + (lane & 31);
-  __syncthreads();  // every wave is done reading the context tile
-  {
-    const float bias = lw.bo[col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = acc_row(r, lane);
-      const size_t gi = ((size_t)t * 32 + row) * kD + col;
-      const float v = acc[0][0][r] + bias + x[gi];
-      x[gi] = v;
-      a[row * kLda + col] = v;
-    }
-  }
-  __syncthreads();
-  rb_layernorm(a, a, kLda, 32, lw.n2g, lw.n2b, kLnEps);
-  __syncthreads();
-  gemm256(a, lw.wq2 + (size_t)w * kTs256, acc);
-  const float bias = lw.bq2[col];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) bf.qc[((size_t)t * 32 + acc_row(r, lane)) * kD + col] = acc[0][0][r] + bias;
+  dec_selfout_q_tile(W.side[0].layers[layer], a, bf.ctx, bf.x, bf.qc, t);
 }
 
 // x += src_attn.linear_out(ctx); x += w_2(relu(w_1(norm3(x)))) with the hidden layer 256 units at a time through LDS
@@ -236,45 +211,7 @@ __global__ __launch_bounds__(kThreads) void k_ad_crossout_ffn(RescoreW W, AttDec
   float* hb = lds + kTileLds;
   const int t = blockIdx.x;
   if (!tile_live(bf.live, d.R(), t)) return;
-  const DecLayerW lw = W.side[0].layers[layer];
-  const int lane = lane_id(), w = wave_id();
-  float* x = bf.x;
-  rb_load_rows(a, kLda, bf.ctx + (size_t)t * 32 * kD, 32, 32);
-  __syncthreads();
-  f32x16 acc[1][1], xa;
-  gemm256(a, lw.wo2 + (size_t)w * kTs256, acc);
-  const int col = w * 32 + (lane & 31);
-  __syncthreads();
-  {
-    const float bias = lw.bo2[col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = acc_row(r, lane);
-      xa[r] = acc[0][0][r] + bias + x[((size_t)t * 32 + row) * kD + col];
-      a[row * kLda + col] = xa[r];
-    }
-  }
-  __syncthreads();
-  rb_layernorm(a, a, kLda, 32, lw.n3g, lw.n3b, kLnEps);
-  __syncthreads();
-  f32x16 out[1][1];
-  acc_zero<1, 1>(out);
-  const int G2 = W.U / 8;  // k-groups of w_2
-  for (int ch = 0; ch < W.U / 256; ++ch) {
-    gemm256(a, lw.w1 + (size_t)(ch * 8 + w) * kTs256, acc);
-    const float b1 = lw.b1[ch * 256 + col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hb[acc_row(r, lane) * kLda + col] = fmaxf(acc[0][0][r] + b1, 0.f);
-    __syncthreads();
-    const f32x4* w2t = lw.w2 + ((size_t)w * G2 + ch * kG256) * 64;
-    BRing<1> ring;
-    ring_prime<1, kPF>(ring, w2t, 0);
-    rb_gemm<1, 1, kG256>(hb, kLda, w2t, 0, nullptr, 0, ring, out);
-    __syncthreads();
-  }
-  const float b2 = lw.b2[col];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) x[((size_t)t * 32 + acc_row(r, lane)) * kD + col] = xa[r] + out[0][0][r] + b2;
+  dec_crossout_ffn_tile(W.side[0].layers[layer], W.U, a, hb, bf.ctx, bf.x, t);
 }
 
 // after_norm -> 256 columns of output_layer per workgroup: logits [Rp][Vp] (columns v < V only)
@@ -299,8 +236,13 @@ __global__ __launch_bounds__(kThreads) void k_ad_output(RescoreW W, AttDecDims d
   }
 }
 
-// log-softmax over v < V of a live row and its N largest entries, largest first, lower id first on equal values
-__global__ __launch_bounds__(256) void k_ad_topn(AttDecDims d, AttDecBufs bf, int V, int Vp) {
+// The three search kernels serve both modes: kJoint = false is the search of the SEMANTICS above, kJoint = true the
+// CTC-joint one (attn_decode_joint.hip says what differs); jb is read only when kJoint.
+
+// log-softmax over v < V of a live row and its N largest entries, largest first, lower id first on equal values.
+// The rounds compare the raw logit (the same order as lg - lse, without its rounding); kJoint: comb, finite entries only
+template <bool kJoint>
+__global__ __launch_bounds__(256) void k_ad_topn(AttDecDims d, AttDecBufs bf, AttJointBufs jb, int step, int V, int Vp) {
   __shared__ float s_v[4];
   __shared__ int s_i[4];
   __shared__ float s_sum[256];
@@ -327,16 +269,24 @@ __global__ __launch_bounds__(256) void k_ad_topn(AttDecDims d, AttDecBufs bf, in
     __syncthreads();
   }
   const float lse = M + logf(s_sum[0]);
-  // round 0 is the maximum found above; round j takes the first entry behind round j - 1's in the order
-  float pv = mv;
-  int pi = mi;
+  const float* cp = kJoint ? jb.cpsi + (size_t)r * Vp : nullptr;
+  const float psig = kJoint ? jb.psi[(step - 1) & 1][r] : 0.f;
+  auto key = [&](int v) {
+    if constexpr (kJoint)
+      return __fadd_rn(lg[v] - lse, __fmul_rn(jb.weight, cp[v] - psig));
+    else
+      return lg[v];
+  };
+  // round j takes the first entry behind round j - 1's in the order (plain: round 0 is the maximum found above)
+  float pv = kJoint ? INFINITY : mv;
+  int pi = kJoint ? -1 : mi;
   for (int j = 0; j < d.N; ++j) {
-    if (j > 0) {
+    if (kJoint || j > 0) {
       float bv = -INFINITY;
       int bi = V;
       for (int v = threadIdx.x; v < V; v += 256) {
-        const float x = lg[v];
-        if (cand_before(pv, pi, x, v) && cand_before(x, v, bv, bi)) {
+        const float x = key(v);
+        if ((!kJoint || x > -INFINITY) && cand_before(pv, pi, x, v) && cand_before(x, v, bv, bi)) {
           bv = x;
           bi = v;
         }
@@ -346,14 +296,23 @@ __global__ __launch_bounds__(256) void k_ad_topn(AttDecDims d, AttDecBufs bf, in
       pi = bi;
     }
     if (threadIdx.x == 0) {
-      bf.cand_lp[(size_t)r * d.N + j] = pv - lse;
-      bf.cand_tok[(size_t)r * d.N + j] = min(pi, V - 1);
+      const size_t ci = (size_t)r * d.N + j;
+      const int tok = min(pi, V - 1);
+      bf.cand_lp[ci] = kJoint ? pv : pv - lse;  // kJoint: -inf when nothing is left to offer
+      bf.cand_tok[ci] = tok;
+      if constexpr (kJoint) {
+        jb.cand_att[ci] = lg[tok] - lse;
+        jb.cand_psi[ci] = cp[tok];
+      }
     }
   }
 }
 
-// per utterance: the N best of its candidates become the new rows (state buffer nw = step & 1 from cur = (step - 1) & 1)
-__global__ __launch_bounds__(1024) void k_ad_select(AttDecDims d, AttDecBufs bf, int step, int V, AttDecOut out) {
+// per utterance: the N best of its candidates become the new rows (state buffer nw = step & 1 from cur = (step - 1) & 1).
+// kJoint: fewer than N finite candidates leave rows at -inf (`some`), Psi of the new rows and the two summands
+template <bool kJoint>
+__global__ __launch_bounds__(1024) void k_ad_select(AttDecDims d, AttDecBufs bf, AttJointBufs jb, int step, int V,
+                                                    AttDecOut out) {
   __shared__ double s_sc[kAttDecMaxBeam * kAttDecMaxBeam];
   __shared__ int s_par[kAttDecMaxBeam], s_nlive[kAttDecMaxBeam];
   const int b = blockIdx.x;
@@ -363,17 +322,30 @@ __global__ __launch_bounds__(1024) void k_ad_select(AttDecDims d, AttDecBufs bf,
   const int c = threadIdx.x, k = c / N, j = c - k * N;
   double val = -INFINITY;
   int tok = V - 1, was_ended = 0;
-  float lp = 0.f;
+  float lp = 0.f;  // the attention summand
+  [[maybe_unused]] float cpsi = 0.f, psig = 0.f;
   if (c < NN) {
     const int r = b * N + k;
     const double s = bf.score[cur][r];
     was_ended = bf.ended[cur][r];
     if (was_ended) {
-      if (j == 0) val = s;
+      if (j == 0) {
+        val = s;
+        if constexpr (kJoint) psig = jb.psi[cur][r];
+      }
     } else if (s > -INFINITY) {
-      lp = bf.cand_lp[(size_t)r * N + j];
-      tok = bf.cand_tok[(size_t)r * N + j];
-      val = s + (double)lp;
+      const float key = bf.cand_lp[(size_t)r * N + j];
+      if (!kJoint || key > -INFINITY) {
+        tok = bf.cand_tok[(size_t)r * N + j];
+        if constexpr (kJoint) {
+          lp = jb.cand_att[(size_t)r * N + j];
+          cpsi = jb.cand_psi[(size_t)r * N + j];
+          psig = jb.psi[cur][r];
+        } else {
+          lp = key;
+        }
+        val = s + (double)key;
+      }
     }
     s_sc[c] = val;
   }
@@ -386,19 +358,30 @@ __global__ __launch_bounds__(1024) void k_ad_select(AttDecDims d, AttDecBufs bf,
     }
     if (rank < N) {
       const int nr = b * N + rank;
-      const int e = (was_ended || tok == V - 1) ? 1 : 0;
+      const bool some = kJoint ? val > -INFINITY : true;
+      const int e = (some && (was_ended || tok == V - 1)) ? 1 : 0;
       const int lv = (!e && val > -INFINITY) ? 1 : 0;
       bf.score[nw][nr] = val;
       bf.ended[nw][nr] = e;
       bf.live[nr] = lv;
-      bf.last_tok[nr] = tok;
+      bf.last_tok[nr] = some ? tok : V - 1;
       const size_t ti = (size_t)p * R + nr;
       bf.tr_par[ti] = k;
-      bf.tr_tok[ti] = tok;
-      bf.tr_lp[ti] = was_ended ? 0.f : lp;
-      if (out.trace_parent) out.trace_parent[ti] = k;
-      if (out.trace_token) out.trace_token[ti] = tok;
-      if (out.trace_score) out.trace_score[ti] = val;
+      bf.tr_tok[ti] = some ? tok : V - 1;
+      bf.tr_lp[ti] = (some && !was_ended) ? lp : 0.f;
+      [[maybe_unused]] float npsi = 0.f;
+      if constexpr (kJoint) {
+        npsi = some ? (was_ended ? psig : cpsi) : 0.f;
+        jb.psi[nw][nr] = npsi;
+        jb.tr_ctc[ti] = (some && !was_ended) ? cpsi - psig : 0.f;
+      }
+      if (some) {
+        if (out.trace_parent) out.trace_parent[ti] = k;
+        if (out.trace_token) out.trace_token[ti] = tok;
+        if (out.trace_score) out.trace_score[ti] = val;
+        if constexpr (kJoint)
+          if (jb.trace_ctc) jb.trace_ctc[ti] = npsi;
+      }
       s_par[rank] = k;
       s_nlive[rank] = lv;
     }
@@ -416,24 +399,32 @@ __global__ __launch_bounds__(1024) void k_ad_select(AttDecDims d, AttDecBufs bf,
   }
 }
 
-// the final hypotheses, read from the back-pointers
-__global__ __launch_bounds__(64) void k_ad_finish(AttDecDims d, AttDecBufs bf, int V, AttDecOut out) {
+// the final hypotheses, read from the back-pointers; kJoint: a row at -inf has an empty hypothesis, and the CTC tap
+template <bool kJoint>
+__global__ __launch_bounds__(64) void k_ad_finish(AttDecDims d, AttDecBufs bf, AttJointBufs jb, int V, AttDecOut out) {
   const int b = blockIdx.x, N = d.N, R = d.R(), P = d.P;
   const int steps = bf.utt_steps[b], buf = steps & 1;
   for (int k = threadIdx.x; k < N; k += blockDim.x) {
     const int r = b * N + k;
-    out.scores[r] = bf.score[buf][r];
+    const double sc = bf.score[buf][r];
+    const int from = kJoint ? (sc > -INFINITY ? steps : 0) : steps;
+    out.scores[r] = sc;
     out.ended[r] = bf.ended[buf][r];
-    for (int i = steps; i < P; ++i) out.tokens[(size_t)r * P + i] = -1;
+    for (int i = from; i < P; ++i) out.tokens[(size_t)r * P + i] = -1;
     if (out.token_logp)
-      for (int i = steps; i <= P; ++i) out.token_logp[(size_t)r * (P + 1) + i] = 0.f;
+      for (int i = from; i <= P; ++i) out.token_logp[(size_t)r * (P + 1) + i] = 0.f;
+    if constexpr (kJoint)
+      if (jb.token_ctc)
+        for (int i = from; i <= P; ++i) jb.token_ctc[(size_t)r * (P + 1) + i] = 0.f;
     int curk = k, len = 0;
-    for (int i = steps; i >= 1; --i) {
+    for (int i = from; i >= 1; --i) {
       const size_t ti = (size_t)(i - 1) * R + b * N + curk;
       const int tok = bf.tr_tok[ti];
       out.tokens[(size_t)r * P + i - 1] = tok != V - 1 ? tok : -1;
       len += tok != V - 1 ? 1 : 0;
       if (out.token_logp) out.token_logp[(size_t)r * (P + 1) + i - 1] = bf.tr_lp[ti];
+      if constexpr (kJoint)
+        if (jb.token_ctc) jb.token_ctc[(size_t)r * (P + 1) + i - 1] = jb.tr_ctc[ti];
       curk = bf.tr_par[ti];
     }
     out.lens[r] = len;
@@ -445,42 +436,49 @@ __global__ __launch_bounds__(64) void k_ad_finish(AttDecDims d, AttDecBufs bf, i
   }
 }
 
+template <bool kJoint>
+void launch_search(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb, int step,
+                   const AttDecOut& out, hipStream_t st) {
+  PPASR_LAUNCH(k_ad_topn<kJoint>, dim3(d.R()), dim3(256), 0, st, d, bf, jb, step, W.V, W.Vp);
+  PPASR_LAUNCH(k_ad_select<kJoint>, dim3(d.B), dim3(1024), 0, st, d, bf, jb, step, W.V, out);
+}
+
 }  // namespace
 
-void launch_attdec_begin(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
-                         const int32_t* out_lens, hipStream_t st) {
-  launch_dec_kv(W, d.B, d.Tp, W.n_left, memory, out_lens, bf.kv, st);
-  PPASR_LAUNCH(k_ad_init, dim3(((d.Rp() > d.B ? d.Rp() : d.B) + 255) / 256), dim3(256), 0, st, d, bf, W.V);
-}
-
-void launch_attdec_decoder(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const int32_t* out_lens, int step,
-                           hipStream_t st) {
+void launch_attention_decode(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs* joint,
+                             const float* memory, const int32_t* out_lens, const AttDecOut& out, hipStream_t st) {
+  const AttJointBufs jb = joint ? *joint : AttJointBufs{};
   const int L = W.n_left, R = d.R(), tiles = d.Rp() / 32;
-  const int p = step - 1, cur = (step - 1) & 1;
-  for (int l = 0; l < L; ++l) {
-    PPASR_LAUNCH(k_ad_qkv, dim3(tiles), dim3(kThreads), 0, st, W, d, bf, l, p);
-    PPASR_LAUNCH(k_ad_attn<true>, dim3(R), dim3(256), 0, st, d, bf, l, p, cur, L, out_lens);
-    PPASR_LAUNCH(k_ad_selfout_q, dim3(tiles), dim3(kThreads), 0, st, W, d, bf, l);
-    PPASR_LAUNCH(k_ad_attn<false>, dim3(R), dim3(256), 0, st, d, bf, l, p, cur, L, out_lens);
-    PPASR_LAUNCH(k_ad_crossout_ffn, dim3(tiles), dim3(kThreads), kAdFfnLds, st, W, d, bf, l);
-  }
-  PPASR_LAUNCH(k_ad_output, dim3(tiles, W.Vp / 256), dim3(kThreads), 0, st, W, d, bf);
-}
-
-void launch_attention_decode(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const float* memory,
-                             const int32_t* out_lens, const AttDecOut& out, hipStream_t st) {
-  launch_attdec_begin(W, d, bf, memory, out_lens, st);
+  launch_dec_kv(W, d.B, d.Tp, L, memory, out_lens, bf.kv, st);
+  PPASR_LAUNCH(k_ad_init, dim3(((d.Rp() > d.B ? d.Rp() : d.B) + 255) / 256), dim3(256), 0, st, d, bf, W.V);
+  if (joint) launch_aj_init(d, jb, st);
   for (int step = 1; step <= d.P; ++step) {
-    launch_attdec_decoder(W, d, bf, out_lens, step, st);
-    PPASR_LAUNCH(k_ad_topn, dim3(d.R()), dim3(256), 0, st, d, bf, W.V, W.Vp);
-    PPASR_LAUNCH(k_ad_select, dim3(d.B), dim3(1024), 0, st, d, bf, step, W.V, out);
+    const int p = step - 1, cur = (step - 1) & 1;
+    for (int l = 0; l < L; ++l) {
+      PPASR_LAUNCH(k_ad_qkv, dim3(tiles), dim3(kThreads), 0, st, W, d, bf, l, p);
+      PPASR_LAUNCH(k_ad_attn<true>, dim3(R), dim3(256), 0, st, d, bf, l, p, cur, L, out_lens);
+      PPASR_LAUNCH(k_ad_selfout_q, dim3(tiles), dim3(kThreads), 0, st, W, d, bf, l);
+      PPASR_LAUNCH(k_ad_attn<false>, dim3(R), dim3(256), 0, st, d, bf, l, p, cur, L, out_lens);
+      PPASR_LAUNCH(k_ad_crossout_ffn, dim3(tiles), dim3(kThreads), kFfnLds, st, W, d, bf, l);
+    }
+    PPASR_LAUNCH(k_ad_output, dim3(tiles, W.Vp / 256), dim3(kThreads), 0, st, W, d, bf);
+    if (joint) {
+      launch_aj_psi(d, bf, jb, step, W.Vp, st);
+      launch_search<true>(W, d, bf, jb, step, out, st);
+      launch_aj_update(d, bf, jb, step, st);
+    } else {
+      launch_search<false>(W, d, bf, jb, step, out, st);
+    }
   }
-  PPASR_LAUNCH(k_ad_finish, dim3(d.B), dim3(64), 0, st, d, bf, W.V, out);
+  if (joint)
+    PPASR_LAUNCH(k_ad_finish<true>, dim3(d.B), dim3(64), 0, st, d, bf, jb, W.V, out);
+  else
+    PPASR_LAUNCH(k_ad_finish<false>, dim3(d.B), dim3(64), 0, st, d, bf, jb, W.V, out);
 }
 
 hipError_t configure_attention_decode_kernels() {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(k_ad_crossout_ffn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)kAdFfnLds);
+                             (int)kFfnLds);
 }
 
 }  // namespace ppasr

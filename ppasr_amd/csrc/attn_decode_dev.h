@@ -1,4 +1,4 @@
-// attn_decode_dev.h -- device helpers shared by the top-N passes of attn_decode.hip and attn_decode_joint.hip.
+// attn_decode_dev.h -- device helpers of the top-N pass of attn_decode.hip (both of its instantiations).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,8 +1,8 @@
 // attn_decode_joint.hip -- CTC-joint scoring inside the attention beam search (WeNet's `ctc_weight` in its attention beam
 // search, its CTCPrefixScorer; ESPnet's joint decoding).  ppasr_attention_decode_joint is ppasr_attention_decode with one
 // more term per candidate: how probable it is, under the CTC head, that the transcript STARTS with the candidate's
-// hypothesis.  The decoder's step kernels are those of attn_decode.hip, launched as they are there; only the top-N pass
-// and the selection have variants here, beside the CTC prefix kernels.
+// hypothesis.  The kernels and the launch loop are those of attn_decode.hip (its top-N pass, selection and finish in their
+// kJoint = true instantiation); here are the CTC prefix kernels that loop launches beside them.
 //
 // SEMANTICS (the tests hold the code to these; everything not said here is the header comment of attn_decode.hip)
 //   Emissions.  ctc_probs [B, Tp, V] f32 is the head's softmax output, `blank` its blank column.  For utterance b,
@@ -45,17 +45,16 @@
 //                Why the log domain: a probability-domain product scaled by the row's largest phi loses every term whose
 //                phi lies more than e^-87 below it, and a candidate whose emission is FLT_MIN exactly where phi peaks
 //                gets its whole mass from such terms (the "extreme" table of the tests).
-//   k_aj_topn    k_ad_topn's log-softmax, comb, and the row's N largest finite entries
-//   k_aj_select  k_ad_select with rows at -inf, Psi of the new rows and the two summands
+//   k_ad_topn<true>    the log-softmax as in the plain mode, comb, and the row's N largest finite entries
+//   k_ad_select<true>  the selection with rows at -inf, Psi of the new rows and the two summands
 //   k_aj_update  rn' / rb' of the new live rows only: the N chosen (parent, token) pairs, one wave each, the frames in
 //                order (the recurrence is sequential in t)
-// and k_aj_finish once at the end.  No atomics; a row's result depends on its own inputs only; every word that is read
-// was written by this call; a workgroup of a finished utterance returns at its first flag read.
+// and k_ad_finish<true> once at the end.  No atomics; a row's result depends on its own inputs only; every word that is
+// read was written by this call; a workgroup of a finished utterance returns at its first flag read.
 #include <float.h>
 #include <math.h>
 
 #include "attn_decode.h"
-#include "attn_decode_dev.h"
 #include "launch.h"
 
 namespace ppasr {
@@ -181,144 +180,6 @@ __global__ __launch_bounds__(256) void k_aj_psi(AttDecDims d, AttDecBufs bf, Att
     }
 }
 
-// k_ad_topn with comb in place of the log-probability, and only finite entries offered
-__global__ __launch_bounds__(256) void k_aj_topn(AttDecDims d, AttDecBufs bf, AttJointBufs jb, int step, int Vp) {
-  __shared__ float s_v[4];
-  __shared__ int s_i[4];
-  __shared__ float s_sum[256];
-  const int r = blockIdx.x;
-  if (bf.live[r] == 0) return;
-  const int V = jb.V, cur = (step - 1) & 1;
-  const float* lg = bf.logits + (size_t)r * Vp;
-  const float* cp = jb.cpsi + (size_t)r * Vp;
-  float mv = -INFINITY;
-  int mi = V;
-  for (int v = threadIdx.x; v < V; v += 256) {
-    const float x = lg[v];
-    if (cand_before(x, v, mv, mi)) {
-      mv = x;
-      mi = v;
-    }
-  }
-  block_first(mv, mi, s_v, s_i);
-  const float M = mv;
-  float sum = 0.f;
-  for (int v = threadIdx.x; v < V; v += 256) sum += expf(lg[v] - M);
-  s_sum[threadIdx.x] = sum;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {  // a fixed tree: the sum depends on the row's logits only
-    if ((int)threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
-    __syncthreads();
-  }
-  const float lse = M + logf(s_sum[0]);
-  const float psig = jb.psi[cur][r], w = jb.weight;
-  auto comb = [&](int v) { return __fadd_rn(lg[v] - lse, __fmul_rn(w, cp[v] - psig)); };
-  // round j takes the first finite entry behind round j - 1's in the order
-  float pv = INFINITY;
-  int pi = -1;
-  for (int j = 0; j < d.N; ++j) {
-    float bv = -INFINITY;
-    int bi = V;
-    for (int v = threadIdx.x; v < V; v += 256) {
-      const float x = comb(v);
-      if (x > -INFINITY && cand_before(pv, pi, x, v) && cand_before(x, v, bv, bi)) {
-        bv = x;
-        bi = v;
-      }
-    }
-    block_first(bv, bi, s_v, s_i);
-    pv = bv;
-    pi = bi;
-    if (threadIdx.x == 0) {
-      const size_t ci = (size_t)r * d.N + j;
-      const int tok = min(pi, V - 1);
-      bf.cand_lp[ci] = pv;  // -inf: nothing left to offer
-      bf.cand_tok[ci] = tok;
-      jb.cand_att[ci] = lg[tok] - lse;
-      jb.cand_psi[ci] = cp[tok];
-    }
-  }
-}
-
-// k_ad_select with rows at -inf (fewer than N finite candidates), Psi of the new rows and the two summands
-__global__ __launch_bounds__(1024) void k_aj_select(AttDecDims d, AttDecBufs bf, AttJointBufs jb, int step, AttDecOut out) {
-  __shared__ double s_sc[kAttDecMaxBeam * kAttDecMaxBeam];
-  __shared__ int s_par[kAttDecMaxBeam], s_nlive[kAttDecMaxBeam];
-  const int b = blockIdx.x;
-  if (bf.utt_live[b] == 0) return;
-  const int N = d.N, NN = N * N, R = d.R(), p = step - 1, V = jb.V;
-  const int cur = (step - 1) & 1, nw = step & 1;
-  const int c = threadIdx.x, k = c / N, j = c - k * N;
-  double val = -INFINITY;
-  int tok = V - 1, was_ended = 0;
-  float att = 0.f, cpsi = 0.f, psig = 0.f;
-  if (c < NN) {
-    const int r = b * N + k;
-    const double s = bf.score[cur][r];
-    was_ended = bf.ended[cur][r];
-    if (was_ended) {
-      if (j == 0) {
-        val = s;
-        psig = jb.psi[cur][r];
-      }
-    } else if (s > -INFINITY) {
-      const float lp = bf.cand_lp[(size_t)r * N + j];
-      if (lp > -INFINITY) {
-        tok = bf.cand_tok[(size_t)r * N + j];
-        att = jb.cand_att[(size_t)r * N + j];
-        cpsi = jb.cand_psi[(size_t)r * N + j];
-        psig = jb.psi[cur][r];
-        val = s + (double)lp;
-      }
-    }
-    s_sc[c] = val;
-  }
-  __syncthreads();
-  if (c < NN) {
-    int rank = 0;
-    for (int o = 0; o < NN; ++o) {
-      const double v = s_sc[o];
-      rank += (v > val || (v == val && o < c)) ? 1 : 0;
-    }
-    if (rank < N) {
-      const int nr = b * N + rank;
-      const bool some = val > -INFINITY;
-      const int e = (some && (was_ended || tok == V - 1)) ? 1 : 0;
-      const int lv = (!e && some) ? 1 : 0;
-      const float npsi = some ? (was_ended ? psig : cpsi) : 0.f;
-      bf.score[nw][nr] = val;
-      bf.ended[nw][nr] = e;
-      bf.live[nr] = lv;
-      bf.last_tok[nr] = some ? tok : V - 1;
-      jb.psi[nw][nr] = npsi;
-      const size_t ti = (size_t)p * R + nr;
-      bf.tr_par[ti] = k;
-      bf.tr_tok[ti] = some ? tok : V - 1;
-      bf.tr_lp[ti] = (some && !was_ended) ? att : 0.f;
-      jb.tr_ctc[ti] = (some && !was_ended) ? cpsi - psig : 0.f;
-      if (some) {
-        if (out.trace_parent) out.trace_parent[ti] = k;
-        if (out.trace_token) out.trace_token[ti] = tok;
-        if (out.trace_score) out.trace_score[ti] = val;
-        if (jb.trace_ctc) jb.trace_ctc[ti] = npsi;
-      }
-      s_par[rank] = k;
-      s_nlive[rank] = lv;
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < N * (p + 1); i += blockDim.x) {
-    const int kn = i / (p + 1), jj = i - kn * (p + 1), par = s_par[kn];
-    bf.anc[nw][((size_t)b * N + kn) * 256 + jj] = jj < p ? bf.anc[cur][((size_t)b * N + par) * 256 + jj] : (uint8_t)par;
-  }
-  if (threadIdx.x == 0) {
-    int nl = 0;
-    for (int i = 0; i < N; ++i) nl += s_nlive[i];
-    bf.utt_live[b] = nl;
-    bf.utt_steps[b] = step;
-  }
-}
-
 // rn' / rb' of a new live row from its parent's state and its token: a wave per row, the frames in order
 __global__ __launch_bounds__(64) void k_aj_update(AttDecDims d, AttDecBufs bf, AttJointBufs jb, int step) {
   const int nr = blockIdx.x;
@@ -358,40 +219,6 @@ __global__ __launch_bounds__(64) void k_aj_update(AttDecDims d, AttDecBufs bf, A
   }
 }
 
-// k_ad_finish with the CTC tap and the rows at -inf (an empty hypothesis)
-__global__ __launch_bounds__(64) void k_aj_finish(AttDecDims d, AttDecBufs bf, AttJointBufs jb, AttDecOut out) {
-  const int b = blockIdx.x, N = d.N, R = d.R(), P = d.P, V = jb.V;
-  const int steps = bf.utt_steps[b], buf = steps & 1;
-  for (int k = threadIdx.x; k < N; k += blockDim.x) {
-    const int r = b * N + k;
-    const double sc = bf.score[buf][r];
-    const int from = sc > -INFINITY ? steps : 0;
-    out.scores[r] = sc;
-    out.ended[r] = bf.ended[buf][r];
-    for (int i = from; i < P; ++i) out.tokens[(size_t)r * P + i] = -1;
-    for (int i = from; i <= P; ++i) {
-      if (out.token_logp) out.token_logp[(size_t)r * (P + 1) + i] = 0.f;
-      if (jb.token_ctc) jb.token_ctc[(size_t)r * (P + 1) + i] = 0.f;
-    }
-    int curk = k, len = 0;
-    for (int i = from; i >= 1; --i) {
-      const size_t ti = (size_t)(i - 1) * R + b * N + curk;
-      const int tok = bf.tr_tok[ti];
-      out.tokens[(size_t)r * P + i - 1] = tok != V - 1 ? tok : -1;
-      len += tok != V - 1 ? 1 : 0;
-      if (out.token_logp) out.token_logp[(size_t)r * (P + 1) + i - 1] = bf.tr_lp[ti];
-      if (jb.token_ctc) jb.token_ctc[(size_t)r * (P + 1) + i - 1] = jb.tr_ctc[ti];
-      curk = bf.tr_par[ti];
-    }
-    out.lens[r] = len;
-  }
-  if (b == 0 && threadIdx.x == 0) {
-    int mx = 0;
-    for (int i = 0; i < d.B; ++i) mx = max(mx, bf.utt_steps[i]);
-    out.steps_run[0] = mx;
-  }
-}
-
 template <int NR>
 void launch_psi(const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb, int step, int Vp, hipStream_t st) {
   PPASR_LAUNCH(k_aj_psi<NR>, dim3(d.B, (jb.V + 255) / 256), dim3(256), 0, st, d, bf, jb, step, Vp);
@@ -399,23 +226,21 @@ void launch_psi(const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& j
 
 }  // namespace
 
-void launch_attention_decode_joint(const RescoreW& W, const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb,
-                                   const float* memory, const int32_t* out_lens, const AttDecOut& out, hipStream_t st) {
-  launch_attdec_begin(W, d, bf, memory, out_lens, st);
+void launch_aj_init(const AttDecDims& d, const AttJointBufs& jb, hipStream_t st) {
   PPASR_LAUNCH(k_aj_init, dim3(d.B), dim3(64), 0, st, d, jb);
-  for (int step = 1; step <= d.P; ++step) {
-    launch_attdec_decoder(W, d, bf, out_lens, step, st);
-    if (d.N <= 8)
-      launch_psi<8>(d, bf, jb, step, W.Vp, st);
-    else if (d.N <= 16)
-      launch_psi<16>(d, bf, jb, step, W.Vp, st);
-    else
-      launch_psi<32>(d, bf, jb, step, W.Vp, st);
-    PPASR_LAUNCH(k_aj_topn, dim3(d.R()), dim3(256), 0, st, d, bf, jb, step, W.Vp);
-    PPASR_LAUNCH(k_aj_select, dim3(d.B), dim3(1024), 0, st, d, bf, jb, step, out);
-    PPASR_LAUNCH(k_aj_update, dim3(d.R()), dim3(64), 0, st, d, bf, jb, step);
-  }
-  PPASR_LAUNCH(k_aj_finish, dim3(d.B), dim3(64), 0, st, d, bf, jb, out);
+}
+
+void launch_aj_psi(const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb, int step, int Vp, hipStream_t st) {
+  if (d.N <= 8)
+    launch_psi<8>(d, bf, jb, step, Vp, st);
+  else if (d.N <= 16)
+    launch_psi<16>(d, bf, jb, step, Vp, st);
+  else
+    launch_psi<32>(d, bf, jb, step, Vp, st);
+}
+
+void launch_aj_update(const AttDecDims& d, const AttDecBufs& bf, const AttJointBufs& jb, int step, hipStream_t st) {
+  PPASR_LAUNCH(k_aj_update, dim3(d.R()), dim3(64), 0, st, d, bf, jb, step);
 }
 
 }  // namespace ppasr

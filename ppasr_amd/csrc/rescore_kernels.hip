@@ -208,32 +208,7 @@ __global__ __launch_bounds__(kThreads) void k_dec_selfout_q(RescoreW W, RescoreD
   if (t >= tab.counts[0]) return;
   const DecSideW& S = W.side[tab.tile_info[t] / d.B];
   if (layer >= S.nblk) return;
-  const DecLayerW lw = S.layers[layer];
-  const int lane = lane_id(), w = wave_id();
-  rb_load_rows(a, kLda, ctx + (size_t)t * 32 * kD, 32, 32);
-  __syncthreads();
-  f32x16 acc[1][1];
-  gemm256(a, lw.wo + (size_t)w * kTs256, acc);
-  const int col = w * 32 + (lane & 31);
-  __syncthreads();  // every wave is done reading the context tile
-  {
-    const float bias = lw.bo[col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = acc_row(r, lane);
-      const size_t gi = ((size_t)t * 32 + row) * kD + col;
-      const float v = acc[0][0][r] + bias + x[gi];
-      x[gi] = v;
-      a[row * kLda + col] = v;
-    }
-  }
-  __syncthreads();
-  rb_layernorm(a, a, kLda, 32, lw.n2g, lw.n2b, kLnEps);
-  __syncthreads();
-  gemm256(a, lw.wq2 + (size_t)w * kTs256, acc);
-  const float bias = lw.bq2[col];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) qc[((size_t)t * 32 + acc_row(r, lane)) * kD + col] = acc[0][0][r] + bias;
+  dec_selfout_q_tile(S.layers[layer], a, ctx, x, qc, t);
 }
 
 // Cross-attention of one 32-row tile and head over the utterance's valid memory frames.  A tile of 64 keys / values staged
@@ -325,44 +300,7 @@ __global__ __launch_bounds__(kThreads) void k_dec_crossout_ffn(RescoreW W, Resco
   if (t >= tab.counts[0]) return;
   const DecSideW& S = W.side[tab.tile_info[t] / d.B];
   if (layer >= S.nblk) return;
-  const DecLayerW lw = S.layers[layer];
-  const int lane = lane_id(), w = wave_id();
-  rb_load_rows(a, kLda, ctx + (size_t)t * 32 * kD, 32, 32);
-  __syncthreads();
-  f32x16 acc[1][1], xa;
-  gemm256(a, lw.wo2 + (size_t)w * kTs256, acc);
-  const int col = w * 32 + (lane & 31);
-  __syncthreads();
-  {
-    const float bias = lw.bo2[col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = acc_row(r, lane);
-      xa[r] = acc[0][0][r] + bias + x[((size_t)t * 32 + row) * kD + col];
-      a[row * kLda + col] = xa[r];
-    }
-  }
-  __syncthreads();
-  rb_layernorm(a, a, kLda, 32, lw.n3g, lw.n3b, kLnEps);
-  __syncthreads();
-  f32x16 out[1][1];
-  acc_zero<1, 1>(out);
-  const int G2 = W.U / 8;  // k-groups of w_2
-  for (int ch = 0; ch < W.U / 256; ++ch) {
-    gemm256(a, lw.w1 + (size_t)(ch * 8 + w) * kTs256, acc);
-    const float b1 = lw.b1[ch * 256 + col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hb[acc_row(r, lane) * kLda + col] = fmaxf(acc[0][0][r] + b1, 0.f);
-    __syncthreads();
-    const f32x4* w2t = lw.w2 + ((size_t)w * G2 + ch * kG256) * 64;
-    BRing<1> ring;
-    ring_prime<1, kPF>(ring, w2t, 0);
-    rb_gemm<1, 1, kG256>(hb, kLda, w2t, 0, nullptr, 0, ring, out);
-    __syncthreads();
-  }
-  const float b2 = lw.b2[col];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) x[((size_t)t * 32 + acc_row(r, lane)) * kD + col] = xa[r] + out[0][0][r] + b2;
+  dec_crossout_ffn_tile(S.layers[layer], W.U, a, hb, ctx, x, t);
 }
 
 // after_norm -> output_layer over the vocabulary 256 columns at a time; per row only the running max / sum and the target's
@@ -536,8 +474,6 @@ __global__ __launch_bounds__(64) void k_dec_score(RescoreDims d, RowTab tab, con
     best[b] = bi;
   }
 }
-
-constexpr size_t kFfnLds = 2 * (size_t)kTileLds * sizeof(float);
 
 // encoder output of an offline encode (ppasr_set_memory_out): LayerNorm over D (encoder.after_norm; g == nullptr: a copy)
 // of the rows the CTC head reads, one wave per row; ragged batches: rows behind the valid frames are 0
