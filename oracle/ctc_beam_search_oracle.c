@@ -14,7 +14,10 @@
  * back-off n-gram model: min_cutoff pruning, alpha * ln P_lm + beta per extension, approx_ctc result score) is restated
  * over n-gram arrays handed in by the tests (which parse the ARPA file themselves); KenLM itself is not available.
  *
- * Build: make -C oracle   ->  oracle/_build/libctc_beam_oracle.so   (loaded with ctypes by tests/)
+ * The scorer-less search of this file is pinned by tests/ctc_beam_oracle64.py, a float64 definition that equals path
+ * enumeration over all V^T labelings (tests/test_ctc_beam_oracle_cpu.py); the upstream module itself stays unpinned.
+ *
+ * Build: make -C oracle  ->  oracle/_build/libctc_beam_oracle.so   (loaded with ctypes by tests/)
  */
 #include <float.h>
 #include <math.h>

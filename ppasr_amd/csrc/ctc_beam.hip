@@ -17,6 +17,13 @@
 //     character, then list order), then an ordered compaction; the list holds ~ beam ln beam entries
 //     instead of beam x candidates wherever a verified bound allows it (see k_ctc_beam), and lives in HBM
 //     scratch when it outgrows LDS (unpruned searches: beam x (1 + V) entries).
+// Prefixes of probability zero: upstream's trie creates a child even where its mass is minus infinity (a repeated
+// character behind a prefix without blank mass) and keeps a prefix that received nothing in a frame, so an under-full
+// beam also holds infeasible prefixes (L + repeats > T).  So does this search: they are returned behind every finite
+// hypothesis, with their tokens and lengths and the score FLT_MAX (= -kNegInf), ordered among themselves by last
+// character; lens = -1 (score 0, tokens -1) marks only the rows beyond the prefixes that exist.  Where a full beam cuts
+// between two such prefixes of one last character, which of them stays is not defined (container order upstream).
+// tests/ctc_beam_oracle64.py is the float64 definition all of this is held to (tests/test_ctc_beam_edges_gpu.py).
 // External scorer (`ext_scorer`, character-based n-gram LM, lm.h): the min_cutoff pruning of (character, prefix) pairs,
 // alpha * log P_lm + beta on every extension, and the approximate-CTC result score with the LM weight removed.  The LM
 // term of a (hypothesis, candidate) pair is computed on the fly inside its score key (the key is inverted back to the
