@@ -552,6 +552,14 @@ PPASR_API size_t       ppasr_beam_pool_workspace_bytes(ppasr_beam_pool pool, int
 PPASR_API ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool pool, const int* sessions_host, int n, const float* probs, int T,
                                               const int32_t* frame_lens_host, int max_tokens, int32_t* tokens, int32_t* lens,
                                               double* scores, void* workspace, size_t workspace_bytes, void* stream);
+/* The nbest best prefixes of each listed session's CURRENT beam: tokens [n][nbest][max_tokens] (-1 padded), lens
+ * [n][nbest] (-1: the beam holds fewer hypotheses), scores [n][nbest] f64 = -log P -- the conventions of
+ * ppasr_ctc_beam_search.  It is ppasr_beam_pool_decode with T = 0: one search launch that finalizes and consumes no frame,
+ * so no session is advanced, grown or compacted and every state block keeps its bits (workspace:
+ * ppasr_beam_pool_workspace_bytes(pool, n, 0)).  PPASR_EINVAL: nbest outside [1, beam_size], and what decode refuses. */
+PPASR_API ppasr_status ppasr_beam_sessions_nbest(ppasr_beam_pool pool, const int* sessions_host, int n, int nbest, int max_tokens,
+                                             int32_t* tokens, int32_t* lens, double* scores, void* workspace,
+                                             size_t workspace_bytes, void* stream);
 
 /* ---- compaction of a pool's prefix arenas: long streams in bounded memory --------------------------------------
  * A session's arena otherwise keeps every prefix node it ever created (36 bytes per node, beam_size nodes per frame) and
@@ -808,6 +816,36 @@ PPASR_API ppasr_status ppasr_prob_arena_reset(ppasr_prob_arena arena, int sessio
 PPASR_API long long    ppasr_prob_arena_frames(ppasr_prob_arena arena, int session);
 PPASR_API long long    ppasr_prob_arena_free_pages(ppasr_prob_arena arena);
 PPASR_API ppasr_status ppasr_prob_arena_read(ppasr_prob_arena arena, int session, float* dense_dev, void* stream);
+/* read_many: dense_dev [n][Tp][V] = the listed sessions' rows, zeros at and behind each session's frame count, and
+ *   lens_dev [n] i32 = the counts: ONE launch, nothing read back.  Each session's rows equal ppasr_prob_arena_read byte for
+ *   byte.  PPASR_EINVAL: Tp below the longest listed session, a session outside the arena or listed twice, n < 1, a NULL
+ *   pointer (dense_dev may be NULL when Tp = 0); PPASR_EUNSUPPORTED: n * Tp > 2^30. */
+PPASR_API ppasr_status ppasr_prob_arena_read_many(ppasr_prob_arena arena, const int* sessions_host, int n, int Tp,
+                                                  float* dense_dev, int32_t* lens_dev, void* stream);
+/* ---- encoder memory of streaming rounds, for attention rescoring at end of stream ----
+ * The arena is a row store of any width >= 2: created with V = 256 it keeps the ENCODER OUTPUT of streams (what
+ * ppasr_set_memory_out gives for an offline encode: encoder.after_norm of the rows the CTC head reads).
+ * ppasr_encode_chunk_group_mem is ppasr_encode_chunk_group plus (mem, mem_frames_host): rows 0 .. mem_frames_host[k] - 1
+ * (NULL: all c; 0: nothing is kept for that session) of list position k's c frames go behind the last frame arena
+ * session sessions_host[k] holds.  With mem = NULL it IS ppasr_encode_chunk_group, launch for launch; with an arena the
+ * round ends with ONE more kernel launch, whatever n is, and every other output is the same bits.  Arena and group calls
+ * go on one stream (the arena's rule).  All or nothing: the pages are planned and every argument is checked before any
+ * device work of the round; a refused round changes no session of the group and nothing in the arena.
+ *   PPASR_ENOSPACE: the round needs more pages than are free.
+ *   PPASR_EINVAL: arena rows not 256 wide; an arena with fewer sessions than the group; a mem_frames_host entry outside
+ *     [0, c]; whatever ppasr_encode_chunk_group refuses.
+ *   PPASR_EUNSUPPORTED: every group but the Conformer's on the fused 256-wide route -- DeepSpeech2, the general route,
+ *     Squeezeformer and Efficient-Conformer groups.
+ * ppasr_encode_chunk_mem: the same for one stream handle (ppasr_encode_chunk plus the arena, the session that takes the
+ * rows and mem_frames in [0, c], < 0: all c); Conformer handles on the fused route, PPASR_EUNSUPPORTED otherwise. */
+PPASR_API ppasr_status ppasr_encode_chunk_group_mem(ppasr_stream_group g, const int* sessions_host, int n, const float* feats,
+                                                    int T, float* probs, int32_t* frame_argmax, float* frame_maxprob,
+                                                    int* c_out_host, void* workspace, size_t workspace_bytes,
+                                                    ppasr_prob_arena mem, const int* mem_frames_host, void* stream);
+PPASR_API ppasr_status ppasr_encode_chunk_mem(ppasr_stream s, const float* feats, int T, int required_cache_size, float* probs,
+                                              int32_t* frame_argmax, float* frame_maxprob, int* c_out_host, void* workspace,
+                                              size_t workspace_bytes, ppasr_prob_arena mem, int session, int mem_frames,
+                                              void* stream);
 PPASR_API size_t ppasr_ctc_align_arena_workspace_bytes(int n, int Tp, int max_tokens);
 PPASR_API ppasr_status ppasr_ctc_align_arena(ppasr_prob_arena arena, const int* sessions_host, int n, int blank,
                                              const int32_t* tokens, const int32_t* n_tokens, int max_tokens,

@@ -229,6 +229,15 @@ SYMBOLS = [
     ("ppasr_prob_arena_frames", ctypes.c_longlong, [_vp, ctypes.c_int]),
     ("ppasr_prob_arena_free_pages", ctypes.c_longlong, [_vp]),
     ("ppasr_prob_arena_read", ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    ("ppasr_prob_arena_read_many", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    ("ppasr_encode_chunk_group_mem", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _vp, ctypes.c_int, _vp,
+                                                    _vp, _vp, ctypes.POINTER(ctypes.c_int), _vp, ctypes.c_size_t, _vp,
+                                                    ctypes.POINTER(ctypes.c_int), _vp]),
+    ("ppasr_encode_chunk_mem", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+                                              ctypes.POINTER(ctypes.c_int), _vp, ctypes.c_size_t, _vp, ctypes.c_int,
+                                              ctypes.c_int, _vp]),
+    ("ppasr_beam_sessions_nbest", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                             _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     ("ppasr_ctc_align_arena_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("ppasr_ctc_align_arena", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, _vp, _vp,
                                              ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),

@@ -7,23 +7,59 @@
 
 #include <algorithm>
 
-// The CTC tables of many streaming sessions in pages of one slab (ppasr_prob_arena_*).  The page lists and the free list
-// live here, on the host; a call uploads the part of them its launch needs through the ring.
-struct ppasr_prob_arena_s {
-  int n_sessions = 0, V = 0, P = 0, n_pages = 0;
-  float* slab = nullptr;                 // device [n_pages][P][V]
-  std::vector<std::vector<int>> pages;   // per session, in frame order
-  std::vector<long long> frames;         // per session
-  std::vector<int> free_list;            // (a stack: the page freed last is handed out first)
-  StagingRing ring;
-  // one call's table, int32: [n_sessions] first frame (append) or frame count (align), [n_sessions] rows to append,
-  // [n_sessions] page_off, then the page lists.  The sessions of a call are distinct, so the lists hold at most n_pages.
-  size_t table_ints() const { return 3 * (size_t)n_sessions + (size_t)n_pages; }
-  ~ppasr_prob_arena_s() {
-    ring.destroy();
-    (void)hipFree(slab);
+// ---- the two halves of an append (capi_internal.h): ppasr_prob_arena_append and the encoder rounds that keep their memory ----
+ppasr_status arena_plan_append(const ppasr_prob_arena_s* a, const int* sessions, int n, int c, const int* frames, const char* who,
+                               long long* rows_out) {
+  const std::string w(who);
+  if (!session_list_ok(sessions, n, a->n_sessions))
+    return fail(PPASR_EINVAL, w + ": sessions must be distinct indices in [0, n_sessions)");
+  const int P = a->P;
+  long long need = 0, rows = 0;
+  for (int k = 0; k < n; ++k) {
+    const int f = frames ? frames[k] : c;
+    if (f < 0 || f > c) return fail(PPASR_EINVAL, w + ": frames[k] outside [0, c]");
+    need += (a->frames[sessions[k]] + f + P - 1) / P - (long long)a->pages[sessions[k]].size();
+    rows += f;
   }
-};
+  if (need > (long long)a->free_list.size())
+    return fail(PPASR_ENOSPACE, w + ": the round needs " + std::to_string(need) + " pages, " +
+                                    std::to_string(a->free_list.size()) + " are free");
+  if (rows_out) *rows_out = rows;
+  return PPASR_OK;
+}
+
+ppasr_status arena_stage_append(ppasr_prob_arena_s* a, const int* sessions, int n, int c, const int* frames, ArenaAppendTab* tab,
+                                hipStream_t st) {
+  const int P = a->P;
+  HIP_TRY(a->ring.acquire(&tab->en));
+  int32_t* h = reinterpret_cast<int32_t*>(tab->en.host);
+  int32_t *first = h, *count = h + a->n_sessions, *page_off = h + 2 * a->n_sessions, *pages = h + 3 * a->n_sessions;
+  int used = 0;
+  for (int k = 0; k < n; ++k) {
+    const int s = sessions[k], f = frames ? frames[k] : c;
+    std::vector<int>& pg = a->pages[s];
+    const long long f0 = a->frames[s];
+    while ((long long)pg.size() * P < f0 + f) {
+      pg.push_back(a->free_list.back());
+      a->free_list.pop_back();
+    }
+    first[k] = (int)f0;
+    count[k] = f;
+    page_off[k] = used;
+    // the pages this entry's frames f0 .. f0 + f - 1 touch (at most n_pages over the whole call: sessions are distinct)
+    if (f > 0)
+      for (long long j = f0 / P; j <= (f0 + f - 1) / P; ++j) pages[used++] = pg[j];
+    a->frames[s] = f0 + f;
+  }
+  const size_t bytes = (size_t)(3 * a->n_sessions + used) * sizeof(int32_t);
+  HIP_TRY(hipMemcpyAsync(tab->en.dev, tab->en.host, bytes, hipMemcpyHostToDevice, st));
+  const int32_t* d = reinterpret_cast<const int32_t*>(tab->en.dev);
+  tab->first = d;
+  tab->count = d + a->n_sessions;
+  tab->page_off = d + 2 * a->n_sessions;
+  tab->pages = d + 3 * a->n_sessions;
+  return PPASR_OK;
+}
 
 extern "C" {
 
@@ -90,46 +126,17 @@ ppasr_status ppasr_prob_arena_append(ppasr_prob_arena a, const int* sessions, in
     return fail(PPASR_EINVAL, "prob_arena_append: sessions must be distinct indices in [0, n_sessions)");
   if (c > 0 && !probs) return fail(PPASR_EINVAL, "prob_arena_append: null argument");
   if ((long long)n * c > (1ll << 30)) return fail(PPASR_EUNSUPPORTED, "prob_arena_append: round too large (n * c > 2^30)");
-  const int P = a->P;
-  long long need = 0, rows = 0;
-  for (int k = 0; k < n; ++k) {
-    const int f = frames ? frames[k] : c;
-    if (f < 0 || f > c) return fail(PPASR_EINVAL, "prob_arena_append: frames[k] outside [0, c]");
-    need += (a->frames[sessions[k]] + f + P - 1) / P - (long long)a->pages[sessions[k]].size();
-    rows += f;
-  }
-  if (need > (long long)a->free_list.size())
-    return fail(PPASR_ENOSPACE, "prob_arena_append: the round needs " + std::to_string(need) + " pages, " +
-                                    std::to_string(a->free_list.size()) + " are free");
+  long long rows = 0;
+  ppasr_status r = arena_plan_append(a, sessions, n, c, frames, "prob_arena_append", &rows);
+  if (r != PPASR_OK) return r;
   if (rows == 0) return PPASR_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  StagingRing::Entry en;
-  HIP_TRY(a->ring.acquire(&en));
-  int32_t* h = reinterpret_cast<int32_t*>(en.host);
-  int32_t *first = h, *count = h + a->n_sessions, *page_off = h + 2 * a->n_sessions, *pages = h + 3 * a->n_sessions;
-  int used = 0;
-  for (int k = 0; k < n; ++k) {
-    const int s = sessions[k], f = frames ? frames[k] : c;
-    std::vector<int>& pg = a->pages[s];
-    const long long f0 = a->frames[s];
-    while ((long long)pg.size() * P < f0 + f) {
-      pg.push_back(a->free_list.back());
-      a->free_list.pop_back();
-    }
-    first[k] = (int)f0;
-    count[k] = f;
-    page_off[k] = used;
-    // the pages this entry's frames f0 .. f0 + f - 1 touch (at most n_pages over the whole call: sessions are distinct)
-    if (f > 0)
-      for (long long j = f0 / P; j <= (f0 + f - 1) / P; ++j) pages[used++] = pg[j];
-    a->frames[s] = f0 + f;
-  }
-  const size_t bytes = (size_t)(3 * a->n_sessions + used) * sizeof(int32_t);
-  HIP_TRY(hipMemcpyAsync(en.dev, en.host, bytes, hipMemcpyHostToDevice, st));
-  const int32_t* d = reinterpret_cast<const int32_t*>(en.dev);
-  launch_arena_append(probs, n, c, a->V, P, d, d + a->n_sessions, d + 2 * a->n_sessions, d + 3 * a->n_sessions, a->slab, st);
+  ArenaAppendTab tab{};
+  r = arena_stage_append(a, sessions, n, c, frames, &tab, st);
+  if (r != PPASR_OK) return r;
+  launch_arena_append(probs, n, c, a->V, a->P, tab.first, tab.count, tab.page_off, tab.pages, a->slab, st);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(a->ring.release(en, st));
+  HIP_TRY(a->ring.release(tab.en, st));
   return PPASR_OK;
 }
 
@@ -164,6 +171,37 @@ ppasr_status ppasr_prob_arena_read(ppasr_prob_arena a, int session, float* dense
   std::memcpy(en.host, pg.data(), pg.size() * sizeof(int32_t));
   HIP_TRY(hipMemcpyAsync(en.dev, en.host, pg.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
   launch_arena_read(a->slab, a->V, a->P, reinterpret_cast<const int32_t*>(en.dev), (int)T, dense, st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(a->ring.release(en, st));
+  return PPASR_OK;
+}
+
+ppasr_status ppasr_prob_arena_read_many(ppasr_prob_arena a, const int* sessions, int n, int Tp, float* dense, int32_t* lens,
+                                        void* stream) {
+  if (!a || !sessions || !lens) return fail(PPASR_EINVAL, "prob_arena_read_many: null argument");
+  if (n < 1 || Tp < 0) return fail(PPASR_EINVAL, "prob_arena_read_many: n >= 1 and Tp >= 0");
+  if (!session_list_ok(sessions, n, a->n_sessions))
+    return fail(PPASR_EINVAL, "prob_arena_read_many: sessions must be distinct indices in [0, n_sessions)");
+  for (int k = 0; k < n; ++k)
+    if (a->frames[sessions[k]] > Tp) return fail(PPASR_EINVAL, "prob_arena_read_many: Tp below the longest listed session");
+  if (Tp > 0 && !dense) return fail(PPASR_EINVAL, "prob_arena_read_many: null argument");
+  if ((long long)n * Tp > (1ll << 30)) return fail(PPASR_EUNSUPPORTED, "prob_arena_read_many: gather too large (n * Tp > 2^30)");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  StagingRing::Entry en;
+  HIP_TRY(a->ring.acquire(&en));
+  int32_t* h = reinterpret_cast<int32_t*>(en.host);
+  int32_t *count = h, *page_off = h + 2 * a->n_sessions, *pages = h + 3 * a->n_sessions;
+  int used = 0;
+  for (int k = 0; k < n; ++k) {
+    const std::vector<int>& pg = a->pages[sessions[k]];
+    count[k] = (int)a->frames[sessions[k]];
+    page_off[k] = used;
+    std::memcpy(pages + used, pg.data(), pg.size() * sizeof(int32_t));
+    used += (int)pg.size();
+  }
+  HIP_TRY(hipMemcpyAsync(en.dev, en.host, (size_t)(3 * a->n_sessions + used) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int32_t* d = reinterpret_cast<const int32_t*>(en.dev);
+  launch_arena_read_many(a->slab, a->V, a->P, d, d + 2 * a->n_sessions, d + 3 * a->n_sessions, n, Tp, dense, lens, st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(a->ring.release(en, st));
   return PPASR_OK;

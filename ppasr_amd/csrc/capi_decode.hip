@@ -378,9 +378,12 @@ size_t ppasr_beam_pool_workspace_bytes(ppasr_beam_pool p, int n, int T) {
   return pool_rec_bytes(p->cfg, n, T) + beam_scratch_bytes(p->cfg, n, T);
 }
 
-ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host, int n, const float* probs, int T,
-                                    const int32_t* frame_lens_host, int max_tokens, int32_t* tokens, int32_t* lens,
-                                    double* scores, void* workspace, size_t workspace_bytes, void* stream) {
+// one decode call of a pool: T frames for every listed session (T = 0: none -- the search kernel loads each state block,
+// stores the words it loaded back and finalizes, so the sessions stay bit for bit as they were), then the nbest best
+// prefixes of each session's beam -> tokens [n][nbest][max_tokens], lens / scores [n][nbest]
+static ppasr_status pool_decode(ppasr_beam_pool p, const int* sessions_host, int n, const float* probs, int T,
+                                const int32_t* frame_lens_host, int nbest, int max_tokens, int32_t* tokens, int32_t* lens,
+                                double* scores, void* workspace, size_t workspace_bytes, void* stream) {
   // ---- every check before any device work: a refused call changes no session ----
   if (!p || !sessions_host || !tokens || !lens || !scores || (!probs && T > 0)) return fail(PPASR_EINVAL, "null argument");
   if (n < 1 || n > p->n_sessions || T < 0 || max_tokens < 1) return fail(PPASR_EINVAL, "beam pool: bad n / T / max_tokens");
@@ -468,6 +471,7 @@ ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host,
   HIP_TRY(hipMemcpyAsync(en.dev, en.host, used, hipMemcpyHostToDevice, hs));
   BeamConfig c = p->cfg;
   c.max_tokens = max_tokens;
+  c.nbest = nbest;
   c.max_nodes = 0;  // (per session: the slot table)
   {
     const char* f = getenv("PPASR_BEAM_FAST");  // (read per call, as ppasr_ctc_beam_search_ws does)
@@ -485,6 +489,20 @@ ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host,
     p->used[sessions_host[b]] += fl[b];
   }
   return PPASR_OK;
+}
+
+ppasr_status ppasr_beam_pool_decode(ppasr_beam_pool p, const int* sessions_host, int n, const float* probs, int T,
+                                    const int32_t* frame_lens_host, int max_tokens, int32_t* tokens, int32_t* lens,
+                                    double* scores, void* workspace, size_t workspace_bytes, void* stream) {
+  return pool_decode(p, sessions_host, n, probs, T, frame_lens_host, 1, max_tokens, tokens, lens, scores, workspace,
+                     workspace_bytes, stream);
+}
+
+ppasr_status ppasr_beam_sessions_nbest(ppasr_beam_pool p, const int* sessions_host, int n, int nbest, int max_tokens, int32_t* tokens,
+                                   int32_t* lens, double* scores, void* workspace, size_t workspace_bytes, void* stream) {
+  if (p && (nbest < 1 || nbest > p->cfg.beam)) return fail(PPASR_EINVAL, "beam pool: nbest must lie in [1, beam_size]");
+  return pool_decode(p, sessions_host, n, nullptr, 0, nullptr, nbest, max_tokens, tokens, lens, scores, workspace, workspace_bytes,
+                     stream);
 }
 
 // ---- compaction of the pool's prefix arenas (include/ppasr_hip.h: ppasr_beam_arena_*) ----

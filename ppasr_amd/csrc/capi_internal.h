@@ -90,6 +90,38 @@ struct StagingRing {
   }
 };
 
+// The rows of many streaming sessions in pages of one slab (ppasr_prob_arena_*, capi_align.hip): CTC tables (rows V wide)
+// or encoder memory (rows 256 wide).  The page lists and the free list live here, on the host; a call uploads the part of
+// them its launch needs through the ring.
+struct ppasr_prob_arena_s {
+  int n_sessions = 0, V = 0, P = 0, n_pages = 0;
+  float* slab = nullptr;                 // device [n_pages][P][V]
+  std::vector<std::vector<int>> pages;   // per session, in frame order
+  std::vector<long long> frames;         // per session
+  std::vector<int> free_list;            // (a stack: the page freed last is handed out first)
+  StagingRing ring;
+  // one call's table, int32: [n_sessions] first frame (append) or frame count (align, gather), [n_sessions] rows to append,
+  // [n_sessions] page_off, then the page lists.  The sessions of a call are distinct, so the lists hold at most n_pages.
+  size_t table_ints() const { return 3 * (size_t)n_sessions + (size_t)n_pages; }
+  ~ppasr_prob_arena_s() {
+    ring.destroy();
+    (void)hipFree(slab);
+  }
+};
+// An append in two halves, so that a caller with device work of its own in between stays all-or-nothing.
+// arena_plan_append: the checks of a round of rows [n][c] (frames[k] of entry k, NULL: all c) -- the session list, the
+// counts, the pages the round needs against the free ones; changes nothing.  *rows_out (may be null): the rows to append.
+// arena_stage_append: a planned round takes its pages, moves the sessions' frame counts on and uploads the tables of
+// launch_arena_append / launch_memory_append on `st`; the caller launches, then releases tab->en behind its launch.
+struct ArenaAppendTab {
+  const int32_t *first, *count, *page_off, *pages;  // device
+  StagingRing::Entry en;
+};
+ppasr_status arena_plan_append(const ppasr_prob_arena_s* a, const int* sessions, int n, int c, const int* frames, const char* who,
+                               long long* rows_out);
+ppasr_status arena_stage_append(ppasr_prob_arena_s* a, const int* sessions, int n, int c, const int* frames, ArenaAppendTab* tab,
+                                hipStream_t st);
+
 struct Blob {
   const float* p;
   int ndim;

@@ -420,11 +420,45 @@ ppasr_status sq_stream_layers(const ppasr_model_s* h, const StreamRows& v, const
   return PPASR_OK;
 }
 
+// Where a round keeps its encoder output (ppasr_encode_chunk_mem / ppasr_encode_chunk_group_mem): list position k's rows go
+// behind the last frame arena session sessions[k] holds, frames[k] of them (null: all).  No arena: nowhere, no launch.
+struct MemOut {
+  ppasr_prob_arena_s* arena;
+  const int* sessions;
+  const int* frames;
+};
+
+// what a round with a memory arena needs, checked before any device work: a model whose head rows become the encoder
+// output through after_norm on the fused route (the set ppasr_set_memory_out serves, without the general route; the
+// Squeezeformer's and the Efficient-Conformer's streams are not built: DESIGN section 8), an arena of 256-wide rows with
+// a slot for every session, and the pages of this round (arena_plan_append: PPASR_ENOSPACE, nothing changed)
+ppasr_status mem_check(const ppasr_model_s* h, const MemOut& mem, int n, int n_sessions, int c, const char* who) {
+  const std::string w(who);
+  if (h->desc.model_type != PPASR_MODEL_CONFORMER || h->generic)
+    return fail(PPASR_EUNSUPPORTED, w + ": a memory arena is built for Conformer streams on the fused 256-wide route "
+                                        "(not DeepSpeech2, the general route, the Squeezeformer or the Efficient-Conformer)");
+  if (mem.arena->V != kD) return fail(PPASR_EINVAL, w + ": the memory arena must hold rows of 256 floats");
+  if (mem.arena->n_sessions < n_sessions) return fail(PPASR_EINVAL, w + ": the memory arena has fewer sessions than the caller");
+  return arena_plan_append(mem.arena, mem.sessions, n, c, mem.frames, who, nullptr);
+}
+
+// the round's encoder output: after_norm of the rows x the head reads, [n][frames][256], into the arena's pages; one launch
+ppasr_status keep_memory(const ppasr_model_s* h, const MemOut& mem, int n, const float* x, int frames, hipStream_t st) {
+  ArenaAppendTab tab{};
+  ppasr_status r = arena_stage_append(mem.arena, mem.sessions, n, frames, mem.frames, &tab, st);
+  if (r != PPASR_OK) return r;
+  launch_memory_append(x, h->head.ln_g, h->head.ln_b, n, frames, kD, mem.arena->P, tab.first, tab.count, tab.page_off, tab.pages,
+                       mem.arena->slab, st);
+  HIP_TRY(mem.arena->ring.release(tab.en, st));
+  return PPASR_OK;
+}
+
 // One streaming round on the fused 256-wide route -- a stream handle's chunk or a session group's listed chunks: front
-// end, the family's layers, head.  *frames = the encoder frames each chunk leaves with
+// end, the family's layers, head and, with a memory arena, the encoder output.  *frames = the encoder frames each chunk
+// leaves with
 ppasr_status stream_round(const ppasr_model_s* h, const StreamRows& v, const StreamWs& w, const float* feats, int T,
                           float* conv2_part, float* probs, int32_t* frame_argmax, float* frame_maxprob, hipStream_t st,
-                          int* frames) {
+                          int* frames, const MemOut& mem) {
   stream_front(h, v, w, feats, T, conv2_part, st);
   float* x_final = w.xa;
   *frames = v.c;
@@ -435,7 +469,7 @@ ppasr_status stream_round(const ppasr_model_s* h, const StreamRows& v, const Str
     *frames = conformer_stream_layers(h, v, w, st);
   }
   stream_head(h, v, w, x_final, *frames, probs, frame_argmax, frame_maxprob, st);
-  return PPASR_OK;
+  return mem.arena ? keep_memory(h, mem, v.n, x_final, *frames, st) : PPASR_OK;
 }
 
 // every layer's pointwise_conv1 and history rows (kernel_i - 1) for k_pw1_glu_layers -> tab_dev [L] (the general route
@@ -542,6 +576,14 @@ size_t ppasr_chunk_workspace_bytes(ppasr_handle h, int T) {
 ppasr_status ppasr_encode_chunk(ppasr_stream s, const float* feats, int T, int required_cache_size, float* probs,
                                 int32_t* frame_argmax, float* frame_maxprob, int* c_out_host, void* workspace,
                                 size_t workspace_bytes, void* stream) {
+  return ppasr_encode_chunk_mem(s, feats, T, required_cache_size, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
+                                workspace_bytes, nullptr, 0, -1, stream);
+}
+
+ppasr_status ppasr_encode_chunk_mem(ppasr_stream s, const float* feats, int T, int required_cache_size, float* probs,
+                                    int32_t* frame_argmax, float* frame_maxprob, int* c_out_host, void* workspace,
+                                    size_t workspace_bytes, ppasr_prob_arena mem_arena, int mem_session, int mem_frames,
+                                    void* stream) {
   if (!s || !feats || !workspace) return fail(PPASR_EINVAL, "null argument");
   ppasr_model_s* h = s->m;
   if (T < h->min_frames())
@@ -551,6 +593,11 @@ ppasr_status ppasr_encode_chunk(ppasr_stream s, const float* feats, int T, int r
   ChunkPlan p{};
   ppasr_status r = plan_chunk(s, c, required_cache_size, &p);
   if (r != PPASR_OK) return r;
+  const MemOut mem{mem_arena, &mem_session, mem_frames < 0 ? nullptr : &mem_frames};
+  if (mem_arena) {
+    r = mem_check(h, mem, 1, 1, c, "encode_chunk_mem");
+    if (r != PPASR_OK) return r;
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const WsLayout wl = ws_layout(h, 1, T);
   float* ws = static_cast<float*>(workspace);
@@ -569,7 +616,7 @@ ppasr_status ppasr_encode_chunk(ppasr_stream s, const float* feats, int T, int r
   float* shift_tmp = w.behind;
   int frames = c;
   r = stream_round(h, handle_rows(s, p), w, feats, T, shift_tmp + (size_t)h->desc.max_len * kD, probs, frame_argmax,
-                   frame_maxprob, st, &frames);
+                   frame_maxprob, st, &frames, mem);
   if (r != PPASR_OK) return r;
   r = finish_chunk(s, p, shift_tmp, st);
   if (r != PPASR_OK) return r;
@@ -742,24 +789,28 @@ StreamRows group_rows(const ppasr_stream_group_s* g, const SessDesc* desc, int n
 // with the descriptors `desc` the round staged (device) and the workspace ws; *frames = the encoder frames each session
 // emitted.  A body that fails returns before the round commits anything. ----
 typedef ppasr_status (*GroupBody)(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
-                                  int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames);
+                                  int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames,
+                                  const MemOut& mem);
 
 // Conformer, Squeezeformer and Efficient-Conformer on the fused 256-wide route: a stream handle's chunk for every listed
 // session, rows stacked.  The Efficient-Conformer's plans (plan_chunk_for) double the offset, do not trim the half-rate
 // cache and refuse odd cache lengths; its half-rate descriptors carry {sess, cache_r, pos0}, pos0 = 2 offset - cache_t (the
 // half-rate layers read every second positional row).
 ppasr_status fused_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
-                              int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
+                              int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames,
+                                  const MemOut& mem) {
   ppasr_model_s* h = g->m;
   const int c = h->front_dims(T).Tp;
   const StreamWs w = carve_ws(ws, ws_layout(h, n, T), n * c);
-  return stream_round(h, group_rows(g, desc, n, c, w.behind), w, feats, T, nullptr, probs, frame_argmax, frame_maxprob, st, frames);
+  return stream_round(h, group_rows(g, desc, n, c, w.behind), w, feats, T, nullptr, probs, frame_argmax, frame_maxprob, st, frames,
+                      mem);
 }
 
 // general route: generic_group_chunk over the listed sessions.  pos0 = offset - cache_t picks the relative positional
 // rows; abs_pos adds row offset + t.
 ppasr_status gen_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
-                            int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
+                            int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames,
+                                  const MemOut& mem) {
   *frames = g->m->front_dims(T).Tp;
   return generic_group_chunk(g->m, desc, n, g->kc, g->vc, g->cap, g->xh_hist, g->lo, feats, T, probs, frame_argmax,
                              frame_maxprob, ws, st);
@@ -767,7 +818,8 @@ ppasr_status gen_group_body(ppasr_stream_group g, const SessDesc* desc, int n, c
 
 // DeepSpeech2: ds2_group_round on the listed sessions' slots (desc holds plain slot indices)
 ppasr_status ds2_group_body(ppasr_stream_group g, const SessDesc* desc, int n, const float* feats, int T, float* probs,
-                            int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames) {
+                            int32_t* frame_argmax, float* frame_maxprob, float* ws, hipStream_t st, int* frames,
+                                  const MemOut& mem) {
   const Ds2W& W = g->m->ds2;
   float* state_h = g->ds2_state;
   float* state_c = W.gates == 4 ? g->ds2_state + (size_t)g->n_sessions * W.n_layers * W.H : nullptr;
@@ -900,6 +952,16 @@ size_t ppasr_group_chunk_workspace_bytes(ppasr_handle h, int n, int T) {
 ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
                                       float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
                                       void* workspace, size_t workspace_bytes, void* stream) {
+  return ppasr_encode_chunk_group_mem(g, sessions_host, n, feats, T, probs, frame_argmax, frame_maxprob, c_out_host, workspace,
+                                      workspace_bytes, nullptr, nullptr, stream);
+}
+
+// ppasr_encode_chunk_group, and the round's encoder output behind the listed sessions' frames in the arena `mem_arena`
+// (mem_frames_host [n]: rows kept per list position, NULL: all; no arena: the plain round, launch for launch)
+ppasr_status ppasr_encode_chunk_group_mem(ppasr_stream_group g, const int* sessions_host, int n, const float* feats, int T,
+                                          float* probs, int32_t* frame_argmax, float* frame_maxprob, int* c_out_host,
+                                          void* workspace, size_t workspace_bytes, ppasr_prob_arena mem_arena,
+                                          const int* mem_frames_host, void* stream) {
   if (!g || !sessions_host || !feats || !workspace || n < 1 || n > g->n_sessions) return fail(PPASR_EINVAL, "bad argument");
   ppasr_model_s* h = g->m;
   if (T < 7) return fail(PPASR_EINVAL, "chunk shorter than the conv front-end's receptive field (7 frames)");
@@ -911,6 +973,14 @@ ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int* sessions_
   for (size_t b = 0; b < plans.size(); ++b) {
     const int s = sessions_host[b];
     ppasr_status r = plan_chunk_for(h, g->cache_t[s], g->cache_r[s], g->offset[s], g->cap, c, -1, &plans[b]);
+    if (r != PPASR_OK) return r;
+  }
+  const MemOut mem{mem_arena, sessions_host, mem_frames_host};
+  if (mem_arena) {
+    if (g->family != GroupFamily::kConformer)
+      return fail(PPASR_EUNSUPPORTED, "encode_chunk_group_mem: a memory arena is built for Conformer groups on the fused 256-wide "
+                                      "route (not DeepSpeech2, general-route, Squeezeformer or Efficient-Conformer groups)");
+    ppasr_status r = mem_check(h, mem, n, g->n_sessions, c, "encode_chunk_group_mem");
     if (r != PPASR_OK) return r;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -932,7 +1002,8 @@ ppasr_status ppasr_encode_chunk_group(ppasr_stream_group g, const int* sessions_
   HIP_TRY(hipMemcpyAsync(en.dev, en.host, staged, hipMemcpyHostToDevice, st));
   int frames = 0;
   ppasr_status r = kGroupKinds[(int)g->family].body(g, reinterpret_cast<const SessDesc*>(en.dev), n, feats, T, probs,
-                                                    frame_argmax, frame_maxprob, static_cast<float*>(workspace), st, &frames);
+                                                    frame_argmax, frame_maxprob, static_cast<float*>(workspace), st, &frames,
+                                                    mem);
   if (r != PPASR_OK) return r;
   for (int b = 0; b < n; ++b) {
     const int s = sessions_host[b];

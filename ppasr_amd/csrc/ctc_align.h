@@ -74,5 +74,8 @@ void launch_arena_append(const float* probs, int n, int c, int V, int P, const i
                          const int32_t* page_off, const int32_t* pages, float* slab, hipStream_t st);
 // dense [T][V] (T > 0) = the frames held in pages[0 .. (T - 1) / P]
 void launch_arena_read(const float* slab, int V, int P, const int32_t* pages, int T, float* dense, hipStream_t st);
+// dense [n][Tp][V] = the count[k] <= Tp frames of entry k (pages[page_off[k] ..]), zeros behind them; lens [n] = count
+void launch_arena_read_many(const float* slab, int V, int P, const int32_t* count, const int32_t* page_off, const int32_t* pages,
+                            int n, int Tp, float* dense, int32_t* lens, hipStream_t st);
 
 }  // namespace ppasr

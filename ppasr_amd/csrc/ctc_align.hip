@@ -128,6 +128,27 @@ __global__ __launch_bounds__(256) void arena_read_kernel(const uint32_t* __restr
   for (int v = threadIdx.x; v < V; v += 256) dst[v] = src[v];
 }
 
+// the pages of n sessions as one dense [n][Tp][V] table: workgroup (k, t) copies frame t of entry k, or writes zeros when
+// the session holds no such frame; the workgroup of frame 0 also writes the session's frame count (grid n * max(Tp, 1))
+__global__ __launch_bounds__(256) void arena_read_many_kernel(const uint32_t* __restrict__ slab, int V, int P,
+                                                              const int32_t* __restrict__ count,
+                                                              const int32_t* __restrict__ page_off,
+                                                              const int32_t* __restrict__ pages, int Tp,
+                                                              uint32_t* __restrict__ dense, int32_t* __restrict__ lens) {
+  const int span = Tp > 0 ? Tp : 1;
+  const int k = blockIdx.x / span, t = blockIdx.x - k * span;
+  const int T = count[k];
+  if (t == 0 && threadIdx.x == 0) lens[k] = T;
+  if (t >= Tp) return;
+  uint32_t* dst = dense + ((size_t)k * Tp + t) * V;
+  if (t >= T) {
+    for (int v = threadIdx.x; v < V; v += 256) dst[v] = 0u;
+    return;
+  }
+  const uint32_t* src = slab + ((size_t)pages[page_off[k] + t / P] * P + t % P) * V;
+  for (int v = threadIdx.x; v < V; v += 256) dst[v] = src[v];
+}
+
 struct Emis {
   float4 v;  // e(t, token 4i .. 4i+3) of lane i
   float eb;  // e(t, blank)
@@ -375,6 +396,12 @@ void launch_arena_append(const float* probs, int n, int c, int V, int P, const i
 void launch_arena_read(const float* slab, int V, int P, const int32_t* pages, int T, float* dense, hipStream_t st) {
   PPASR_LAUNCH(arena_read_kernel, dim3((unsigned)T), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(slab), V, P, pages,
                reinterpret_cast<uint32_t*>(dense));
+}
+
+void launch_arena_read_many(const float* slab, int V, int P, const int32_t* count, const int32_t* page_off, const int32_t* pages,
+                            int n, int Tp, float* dense, int32_t* lens, hipStream_t st) {
+  PPASR_LAUNCH(arena_read_many_kernel, dim3((unsigned)n * (Tp > 0 ? Tp : 1)), dim3(256), 0, st,
+               reinterpret_cast<const uint32_t*>(slab), V, P, count, page_off, pages, Tp, reinterpret_cast<uint32_t*>(dense), lens);
 }
 
 }  // namespace ppasr

@@ -68,6 +68,11 @@ struct RescoreLoss {
 
 void launch_memory_out(const float* x, const float* g, const float* b, float* out, int M, int D, const PadSkip& ps,
                        hipStream_t st);
+// the same rows of a streaming round, x [n][c][D] (n * c > 0), into a row arena of width D (slab [n_pages][P][D]): rows
+// 0 .. count[k] - 1 of list position k become frames first[k] .. of its session, whose pages from page first[k] / P on are
+// pages[page_off[k] ..] (the tables of launch_arena_append, ctc_align.h; device arrays).  One launch
+void launch_memory_append(const float* x, const float* g, const float* b, int n, int c, int D, int P, const int32_t* first,
+                          const int32_t* count, const int32_t* page_off, const int32_t* pages, float* slab, hipStream_t st);
 hipError_t configure_rescore_kernels();
 // k_dec_kv alone, over the first `slots` layer slots (the left decoder's when slots = n_left): kv [B * Tp][512 * slots]
 void launch_dec_kv(const RescoreW& W, int B, int Tp, int slots, const float* memory, const int32_t* out_lens, float* kv,

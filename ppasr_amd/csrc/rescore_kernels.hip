@@ -475,23 +475,10 @@ __global__ __launch_bounds__(64) void k_dec_score(RescoreDims d, RowTab tab, con
   }
 }
 
-// encoder output of an offline encode (ppasr_set_memory_out): LayerNorm over D (encoder.after_norm; g == nullptr: a copy)
-// of the rows the CTC head reads, one wave per row; ragged batches: rows behind the valid frames are 0
-__global__ __launch_bounds__(256) void k_memory_out(const float* __restrict__ x, const float* __restrict__ g,
-                                                    const float* __restrict__ bta, float* __restrict__ out, int M, int D,
-                                                    const int64_t* __restrict__ lens, int Tp, int mul) {
-  const int row = blockIdx.x * 4 + wave_id();
-  if (row >= M) return;
-  const int lane = lane_id();
-  float* o = out + (size_t)row * D;
-  if (lens) {
-    const int b = row / Tp, t = row - b * Tp;
-    if ((int64_t)mul * t >= lens[b]) {
-      for (int c = lane; c < D; c += 64) o[c] = 0.f;
-      return;
-    }
-  }
-  const float* xr = x + (size_t)row * D;
+// one row of the encoder output, by one wave: o = LayerNorm(xr) over D (encoder.after_norm; g == nullptr: a copy).  Shared
+// by the offline and the streaming kernel below, so that a frame's memory is the same bits on either path
+__device__ __forceinline__ void memory_row(const float* __restrict__ xr, const float* __restrict__ g,
+                                           const float* __restrict__ bta, float* __restrict__ o, int D, int lane) {
   if (!g) {
     for (int c = lane; c < D; c += 64) o[c] = xr[c];
     return;
@@ -508,11 +495,54 @@ __global__ __launch_bounds__(256) void k_memory_out(const float* __restrict__ x,
   for (int c = lane; c < D; c += 64) o[c] = (xr[c] - mean) * rstd * g[c] + bta[c];
 }
 
+// encoder output of an offline encode (ppasr_set_memory_out): memory_row of the rows the CTC head reads, one wave per
+// row; ragged batches: rows behind the valid frames are 0
+__global__ __launch_bounds__(256) void k_memory_out(const float* __restrict__ x, const float* __restrict__ g,
+                                                    const float* __restrict__ bta, float* __restrict__ out, int M, int D,
+                                                    const int64_t* __restrict__ lens, int Tp, int mul) {
+  const int row = blockIdx.x * 4 + wave_id();
+  if (row >= M) return;
+  const int lane = lane_id();
+  float* o = out + (size_t)row * D;
+  if (lens) {
+    const int b = row / Tp, t = row - b * Tp;
+    if ((int64_t)mul * t >= lens[b]) {
+      for (int c = lane; c < D; c += 64) o[c] = 0.f;
+      return;
+    }
+  }
+  memory_row(x + (size_t)row * D, g, bta, o, D, lane);
+}
+
+// encoder output of a streaming round (ppasr_encode_chunk_group_mem / ppasr_encode_chunk_mem): memory_row of row r of list
+// position k (x [n][c][D]) goes to frame first[k] + r of its session in a row arena of width D -- the page addressing of
+// arena_append_kernel (ctc_align.hip): the session's pages from page first[k] / P on are pages[page_off[k] ..].  One wave
+// per row; rows r >= count[k] are not kept.
+__global__ __launch_bounds__(256) void k_memory_append(const float* __restrict__ x, const float* __restrict__ g,
+                                                       const float* __restrict__ bta, int M, int c, int D, int P,
+                                                       const int32_t* __restrict__ first, const int32_t* __restrict__ count,
+                                                       const int32_t* __restrict__ page_off,
+                                                       const int32_t* __restrict__ pages, float* __restrict__ slab) {
+  const int row = blockIdx.x * 4 + wave_id();
+  if (row >= M) return;
+  const int k = row / c, r = row - k * c;
+  if (r >= count[k]) return;
+  const int f = first[k] + r;
+  const int page = pages[page_off[k] + f / P - first[k] / P];
+  memory_row(x + (size_t)row * D, g, bta, slab + ((size_t)page * P + f % P) * D, D, lane_id());
+}
+
 }  // namespace
 
 void launch_memory_out(const float* x, const float* g, const float* b, float* out, int M, int D, const PadSkip& ps,
                        hipStream_t st) {
   PPASR_LAUNCH(k_memory_out, dim3((M + 3) / 4), dim3(256), 0, st, x, g, b, out, M, D, ps.lens, ps.Tp, ps.mul);
+}
+
+void launch_memory_append(const float* x, const float* g, const float* b, int n, int c, int D, int P, const int32_t* first,
+                          const int32_t* count, const int32_t* page_off, const int32_t* pages, float* slab, hipStream_t st) {
+  const int M = n * c;
+  PPASR_LAUNCH(k_memory_append, dim3((M + 3) / 4), dim3(256), 0, st, x, g, b, M, c, D, P, first, count, page_off, pages, slab);
 }
 
 void launch_dec_kv(const RescoreW& W, int B, int Tp, int slots, const float* memory, const int32_t* out_lens, float* kv,

@@ -407,6 +407,35 @@ class BeamSearchSessions:
             self._lib.ppasr_beam_pool_status(self._h, out.ctypes.data_as(ctypes.c_void_p), self._stream())
         return out
 
+    def nbest(self, sessions, nbest, max_tokens=None):
+        """The ``nbest`` best prefixes of each listed session's current beam (``ppasr_beam_sessions_nbest``) -> device tensors
+        (tokens [n, nbest, L] i32, -1 padded; lens [n, nbest] i32, -1: the beam holds fewer; scores [n, nbest] f64 =
+        -log P), L = ``max_tokens`` or the longest listed session's frame count.  One launch, nothing read back; no
+        session is advanced or otherwise changed.  ValueError, before any device work: ``nbest`` outside
+        [1, beam_size], a bad session list."""
+        if isinstance(nbest, (bool, np.bool_)) or not isinstance(nbest, (int, np.integer)) or not 1 <= nbest <= self.beam_size:
+            raise ValueError(f"BeamSearchSessions.nbest: nbest must be an integer in [1, beam_size = {self.beam_size}]")
+        ids = [int(s) for s in sessions]
+        n, K = len(ids), int(nbest)
+        if n < 1 or len(set(ids)) != n or any(not 0 <= s < self.n_sessions for s in ids):
+            raise ValueError("BeamSearchSessions.nbest: sessions must be distinct indices in [0, n_sessions)")
+        L = int(max_tokens) if max_tokens is not None else max(max(self.frames(s) for s in ids), 1)
+        if L < 1:
+            raise ValueError("BeamSearchSessions.nbest: max_tokens must be >= 1")
+        tokens = torch.empty(n, K, L, dtype=torch.int32, device=self._device)
+        lens = torch.empty(n, K, dtype=torch.int32, device=self._device)
+        scores = torch.empty(n, K, dtype=torch.float64, device=self._device)
+        with torch.cuda.device(self._device):
+            stream = self._stream()
+            need = int(self._lib.ppasr_beam_pool_workspace_bytes(self._h, n, 0))
+            ws = self._ws.get(stream)
+            if need and (ws is None or ws.numel() < need):
+                ws = self._ws[stream] = torch.empty(need, dtype=torch.uint8, device=self._device)
+            _lib.check(self._lib.ppasr_beam_sessions_nbest(self._h, (ctypes.c_int * n)(*ids), n, K, L, tokens.data_ptr(),
+                                                       lens.data_ptr(), scores.data_ptr(),
+                                                       None if not need else ws.data_ptr(), need, stream))
+        return tokens, lens, scores
+
     def decode_chunks(self, sessions, probs, lens=None, return_ids=False):
         """sessions: distinct indices (n); probs [n,c,V] (device tensor or array); lens [n] frames of each chunk (None:
         all c).  -> [(score, text)] by list position: each session's current best after this chunk.  One device-to-host

@@ -181,6 +181,21 @@ class ProbArena:
             _lib.check(self._lib.ppasr_prob_arena_read(self._h, int(session), dense.data_ptr() if T else None, self._stream()))
         return dense
 
+    def read_many(self, sessions, Tp=None):
+        """-> (dense [n, Tp, V], lens [n] i32) device tensors: the listed sessions' rows with zeros behind each session's
+        frames, and the frame counts.  Tp None: the longest listed session.  One launch, nothing read back."""
+        ids, c_ids = self._list(sessions, "read_many")
+        longest = max(self.frames(s) for s in ids)
+        Tp = longest if Tp is None else int(Tp)
+        if Tp < longest:
+            raise ValueError(f"ProbArena.read_many: Tp = {Tp} is below the longest listed session ({longest} frames)")
+        dense = torch.empty(len(ids), Tp, self.V, dtype=torch.float32, device=self._device)
+        lens = torch.empty(len(ids), dtype=torch.int32, device=self._device)
+        with torch.cuda.device(self._device):
+            _lib.check(self._lib.ppasr_prob_arena_read_many(self._h, c_ids, len(ids), Tp, dense.data_ptr() if Tp else None,
+                                                            lens.data_ptr(), self._stream()))
+        return dense, lens
+
     def align_ids(self, sessions, tokens, n_tokens, blank_index=0):
         """``ctc_align_ids`` over the listed sessions' tables: B = n, T = the longest listed session, each session's own
         frame count as its frame_lens.  Every output equals ``ctc_align_ids`` on the dense tables, bit for bit."""

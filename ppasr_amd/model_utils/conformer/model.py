@@ -356,8 +356,12 @@ class ConformerStream:
         with torch.cuda.device(m.device):
             _lib.check(self.lib.ppasr_stream_reset(self._s, torch.cuda.current_stream(m.device).cuda_stream))
 
-    def encode_chunk(self, speech, required_cache_size=-1, want_probs=True, want_frames=False):
-        """speech [1,t,F] -> ctc_probs [1,c,V] (device tensor); caches / offset advance on the device."""
+    def encode_chunk(self, speech, required_cache_size=-1, want_probs=True, want_frames=False, memory_arena=None,
+                     memory_frames=None, memory_session=0):
+        """speech [1,t,F] -> ctc_probs [1,c,V] (device tensor); caches / offset advance on the device.
+        memory_arena: a ``ProbArena`` of 256-wide rows -- the chunk's encoder output goes behind the frames of its
+        session ``memory_session``, ``memory_frames`` rows of it (None: all c), with one more launch
+        (``ppasr_encode_chunk_mem``)."""
         m = self.model
         x = torch.as_tensor(speech, dtype=torch.float32).to(m.device).contiguous()
         assert x.dim() == 3 and x.shape[0] == 1 and x.shape[2] == m.input_dim  # encoder.py:238
@@ -373,9 +377,17 @@ class ConformerStream:
         ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(m.device):
             stream = torch.cuda.current_stream(m.device).cuda_stream
-            _lib.check(self.lib.ppasr_encode_chunk(self._s, x.data_ptr(), T, int(required_cache_size), ptr(probs),
-                                                   ptr(fa), ptr(fp), ctypes.byref(c_out), self._ws.data_ptr(),
-                                                   self._ws.numel(), stream))
+            if memory_arena is None:
+                if memory_frames is not None:
+                    raise ValueError("encode_chunk: memory_frames needs a memory_arena")
+                _lib.check(self.lib.ppasr_encode_chunk(self._s, x.data_ptr(), T, int(required_cache_size), ptr(probs),
+                                                       ptr(fa), ptr(fp), ctypes.byref(c_out), self._ws.data_ptr(),
+                                                       self._ws.numel(), stream))
+            else:
+                _lib.check(self.lib.ppasr_encode_chunk_mem(self._s, x.data_ptr(), T, int(required_cache_size), ptr(probs),
+                                                           ptr(fa), ptr(fp), ctypes.byref(c_out), self._ws.data_ptr(),
+                                                           self._ws.numel(), memory_arena._h, int(memory_session),
+                                                           -1 if memory_frames is None else int(memory_frames), stream))
         if want_frames:
             return probs, fa, fp
         return probs
@@ -433,11 +445,15 @@ class StreamHandleSet:
         for i in (range(self.n_sessions) if int(session) < 0 else [int(session)]):
             self._streams[i].reset()
 
-    def encode_chunks(self, sessions, speech, want_probs=False):
+    def encode_chunks(self, sessions, speech, want_probs=False, memory_arena=None, memory_frames=None):
         m = self.model
         x = torch.as_tensor(speech, dtype=torch.float32).to(m.device)
         assert x.dim() == 3 and int(x.shape[0]) == len(sessions)
-        outs = [self._streams[int(sid)].encode_chunk(x[k:k + 1], -16, want_probs=want_probs, want_frames=True)
+        if memory_arena is None and memory_frames is not None:
+            raise ValueError("encode_chunks: memory_frames needs a memory_arena")
+        mem = lambda k, sid: {} if memory_arena is None else dict(
+            memory_arena=memory_arena, memory_session=int(sid), memory_frames=None if memory_frames is None else memory_frames[k])
+        outs = [self._streams[int(sid)].encode_chunk(x[k:k + 1], -16, want_probs=want_probs, want_frames=True, **mem(k, sid))
                 for k, sid in enumerate(sessions)]
         fa = torch.cat([o[1] for o in outs], 0)
         fp = torch.cat([o[2] for o in outs], 0)
@@ -493,9 +509,13 @@ class ConformerStreamGroup:
             _lib.check(self.lib.ppasr_stream_group_reset(self._g, int(session),
                                                          torch.cuda.current_stream(m.device).cuda_stream))
 
-    def encode_chunks(self, sessions, speech, want_probs=False):
+    def encode_chunks(self, sessions, speech, want_probs=False, memory_arena=None, memory_frames=None):
         """sessions: list of distinct slot indices (len n); speech [n,t,F] -> (frame_argmax [n,c] i32, frame_maxprob [n,c])
-        device tensors, plus ctc_probs [n,c,V] when ``want_probs``."""
+        device tensors, plus ctc_probs [n,c,V] when ``want_probs``.  memory_arena: a ``ProbArena`` of 256-wide rows with
+        a slot per session -- the round's encoder output (``encoder.after_norm`` of the rows the head reads) goes behind
+        the listed sessions' frames there, ``memory_frames[k]`` rows of list position k (None: all c), with one more
+        launch (``ppasr_encode_chunk_group_mem``); a round the arena has no pages for raises ``PPASRHipError`` with
+        status ``PPASR_ENOSPACE`` and changes neither a session nor the arena."""
         m = self.model
         x = torch.as_tensor(speech, dtype=torch.float32).to(m.device).contiguous()
         n, T = int(x.shape[0]), int(x.shape[1])
@@ -512,11 +532,25 @@ class ConformerStreamGroup:
         fp = torch.empty(n, c, dtype=torch.float32, device=m.device)
         ids = (ctypes.c_int * n)(*[int(s) for s in sessions])
         c_out = ctypes.c_int(0)
+        if memory_arena is None and memory_frames is not None:
+            raise ValueError("encode_chunks: memory_frames needs a memory_arena")
+        c_fr = None
+        if memory_frames is not None:
+            fr = [int(f) for f in memory_frames]
+            if len(fr) != n:
+                raise ValueError("encode_chunks: memory_frames must hold one value per listed session")
+            c_fr = (ctypes.c_int * n)(*fr)
         with torch.cuda.device(m.device):
-            _lib.check(self.lib.ppasr_encode_chunk_group(self._g, ids, n, x.data_ptr(), T,
-                                                         None if probs is None else probs.data_ptr(), fa.data_ptr(),
-                                                         fp.data_ptr(), ctypes.byref(c_out), ws.data_ptr(), ws.numel(),
-                                                         key))
+            if memory_arena is None:
+                _lib.check(self.lib.ppasr_encode_chunk_group(self._g, ids, n, x.data_ptr(), T,
+                                                             None if probs is None else probs.data_ptr(), fa.data_ptr(),
+                                                             fp.data_ptr(), ctypes.byref(c_out), ws.data_ptr(), ws.numel(),
+                                                             key))
+            else:
+                _lib.check(self.lib.ppasr_encode_chunk_group_mem(self._g, ids, n, x.data_ptr(), T,
+                                                                 None if probs is None else probs.data_ptr(), fa.data_ptr(),
+                                                                 fp.data_ptr(), ctypes.byref(c_out), ws.data_ptr(),
+                                                                 ws.numel(), memory_arena._h, c_fr, key))
         return (fa, fp, probs) if want_probs else (fa, fp)
 
 

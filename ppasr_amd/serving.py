@@ -30,6 +30,9 @@ _DECODERS = ("ctc_greedy", "ctc_beam_search")
 # keys of ctc_beam_search_decoder_conf (configs/conformer.yml); the shipped values except the language model
 _BEAM_DEFAULTS = dict(alpha=2.2, beta=4.3, beam_size=300, num_processes=10, cutoff_prob=0.99, cutoff_top_n=40,
                       language_model_path=None)
+# decoder="attention_rescoring": PPASRPredictor's defaults for attention_rescoring_decoder_conf
+_RESCORING_DEFAULTS = dict(beam_size=10, ctc_weight=0.5, reverse_weight=0.3, cutoff_prob=0.99, cutoff_top_n=40)
+_MAX_RESCORE_TOKENS = 255  # tokens per hypothesis the rescoring kernels take (attention_rescoring.MAX_ROWS - 1)
 
 
 class _Session:
@@ -51,7 +54,7 @@ class _Session:
 class StreamPool:
     def __init__(self, model, vocab_list, n_sessions, preprocess_conf=None, max_seconds=200.0, blank_index=0, group=None,
                  decoder="ctc_greedy", decoder_conf=None, beam_compact=False, timestamps=False, table_seconds=30.0,
-                 page_frames=16):
+                 page_frames=16, rescorer=None, memory_seconds=30.0):
         """group: a ready session group for `model` with `n_sessions` slots (e.g. ``SqueezeformerStreamGroup``,
         ``GeneralConformerStreamGroup``); None =
         ``make_stream_group``'s choice.  decoder: "ctc_greedy" or "ctc_beam_search"; decoder_conf: keys of
@@ -64,7 +67,15 @@ class StreamPool:
         probabilities in an arena of ``page_frames``-row pages (n_sessions x ceil(table_seconds x frames per second /
         page_frames) pages of page_frames x V floats, allocated once); a session that outgrows its share, or whose
         hypothesis exceeds 255 tokens, gets ``"timestamps": None`` (with ``"table_overflow": True`` in the first case)
-        and keeps its text and score.  Off (the default): no arena, no extra launch, results as before."""
+        and keeps its text and score.  Off (the default): no arena, no extra launch, results as before.
+        decoder="attention_rescoring" with rescorer=<AttentionRescorer>: WeNet's two-pass mode for streams.  While audio
+        arrives the pool is a ``ctc_beam_search`` pool without a scorer (decoder_conf: beam_size, ctc_weight,
+        reverse_weight, cutoff_prob, cutoff_top_n, over ``PPASRPredictor``'s rescoring defaults) whose encoder rounds
+        also keep their encoder output, ``memory_seconds`` per session, in an arena of ``page_frames``-row pages of 256
+        floats -- one more launch per round.  ``finish`` / ``finish_many`` then rescore the beam's n-best list over that
+        memory: ``{"text", "score", "rescored": True}``, score = the total as offline ``attention_rescoring`` returns
+        it.  A session that outgrew ``memory_seconds`` (``"memory_overflow": True``) or whose best hypothesis exceeds
+        255 tokens keeps its CTC result with ``"rescored": False``.  Conformer models on the fused route."""
         if not isinstance(timestamps, (bool, np.bool_)):
             raise ValueError("StreamPool: timestamps must be True or False")
         if isinstance(table_seconds, (bool, np.bool_)) or not isinstance(table_seconds, (int, float, np.integer, np.floating)) \
@@ -72,18 +83,33 @@ class StreamPool:
             raise ValueError("StreamPool: table_seconds must be a positive number of seconds")
         if isinstance(page_frames, (bool, np.bool_)) or not isinstance(page_frames, (int, np.integer)) or page_frames < 1:
             raise ValueError("StreamPool: page_frames must be an integer >= 1")
-        if decoder not in _DECODERS:
-            raise ValueError(f"StreamPool: unknown decoder {decoder!r} (one of {', '.join(_DECODERS)})")
+        rescoring = decoder == "attention_rescoring"
+        if decoder not in _DECODERS and not rescoring:
+            raise ValueError(f"StreamPool: unknown decoder {decoder!r} (one of {', '.join(_DECODERS)}, attention_rescoring)")
+        if rescoring and rescorer is None:
+            raise ValueError("StreamPool: decoder='attention_rescoring' needs rescorer=<AttentionRescorer> (the checkpoint's "
+                             "attention decoder): without one a pool decodes with ctc_greedy or ctc_beam_search")
+        if rescorer is not None and not rescoring:
+            raise ValueError("StreamPool: rescorer applies to decoder='attention_rescoring' only")
+        if isinstance(memory_seconds, (bool, np.bool_)) or not isinstance(memory_seconds, (int, float, np.integer, np.floating)) \
+                or not 0 < float(memory_seconds) < float("inf"):
+            raise ValueError("StreamPool: memory_seconds must be a positive number of seconds")
         if not isinstance(beam_compact, (bool, np.bool_)):
             raise ValueError("StreamPool: beam_compact must be True or False")
         if beam_compact and decoder != "ctc_beam_search":
             raise ValueError("StreamPool: beam_compact applies to decoder='ctc_beam_search' only")
         conf = dict(decoder_conf or {})
-        unknown = sorted(set(conf) - set(_BEAM_DEFAULTS))
+        known = _RESCORING_DEFAULTS if rescoring else _BEAM_DEFAULTS
+        if rescoring and "language_model_path" in conf:
+            raise ValueError("StreamPool: decoder='attention_rescoring' takes no language_model_path: the n-best list is the "
+                             "plain CTC prefix beam search's, as offline")
+        unknown = sorted(set(conf) - set(known))
         if unknown:
-            raise ValueError(f"StreamPool: unknown decoder_conf keys {unknown} (known: {sorted(_BEAM_DEFAULTS)})")
-        if conf and decoder != "ctc_beam_search":
-            raise ValueError("StreamPool: decoder_conf applies to decoder='ctc_beam_search' only")
+            raise ValueError(f"StreamPool: unknown decoder_conf keys {unknown} (known: {sorted(known)})")
+        if conf and decoder == "ctc_greedy":
+            raise ValueError("StreamPool: decoder_conf applies to decoder='ctc_beam_search' and 'attention_rescoring' only")
+        if rescoring and timestamps:
+            raise ValueError("StreamPool: timestamps=True is not built for decoder='attention_rescoring'")
         self.decoder = decoder
         self.model = model
         self.vocab = list(vocab_list)
@@ -116,6 +142,21 @@ class StreamPool:
             self.session_pages = max(1, -(-frames // int(page_frames)))
             self.arena = ProbArena(n_sessions, len(self.vocab), page_frames=int(page_frames),
                                    n_pages=int(n_sessions) * self.session_pages, device=self.beam._device)
+        self.rescorer = rescorer
+        self.memory = None       # attention_rescoring: the sessions' encoder output, a ProbArena of 256-wide rows
+        self.memory_pages = 0    # pages a session may hold there
+        if rescoring:
+            from ppasr_amd.decoders.beam_search_decoder import BeamSearchSessions
+            from ppasr_amd.decoders.ctc_alignment import ProbArena
+            self.rescoring_conf = {**_RESCORING_DEFAULTS, **conf}
+            rc = self.rescoring_conf
+            self.beam = BeamSearchSessions(n_sessions, alpha=0.0, beta=0.0, vocab_list=self.vocab, blank_id=blank_index,
+                                           beam_size=rc["beam_size"], cutoff_prob=rc["cutoff_prob"],
+                                           cutoff_top_n=rc["cutoff_top_n"])
+            frames = int(np.ceil(float(memory_seconds) / self.frame_seconds - 1e-6))
+            self.memory_pages = max(1, -(-frames // int(page_frames)))
+            self.memory = ProbArena(n_sessions, int(rescorer.d_model), page_frames=int(page_frames),
+                                    n_pages=int(n_sessions) * self.memory_pages, device=self.beam._device)
 
     def _rate_of(self, session, sample_rate):
         """The rate of a packet for `session` (None = the featurizer's) -> (rate, the session's resampler or None: a new
@@ -246,6 +287,12 @@ class StreamPool:
 
     def _advance(self, ids, chunks):
         """One encoder round for the listed sessions, then their decoder step -> result dicts by list position."""
+        if self.memory is not None:
+            # the encoder round keeps its output (one more launch), the search is the beam-search pool's
+            c = int(self.model.out_frames(int(chunks.shape[1])))
+            _, _, probs = self.group.encode_chunks(ids, chunks, want_probs=True, memory_arena=self.memory,
+                                                   memory_frames=self._memory_frames(ids, c))
+            return [{"text": text, "score": score} for score, text in self.beam.decode_chunks(ids, probs)]
         if self.beam is not None:
             # the probabilities stay on the device: the search is queued behind the encoder on the same stream
             _, _, probs = self.group.encode_chunks(ids, chunks, want_probs=True)
@@ -289,6 +336,55 @@ class StreamPool:
             frames.append(0 if s.overflow else c)
         self.arena.append(ids, probs, frames)
 
+    def _memory_frames(self, ids, c):
+        """Rows of this round each listed session keeps in the memory arena (``_keep_table``'s policy): a session whose
+        memory would outgrow its share gives its pages back and keeps nothing from then on (until ``reset``)."""
+        room = self.memory_pages * self.memory.page_frames
+        frames = []
+        for i in ids:
+            s = self.sessions[i]
+            if not s.overflow and self.memory.frames(i) + c > room:
+                s.overflow = True
+                self.memory.reset(i)
+            frames.append(0 if s.overflow else c)
+        return frames
+
+    def finish_many(self, sessions):
+        """``finish`` for many sessions of a ``decoder="attention_rescoring"`` pool: each is flushed as ``finish`` does,
+        then ONE n-best read of the beam-search pool, ONE gather of the sessions' memory, ONE ``ppasr_rescore`` call with
+        B = the sessions that can be rescored, and one read-back.  -> [result dict] by list position (None for a session
+        that never produced output)."""
+        if self.memory is None:
+            raise ValueError("StreamPool.finish_many: built for decoder='attention_rescoring' (finish each session otherwise)")
+        ids = [int(i) for i in sessions]
+        if len(set(ids)) != len(ids) or any(i < 0 or i >= len(self.sessions) for i in ids):
+            raise ValueError(f"StreamPool.finish_many: session indices must be distinct and in 0..{len(self.sessions) - 1}")
+        for i in ids:
+            self._flush(i)
+        out = {i: (None if self.sessions[i].result is None else dict(self.sessions[i].result, rescored=False)) for i in ids}
+        for i in ids:
+            if out[i] is not None and self.sessions[i].overflow:
+                out[i]["memory_overflow"] = True
+        live = [i for i in ids if out[i] is not None and not self.sessions[i].overflow and self.memory.frames(i) > 0]
+        if live:
+            from ppasr_amd.decoders.beam_search_decoder import _text
+            rc = self.rescoring_conf
+            L = min(max(self.beam.frames(i) for i in live), _MAX_RESCORE_TOKENS)
+            tokens, lens, scores = self.beam.nbest(live, rc["beam_size"], max_tokens=max(L, 1))
+            memory, mlens = self.memory.read_many(live)
+            res = self.rescorer.rescore(memory, mlens, tokens, lens, scores, rc["ctc_weight"], rc["reverse_weight"])
+            best = res["best"].to(torch.int64)
+            idx = best[:, None, None].expand(-1, 1, tokens.shape[2])
+            pack = (tokens.gather(1, idx)[:, 0], lens.gather(1, best[:, None])[:, 0],
+                    res["total"].gather(1, best[:, None])[:, 0], lens.max(dim=1).values)
+            tk, ln, sc, longest = [t.cpu().numpy() for t in pack]  # (the read-back)
+            for k, i in enumerate(live):
+                if int(longest[k]) > tokens.shape[2]:  # a hypothesis beyond 255 tokens: the CTC result stays
+                    continue
+                out[i] = {"text": _text(tk[k, :max(int(ln[k]), 0)].tolist(), self.vocab), "score": float(sc[k]),
+                          "rescored": True}
+        return [out[i] for i in ids]
+
     def timestamps(self, session):
         """[{"text", "start", "end", "score"}, ...], one entry per token of the session's current text: start = first
         frame x the model's frame step, end = one past the last frame x the step, clipped to the audio fed so far, score
@@ -321,7 +417,21 @@ class StreamPool:
         -> the session's final result dict (None if it never produced output); with ``timestamps=True`` a copy of it
         with ``"timestamps"`` (``timestamps(session)``) and, for a session that outgrew its table, ``"table_overflow":
         True``.  The session keeps its state until ``reset``.  A session fed at a foreign rate flushes its resampler first: the last model-rate samples, which waited
-        for audio that will not come, are fed like a packet."""
+        for audio that will not come, are fed like a packet.  ``decoder="attention_rescoring"``: the flush, then the
+        second pass -- ``finish_many([session])[0]``."""
+        if self.memory is not None:
+            return self.finish_many([session])[0]
+        s = self.sessions[session]
+        self._flush(session)
+        if not self.with_timestamps or s.result is None:
+            return s.result
+        out = dict(s.result, timestamps=self.timestamps(session))
+        if s.overflow:
+            out["table_overflow"] = True
+        return out
+
+    def _flush(self, session):
+        """The end of a session's audio: the resampler's last samples, the buffered full windows, the last shorter one."""
         s = self.sessions[session]
         if s.resampler is not None:
             rest = s.resampler.flush()
@@ -331,12 +441,6 @@ class StreamPool:
         if s.cached_feat is not None and s.cached_feat.shape[1] >= _CONTEXT:
             s.result = self._advance([session], s.cached_feat)[0]
             s.cached_feat = s.cached_feat[:, s.cached_feat.shape[1] - _KEEP:]
-        if not self.with_timestamps or s.result is None:
-            return s.result
-        out = dict(s.result, timestamps=self.timestamps(session))
-        if s.overflow:
-            out["table_overflow"] = True
-        return out
 
     def _result(self, s):
         hist = np.asarray(s.frame_ids, np.int64)
@@ -354,4 +458,6 @@ class StreamPool:
             self.beam.reset(session)
         if self.arena is not None:
             self.arena.reset(session)
+        if self.memory is not None:
+            self.memory.reset(session)
         self.sessions[session] = _Session()
